@@ -8,15 +8,19 @@ one launch of the hot path: every replica advances by 11 trials (10 learning
 episodes + 1 greedy test episode = 1100 env-steps).  Replica state, weight tables
 and RNG streams are resident in HBM before the timed region starts.
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.  EVERY workload (= every configuration of BASELINE.json) runs on any number of
-ranks: replicas shard across ranks with no data-path collective (weak scaling, a fixed number of replicas per GPU,
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps of the chosen workload and prints its line;
+--full adds everything else the line can hold: the CPU baselines (cpu_baseline) and, for the headline workload, every other
+configuration of BASELINE.json (secondary).  --dump-outputs DIR writes, after the timed steps, what the timed path computed in its
+last step as DIR/<name>.npy (float64; a fixed, seeded sample where the output is large; rank 0's replicas on N ranks).
+
+EVERY workload (= every configuration of BASELINE.json) runs on any number of ranks: replicas shard across ranks with no data-path collective (weak scaling, a fixed number of replicas per GPU,
 grl_amd.parallel.partition); the only collective of a workload is the final RCCL all-reduce of its learning-curve
 statistics [rows][3], inside the timed region.
 
-  --workload pendulum_sarsa (default)   the headline line; the other workloads follow under "secondary", each sharded
+  --workload pendulum_sarsa (default)   the headline line; with --full the other workloads follow under "secondary", each sharded
                                         and timed the same way on the same ranks (--no-secondary / --no-fqi skip them)
   --workload cart_pole_ac               BASELINE configs[2]: 16384 replicas per GPU
   --workload acrobot_walker             BASELINE configs[3]: 8192 rollouts per GPU = 4096 acrobot + 4096 compass walker,
@@ -272,7 +276,7 @@ class Dist:
         torch.cuda.synchronize()
 
 
-def run_rollout_workload(name, D, torch, steps, warmup, replicas=None, table_log2=None, cpu_baseline=True, full_cpu_baseline=False):
+def run_rollout_workload(name, D, torch, steps, warmup, replicas=None, table_log2=None, cpu_baseline=True, full_cpu_baseline=False, dump=None):
     """One workload on all ranks: `warmup` untimed launches, then EXACTLY `steps` timed launches of every context this rank
     owns, bracketed by barrier + synchronize, with the workload's one collective (all-reduce of the curve statistics) inside
     the timed region; MAX of the elapsed time over ranks.  HIP events per launch on the stream each kernel is launched on.
@@ -351,6 +355,8 @@ def run_rollout_workload(name, D, torch, steps, warmup, replicas=None, table_log
         c["env_server"] = c["runner"].env_server_counts()       # (replicas served to the end of the last launch, replicas that fell back)
     all_learn, all_test = parallel.sum_over_ranks([learn, test], D.world, device="cuda")
     curve_host = curve.cpu().numpy()
+    if dump is not None:
+        dump_rollout_outputs(dump, ctx, curve_host)
     for c in ctx:
         c["runner"].close()                                     # frees this workload's tables before the next one allocates
     if D.rank != 0:
@@ -429,7 +435,47 @@ def run_rollout_workload(name, D, torch, steps, warmup, replicas=None, table_log
     return out
 
 
-def run_fqi(D, torch, cpu_baseline=True, replicas=None, batch_size=None, epochs=None):
+DUMP_SAMPLE_REPLICAS = 64                 # --dump-outputs: weights of this many replicas (a seeded sample) ...
+DUMP_SAMPLE_SLOTS = 4000                  # ... at this many seeded slots of each table
+
+
+def dump_rollout_outputs(dump, ctx, curve_host):
+    """What a caller of the timed rollout path receives after its last step, per context (prefix = experiment graph): the
+    all-reduced curve statistics, every replica's last row (test return, steps), environment state and step-budget counters,
+    and the weights of a seeded sample of replicas at seeded slots of every table."""
+    import numpy as np
+    from grl_amd import capi
+    dump["curve"] = curve_host
+    for c in ctx:
+        r, n, p = c["runner"], len(c["seeds"]), c["graph"] + "_"
+        last = [r.rows(k, r.replica_rows(k) - 1, 1) for k in range(n)]
+        dump[p + "last_row_return"] = np.array([x[2][0] for x in last], np.float64)
+        dump[p + "last_row_steps"] = np.array([x[1][0] for x in last], np.float64)
+        dump[p + "rows_per_replica"] = np.array([r.replica_rows(k) for k in range(n)], np.float64)
+        dump[p + "env_state"] = np.array([r.env_state(k) for k in range(n)], np.float64)
+        dump[p + "step_counts"] = np.array(r.step_counts(), np.float64)
+        rng = np.random.default_rng(5)
+        sample = np.sort(rng.choice(n, min(n, DUMP_SAMPLE_REPLICAS), replace=False))
+        dump[p + "weight_sample_replicas"] = sample.astype(np.float64)
+        for t, proj in enumerate([r.cfg.projector] + ([r.cfg.actor_projector] if r.cfg.agent == capi.AGENT_AC else [])):
+            slots = rng.integers(0, proj.memory, DUMP_SAMPLE_SLOTS).astype(np.uint32)
+            dump[p + f"weight_sample_slots_{t}"] = slots.astype(np.float64)
+            dump[p + f"weights_{t}"] = np.array([r.weights(int(k), slots, t) for k in sample], np.float64)
+
+
+def write_dump(dump, d):
+    """DIR/<name>.npy, float64, at most 64 MB in all."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in dump.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit 64 MB)")
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+
+
+def run_fqi(D, torch, cpu_baseline=True, replicas=None, batch_size=None, epochs=None, dump=None):
     """The batch path on all ranks: replicas only -- rank g runs the independent-seed experiments
     g*R .. (g+1)*R - 1; the one collective is the all-reduce of the per-batch test-return statistics [batches][3]."""
     import numpy as np
@@ -460,6 +506,12 @@ def run_fqi(D, torch, cpu_baseline=True, replicas=None, batch_size=None, epochs=
     D.barrier(torch)
     elapsed = parallel.max_over_ranks(time.perf_counter() - t0, D.world, device="cuda")
     its = [r.info(k)["iterations"] for k in range(R)]
+    if dump is not None:
+        # per replica: the test return of each batch, the network's parameters after the timed batch, its iterations and last error
+        dump["fqi_returns"] = returns
+        dump["fqi_params"] = np.array([r.params(k) for k in range(R)], np.float64)
+        dump["fqi_iterations"] = np.array(its, np.float64)
+        dump["fqi_error"] = np.array([r.info(k)["error"] for k in range(R)], np.float64)
     r.close()
     sample_epochs_rank = sum(its) * ep * 2 * n
     sample_epochs, = parallel.sum_over_ranks([sample_epochs_rank], D.world, device="cuda")
@@ -514,6 +566,10 @@ def main():
     ap.add_argument("--table-log2", type=int, default=0)
     ap.add_argument("--replicas-per-wave", type=int, default=0, help="experiments: force the wave layout of the chosen workload (grlx_config.replicas_per_wave)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse on one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the CPU baselines and, for the default workload, the other BASELINE.json configurations")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float64)")
     args = ap.parse_args()
     if args.replicas_per_wave:
         WORKLOADS[args.only or args.workload]["replicas_per_wave"] = args.replicas_per_wave
@@ -532,18 +588,21 @@ def main():
 
     torch.cuda.set_device(D.local_rank % max(torch.cuda.device_count(), 1))
     parallel.init_distributed(args.backend)
-    cpu = not args.no_cpu_baseline and D.world == 1              # cpu_baseline: rank 0 at N = 1 only
+    cpu = args.full and not args.no_cpu_baseline and D.world == 1    # cpu_baseline: --full, rank 0 at N = 1 only
+    dump = {} if args.dump_outputs else None
 
     if args.workload == FQI["key"]:
-        out = run_fqi(D, torch, cpu, args.replicas or args.fqi_replicas or None, args.fqi_batch_size or None, args.fqi_epochs or None)
+        out = run_fqi(D, torch, cpu, args.replicas or args.fqi_replicas or None, args.fqi_batch_size or None, args.fqi_epochs or None, dump=dump)
         head = FQI["key"]
     else:
         w = WORKLOADS[args.workload]
         steps = args.steps if args.steps is not None else w["steps"]
         warmup = args.warmup if args.warmup is not None else w["warmup"]
         out = run_rollout_workload(args.workload, D, torch, steps, warmup, args.replicas or None, args.table_log2 or None, cpu,
-                                   full_cpu_baseline=args.workload == "pendulum_sarsa")
+                                   full_cpu_baseline=args.workload == "pendulum_sarsa", dump=dump)
         head = args.workload
+    if dump is not None and D.rank == 0:
+        write_dump(dump, args.dump_outputs)
     if D.rank == 0:
         metric = {"pendulum_sarsa": "env-steps/sec (batched rollouts), pendulum SARSA-tc", FQI["key"]: "sample-epochs/sec (batch path), pendulum FQI-ANN"}
         line = {"metric": metric.get(head, "env-steps/sec (batched rollouts), " + head), "value": out["value"], "unit": out["unit"], "n_gpus": D.world,
@@ -559,7 +618,7 @@ def main():
             if out["learn_steps"] != line["learn_steps_expected"]:
                 print(f"bench.py: learning steps counted by the devices ({out['learn_steps']}) differ from 10 episodes x 100 steps per replica and "
                       f"launch ({line['learn_steps_expected']})", file=sys.stderr)
-    if args.workload == "pendulum_sarsa" and not args.no_secondary:
+    if args.full and args.workload == "pendulum_sarsa" and not args.no_secondary:
         # the other configurations BASELINE.json names, each sharded over the same ranks and timed the same way
         sec = []
         for name in SECONDARY_ORDER:

@@ -913,12 +913,44 @@ def test_bench_batch_path_on_two_ranks(grlx):
 
 def test_bench_default_line_with_all_secondaries_on_two_ranks(grlx):
     """What the driver's scaling run launches (no --workload): the headline plus every other configuration, all sharded."""
-    out = _bench_two_ranks(["--steps", "2", "--warmup", "1", "--replicas", "128", "--secondary-replicas", "32", "--fqi-replicas", "1",
+    out = _bench_two_ranks(["--full", "--steps", "2", "--warmup", "1", "--replicas", "128", "--secondary-replicas", "32", "--fqi-replicas", "1",
                             "--fqi-batch-size", "2000", "--fqi-epochs", "20"], timeout=1500)
     assert out["n_gpus"] == 2 and out["metric"].startswith("env-steps/sec")
     names = [s["workload"] for s in out["secondary"]]
     assert names == ["cart_pole_ac", "acrobot_q", "compass_walker_q", "acrobot_walker", "acrobot_walker_x2", "pendulum_fqi_ann"]
     assert all(s["n_gpus"] == 2 and s["value"] > 0 and "roofline" in s for s in out["secondary"])
+
+
+def _bench_one_rank(extra, timeout=600):
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1"] + extra, capture_output=True, text=True, timeout=timeout, cwd=root)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
+    return json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+
+
+def test_bench_plain_line_and_dumped_outputs(grlx, tmp_path):
+    """A plain run times exactly --steps launches, carries no CPU baseline and no secondaries, and --dump-outputs writes the
+    same float64 arrays, bit for bit, for the same arguments in two processes."""
+    args = ["--steps", "2", "--warmup", "1", "--replicas", "64"]
+    a = _bench_one_rank(args + ["--dump-outputs", str(tmp_path / "a")])
+    b = _bench_one_rank(args + ["--dump-outputs", str(tmp_path / "b")])
+    for out in (a, b):
+        assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+        assert "cpu_baseline" not in out and "secondary" not in out
+        assert out["learn_steps_expected"] == 64 * 1000 * 2 and abs(out["learn_steps"] - out["learn_steps_expected"]) < 64 * 1000
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "curve.npy" in names and "pendulum_sarsa_last_row_return.npy" in names
+    total = 0
+    for name in names:
+        x, y = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert x.dtype == np.float64 and x.shape == y.shape, name
+        assert_bit_equal(x.ravel(), y.ravel(), name)
+        total += x.nbytes
+    assert total <= 64 << 20
+    rets = np.load(tmp_path / "a" / "pendulum_sarsa_last_row_return.npy")
+    curve = np.load(tmp_path / "a" / "curve.npy")
+    assert rets.shape == (64,) and curve[0, -1, 2] == 64 and np.isclose(curve[0, -1, 0], rets.sum(), rtol=1e-12, atol=0)
 
 
 # ------------------------------------------------ BASELINE.json full sizes ---

@@ -9,7 +9,7 @@ rc=$?
 echo "tests rc=$rc" | tee -a $OUT/tests.log
 tail -4 $OUT/tests.log
 if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo "tests timed out: no further GPU step"; exit $rc; fi
-timeout -k 10 ${BENCH_TIMEOUT:-600} python bench.py ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 ${BENCH_TIMEOUT:-600} python bench.py --full ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err
 brc=$?
 echo "bench rc=$brc"
 tail -c 1200 $OUT/bench.err

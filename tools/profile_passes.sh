@@ -9,7 +9,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --no-cpu-baseline --no-fqi --no-composite"
+BENCH="python3 $ROOT/bench.py --full --no-cpu-baseline --no-fqi --no-composite"
 FQI="python3 $ROOT/bench.py --no-cpu-baseline --workload pendulum_fqi_ann"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $BENCH > $OUT/bench_under_stats.json 2> $OUT/stats.err
 echo "stats pass done"
