@@ -14,6 +14,8 @@
 //    four entries, grlx_table.h), lazily initialised to the value the reference's
 //    8,388,608-draw initialisation gives that slot (LCG jump-ahead, grlx_rng.h).
 //  * the TD update of a step is applied one pass later, under the next step's loads.
+//  * what a trial, a counted step, a tap record and a result row are is the same in every four-replica
+//    kernel: grlx_frame.h (included after grlx_update.h, before the first rollout header).
 //  * sums over the 16 tilings are taken in the reference's serial order
 //    (linear.cpp:147-151) through a 4-way interleaved LDS tile, so Q-values are
 //    bit-identical to a scalar run.
@@ -42,6 +44,7 @@ namespace grlx {
 } // namespace grlx
 
 #include "grlx_update.h"
+#include "grlx_frame.h"
 #include "grlx_env_server.h"
 #include "grlx_env_server_wide.h"
 #include "grlx_rollout.h"
@@ -622,19 +625,8 @@ __global__ void get_weights_kernel(DevParams P, int table, int replica, const ui
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const Table tab = table_of(P, table, replica);
-  uint32_t slot = slots[i];
-  uint32_t b = table_home(tab, slot);
-  double v = initial_weight(P.states[replica], table, table == 1 ? P.lin_actor : P.lin, slot);
-  for (int it = 0; it < kMaxProbe; ++it)
-  {
-    const BucketRegs br = bucket_load(tab, b);
-    uint32_t empty;
-    const int way = bucket_find(br.k, slot, empty);
-    if (way >= 0) { v = (way == 0) ? br.v[0] : (way == 1) ? br.v[1] : (way == 2) ? br.v[2] : br.v[3]; break; }
-    if (empty != 0u) break;
-    b = (b + 1u) & tab.bmask;
-  }
-  out[i] = v;
+  uint32_t slot = slots[i], pos;
+  out[i] = table_peek(tab, slot, pos) ? value_load(tab, pos) : initial_weight(P.states[replica], table, table == 1 ? P.lin_actor : P.lin, slot);
 }
 
 // {action: load}: replicas [first, first+count) take `image` as the initial value of every slot of
@@ -663,20 +655,8 @@ __global__ void export_weights_kernel(DevParams P, int table, int replica, doubl
   const uint32_t memory = (uint32_t)(table == 1 ? P.tile_actor.memory : P.tile.memory);
   for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < memory; slot += gridDim.x * blockDim.x)
   {
-    uint32_t b = table_home(tab, slot);
-    double v = 0;
-    bool found = false;
-    for (int it = 0; it < kMaxProbe; ++it)
-    {
-      const BucketRegs br = bucket_load(tab, b);
-      uint32_t empty;
-      const int way = bucket_find(br.k, slot, empty);
-      if (way >= 0) { v = (way == 0) ? br.v[0] : (way == 1) ? br.v[1] : (way == 2) ? br.v[2] : br.v[3]; found = true; break; }
-      if (empty != 0u) break;
-      b = (b + 1u) & tab.bmask;
-    }
-    if (!found) v = initial_weight(P.states[replica], table, lp, slot);
-    out[slot] = v;
+    uint32_t pos;
+    out[slot] = table_peek(tab, slot, pos) ? value_load(tab, pos) : initial_weight(P.states[replica], table, lp, slot);
   }
 }
 

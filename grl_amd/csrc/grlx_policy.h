@@ -39,6 +39,25 @@ __device__ __forceinline__ int tie_break(const double (&v)[NA], double best, int
   return res;
 }
 
+// QPolicy::act over Q-values whose findmax is (mai, man, best) (q.cpp:143-155, greedy.cpp:63-86, 144-218): greedy with a
+// random tie break in a test trial, else epsilon-greedy -- the decay at episode time 0, the epsilon draw from the sampler's
+// stream S1, then the global stream G for the random action or the tie break.  N: epsilon, decay_rate, decay_min.
+template <int NA>
+__device__ __forceinline__ int eps_greedy_act(const DevParams &N, const double (&q)[NA], int mai, int man, double best, int test, double time,
+                                              double &eps_decay, uint64_t &S1, uint64_t &G)
+{
+  if (test) return (man > 1) ? tie_break<NA>(q, best, man, G) : mai;
+  if (time == 0.) eps_decay = fmax(eps_decay * N.decay_rate, N.decay_min);
+  S1 = lcg_next(S1);
+  const double rnd = lcg_double(S1);
+  if (rnd < eps_decay * N.epsilon)
+  {
+    G = lcg_next(G);
+    return (int)(lcg_long(G) % (uint32_t)NA);
+  }
+  return (man > 1) ? tie_break<NA>(q, best, man, G) : mai;
+}
+
 __device__ __forceinline__ double   in_reg(double v)   { asm volatile("" : "+v"(v)); return v; }
 __device__ __forceinline__ uint32_t in_reg(uint32_t v) { asm volatile("" : "+v"(v)); return v; }
 __device__ __forceinline__ bool     in_reg(bool v)     { uint32_t t = v ? 1u : 0u; asm volatile("" : "+v"(t)); return t != 0u; }

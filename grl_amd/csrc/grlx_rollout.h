@@ -219,7 +219,10 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials)
   __shared__ uint64_t sh_jump[2048];           // LCG jump table (lazy weight initialisation)
   jump_table_to_lds(sh_jump);
 
-  const int lane = threadIdx.x & 63;
+  // The experiment frame (grlx_frame.h) is written out in this body: a call to any of its helpers, though inlined, changes the
+  // register allocation of the timed instantiations, which must stay identical code (tools/kernel_isa_diff.py).  A change to
+  // the frame is made here too; each block names the helper it mirrors.
+  const int lane = threadIdx.x & 63;                        // wave_ids
   const int g = lane >> 4, j = lane & 15;
   const int r_raw = blockIdx.x * kReplicasPerWave + g;
   const bool live = r_raw < P.n_replicas;
@@ -228,7 +231,7 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials)
   const unsigned long long gmask = 0xFFFFull << (16 * g);
 
   ReplicaState &RS = P.states[r];
-  double x[S];
+  double x[S];                                              // run_load
 #pragma unroll
   for (int i = 0; i < S; ++i) x[i] = RS.x[i];
   uint64_t G = RS.G, TL = RS.TL, S1 = RS.S1;
@@ -252,7 +255,7 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials)
   up.use_trace = N.trace_kind == GRLX_TRACE_REPLACING;
   up.dW = up.dT = 0;
 
-  double acts[NA];
+  double acts[NA];                                          // action_keys
 #pragma unroll
   for (int a = 0; a < NA; ++a) acts[a] = N.actions[a];
   // The action coordinate of tiling j and the tiling index itself do not change: their murmur
@@ -302,7 +305,7 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials)
 
   for (int trial = 0; trial < n_trials; ++trial)
   {
-    // online_learning.cpp:154: a replica whose learning steps have reached the steps budget starts no further trial
+    // trial_plan -- online_learning.cpp:154: a replica whose learning steps have reached the steps budget starts no further trial
     const bool act = live && !(P.steps_budget != 0u && (uint64_t)ss >= P.steps_budget);
     if (!__any(act)) break;
     const int ti = N.test_interval;
@@ -395,7 +398,7 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials)
         // -------- policy: Q(s', .) for all actions (q.cpp:94-107): projections
         if (has_next)
         {
-          uint32_t hpre = 449u ^ (uint32_t)(D + 2);
+          uint32_t hpre = 449u ^ (uint32_t)(D + 2);                          // tile_slots_obs_actions
 #pragma unroll
           for (int i = 0; i < D; ++i)
             hpre = murmur_mix(hpre, tile_coord<T>(N.tile, i, tile_quant(N.tile, i, obs[i]), j));
@@ -531,7 +534,7 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials)
           sh_fbflag[j * 4 + g] = 0u;
         }
         wave_sync();
-        // LinearRepresentation::read (linear.cpp:136-184): serial sum over the 16 tilings, mean, clamp.
+        // sum_rows -- LinearRepresentation::read (linear.cpp:136-184): serial sum over the 16 tilings, mean, clamp.
         // Lane r of the replica sums row r (Q(s',a_r) for r < NA, Q(s,a) for r = NA) in the reference's
         // order; the NA+1 results are shared through LDS (lanes beyond NA repeat row 0, harmlessly).
         {
@@ -571,7 +574,7 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials)
         if (has_next)
         {
           findmax<NA>(q, mai, man, best);
-          if (test)
+          if (test)                                                          // eps_greedy_act
           {
             a_next = (man > 1) ? tie_break<NA>(q, best, man, G) : mai;
           }
@@ -688,7 +691,7 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials)
             tp->p_idx[j] = update ? p_slot : 0u;
             tp->p_idx[16 + j] = 0u;
             if (j == 0)
-            {
+            { // tap_common
               tp->test = test;
               tp->action_index = has_next ? a_next : action_index;
               tp->terminal = first ? -1 : terminal;
@@ -707,7 +710,7 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials)
           if (j == 0) *P.tap_count = n + 1u;
         }
 
-        // -------- bookkeeping
+        // -------- bookkeeping (count_step)
         if (!first)
         {
           if (test) test_steps++;
@@ -739,7 +742,7 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials)
     if (!test) trace_flush(tr, tab, true);
     }   // episodes of the trial
 
-    // row of a test trial (online_learning.cpp:238-262) -- or of every trial when test_interval < 0
+    // record_row: row of a test trial (online_learning.cpp:238-262) -- or of every trial when test_interval < 0
     if (act && (ti >= 0 ? test : 1))
     {
       if (rows < (uint32_t)P.max_rows)
@@ -784,7 +787,7 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials)
     }
   }
 
-  // write the replica back
+  // write the replica back (run_store)
   uint32_t ins = inserted;
 #pragma unroll
   for (int off = 8; off > 0; off >>= 1) ins += __shfl_xor(ins, off, 16);
@@ -802,7 +805,7 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials)
     RS.n_slots[0] += ins;
     RS.rows = rows;
   }
-  // status may differ per lane (a probe failure is lane-local): OR over the replica
+  // store_status: status may differ per lane (a probe failure is lane-local): OR over the replica
   uint32_t st = status;
 #pragma unroll
   for (int off = 8; off > 0; off >>= 1) st |= __shfl_xor(st, off, 16);

@@ -79,37 +79,21 @@ __global__ __launch_bounds__(64) void rollout_acc_kernel(DevParams P, int n_tria
   __shared__ double   sh_tv[kAccTrace * 64];         // cached weight per trace entry and lane
   jump_table_to_lds(sh_jump);
 
-  const int lane = threadIdx.x & 63;
-  const int g = lane >> 4, j = lane & 15;
-  const int r_raw = blockIdx.x * kReplicasPerWave + g;
-  const bool live = r_raw < P.n_replicas;
-  const int r = live ? r_raw : 0;
-  const bool tapped = live && (r == P.tap_replica);
-  const unsigned long long gmask = 0xFFFFull << (16 * g);
+  const WaveIds ids = wave_ids(P);
+  const int lane = ids.lane, g = ids.g, j = ids.j;
+  ReplicaState &RS = P.states[ids.r];
+  RunRegs<S> run;
+  run_load<S>(RS, run);
+  uint32_t inserted = 0;
 
-  ReplicaState &RS = P.states[r];
-  double x[S];
-#pragma unroll
-  for (int i = 0; i < S; ++i) x[i] = RS.x[i];
-  uint64_t G = RS.G, TL = RS.TL, S1 = RS.S1;
-  double eps_decay = RS.eps_decay;
-  int64_t tt = RS.tt, ss = RS.ss;
-  uint64_t test_steps = RS.test_steps;
-  uint32_t status = RS.status, rows = RS.rows, inserted = 0;
-
-  const Table tab = table_of(P, 0, r);
+  const Table tab = table_of(P, 0, ids.r);
   const double out_min = N.lin.out_min, out_max = N.lin.out_max;
   const bool limit = N.lin.limit != 0;
   const double ee = N.gl, cut = 0.0001;
 
   double acts[NA];
-#pragma unroll
-  for (int a = 0; a < NA; ++a) acts[a] = N.actions[a];
-  uint32_t key_act[NA];
-#pragma unroll
-  for (int a = 0; a < NA; ++a)
-    key_act[a] = in_reg(murmur_key(tile_coord<T>(N.tile, D, tile_quant(N.tile, D, N.actions[a]), j)));
-  const uint32_t key_j = in_reg(murmur_key(j));
+  uint32_t key_act[NA], key_j;
+  action_keys<T, D, NA>(N.tile, N.actions, j, acts, key_act, key_j);
 
   // the trace of this lane's tiling: positions newest first, bit e of tsh = entry e is a slot shared between tilings
   uint32_t tpos[kAccTrace];
@@ -130,33 +114,27 @@ __global__ __launch_bounds__(64) void rollout_acc_kernel(DevParams P, int n_tria
 
   for (int trial = 0; trial < n_trials; ++trial)
   {
-    // online_learning.cpp:154: a replica whose learning steps have reached the steps budget starts no further trial
-    const bool act = live && !(P.steps_budget != 0u && (uint64_t)ss >= P.steps_budget);
-    if (!__any(act)) break;
-    const int ti = N.test_interval;
-    const int test = (ti >= 0 && tt % (ti + 1) == ti) ? 1 : 0;
-    // a test trial is test_trials greedy episodes (online_learning.cpp:161-170): each starts the environment and the agent anew, while
-    // reward and time keep adding up (:202-203); a learning trial is one episode (its `time` = 0 is the sampler's moment to decay)
-    double total_reward = 0, time = 0;
-    const int subtrials = (test && P.test_trials > 1) ? P.test_trials : 1;
+    const TrialPlan plan = trial_plan(P, N, ids, run.ss, run.tt);
+    if (!__any(plan.act)) break;
+    double total_reward = 0, time = 0;      // of the whole trial; a learning episode's `time` = 0 is the sampler's moment to decay
     for (int st = 0; st < P.test_trials; ++st)
     {
-    const bool episode = act && st < subtrials;
+    const bool episode = plan.act && st < plan.subtrials;
     if (!__any(episode)) break;
     double obs[D], reward = 0;
     int terminal = 0;
     bool running = episode;
     if (episode)
     {
-      Env<ENV>::start(N, test, TL, G, x);
-      Env<ENV>::observe(N, x, obs);
+      Env<ENV>::start(N, plan.test, run.TL, run.G, run.x);
+      Env<ENV>::observe(N, run.x, obs);
     }
     double action = 0;
     int action_index = 0;
     uint32_t p_pos = kInvalidPos, p_slot = 0;
     bool p_sh = false;
     double wp_seen = 0;                                     // weight of p's slot as looked up (and forwarded) one pass ago
-    if (!test)
+    if (!plan.test)
     { // TDAgent::start -> predictor->finalize() -> trace_->clear() (td.cpp:54, sarsa.cpp:126-132); it is empty already
       // (flushed and cleared at the end of the previous learning trial)
 #pragma unroll
@@ -172,37 +150,23 @@ __global__ __launch_bounds__(64) void rollout_acc_kernel(DevParams P, int n_tria
       {
         if (!first)
         {
-          env_step<ENV>(N, x, action, obs, reward, terminal, status);
+          env_step<ENV>(N, run.x, action, obs, reward, terminal, run.status);
           total_reward += reward;
           time += 1;
         }
         const bool has_next = first || terminal != 2;
-        const bool update = !first && !test;
+        const bool update = !first && !plan.test;
 
         uint32_t slot[NA], pos[NA];
         double w[NA];
         bool sh[NA];
 #pragma unroll
         for (int a = 0; a < NA; ++a) { slot[a] = 0; pos[a] = kInvalidPos; w[a] = 0; sh[a] = false; }
-        if (has_next)
-        {
-          uint32_t hpre = 449u ^ (uint32_t)(D + 2);
-#pragma unroll
-          for (int i = 0; i < D; ++i)
-            hpre = murmur_mix(hpre, tile_coord<T>(N.tile, i, tile_quant(N.tile, i, obs[i]), j));
-          const uint32_t hpm = hpre * 0x5bd1e995u;
-#pragma unroll
-          for (int a = 0; a < NA; ++a)
-          {
-            uint32_t h = murmur_absorb(hpm ^ key_act[a], key_j);
-            const uint32_t hm = murmur_final(h), mem = (uint32_t)N.tile.memory;
-            slot[a] = ((mem & (mem - 1u)) == 0u) ? (hm & (mem - 1u)) : (hm % mem);
-          }
-        }
+        if (has_next) tile_slots_obs_actions<T, D, NA>(N.tile, obs, key_act, key_j, j, slot);
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         bool shared_event = false;
         if (has_next)
-          table_get<NA>(tab, N.lin, RS, 0, slot, pos, w, sh, g, j, gmask, sh_mb, sh_ms, sh_mail, sh_jump, status, inserted,
+          table_get<NA>(tab, N.lin, RS, 0, slot, pos, w, sh, g, j, ids.gmask, sh_mb, sh_ms, sh_mail, sh_jump, run.status, inserted,
                         [&](uint32_t mp) { // a slot became shared: its cached value goes to the table (the finder reads it), and
                           // every entry that refers to it is updated serially, on the table, from now on
                           if (p_pos == mp) p_sh = true;
@@ -242,13 +206,7 @@ __global__ __launch_bounds__(64) void rollout_acc_kernel(DevParams P, int n_tria
         for (int a = 0; a < NA; ++a) SHW(a, j, g) = w[a];
         SHW(NA, j, g) = wp;
         wave_sync();
-        {
-          const int row = (j <= NA) ? j : 0;
-          double sum = 0;
-#pragma unroll
-          for (int k = 0; k < 16; ++k) sum += SHW(row, k, g);
-          sh_res[g * 16 + j] = sum / 16;
-        }
+        sum_rows<NA + 1>(sh_w, sh_res, g, j);
         wave_sync();
         double q[NA];
 #pragma unroll
@@ -261,21 +219,7 @@ __global__ __launch_bounds__(64) void rollout_acc_kernel(DevParams P, int n_tria
         if (has_next)
         {
           findmax<NA>(q, mai, man, best);
-          if (test)
-            a_next = (man > 1) ? tie_break<NA>(q, best, man, G) : mai;
-          else
-          {
-            if (time == 0.) eps_decay = fmax(eps_decay * N.decay_rate, N.decay_min);
-            S1 = lcg_next(S1);
-            const double rnd = lcg_double(S1);
-            if (rnd < eps_decay * N.epsilon)
-            {
-              G = lcg_next(G);
-              a_next = (int)(lcg_long(G) % (uint32_t)NA);
-            }
-            else
-              a_next = (man > 1) ? tie_break<NA>(q, best, man, G) : mai;
-          }
+          a_next = eps_greedy_act<NA>(N, q, mai, man, best, plan.test, time, run.eps_decay, run.S1, run.G);
         }
 
         // -------- predictor update (sarsa.cpp:98-124, 167-194 / advantage.cpp:71-110)
@@ -289,7 +233,7 @@ __global__ __launch_bounds__(64) void rollout_acc_kernel(DevParams P, int n_tria
               target += N.gamma * pick<double, NA>(q, a_next);
             else if (SPEC::agent(P) == GRLX_AGENT_EXPECTED_SARSA)
             {
-              const double de = eps_decay * N.epsilon;
+              const double de = run.eps_decay * N.epsilon;
               double v = 0;
 #pragma unroll
               for (int kk = 0; kk < NA; ++kk)
@@ -370,7 +314,7 @@ __global__ __launch_bounds__(64) void rollout_acc_kernel(DevParams P, int n_tria
           // far end (or all of them, when the decay is below the cut) are written back
           const int old_len = (ee < cut) ? 0 : tlen;                 // entries that survive the `ee < cut` reset
           if (ee < cut) ttotal = 1.;
-          if (old_len >= kAccTrace) status |= ST_TRACE_OVERFLOW;       // cannot happen: validated at create
+          if (old_len >= kAccTrace) run.status |= ST_TRACE_OVERFLOW;       // cannot happen: validated at create
           int new_len = (old_len < kAccTrace) ? old_len + 1 : kAccTrace;
           ttotal *= ee;
           while (ttotal < cut && new_len > 1)
@@ -408,7 +352,7 @@ __global__ __launch_bounds__(64) void rollout_acc_kernel(DevParams P, int n_tria
         }
 
         // -------- tap
-        if (tapped && (!first || P.tap_starts))
+        if (ids.tapped && (!first || P.tap_starts))
         {
           uint32_t n = *P.tap_count;
           if (n < (uint32_t)P.tap_capacity)
@@ -418,29 +362,17 @@ __global__ __launch_bounds__(64) void rollout_acc_kernel(DevParams P, int n_tria
             tp->p_idx[16 + j] = 0u;
             if (j == 0)
             {
-              tp->test = test;
-              tp->action_index = has_next ? a_next : action_index;
-              tp->terminal = first ? -1 : terminal;
+              tap_common<NA, S, D>(tp, plan.test, has_next ? a_next : action_index, first ? -1 : terminal, obs,
+                                   has_next ? pick<double, NA>(acts, a_next) : action, reward, run.x, q, has_next);
               tp->trace_len = tr_len_ref;
-              for (int i = 0; i < GRLX_MAX_DIMS; ++i) tp->obs[i] = (i < D) ? obs[i] : 0.;
-              tp->action = has_next ? pick<double, NA>(acts, a_next) : action;
-              tp->reward = reward;
-              for (int i = 0; i < GRLX_MAX_STATE; ++i) tp->state[i] = (i < S) ? x[i] : 0.;
               tp->delta = delta;
-              for (int a = 0; a < kMaxActions; ++a) tp->q[a] = 0.;
-#pragma unroll
-              for (int a = 0; a < NA; ++a) tp->q[a] = has_next ? q[a] : 0.;
             }
           }
           wave_sync();
           if (j == 0) *P.tap_count = n + 1u;
         }
 
-        if (!first)
-        {
-          if (test) test_steps++;
-          else ss++;
-        }
+        count_step(run.ss, run.test_steps, plan.test, first);
         if (has_next)
         {
           action_index = a_next;
@@ -455,7 +387,7 @@ __global__ __launch_bounds__(64) void rollout_acc_kernel(DevParams P, int n_tria
       }
     }
 
-    if (!test)
+    if (!plan.test)
     { // end of a learning trial: the cached weights go to the table, the trace is emptied (the next TDAgent::start would)
       const uint32_t heads = mine_mask() & ~tnh;
 #pragma unroll
@@ -469,47 +401,12 @@ __global__ __launch_bounds__(64) void rollout_acc_kernel(DevParams P, int n_tria
 
     }   // episodes of the trial
 
-    if (act && (ti >= 0 ? test : 1))
-    {
-      if (rows < (uint32_t)P.max_rows)
-      {
-        if (j == 0)
-        {
-          size_t at = (size_t)rows * (size_t)P.n_replicas + (size_t)r;
-          P.row_reward[at] = total_reward / (double)subtrials;              // online_learning.cpp:224-225
-          P.row_time[at] = time / (double)subtrials;
-          P.row_steps[at] = ss;
-          P.row_trial[at] = (ti >= 0) ? (tt + 1 - (tt + 1) / (ti + 1)) : tt;
-        }
-        rows++;
-      }
-      else
-        status |= ST_ROWS_FULL;
-    }
-    tt += act ? 1 : 0;
+    record_row(P, ids, plan, run.rows, run.status, run.ss, run.tt, total_reward, time);
+    run.tt += plan.act ? 1 : 0;
   }
 
-  uint32_t ins = inserted;
-#pragma unroll
-  for (int off = 8; off > 0; off >>= 1) ins += __shfl_xor(ins, off, 16);
-  if (live && j == 0)
-  {
-#pragma unroll
-    for (int i = 0; i < S; ++i) RS.x[i] = x[i];
-    RS.G = G;
-    RS.TL = TL;
-    RS.S1 = S1;
-    RS.eps_decay = eps_decay;
-    RS.tt = tt;
-    RS.ss = ss;
-    RS.test_steps = test_steps;
-    RS.n_slots[0] += ins;
-    RS.rows = rows;
-  }
-  uint32_t st = status;
-#pragma unroll
-  for (int off = 8; off > 0; off >>= 1) st |= __shfl_xor(st, off, 16);
-  if (live && j == 0) RS.status = st;
+  run_store<S>(RS, ids, run, inserted);
+  store_status(RS, ids, run.status);
 }
 
 hipError_t launch_rollout_acc(const DevParams &P, int n_trials, hipStream_t stream, int *variant)

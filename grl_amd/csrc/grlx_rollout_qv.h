@@ -26,15 +26,12 @@ __global__ __launch_bounds__(64) void rollout_qv_kernel(DevParams P, int n_trial
   __shared__ uint64_t sh_jump[2048];
   jump_table_to_lds(sh_jump);
 
-  const int lane = threadIdx.x & 63;
-  const int g = lane >> 4, j = lane & 15;
-  const int r_raw = blockIdx.x * kReplicasPerWave + g;
-  const bool live = r_raw < P.n_replicas;
-  const int r = live ? r_raw : 0;
-  const bool tapped = live && (r == P.tap_replica);
-  const unsigned long long gmask = 0xFFFFull << (16 * g);
+  const WaveIds ids = wave_ids(P);
+  const int g = ids.g, j = ids.j;
 
-  ReplicaState &RS = P.states[r];
+  // (run_load / run_store, tile_slots_obs_actions and tap_common are written out in this kernel: with any of them it needs 8-14
+  //  registers more)
+  ReplicaState &RS = P.states[ids.r];
   double x[S];
 #pragma unroll
   for (int i = 0; i < S; ++i) x[i] = RS.x[i];
@@ -44,7 +41,7 @@ __global__ __launch_bounds__(64) void rollout_qv_kernel(DevParams P, int n_trial
   uint64_t test_steps = RS.test_steps;
   uint32_t status = RS.status, rows = RS.rows, ins_q = 0, ins_v = 0;
 
-  const Table tabQ = table_of(P, 0, r), tabV = table_of(P, 1, r);
+  const Table tabQ = table_of(P, 0, ids.r), tabV = table_of(P, 1, ids.r);
   UpdateParams up;                                  // the V table's update (the one with the trace)
   up.out_min = P.lin_actor.out_min;
   up.out_max = P.lin_actor.out_max;
@@ -57,13 +54,8 @@ __global__ __launch_bounds__(64) void rollout_qv_kernel(DevParams P, int n_trial
   const bool q_limit = P.lin.limit != 0;
 
   double acts[NA];
-#pragma unroll
-  for (int a = 0; a < NA; ++a) acts[a] = P.actions[a];
-  uint32_t key_act[NA];
-#pragma unroll
-  for (int a = 0; a < NA; ++a)
-    key_act[a] = in_reg(murmur_key(tile_coord<T>(P.tile, D, tile_quant(P.tile, D, P.actions[a]), j)));
-  const uint32_t key_j = in_reg(murmur_key(j));
+  uint32_t key_act[NA], key_j;
+  action_keys<T, D, NA>(P.tile, P.actions, j, acts, key_act, key_j);
 
   TraceRegs tr;
   trace_init(tr);
@@ -71,32 +63,26 @@ __global__ __launch_bounds__(64) void rollout_qv_kernel(DevParams P, int n_trial
 
   for (int trial = 0; trial < n_trials; ++trial)
   {
-    // online_learning.cpp:154: a replica whose learning steps have reached the steps budget starts no further trial
-    const bool act = live && !(P.steps_budget != 0u && (uint64_t)ss >= P.steps_budget);
-    if (!__any(act)) break;
-    const int ti = P.test_interval;
-    const int test = (ti >= 0 && tt % (ti + 1) == ti) ? 1 : 0;
-    // a test trial is test_trials greedy episodes (online_learning.cpp:161-170): each starts the environment and the agent anew, while
-    // reward and time keep adding up (:202-203); a learning trial is one episode (its `time` = 0 is the sampler's moment to decay)
-    double total_reward = 0, time = 0;
-    const int subtrials = (test && P.test_trials > 1) ? P.test_trials : 1;
+    const TrialPlan plan = trial_plan(P, P, ids, ss, tt);
+    if (!__any(plan.act)) break;
+    double total_reward = 0, time = 0;      // of the whole trial; a learning episode's `time` = 0 is the sampler's moment to decay
     for (int st = 0; st < P.test_trials; ++st)
     {
-    const bool episode = act && st < subtrials;
+    const bool episode = plan.act && st < plan.subtrials;
     if (!__any(episode)) break;
     double obs[D], reward = 0;
     int terminal = 0;
     bool running = episode;
     if (episode)
     {
-      Env<ENV>::start(P, test, TL, G, x);
+      Env<ENV>::start(P, plan.test, TL, G, x);
       Env<ENV>::observe(P, x, obs);
     }
     double action = 0;
     int action_index = 0;
     uint32_t qp_pos = kInvalidPos, qp_slot = 0, vp_pos = kInvalidPos, vp_slot = 0;
     bool qp_sh = false, vp_sh = false;
-    if (!test) tr_len_ref = 0;          // TDAgent::start -> QVPredictor::finalize -> trace_->clear()
+    if (!plan.test) tr_len_ref = 0;          // TDAgent::start -> QVPredictor::finalize -> trace_->clear()
     bool first = true;
 
     for (;;)
@@ -111,7 +97,7 @@ __global__ __launch_bounds__(64) void rollout_qv_kernel(DevParams P, int n_trial
           time += 1;
         }
         const bool has_next = first || terminal != 2;
-        const bool update = !first && !test;
+        const bool update = !first && !plan.test;
 
         // projections of (s', a_k) for the policy and of s' for V (the latter also in test trials: unused there)
         uint32_t slotQ[NA], posQ[NA], slotV[1] = {0}, posV[1] = {kInvalidPos};
@@ -119,7 +105,7 @@ __global__ __launch_bounds__(64) void rollout_qv_kernel(DevParams P, int n_trial
         bool shQ[NA], shV[1] = {false};
 #pragma unroll
         for (int a = 0; a < NA; ++a) { slotQ[a] = 0; posQ[a] = kInvalidPos; wQ[a] = 0; shQ[a] = false; }
-        const bool need_v = has_next && !test;
+        const bool need_v = has_next && !plan.test;
         if (has_next)
         {
           uint32_t hpre = 449u ^ (uint32_t)(D + 2);
@@ -148,12 +134,12 @@ __global__ __launch_bounds__(64) void rollout_qv_kernel(DevParams P, int n_trial
         if (has_next) table_issue<NA>(tabQ, slotQ, lkQ, brQ);
         if (need_v) table_issue<1>(tabV, slotV, lkV, brV);
         if (has_next)
-          table_get_finish<NA>(tabQ, P.lin, RS, 0, slotQ, lkQ, brQ, posQ, wQ, shQ, g, j, gmask, sh_mb, sh_ms, sh_mail, sh_jump, status, ins_q,
+          table_get_finish<NA>(tabQ, P.lin, RS, 0, slotQ, lkQ, brQ, posQ, wQ, shQ, g, j, ids.gmask, sh_mb, sh_ms, sh_mail, sh_jump, status, ins_q,
                                [&](uint32_t mp) { if (qp_pos == mp) qp_sh = true; });
         if (need_v)
         {
           bool shared_event = false;
-          table_get_finish<1>(tabV, P.lin_actor, RS, 1, slotV, lkV, brV, posV, wV, shV, g, j, gmask, sh_mb, sh_ms, sh_mail, sh_jump, status, ins_v,
+          table_get_finish<1>(tabV, P.lin_actor, RS, 1, slotV, lkV, brV, posV, wV, shV, g, j, ids.gmask, sh_mb, sh_ms, sh_mail, sh_jump, status, ins_v,
                               [&](uint32_t mp) {
                                 trace_share_event(tr, tabV, mp);
                                 if (vp_pos == mp) vp_sh = true;
@@ -172,13 +158,7 @@ __global__ __launch_bounds__(64) void rollout_qv_kernel(DevParams P, int n_trial
         sh_qpos[g * 16 + j] = qp_pos;
         sh_fbflag[j * 4 + g] = 0u;
         wave_sync();
-        { // lane r sums row r in the reference's order (linear.cpp:147-151)
-          const int row = (j < NROWS) ? j : 0;
-          double sum = 0;
-#pragma unroll
-          for (int k = 0; k < 16; ++k) sum += SHW(row, k, g);
-          sh_res[g * 16 + j] = sum / 16;
-        }
+        sum_rows<NROWS>(sh_w, sh_res, g, j);
         wave_sync();
         double q[NA];
 #pragma unroll
@@ -194,21 +174,7 @@ __global__ __launch_bounds__(64) void rollout_qv_kernel(DevParams P, int n_trial
           int mai = 0, man = 1;
           double best = 0;
           findmax<NA>(q, mai, man, best);
-          if (test)
-            a_next = (man > 1) ? tie_break<NA>(q, best, man, G) : mai;
-          else
-          {
-            if (time == 0.) eps_decay = fmax(eps_decay * P.decay_rate, P.decay_min);
-            S1 = lcg_next(S1);
-            const double rnd = lcg_double(S1);
-            if (rnd < eps_decay * P.epsilon)
-            {
-              G = lcg_next(G);
-              a_next = (int)(lcg_long(G) % (uint32_t)NA);
-            }
-            else
-              a_next = (man > 1) ? tie_break<NA>(q, best, man, G) : mai;
-          }
+          a_next = eps_greedy_act<NA>(P, q, mai, man, best, plan.test, time, eps_decay, S1, G);
         }
 
         // -------- predictor (QVPredictor::criticize, qv.cpp:74-108)
@@ -241,7 +207,7 @@ __global__ __launch_bounds__(64) void rollout_qv_kernel(DevParams P, int n_trial
         }
 
         // -------- tap
-        if (tapped && (!first || P.tap_starts))
+        if (ids.tapped && (!first || P.tap_starts))
         {
           uint32_t n = *P.tap_count;
           if (n < (uint32_t)P.tap_capacity)
@@ -251,7 +217,7 @@ __global__ __launch_bounds__(64) void rollout_qv_kernel(DevParams P, int n_trial
             tp->p_idx[16 + j] = update ? vp_slot : 0u;
             if (j == 0)
             {
-              tp->test = test;
+              tp->test = plan.test;
               tp->action_index = has_next ? a_next : action_index;
               tp->terminal = first ? -1 : terminal;
               tp->trace_len = tr_len_ref;
@@ -269,11 +235,7 @@ __global__ __launch_bounds__(64) void rollout_qv_kernel(DevParams P, int n_trial
           if (j == 0) *P.tap_count = n + 1u;
         }
 
-        if (!first)
-        {
-          if (test) test_steps++;
-          else ss++;
-        }
+        count_step(ss, test_steps, plan.test, first);
         if (has_next)
         {
           action_index = a_next;
@@ -294,34 +256,18 @@ __global__ __launch_bounds__(64) void rollout_qv_kernel(DevParams P, int n_trial
     }
 
     // QVPredictor::finalize clears the trace at the next TDAgent::start (qv.cpp:110-116): write it back now
-    if (!test) trace_flush(tr, tabV, true);
+    if (!plan.test) trace_flush(tr, tabV, true);
 
     }   // episodes of the trial
 
-    if (act && (ti >= 0 ? test : 1))
-    {
-      if (rows < (uint32_t)P.max_rows)
-      {
-        if (j == 0)
-        {
-          size_t at = (size_t)rows * (size_t)P.n_replicas + (size_t)r;
-          P.row_reward[at] = total_reward / (double)subtrials;              // online_learning.cpp:224-225
-          P.row_time[at] = time / (double)subtrials;
-          P.row_steps[at] = ss;
-          P.row_trial[at] = (ti >= 0) ? (tt + 1 - (tt + 1) / (ti + 1)) : tt;
-        }
-        rows++;
-      }
-      else
-        status |= ST_ROWS_FULL;
-    }
-    tt += act ? 1 : 0;
+    record_row(P, ids, plan, rows, status, ss, tt, total_reward, time);
+    tt += plan.act ? 1 : 0;
   }
 
   uint32_t iq = ins_q, iv = ins_v;
 #pragma unroll
   for (int off = 8; off > 0; off >>= 1) { iq += __shfl_xor(iq, off, 16); iv += __shfl_xor(iv, off, 16); }
-  if (live && j == 0)
+  if (ids.live && j == 0)
   {
 #pragma unroll
     for (int i = 0; i < S; ++i) RS.x[i] = x[i];
@@ -336,10 +282,7 @@ __global__ __launch_bounds__(64) void rollout_qv_kernel(DevParams P, int n_trial
     RS.n_slots[1] += iv;
     RS.rows = rows;
   }
-  uint32_t st = status;
-#pragma unroll
-  for (int off = 8; off > 0; off >>= 1) st |= __shfl_xor(st, off, 16);
-  if (live && j == 0) RS.status = st;
+  store_status(RS, ids, status);
 }
 
 hipError_t launch_rollout_qv(const DevParams &P, int n_trials, hipStream_t stream, int *variant)

@@ -99,41 +99,25 @@ __global__ __launch_bounds__(64) void rollout_tgt_kernel(DevParams P, int n_tria
   __shared__ uint64_t sh_jump[2048];
   jump_table_to_lds(sh_jump);
 
-  const int lane = threadIdx.x & 63;
-  const int g = lane >> 4, j = lane & 15;
-  const int r_raw = blockIdx.x * kReplicasPerWave + g;
-  const bool live = r_raw < P.n_replicas;
-  const int r = live ? r_raw : 0;
-  const bool tapped = live && (r == P.tap_replica);
-  const unsigned long long gmask = 0xFFFFull << (16 * g);
-
-  ReplicaState &RS = P.states[r];
-  double x[S];
-#pragma unroll
-  for (int i = 0; i < S; ++i) x[i] = RS.x[i];
-  uint64_t G = RS.G, TL = RS.TL, S1 = RS.S1;
-  double eps_decay = RS.eps_decay;
-  int64_t tt = RS.tt, ss = RS.ss;
-  uint64_t test_steps = RS.test_steps;
-  uint32_t status = RS.status, rows = RS.rows, inserted = 0;
+  const WaveIds ids = wave_ids(P);
+  const int g = ids.g, j = ids.j;
+  ReplicaState &RS = P.states[ids.r];
+  RunRegs<S> run;
+  run_load<S>(RS, run);
+  uint32_t inserted = 0;
   int64_t sync_count = RS.sync_count;
   uint32_t K = RS.syncs;
 
-  const Table tab = table_of(P, 0, r);
-  double *tv = TARGET ? P.tvals + ((size_t)r << P.logC) : nullptr;
+  const Table tab = table_of(P, 0, ids.r);
+  double *tv = TARGET ? P.tvals + ((size_t)ids.r << P.logC) : nullptr;
   const double out_min = P.lin.out_min, out_max = P.lin.out_max;
   const bool limit = P.lin.limit != 0;
   const bool use_trace = P.trace_kind == GRLX_TRACE_REPLACING;
   const double ee = P.gl, cut = 0.01;
 
   double acts[NA];
-#pragma unroll
-  for (int a = 0; a < NA; ++a) acts[a] = P.actions[a];
-  uint32_t key_act[NA];
-#pragma unroll
-  for (int a = 0; a < NA; ++a)
-    key_act[a] = in_reg(murmur_key(tile_coord<T>(P.tile, D, tile_quant(P.tile, D, P.actions[a]), j)));
-  const uint32_t key_j = in_reg(murmur_key(j));
+  uint32_t key_act[NA], key_j;
+  action_keys<T, D, NA>(P.tile, P.actions, j, acts, key_act, key_j);
 
   // the trace of this lane's tiling: table positions, newest first (kInvalidPos: index removed by ssub); bit e of tsh:
   // entry e is a slot shared between tilings.  tlen is the reference's entry count (equal in all lanes).
@@ -184,7 +168,7 @@ __global__ __launch_bounds__(64) void rollout_tgt_kernel(DevParams P, int n_tria
       {
         uint32_t s1[1] = {ii};
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-        table_get<1>(tab, P.lin, RS, 0, s1, pos1, w1, sh1, g, j, gmask, sh_mb, sh_ms, sh_mail, sh_jump, status, inserted, on_share);
+        table_get<1>(tab, P.lin, RS, 0, s1, pos1, w1, sh1, g, j, ids.gmask, sh_mb, sh_ms, sh_mail, sh_jump, run.status, inserted, on_share);
         const uint32_t aux = tab.base[(pos1[0] >> 2) & tab.bmask].aux[pos1[0] & 3u];
         moved = pend && aux != 0u && aux != h + 1u;                       // claimed by another hash sum
         if (moved) ii = (ii + 1u >= mem_u) ? 0u : ii + 1u;
@@ -208,7 +192,7 @@ __global__ __launch_bounds__(64) void rollout_tgt_kernel(DevParams P, int n_tria
       wave_sync();
       // a loser's slot is being claimed by a lower tiling with another hash sum: it walks on next round
     }
-    if (pend) status |= ST_TABLE_FULL;
+    if (pend) run.status |= ST_TABLE_FULL;
     if (active)
     {
       slot_out = ii;
@@ -220,32 +204,26 @@ __global__ __launch_bounds__(64) void rollout_tgt_kernel(DevParams P, int n_tria
 
   for (int trial = 0; trial < n_trials; ++trial)
   {
-    // online_learning.cpp:154: a replica whose learning steps have reached the steps budget starts no further trial
-    const bool act = live && !(P.steps_budget != 0u && (uint64_t)ss >= P.steps_budget);
-    if (!__any(act)) break;
-    const int ti = P.test_interval;
-    const int test = (ti >= 0 && tt % (ti + 1) == ti) ? 1 : 0;
-    // a test trial is test_trials greedy episodes (online_learning.cpp:161-170): each starts the environment and the agent anew, while
-    // reward and time keep adding up (:202-203); a learning trial is one episode (its `time` = 0 is the sampler's moment to decay)
-    double total_reward = 0, time = 0;
-    const int subtrials = (test && P.test_trials > 1) ? P.test_trials : 1;
+    const TrialPlan plan = trial_plan(P, P, ids, run.ss, run.tt);
+    if (!__any(plan.act)) break;
+    double total_reward = 0, time = 0;      // of the whole trial; a learning episode's `time` = 0 is the sampler's moment to decay
     for (int st = 0; st < P.test_trials; ++st)
     {
-    const bool episode = act && st < subtrials;
+    const bool episode = plan.act && st < plan.subtrials;
     if (!__any(episode)) break;
     double obs[D], reward = 0;
     int terminal = 0;
     bool running = episode;
     if (episode)
     {
-      Env<ENV>::start(P, test, TL, G, x);
-      Env<ENV>::observe(P, x, obs);
+      Env<ENV>::start(P, plan.test, run.TL, run.G, run.x);
+      Env<ENV>::observe(P, run.x, obs);
     }
     double action = 0;
     int action_index = 0;
     uint32_t p_pos = kInvalidPos, p_slot = 0, hp = 0, hpm_prev = 0;
     bool p_sh = false;
-    if (!test)
+    if (!plan.test)
     { // TDAgent::start -> predictor->finalize() -> trace_->clear()
 #pragma unroll
       for (int e = 0; e < kMaxTrace; ++e) tpos[e] = kInvalidPos;
@@ -284,28 +262,13 @@ __global__ __launch_bounds__(64) void rollout_tgt_kernel(DevParams P, int n_tria
       {
         if (!first)
         {
-          env_step<ENV>(P, x, action, obs, reward, terminal, status);
+          env_step<ENV>(P, run.x, action, obs, reward, terminal, run.status);
           total_reward += reward;
           time += 1;
         }
         has_next = first || terminal != 2;
-        update = !first && !test;
-        if (has_next)
-        {
-          uint32_t hpre = 449u ^ (uint32_t)(D + 2);
-#pragma unroll
-          for (int i = 0; i < D; ++i)
-            hpre = murmur_mix(hpre, tile_coord<T>(P.tile, i, tile_quant(P.tile, i, obs[i]), j));
-          hpm = hpre * 0x5bd1e995u;
-#pragma unroll
-          for (int a = 0; a < NA; ++a)
-          {
-            uint32_t h = murmur_absorb(hpm ^ key_act[a], key_j);
-            hfull[a] = murmur_final(h);
-            const uint32_t mem = (uint32_t)P.tile.memory;
-            slot[a] = ((mem & (mem - 1u)) == 0u) ? (hfull[a] & (mem - 1u)) : (hfull[a] % mem);
-          }
-        }
+        update = !first && !plan.test;
+        if (has_next) hpm = tile_slots_obs_actions<T, D, NA>(P.tile, obs, key_act, key_j, j, slot, hfull);
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       }
       // -------- policy: Q(s', .) -- the batch projections of QPolicy::values: no claims under safe = 1; under safe = 2 each
@@ -317,7 +280,7 @@ __global__ __launch_bounds__(64) void rollout_tgt_kernel(DevParams P, int n_tria
         for (int a = 0; a < NA; ++a) probe(running && has_next, hfull[a], claim_batch, slot[a], pos[a], w[a], sh[a], share_event);
       }
       else if (running && has_next)
-        table_get<NA>(tab, P.lin, RS, 0, slot, pos, w, sh, g, j, gmask, sh_mb, sh_ms, sh_mail, sh_jump, status, inserted, share_event);
+        table_get<NA>(tab, P.lin, RS, 0, slot, pos, w, sh, g, j, ids.gmask, sh_mb, sh_ms, sh_mail, sh_jump, run.status, inserted, share_event);
       // -------- criticize: p = project(prev_obs, prev_action), a single projection (claims under safe = 1)
       if (SAFE)
       {
@@ -355,14 +318,7 @@ __global__ __launch_bounds__(64) void rollout_tgt_kernel(DevParams P, int n_tria
         SHW(NA, j, g) = wp;
       }
       wave_sync();
-      if (running)
-      {
-        const int row = (j < NROWS - 1) ? j : 0;
-        double sum = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) sum += SHW(row, k, g);
-        sh_res[g * 16 + j] = sum / 16;
-      }
+      if (running) sum_rows<NROWS - 1>(sh_w, sh_res, g, j);
       wave_sync();
       if (running)
       {
@@ -378,21 +334,7 @@ __global__ __launch_bounds__(64) void rollout_tgt_kernel(DevParams P, int n_tria
         if (has_next)
         {
           findmax<NA>(q, mai, man, best);
-          if (test)
-            a_next = (man > 1) ? tie_break<NA>(q, best, man, G) : mai;
-          else
-          {
-            if (time == 0.) eps_decay = fmax(eps_decay * P.decay_rate, P.decay_min);
-            S1 = lcg_next(S1);
-            const double rnd = lcg_double(S1);
-            if (rnd < eps_decay * P.epsilon)
-            {
-              G = lcg_next(G);
-              a_next = (int)(lcg_long(G) % (uint32_t)NA);
-            }
-            else
-              a_next = (man > 1) ? tie_break<NA>(q, best, man, G) : mai;
-          }
+          a_next = eps_greedy_act<NA>(P, q, mai, man, best, plan.test, time, run.eps_decay, run.S1, run.G);
         }
       }
       // SARSA under safe = 1: the target reads project(obs, action), a SINGLE projection -- it claims, and a claim made a
@@ -491,7 +433,7 @@ __global__ __launch_bounds__(64) void rollout_tgt_kernel(DevParams P, int n_tria
                 hit = hit || (tpos[e] != kInvalidPos && tpos[e] == sh_ppos[g * 16 + __builtin_ctz(mm)]);
               if (e < tlen && hit) { tpos[e] = kInvalidPos; tsh &= ~(1u << e); }
             }
-            if (tlen >= kMaxTrace) status |= ST_TRACE_OVERFLOW;       // cannot happen: validated at create
+            if (tlen >= kMaxTrace) run.status |= ST_TRACE_OVERFLOW;       // cannot happen: validated at create
 #pragma unroll
             for (int e = kMaxTrace - 1; e > 0; --e) tpos[e] = tpos[e - 1];
             tsh = (tsh << 1) & ((1u << kMaxTrace) - 1u);
@@ -516,7 +458,7 @@ __global__ __launch_bounds__(64) void rollout_tgt_kernel(DevParams P, int n_tria
       if (running)
       {
         // -------- tap
-        if (tapped && (!first || P.tap_starts))
+        if (ids.tapped && (!first || P.tap_starts))
         {
           uint32_t n = *P.tap_count;
           if (n < (uint32_t)P.tap_capacity)
@@ -526,28 +468,16 @@ __global__ __launch_bounds__(64) void rollout_tgt_kernel(DevParams P, int n_tria
             tp->p_idx[16 + j] = 0u;
             if (j == 0)
             {
-              tp->test = test;
-              tp->action_index = has_next ? a_next : action_index;
-              tp->terminal = first ? -1 : terminal;
+              tap_common<NA, S, D>(tp, plan.test, has_next ? a_next : action_index, first ? -1 : terminal, obs,
+                                   has_next ? pick<double, NA>(acts, a_next) : action, reward, run.x, q, has_next);
               tp->trace_len = tlen;
-              for (int i = 0; i < GRLX_MAX_DIMS; ++i) tp->obs[i] = (i < D) ? obs[i] : 0.;
-              tp->action = has_next ? pick<double, NA>(acts, a_next) : action;
-              tp->reward = reward;
-              for (int i = 0; i < GRLX_MAX_STATE; ++i) tp->state[i] = (i < S) ? x[i] : 0.;
               tp->delta = delta;
-              for (int a = 0; a < kMaxActions; ++a) tp->q[a] = 0.;
-#pragma unroll
-              for (int a = 0; a < NA; ++a) tp->q[a] = has_next ? q[a] : 0.;
             }
           }
           wave_sync();
           if (j == 0) *P.tap_count = n + 1u;
         }
-        if (!first)
-        {
-          if (test) test_steps++;
-          else ss++;
-        }
+        count_step(run.ss, run.test_steps, plan.test, first);
         if (has_next)
         {
           action_index = a_next;
@@ -565,49 +495,17 @@ __global__ __launch_bounds__(64) void rollout_tgt_kernel(DevParams P, int n_tria
 
     }   // episodes of the trial
 
-    if (act && (ti >= 0 ? test : 1))
-    {
-      if (rows < (uint32_t)P.max_rows)
-      {
-        if (j == 0)
-        {
-          size_t at = (size_t)rows * (size_t)P.n_replicas + (size_t)r;
-          P.row_reward[at] = total_reward / (double)subtrials;              // online_learning.cpp:224-225
-          P.row_time[at] = time / (double)subtrials;
-          P.row_steps[at] = ss;
-          P.row_trial[at] = (ti >= 0) ? (tt + 1 - (tt + 1) / (ti + 1)) : tt;
-        }
-        rows++;
-      }
-      else
-        status |= ST_ROWS_FULL;
-    }
-    tt += act ? 1 : 0;
+    record_row(P, ids, plan, run.rows, run.status, run.ss, run.tt, total_reward, time);
+    run.tt += plan.act ? 1 : 0;
   }
 
-  uint32_t ins = inserted;
-#pragma unroll
-  for (int off = 8; off > 0; off >>= 1) ins += __shfl_xor(ins, off, 16);
-  if (live && j == 0)
-  {
-#pragma unroll
-    for (int i = 0; i < S; ++i) RS.x[i] = x[i];
-    RS.G = G;
-    RS.TL = TL;
-    RS.S1 = S1;
-    RS.eps_decay = eps_decay;
-    RS.tt = tt;
-    RS.ss = ss;
-    RS.test_steps = test_steps;
-    RS.n_slots[0] += ins;
-    RS.rows = rows;
+  run_store<S>(RS, ids, run, inserted);
+  if (ids.live && j == 0)
+  { // the target network's synchronisation state
     RS.sync_count = sync_count;
     RS.syncs = K;
   }
-  uint32_t st = status;
-#pragma unroll
-  for (int off = 8; off > 0; off >>= 1) st |= __shfl_xor(st, off, 16);
-  if (live && j == 0) RS.status = st;
+  store_status(RS, ids, run.status);
 }
 
 hipError_t launch_rollout_tgt(const DevParams &P, int n_trials, hipStream_t stream, int *variant)
@@ -644,22 +542,9 @@ __global__ void get_target_weights_kernel(DevParams P, int replica, const uint32
   const ReplicaState &rs = P.states[replica];
   const double *tv = P.tvals + ((size_t)replica << P.logC);
   const uint32_t slot = slots[i];
-  uint32_t b = table_home(tab, slot);
+  uint32_t pos;
   double v = target_from_init(P, rs, slot, rs.syncs);
-  for (int it = 0; it < kMaxProbe; ++it)
-  {
-    const BucketRegs br = bucket_load(tab, b);
-    uint32_t empty;
-    const int way = bucket_find(br.k, slot, empty);
-    if (way >= 0)
-    {
-      const double t = tv[(b << 2) | (uint32_t)way];
-      if ((unsigned long long)__double_as_longlong(t) != kTvalUnset) v = t;
-      break;
-    }
-    if (empty != 0u) break;
-    b = (b + 1u) & tab.bmask;
-  }
+  if (table_peek(tab, slot, pos) && (unsigned long long)__double_as_longlong(tv[pos]) != kTvalUnset) v = tv[pos];
   out[i] = v;
 }
 
@@ -676,22 +561,9 @@ __global__ void target_after_load_kernel(DevParams P, int replica, const double 
   for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < n; slot += gridDim.x * blockDim.x)
   {
     if (tau == 0.) { out[slot] = image[slot]; continue; }
-    uint32_t b = table_home(tab, slot);
+    uint32_t pos;
     double v = target_from_init(P, rs, slot, rs.syncs);
-    for (int it = 0; it < kMaxProbe; ++it)
-    {
-      const BucketRegs br = bucket_load(tab, b);
-      uint32_t empty;
-      const int way = bucket_find(br.k, slot, empty);
-      if (way >= 0)
-      {
-        const double t = tv[(b << 2) | (uint32_t)way];
-        if ((unsigned long long)__double_as_longlong(t) != kTvalUnset) v = t;
-        break;
-      }
-      if (empty != 0u) break;
-      b = (b + 1u) & tab.bmask;
-    }
+    if (table_peek(tab, slot, pos) && (unsigned long long)__double_as_longlong(tv[pos]) != kTvalUnset) v = tv[pos];
     out[slot] = tau * image[slot] + (1 - tau) * v;
   }
 }

@@ -107,6 +107,25 @@ __device__ __forceinline__ int bucket_find(const uint4 &k, uint32_t slot, uint32
   return way;
 }
 
+// probe without insertion: the position of `slot`'s entry; false when the slot has none (it was never touched)
+__device__ __forceinline__ bool table_peek(const Table &t, uint32_t slot, uint32_t &pos)
+{
+  uint32_t b = table_home(t, slot);
+  for (int it = 0; it < kMaxProbe; ++it)
+  {
+    uint32_t empty;
+    const int way = bucket_find(bucket_keys(t, b), slot, empty);
+    if (way >= 0)
+    {
+      pos = (b << 2) | (uint32_t)way;
+      return true;
+    }
+    if (empty != 0u) break;
+    b = (b + 1u) & t.bmask;
+  }
+  return false;
+}
+
 // State of one lookup.  hit: pos/val valid.  miss: `bucket` is the first bucket of the
 // probe sequence with an empty way and `empty` its empty-way mask (as loaded).
 struct Lookup {

@@ -60,6 +60,31 @@ __device__ __forceinline__ int tile_quant(const TileParams &tp, int i, double x)
   return (int)__builtin_floor(x * tp.scaling[i]);
 }
 
+// Slots of the NA projections (obs, a_k) in tiling j (q.cpp:94-107).  key_act[k] = murmur_key of action k's coordinate in
+// this tiling, key_j = murmur_key(j): constants of the lane.  The hash of obs is shared by the NA projections; returned
+// multiplied, ready for murmur_mix's xor, for a caller that projects (obs, a) once more.  hfull: the full 32-bit hash sums,
+// for the caller that claims slots by them (tile_coding.h:116-151).
+template <int T, int D, int NA>
+__device__ __forceinline__ uint32_t tile_slots_obs_actions(const TileParams &tile, const double (&obs)[D], const uint32_t (&key_act)[NA],
+                                                           uint32_t key_j, int j, uint32_t (&slot)[NA], uint32_t *hfull = nullptr)
+{
+  uint32_t hpre = 449u ^ (uint32_t)(D + 2);
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+    hpre = murmur_mix(hpre, tile_coord<T>(tile, i, tile_quant(tile, i, obs[i]), j));
+  const uint32_t hpm = hpre * 0x5bd1e995u;                           // shared by the NA projections
+#pragma unroll
+  for (int a = 0; a < NA; ++a)
+  {
+    uint32_t h = hpm ^ key_act[a];                                   // murmur_mix(hpre, coordinate of action a)
+    h = murmur_absorb(h, key_j);                                     // murmur_mix(h, j)
+    const uint32_t hm = murmur_final(h), mem = (uint32_t)tile.memory;
+    if (hfull) hfull[a] = hm;
+    slot[a] = ((mem & (mem - 1u)) == 0u) ? (hm & (mem - 1u)) : (hm % mem);
+  }
+  return hpm;
+}
+
 // generic (runtime T) projection of one input for tiling j
 __device__ inline uint32_t tile_slot_generic(const TileParams &tp, const double *in, int j)
 {

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Run one of the BASELINE.json configurations for profiling: run_config.py <name> <replicas> <warm trials> <trials>
-name: pendulum | pendulum_q | cart_pole_ac | acrobot | compass_walker"""
+name: pendulum | pendulum_q | pendulum_acc | pendulum_adv | pendulum_qv | pendulum_tgt | cart_pole_ac | acrobot | compass_walker"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -10,6 +10,7 @@ configs.NO_ORACLE = True            # the grlx_config half of the builders only:
 
 name, n, warm, trials = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
 make = {"pendulum_acc": lambda g, k: configs.pendulum(g, k, trace=2), "pendulum_adv": lambda g, k: configs.pendulum(g, k, agent=4, kappa=0.2),
+        "pendulum_tgt": lambda g, k: configs.pendulum(g, k, target_interval=190, target_tau=0.4),      # target network: rollout_tgt_kernel
         "pendulum_qv": configs.pendulum_qv, "pendulum": configs.pendulum, "pendulum_q": lambda g, k: configs.pendulum(g, k, agent=1), "cart_pole_ac": configs.cart_pole_ac,
         "acrobot": configs.acrobot, "compass_walker": configs.compass_walker}[name]
 cfg, _ = make(grl_amd, n)
