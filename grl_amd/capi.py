@@ -15,6 +15,7 @@ OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_TABLE_FULL, ERR_DOMAIN, ERR_ROWS_FU
 ENV_PENDULUM, ENV_CART_POLE, ENV_ACROBOT, ENV_COMPASS_WALKER, ENV_CART_POLE_BALANCING, ENV_EXTERNAL = 0, 1, 2, 3, 4, 5
 AGENT_SARSA, AGENT_Q, AGENT_AC, AGENT_EXPECTED_SARSA, AGENT_ADVANTAGE, AGENT_QV = 0, 1, 2, 3, 4, 5
 TRACE_NONE, TRACE_REPLACING, TRACE_ACCUMULATING = 0, 1, 2
+PARAM_ALPHA, PARAM_GAMMA, PARAM_LAMBDA, PARAM_EPSILON = 0, 1, 2, 3
 
 
 class TileSpec(C.Structure):
@@ -90,6 +91,9 @@ _SIGS = {
     "grlx_replicas_per_wave": (C.c_int, [C.c_void_p]),
     "grlx_read_row_times": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_double)]),
     "grlx_curve_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "grlx_curve_stats_grouped": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "grlx_set_replica_params": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_double)]),
+    "grlx_get_replica_params": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_double)]),
     "grlx_step_counts": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64)]),
     "grlx_get_env_state": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_double)]),
     "grlx_get_rng": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_uint64)]),

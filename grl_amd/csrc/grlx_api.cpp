@@ -344,6 +344,12 @@ struct grlx_ctx {
   double       *stage_f64 = nullptr;      // [N][GRLX_MAX_DIMS] obs | [N] reward | [N] action
   int32_t      *stage_i32 = nullptr;      // [N] active | [N] terminal
   uint64_t     step_calls = 0;            // agent calls since the last look at the tables' load
+  // hyper-parameter sweep (grlx_set_replica_params): the per-replica values as given ([GRLX_PARAM_*][replica]; empty = none set: not a
+  // sweep context) and their device records, handed to launch_rollout once the context is a sweep context
+  std::vector<double> sweep_host[4];
+  SweepParams  *sweep_dev = nullptr;
+  bool         sweep = false;
+  bool         launched = false;          // a rollout or per-step kernel has run in this context: its replicas' parameters are fixed
 };
 
 // small RAII helper for the copy-in / copy-out entry points
@@ -691,6 +697,7 @@ int grlx_destroy(grlx_ctx *ctx)
   (void)hipFree(ctx->queue);
   if (ctx->env_mail) (void)hipFree(ctx->env_mail);
   if (ctx->park) (void)hipFree(ctx->park);
+  if (ctx->sweep_dev) (void)hipFree(ctx->sweep_dev);
   if (ctx->agent_rep) (void)hipFree(ctx->agent_rep);
   if (ctx->agent_lane) (void)hipFree(ctx->agent_lane);
   if (ctx->stage_f64) (void)hipFree(ctx->stage_f64);
@@ -713,6 +720,7 @@ int grlx_destroy(grlx_ctx *ctx)
 int grlx_set_diag(grlx_ctx *ctx, int enable)
 {
   if (!ctx) return fail(GRLX_ERR_INVALID, "null ctx");
+  if (enable && ctx->sweep) return fail(GRLX_ERR_INVALID, "diagnostics are not built for a sweep context (grlx_set_replica_params)");
   const size_t waves = ((size_t)ctx->P.n_replicas + kReplicasPerWave - 1) / kReplicasPerWave;
   if (enable && !ctx->diag)
   {
@@ -909,6 +917,7 @@ static int run_trials(grlx_ctx *ctx, int n_trials, uint64_t steps_budget, void *
   if (steps_budget != 0) kTrialsPerLaunch = n_trials;
   ctx->run_stream = (hipStream_t)stream;
   ctx->run_pending = true;
+  ctx->launched = true;
   for (int done = 0; done < n_trials; done += kTrialsPerLaunch)
   {
     const int n = (n_trials - done < kTrialsPerLaunch) ? n_trials - done : kTrialsPerLaunch;
@@ -942,6 +951,8 @@ static int run_trials(grlx_ctx *ctx, int n_trials, uint64_t steps_budget, void *
       HIP_TRY(launch_rollout_tgt(Pb, n, (hipStream_t)stream, &ctx->last_kernel));
     else if (ctx->cfg.trace == GRLX_TRACE_ACCUMULATING)
       HIP_TRY(launch_rollout_acc(Pb, n, (hipStream_t)stream, &ctx->last_kernel));
+    else if (ctx->sweep)        // (without the environment server)
+      HIP_TRY(launch_rollout(Pb, n, (hipStream_t)stream, &ctx->last_kernel, ctx->sweep_dev));
     else if (ctx->env_server && env_server_serves(Pb) && (size_t)ctx->P.n_replicas * env_server_mail_bytes(Pb) < (1ull << 31) && env_server_ready(ctx))
     { // the server's launch forks off the caller's stream and joins it again: for the caller, still one stream-ordered operation
       Pb.env_mail = ctx->env_mail;
@@ -1087,6 +1098,115 @@ int grlx_read_row_times(grlx_ctx *ctx, int replica, int first, int count, double
   DRAIN(ctx);
   HIP_TRY(hipMemcpy2D(episode_time, sizeof(double), ctx->row_time + (size_t)first * N + (size_t)replica, N * sizeof(double), sizeof(double),
                       (size_t)count, hipMemcpyDeviceToHost));
+  return GRLX_OK;
+}
+
+int grlx_curve_stats_grouped(grlx_ctx *ctx, int first, int count, int group_size, double *out_dev, void *stream)
+{
+  if (!ctx || !out_dev || first < 0 || count < 0 || first + count > ctx->P.max_rows) return fail(GRLX_ERR_INVALID, "bad argument");
+  if (group_size < 1 || ctx->P.n_replicas % group_size != 0)
+    return fail(GRLX_ERR_INVALID, "group_size = %d does not divide the %d replicas into whole groups", group_size, ctx->P.n_replicas);
+  if (ctx->run_pending && ctx->run_stream != (hipStream_t)stream) DRAIN(ctx);
+  HIP_TRY(launch_curve_stats_grouped(ctx->P, first, count, group_size, out_dev, (hipStream_t)stream));
+  return GRLX_OK;
+}
+
+// ---- hyper-parameter sweep: alpha, gamma, lambda, epsilon per replica --------------------------------------------------------------
+namespace {
+const char *const kSweepParamName[4] = {"alpha", "gamma", "lambda", "epsilon"};
+
+double sweep_config_value(const grlx_ctx *ctx, int param)
+{
+  switch (param)
+  {
+    case GRLX_PARAM_ALPHA: return ctx->cfg.alpha;
+    case GRLX_PARAM_GAMMA: return ctx->cfg.gamma;
+    case GRLX_PARAM_LAMBDA: return ctx->cfg.lambda;
+    default: return ctx->cfg.epsilon;
+  }
+}
+
+// what a sweep context is built for; the message names what is not
+int sweep_admits(const grlx_ctx *ctx)
+{
+  const grlx_config &c = ctx->cfg;
+  if (c.env == GRLX_ENV_EXTERNAL)
+    return fail(GRLX_ERR_INVALID, "per-replica parameters are not built for GRLX_ENV_EXTERNAL (the per-step entry points read the shared values)");
+  if (c.agent != GRLX_AGENT_SARSA && c.agent != GRLX_AGENT_Q && c.agent != GRLX_AGENT_EXPECTED_SARSA)
+    return fail(GRLX_ERR_INVALID, "per-replica parameters are built for the agents SARSA, Q and Expected SARSA (agent %d is not)", c.agent);
+  if (c.trace != GRLX_TRACE_REPLACING && c.trace != GRLX_TRACE_NONE)
+    return fail(GRLX_ERR_INVALID, "per-replica parameters are built for a replacing trace or none (an accumulating trace is not)");
+  if (c.target_interval > 0) return fail(GRLX_ERR_INVALID, "per-replica parameters are not built with a target network (representation interval > 0)");
+  if (c.projector.safe != 0) return fail(GRLX_ERR_INVALID, "per-replica parameters are not built with projector/tile_coding:safe");
+  if (ctx->P.tap_capacity > 0) return fail(GRLX_ERR_INVALID, "per-replica parameters are not built with taps");
+  if (ctx->P.diag_out) return fail(GRLX_ERR_INVALID, "per-replica parameters are not built with diagnostics (grlx_set_diag)");
+  if (c.replicas_per_wave != 0 && c.replicas_per_wave != 4 && c.replicas_per_wave != 8)
+    return fail(GRLX_ERR_INVALID, "per-replica parameters are built for replicas_per_wave 0, 4 or 8 (%d is not)", c.replicas_per_wave);
+  return GRLX_OK;
+}
+} // namespace
+
+int grlx_get_replica_params(grlx_ctx *ctx, int param, double *values)
+{
+  if (!ctx || !values) return fail(GRLX_ERR_INVALID, "null argument");
+  if (param < 0 || param > 3) return fail(GRLX_ERR_INVALID, "param %d is not one of GRLX_PARAM_*", param);
+  const size_t N = (size_t)ctx->P.n_replicas;
+  for (size_t r = 0; r < N; ++r) values[r] = ctx->sweep_host[param].empty() ? sweep_config_value(ctx, param) : ctx->sweep_host[param][r];
+  return GRLX_OK;
+}
+
+int grlx_set_replica_params(grlx_ctx *ctx, int param, const double *values)
+{
+  if (!ctx || !values) return fail(GRLX_ERR_INVALID, "null argument");
+  if (param < 0 || param > 3) return fail(GRLX_ERR_INVALID, "param %d is not one of GRLX_PARAM_*", param);
+  if (ctx->launched) return fail(GRLX_ERR_INVALID, "grlx_set_replica_params is allowed only before the first launch of the context");
+  int rc = sweep_admits(ctx);
+  if (rc != GRLX_OK) return rc;
+  const size_t N = (size_t)ctx->P.n_replicas;
+  // the four values of every replica with this call applied, validated as make_params validates the shared ones
+  std::vector<double> v[4];
+  for (int k = 0; k < 4; ++k)
+  {
+    v[k].resize(N);
+    rc = grlx_get_replica_params(ctx, k, v[k].data());
+    if (rc != GRLX_OK) return rc;
+  }
+  v[param].assign(values, values + N);
+  std::vector<SweepParams> rec(N);
+  for (size_t r = 0; r < N; ++r)
+  {
+    if (!std::isfinite(values[r])) return fail(GRLX_ERR_INVALID, "%s of replica %zu is not finite (%g)", kSweepParamName[param], r, values[r]);
+    SweepParams &w = rec[r];
+    w.alpha = v[GRLX_PARAM_ALPHA][r];
+    w.gamma = v[GRLX_PARAM_GAMMA][r];
+    w.gl = v[GRLX_PARAM_GAMMA][r] * v[GRLX_PARAM_LAMBDA][r];      // pow(gamma*lambda, tau) with tau = 1, as make_params forms it
+    w.epsilon = v[GRLX_PARAM_EPSILON][r];
+    if (ctx->cfg.trace == GRLX_TRACE_REPLACING)
+    {
+      if (!(w.gl > 0 && w.gl < 1))
+        return fail(GRLX_ERR_INVALID, "replica %zu: %s = %g gives gamma*lambda = %g, which must be in (0,1) with a trace", r, kSweepParamName[param], values[r], w.gl);
+      double tot = 1;
+      int n = 0;
+      while (tot >= 0.01 && n <= kMaxTrace) { tot *= w.gl; n++; }
+      if (n > kMaxTrace)
+        return fail(GRLX_ERR_INVALID, "replica %zu: %s = %g gives gamma*lambda = %g, which needs a trace longer than %d entries", r, kSweepParamName[param],
+                    values[r], w.gl, kMaxTrace);
+    }
+  }
+  if (!ctx->sweep_dev)
+  {
+    hipError_t e = hipMalloc((void **)&ctx->sweep_dev, sizeof(SweepParams) * N);
+    if (e != hipSuccess)
+    {
+      ctx->sweep_dev = nullptr;
+      return fail(e == hipErrorOutOfMemory ? GRLX_ERR_OOM : GRLX_ERR_HIP, "hipMalloc of the per-replica parameters failed: %s", hipGetErrorString(e));
+    }
+  }
+  HIP_TRY(hipMemcpy(ctx->sweep_dev, rec.data(), sizeof(SweepParams) * N, hipMemcpyHostToDevice));
+  ctx->sweep_host[param] = std::move(v[param]);
+  ctx->sweep = true;
+  // the layouts of more than 8 replicas per wave are not built for a sweep: the automatic choice falls back to 8
+  if (ctx->P.replicas_per_wave > 8) ctx->P.replicas_per_wave = 8;
   return GRLX_OK;
 }
 
@@ -1306,11 +1426,19 @@ static const int32_t *stage_active(grlx_ctx *ctx, const int32_t *active, hipErro
   return ctx->stage_i32;
 }
 
+#define SWEEP_REFUSES(ctx, what)                                                                                                  \
+  do {                                                                                                                            \
+    if ((ctx) && (ctx)->sweep)                                                                                                    \
+      return fail(GRLX_ERR_INVALID, what " is not built for a sweep context (grlx_set_replica_params): it would run on the shared values"); \
+  } while (0)
+
 int grlx_env_start(grlx_ctx *ctx, int test, const int32_t *active, double *obs)
 {
+  SWEEP_REFUSES(ctx, "grlx_env_start");
   if (!ctx || !obs) return fail(GRLX_ERR_INVALID, "bad argument");
   if (ctx->cfg.env == GRLX_ENV_EXTERNAL) return fail(GRLX_ERR_INVALID, "this context has no environment (GRLX_ENV_EXTERNAL)");
   DRAIN(ctx);
+  ctx->launched = true;
   int rc = step_buffers(ctx);
   if (rc != GRLX_OK) return rc;
   const size_t N = (size_t)ctx->P.n_replicas, D = (size_t)ctx->D;
@@ -1325,9 +1453,11 @@ int grlx_env_start(grlx_ctx *ctx, int test, const int32_t *active, double *obs)
 
 int grlx_env_advance(grlx_ctx *ctx, const int32_t *active, const double *action, double *obs, double *reward, int32_t *terminal)
 {
+  SWEEP_REFUSES(ctx, "grlx_env_advance");
   if (!ctx || !action || !obs || !reward || !terminal) return fail(GRLX_ERR_INVALID, "bad argument");
   if (ctx->cfg.env == GRLX_ENV_EXTERNAL) return fail(GRLX_ERR_INVALID, "this context has no environment (GRLX_ENV_EXTERNAL)");
   DRAIN(ctx);
+  ctx->launched = true;
   int rc = step_buffers(ctx);
   if (rc != GRLX_OK) return rc;
   const size_t N = (size_t)ctx->P.n_replicas, D = (size_t)ctx->D;
@@ -1388,11 +1518,13 @@ static int agent_ready(grlx_ctx *ctx)
 static int agent_call(grlx_ctx *ctx, int mode, int test, const int32_t *active, double tau, const double *obs, const double *reward,
                       const int32_t *terminal, double *action)
 {
+  SWEEP_REFUSES(ctx, "grlx_agent_start / _step / _end");
   if (!ctx || !obs || (mode != STEP_START && !reward) || (mode != STEP_END && !action)) return fail(GRLX_ERR_INVALID, "bad argument");
   if (mode != STEP_START && tau != 1.) return fail(GRLX_ERR_INVALID, "Agent::step / end: tau must be 1 (environment/modeled:discrete_time = 1)");
   DRAIN(ctx);
   int rc = agent_ready(ctx);
   if (rc != GRLX_OK) return rc;
+  ctx->launched = true;
   // the tables these calls fill grow like the fused path's: looked at every 64 calls, between two calls
   if ((ctx->step_calls++ & 63u) == 63u && ctx->P.logC < ctx->logC_max)
   {

@@ -72,6 +72,14 @@ struct __attribute__((aligned(16))) AgentRep {
   int32_t pad;
 };
 
+// The learning parameters of ONE replica of a sweep context (grlx_set_replica_params): what the rollout kernels otherwise read from the
+// shared block.  gl = gamma * lambda, formed on the host by the expression of make_params.  The records live in one device array
+// [replica] that the sweep kernels receive as an argument of their own, after the parameter block: DevParams itself does not grow, so
+// neither the block nor the offsets of the kernel arguments behind it move in any other kernel.
+struct __attribute__((aligned(32))) SweepParams {
+  double alpha, gamma, gl, epsilon;
+};
+
 struct TileParams {
   int32_t  T, D, memory;
   double   scaling[GRLX_MAX_DIMS];
@@ -151,7 +159,8 @@ struct DevParams {
 // ---------------------------------------------------------------------------
 // launchers implemented in grlx_kernels.hip
 // *variant (optional) receives the GRLX_KERNEL_* instantiation that was launched
-hipError_t launch_rollout(const DevParams &P, int n_trials, hipStream_t stream, int *variant);
+// sweep (optional): the per-replica learning parameters of a sweep context; set, the SpecSweep instantiations are launched
+hipError_t launch_rollout(const DevParams &P, int n_trials, hipStream_t stream, int *variant, const SweepParams *sweep = nullptr);
 bool       env_server_serves(const DevParams &P);                                   // is this context's rollout kernel one the environment server works for?
 size_t     env_server_mail_bytes(const DevParams &P);                               // ... and the size of a replica's mailbox there (0: not served)
 hipError_t launch_env_server(const DevParams &P, hipStream_t stream);
@@ -193,6 +202,8 @@ hipError_t launch_get_weights(const DevParams &P, int table, int replica, const 
 hipError_t launch_math(int op, const double *x, const double *y, int n, double *out, hipStream_t stream);
 hipError_t launch_rand48_at(uint64_t x0, const uint64_t *skip, int n, double *out, hipStream_t stream);
 hipError_t launch_curve_stats(const DevParams &P, int first, int count, double *out_dev, hipStream_t stream);
+// ... per group of group_size consecutive replicas: out[count][n_replicas / group_size][3]
+hipError_t launch_curve_stats_grouped(const DevParams &P, int first, int count, int group_size, double *out_dev, hipStream_t stream);
 hipError_t launch_reload_entries(const DevParams &P, int table, int first_replica, int n_replicas, const double *image_dev, hipStream_t stream);
 hipError_t launch_step_counts(const DevParams &P, uint64_t *out_dev /*[3]: learn, test, status-or*/, hipStream_t stream);
 // sparse-table growth (grlx_api.cpp: grow_tables).  max over replicas and tables of the occupied slots; every entry of the

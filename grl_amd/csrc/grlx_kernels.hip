@@ -261,10 +261,36 @@ hipError_t launch_env_server(const DevParams &P, hipStream_t stream)
   return hipGetLastError();
 }
 
-hipError_t launch_rollout(const DevParams &P, int n_trials, hipStream_t stream, int *variant)
+hipError_t launch_rollout(const DevParams &P, int n_trials, hipStream_t stream, int *variant, const SweepParams *sweep)
 {
   if (variant) *variant = GRLX_KERNEL_GENERIC;
   int waves = (P.n_replicas + kReplicasPerWave - 1) / kReplicasPerWave;
+  if (sweep)
+  { // a hyper-parameter sweep (grlx_set_replica_params): the production ordering with the learning parameters of every replica its own.
+    // What grlx_api.cpp admits as a sweep context has one of these instantiations; anything else is an error, never the shared values.
+    const bool inplace = P.diag_out != nullptr || (P.tap_replica >= 0 && P.tap_capacity > 0);
+    const bool td = P.agent == GRLX_AGENT_SARSA || P.agent == GRLX_AGENT_Q || P.agent == GRLX_AGENT_EXPECTED_SARSA;
+    if (inplace || !td || P.env_mail || P.trace_kind == GRLX_TRACE_ACCUMULATING || P.target_interval != 0 || P.tile_safe != 0 ||
+        (P.replicas_per_wave != 4 && P.replicas_per_wave != 8))
+      return hipErrorInvalidValue;
+    const int wwaves = (P.n_replicas + 7) / 8;
+#define GRLX_LAUNCH_SWEEP(ENVID, NACT)                                                                                \
+    if (P.env == ENVID && P.A == NACT)                                                                              \
+    {                                                                                                               \
+      if (P.replicas_per_wave == 8)                                                                                 \
+        hipLaunchKernelGGL((rollout_wide_sweep_kernel<ENVID, NACT>), dim3(wwaves), dim3(64), 0, stream, P, n_trials, sweep); \
+      else                                                                                                          \
+        hipLaunchKernelGGL((rollout_sweep_kernel<ENVID, NACT>), dim3(waves), dim3(64), 0, stream, P, n_trials, sweep);    \
+      return hipGetLastError();                                                                                     \
+    }
+    GRLX_LAUNCH_SWEEP(GRLX_ENV_PENDULUM, 3)
+    GRLX_LAUNCH_SWEEP(GRLX_ENV_PENDULUM, 5)
+    GRLX_LAUNCH_SWEEP(GRLX_ENV_ACROBOT, 3)
+    GRLX_LAUNCH_SWEEP(GRLX_ENV_CART_POLE, 3)
+    GRLX_LAUNCH_SWEEP(GRLX_ENV_COMPASS_WALKER, 3)
+#undef GRLX_LAUNCH_SWEEP
+    return hipErrorInvalidValue;
+  }
   if (P.env_mail && env_server_wide(P))
   { // the wide kernels' environment server (launch_env_server picks the same numeric parameters)
     const int wwaves = (P.n_replicas + 7) / 8;
@@ -758,6 +784,59 @@ hipError_t launch_curve_stats(const DevParams &P, int first, int count, double *
 {
   if (count == 0) return hipSuccess;
   hipLaunchKernelGGL(curve_stats_kernel, dim3(count), dim3(256), 0, stream, P, first, out_dev);
+  return hipGetLastError();
+}
+
+// ... over groups of group_size consecutive replicas (the repetitions of one point of a sweep): one block per (row, group); every
+// thread accumulates strided over its group, then the same tree.  out[row][group][3]; block = row * n_groups + group
+__global__ __launch_bounds__(256) void curve_stats_grouped_kernel(DevParams P, int first, int group_size, double *out)
+{
+  __shared__ double s1[256], s2[256], s3[256];
+  const int n_groups = P.n_replicas / group_size;
+  const int row = first + (int)(blockIdx.x / (unsigned)n_groups);
+  const int r0 = (int)(blockIdx.x % (unsigned)n_groups) * group_size;
+  double a = 0, b = 0, n = 0;
+  for (int k = threadIdx.x; k < group_size; k += 256)
+  {
+    const int r = r0 + k;
+    if (r < P.n_replicas && (uint32_t)row < P.states[r].rows)
+    {
+      double v = P.row_reward[(size_t)row * P.n_replicas + r];
+      a += v;
+      b += v * v;
+      n += 1;
+    }
+  }
+  s1[threadIdx.x] = a;
+  s2[threadIdx.x] = b;
+  s3[threadIdx.x] = n;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1)
+  {
+    if ((int)threadIdx.x < off)
+    {
+      s1[threadIdx.x] += s1[threadIdx.x + off];
+      s2[threadIdx.x] += s2[threadIdx.x + off];
+      s3[threadIdx.x] += s3[threadIdx.x + off];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0)
+  {
+    const size_t at = (size_t)blockIdx.x * 3;
+    out[at + 0] = s1[0];
+    out[at + 1] = s2[0];
+    out[at + 2] = s3[0];
+  }
+}
+
+hipError_t launch_curve_stats_grouped(const DevParams &P, int first, int count, int group_size, double *out_dev, hipStream_t stream)
+{
+  if (count == 0) return hipSuccess;
+  if (group_size < 1 || P.n_replicas % group_size != 0) return hipErrorInvalidValue;
+  const long long blocks = (long long)count * (P.n_replicas / group_size);
+  if (blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(curve_stats_grouped_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, P, first, group_size, out_dev);
   return hipGetLastError();
 }
 

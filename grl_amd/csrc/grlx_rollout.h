@@ -58,9 +58,21 @@ constexpr DevParams make_spec_pendulum_tc()
 }
 __device__ const DevParams d_spec_pendulum_tc = make_spec_pendulum_tc();
 
+// Where a SPEC policy takes the four learning parameters of a replica from.  SpecShared: the numeric block N, one value for every replica
+// (a literal in a specialised build) -- what every policy but SpecSweep inherits.  `Rep` is what a lane keeps per replica: nothing here.
+struct SpecShared {
+  static constexpr bool kPerReplica = false;
+  struct Rep {};
+  __device__ static __forceinline__ Rep replica(const SweepParams *, int) { return Rep{}; }
+  __device__ static __forceinline__ double alpha(const DevParams &N, const Rep &) { return N.alpha; }
+  __device__ static __forceinline__ double gamma(const DevParams &N, const Rep &) { return N.gamma; }
+  __device__ static __forceinline__ double gl(const DevParams &N, const Rep &) { return N.gl; }
+  __device__ static __forceinline__ double epsilon(const DevParams &N, const Rep &) { return N.epsilon; }
+};
+
 // AGENT: the predictor kind is a compile-time constant of the instantiation too (one per TD agent)
 template <int AGENT>
-struct SpecPendulumTcA {
+struct SpecPendulumTcA : SpecShared {
   __device__ static __forceinline__ int agent(const DevParams &) { return AGENT; }
   // every numeric field the rollout kernel reads must equal the constant, bit for bit
   static bool matches(const DevParams &P)
@@ -169,21 +181,38 @@ constexpr DevParams make_spec_acrobot_q()
 }
 __device__ const DevParams d_spec_walker_q = make_spec_walker_q();
 __device__ const DevParams d_spec_acrobot_q = make_spec_acrobot_q();
-struct SpecWalkerQ {
+struct SpecWalkerQ : SpecShared {
   static constexpr int kEnv = GRLX_ENV_COMPASS_WALKER;
   __device__ static __forceinline__ int agent(const DevParams &) { return GRLX_AGENT_Q; }
   static bool matches(const DevParams &P) { constexpr DevParams C = make_spec_walker_q(); return spec_numeric_equal(P, C); }
   __device__ static __forceinline__ const DevParams &numeric(const DevParams &) { return d_spec_walker_q; }
 };
-struct SpecAcrobotQ {
+struct SpecAcrobotQ : SpecShared {
   static constexpr int kEnv = GRLX_ENV_ACROBOT;
   __device__ static __forceinline__ int agent(const DevParams &) { return GRLX_AGENT_Q; }
   static bool matches(const DevParams &P) { constexpr DevParams C = make_spec_acrobot_q(); return spec_numeric_equal(P, C); }
   __device__ static __forceinline__ const DevParams &numeric(const DevParams &) { return d_spec_acrobot_q; }
 };
-struct SpecNone {
+struct SpecNone : SpecShared {
   __device__ static __forceinline__ const DevParams &numeric(const DevParams &P) { return P; }
   __device__ static __forceinline__ int agent(const DevParams &P) { return P.agent; }
+};
+// A hyper-parameter sweep (grlx_set_replica_params): the run-time block, except that alpha, gamma, gamma*lambda and epsilon are the
+// replica's own (sweep[replica], the kernel's third argument), held per lane -- the replicas of a wave differ.
+struct SpecSweep {
+  __device__ static __forceinline__ const DevParams &numeric(const DevParams &P) { return P; }
+  __device__ static __forceinline__ int agent(const DevParams &P) { return P.agent; }
+  static constexpr bool kPerReplica = true;
+  struct Rep { double alpha, gamma, gl, epsilon; };
+  __device__ static __forceinline__ Rep replica(const SweepParams *sweep, int r)
+  {
+    const SweepParams &w = sweep[r];
+    return Rep{w.alpha, w.gamma, w.gl, w.epsilon};
+  }
+  __device__ static __forceinline__ double alpha(const DevParams &, const Rep &R) { return R.alpha; }
+  __device__ static __forceinline__ double gamma(const DevParams &, const Rep &R) { return R.gamma; }
+  __device__ static __forceinline__ double gl(const DevParams &, const Rep &R) { return R.gl; }
+  __device__ static __forceinline__ double epsilon(const DevParams &, const Rep &R) { return R.epsilon; }
 };
 
 // ADV: advantage learning (predictor/critic/advantage, advantage.cpp:222-268) also reads A(s, .) of the
@@ -200,7 +229,7 @@ struct SpecNone {
 #endif
 // SERVED: the environment steps come from the environment server (grlx_env_server.h) -- its own kernel, rollout_served_kernel below.
 template <int ENV, int NA, bool DIAG, typename SPEC, bool DEFER, bool ADV, bool TAP, bool SERVED>
-__device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials)
+__device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials, const SweepParams *sweep = nullptr)
 {
   static_assert(!(ADV && DEFER), "the advantage-learning instantiation updates in place");
   constexpr int NROWS = ADV ? 2 * NA : NA + 1;      // LDS rows of weights summed per pass
@@ -240,6 +269,7 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials)
   uint64_t test_steps = RS.test_steps;
   uint32_t status = RS.status, rows = RS.rows, inserted = 0;
 
+  const typename SPEC::Rep rep = SPEC::replica(sweep, r);   // the replica's own learning parameters (a sweep context; else nothing)
   const Table tab = table_of(P, 0, r);
   // the two fields the slot-creation path reads (start of the initialisation stream, loaded policy image): kept in registers
   // instead of loaded behind a miss -- in the first few hundred trials most passes of a wave create a slot somewhere
@@ -250,7 +280,7 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials)
   up.out_min = N.lin.out_min;
   up.out_max = N.lin.out_max;
   up.limit = N.lin.limit != 0;
-  up.ee = N.gl;                                 // pow(gamma*lambda, tau), tau = 1 (discrete_time)
+  up.ee = SPEC::gl(N, rep);                     // pow(gamma*lambda, tau), tau = 1 (discrete_time)
   up.cut = (N.trace_kind == GRLX_TRACE_REPLACING) ? 0.01 : 0.0001;
   up.use_trace = N.trace_kind == GRLX_TRACE_REPLACING;
   up.dW = up.dT = 0;
@@ -448,6 +478,10 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials)
           up.dW = pd_dW;
           up.dT = pd_dT;
           td_update_lane<true>(tr, tab, up, pd_pos, pd_sh, pd_wp, g, j, sh_ppos, sh_fb, sh_fbflag, status, ev);
+          // a sweep context without a trace: the update stored p's weight straight into the table, behind the loads of Q(s', .)
+          // already in flight, and no trace entry forwards it (p of consecutive steps is often the same slot) -- load again below
+          if constexpr (SPEC::kPerReplica)
+            if (!up.use_trace) ev.n = 2u;
           pd = false;
         }
         DIAG_STAMP(5)
@@ -583,7 +617,7 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials)
             if (time == 0.) eps_decay = fmax(eps_decay * N.decay_rate, N.decay_min);
             S1 = lcg_next(S1);
             double rnd = lcg_double(S1);
-            if (rnd < eps_decay * N.epsilon)
+            if (rnd < eps_decay * SPEC::epsilon(N, rep))
             {
               G = lcg_next(G);
               a_next = (int)(lcg_long(G) % (uint32_t)NA);
@@ -624,10 +658,10 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials)
           else if (has_next)
           {
             if (SPEC::agent(P) == GRLX_AGENT_SARSA)
-              target += N.gamma * pick<double, NA>(q, a_next);
+              target += SPEC::gamma(N, rep) * pick<double, NA>(q, a_next);
             else if (SPEC::agent(P) == GRLX_AGENT_EXPECTED_SARSA)
             { // QPolicy::value (q.cpp:60-73) = sum_a Q(s',a) * EpsilonGreedySampler::distribution (greedy.cpp:220-238)
-              const double de = eps_decay * N.epsilon;
+              const double de = eps_decay * SPEC::epsilon(N, rep);
               double v = 0;
 #pragma unroll
               for (int kk = 0; kk < NA; ++kk)
@@ -637,19 +671,19 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials)
                 d += de / NA;
                 v += q[kk] * d;
               }
-              target += N.gamma * v;
+              target += SPEC::gamma(N, rep) * v;
             }
             else
             {
               double v = -__builtin_inf();
 #pragma unroll
               for (int kk = 0; kk < NA; ++kk) v = fmax(v, q[kk]);
-              target += N.gamma * v;
+              target += SPEC::gamma(N, rep) * v;
             }
           }
           delta = target - qsa;
-          const double dW = N.alpha * (target - qsa);          // LinearRepresentation::write (linear.cpp:186-196)
-          const double dT = N.alpha * delta;                   // VectorConstructor(alpha_*delta)
+          const double dW = SPEC::alpha(N, rep) * (target - qsa);          // LinearRepresentation::write (linear.cpp:186-196)
+          const double dT = SPEC::alpha(N, rep) * delta;                   // VectorConstructor(alpha_*delta)
           if (DEFER)
           { // applied on the next pass, after that pass's loads are in flight
             if (TAP && up.use_trace)
@@ -816,6 +850,13 @@ template <int ENV, int NA, bool DIAG, typename SPEC, bool DEFER = !DIAG, bool AD
 __global__ __launch_bounds__(64) GRLX_ROLLOUT_OCCUPANCY void rollout_kernel(DevParams P, int n_trials)
 {
   rollout_body<ENV, NA, DIAG, SPEC, DEFER, ADV, TAP, false>(P, n_trials);
+}
+
+// A hyper-parameter sweep: the production form (deferred update, no taps, no stamps) with SPEC = SpecSweep and the per-replica records
+template <int ENV, int NA>
+__global__ __launch_bounds__(64) GRLX_ROLLOUT_OCCUPANCY void rollout_sweep_kernel(DevParams P, int n_trials, const SweepParams *sweep)
+{
+  rollout_body<ENV, NA, false, SpecSweep, true, false, false, false>(P, n_trials, sweep);
 }
 
 // The instantiation the environment server works for.  208 (x 2: vector + accumulation registers) = 416 of the SIMD's 512 registers,

@@ -238,7 +238,7 @@ __device__ __forceinline__ void wide_rep_load(WideRep &s, const uint64_t *sh64, 
 // diagnostic instantiations stay with rollout_kernel.
 // SERVED: the environment steps come from the environment server of the wide kernels (grlx_env_server_wide.h) -- rollout_wide_served_kernel below.
 template <int ENV, int NA, int B, typename SPEC, bool SERVED>
-__device__ __forceinline__ void rollout_wide_body(const DevParams &P, int n_trials)
+__device__ __forceinline__ void rollout_wide_body(const DevParams &P, int n_trials, const SweepParams *sweep = nullptr)
 {
   static_assert(B == 2 || B == 3 || B == 4 || B == 8, "sub-batches per wave");
   static_assert(!SERVED || (B == 2 && NA == 3), "what the environment server of the wide kernels works for");
@@ -307,7 +307,7 @@ __device__ __forceinline__ void rollout_wide_body(const DevParams &P, int n_tria
   up.out_min = N.lin.out_min;
   up.out_max = N.lin.out_max;
   up.limit = N.lin.limit != 0;
-  up.ee = N.gl;
+  up.ee = N.gl;                                         // (a sweep context: the sub-batch's replica's own, set at each of its turns)
   up.cut = (N.trace_kind == GRLX_TRACE_REPLACING) ? 0.01 : 0.0001;
   up.use_trace = N.trace_kind == GRLX_TRACE_REPLACING;
   up.dW = up.dT = 0;
@@ -460,6 +460,9 @@ __device__ __forceinline__ void rollout_wide_body(const DevParams &P, int n_tria
         const int r = live ? wave0 + q : 0;
         const ReplicaState &RS = P.states[r];
         const Table tab = table_of(P, 0, r);
+        // a sweep context: the learning parameters of this sub-batch's replica, requested now and first read at the sampler
+        const typename SPEC::Rep rep = SPEC::replica(sweep, r);
+        if constexpr (SPEC::kPerReplica) up.ee = SPEC::gl(N, rep);
         WideLane c;
         if (in_memory(b)) wide_unpark_decode(c, nxt.q, nxt.i);               // requested during the previous sub-batch's turn
         else unpark_state(c, b);
@@ -523,6 +526,10 @@ __device__ __forceinline__ void rollout_wide_body(const DevParams &P, int n_tria
           up.dW = c.pd_dW;
           up.dT = c.pd_dT;
           td_update_lane<true>(c.tr, tab, up, c.pd_pos, c.pd_sh, c.pd_wp, g, j, sh_ppos, sh_fb, sh_fbflag, c.status, ev);
+          // a sweep context without a trace: the update stored p's weight straight into the table behind the loads in flight and
+          // no trace entry forwards it -- load again below (see rollout_kernel)
+          if constexpr (SPEC::kPerReplica)
+            if (!up.use_trace) ev.n = 2u;
           c.pd = false;
         }
 
@@ -609,7 +616,7 @@ __device__ __forceinline__ void rollout_wide_body(const DevParams &P, int n_tria
               if (s.time == 0.) s.eps_decay = fmax(s.eps_decay * N.decay_rate, N.decay_min);
               s.S1 = lcg_next(s.S1);
               const double rnd = lcg_double(s.S1);
-              if (rnd < s.eps_decay * N.epsilon)
+              if (rnd < s.eps_decay * SPEC::epsilon(N, rep))
               {
                 s.G = lcg_next(s.G);
                 a_next = (int)(lcg_long(s.G) % (uint32_t)NA);
@@ -626,10 +633,10 @@ __device__ __forceinline__ void rollout_wide_body(const DevParams &P, int n_tria
             if (has_next)
             {
               if (SPEC::agent(P) == GRLX_AGENT_SARSA)
-                target += N.gamma * pick<double, NA>(qv, a_next);
+                target += SPEC::gamma(N, rep) * pick<double, NA>(qv, a_next);
               else if (SPEC::agent(P) == GRLX_AGENT_EXPECTED_SARSA)
               {
-                const double de = s.eps_decay * N.epsilon;
+                const double de = s.eps_decay * SPEC::epsilon(N, rep);
                 double v = 0;
 #pragma unroll
                 for (int kk = 0; kk < NA; ++kk)
@@ -639,20 +646,20 @@ __device__ __forceinline__ void rollout_wide_body(const DevParams &P, int n_tria
                   d += de / NA;
                   v += qv[kk] * d;
                 }
-                target += N.gamma * v;
+                target += SPEC::gamma(N, rep) * v;
               }
               else
               {
                 double v = -__builtin_inf();
 #pragma unroll
                 for (int kk = 0; kk < NA; ++kk) v = fmax(v, qv[kk]);
-                target += N.gamma * v;
+                target += SPEC::gamma(N, rep) * v;
               }
             }
             const double delta = target - qsa;
             c.pd = true;
-            c.pd_dW = N.alpha * (target - qsa);
-            c.pd_dT = N.alpha * delta;
+            c.pd_dW = SPEC::alpha(N, rep) * (target - qsa);
+            c.pd_dT = SPEC::alpha(N, rep) * delta;
             c.pd_pos = c.p_pos;
             c.status |= (c.p_pos == kInvalidPos) ? ST_BAD_POS : 0u;
             c.pd_sh = c.p_sh;
@@ -827,6 +834,13 @@ template <int ENV, int NA, int B, typename SPEC>
 __global__ __launch_bounds__(64) void rollout_wide_kernel(DevParams P, int n_trials)
 {
   rollout_wide_body<ENV, NA, B, SPEC, false>(P, n_trials);
+}
+
+// A hyper-parameter sweep (SpecSweep): two sub-batches per wave, every replica with its own learning parameters
+template <int ENV, int NA>
+__global__ __launch_bounds__(64) void rollout_wide_sweep_kernel(DevParams P, int n_trials, const SweepParams *sweep)
+{
+  rollout_wide_body<ENV, NA, 2, SpecSweep, false>(P, n_trials, sweep);
 }
 
 // The instantiation the environment server of the wide kernels works for (grlx_env_server_wide.h): the same body, its environment

@@ -1,6 +1,10 @@
 // grlxd.cpp -- deployer for the accelerated path, command-line compatible with the
 // reference's `grld [-v] [-s seed] <yaml file> [yaml file...]` (base/src/deployer.cpp:38-150),
-// plus -r replicas, -t trials (override), -l (3-column golden layout), -q (no rows on stdout), and
+// plus -r replicas, -t trials (override), -l (3-column golden layout), -q (no rows on stdout),
+// -p <path>=v1,v2,... (repeatable): a grid sweep over predictor alpha / gamma / lambda and the sampler's epsilon, the study of the reference's
+// bin/grlo as the clones of one run: -r is then the repetitions per point, clone i = point * repetitions + k (points: the Cartesian product
+// in the order of the -p options, the last fastest) with seed + i and identity "@i"; <output>-<run>-sweep.txt holds the statistics per point,
+// -n: print the plan (one line per clone: i seed alpha gamma lambda epsilon) and exit before anything touches HIP, and
 // -g N: one process per GPU (rank r on the r-th visible device, started before anything touches HIP), every rank running -r replicas
 // (clones r * replicas ..., seeds and "@i" identities counted over the whole job), the learning curves reduced with one RCCL all-reduce
 // per run (multi_gpu.h); rank 0 prints the rows and writes <output>-<run>-mean.txt.  The model is experiment/multi (multi.cpp:44-75).
@@ -21,13 +25,47 @@
 
 using namespace grlx_host;
 
+namespace {
+// the parameters a sweep may vary: the four of the reference's bin/optimize.yaml that the device path holds per replica (index: GRLX_PARAM_*)
+const char *const kSweepPaths[4] = {"/experiment/agent/predictor/alpha", "/experiment/agent/predictor/gamma", "/experiment/agent/predictor/lambda",
+                                    "/experiment/agent/policy/sampler/epsilon"};
+struct SweepAxis { int param; std::vector<double> values; };
+
+SweepAxis parse_sweep_axis(const std::string &arg)
+{
+  const size_t eq = arg.find('=');
+  const std::string path = arg.substr(0, eq);
+  SweepAxis axis;
+  axis.param = -1;
+  for (int k = 0; k < 4; ++k)
+    if (path == kSweepPaths[k]) axis.param = k;
+  if (axis.param < 0)
+    throw Exception("-p: unknown path '" + path + "' (a sweep varies " + kSweepPaths[0] + ", " + kSweepPaths[1] + ", " + kSweepPaths[2] + " or " + kSweepPaths[3] + ")");
+  const std::string list = eq == std::string::npos ? "" : arg.substr(eq + 1);
+  for (size_t at = 0; at < list.size();)
+  {
+    size_t end = list.find(',', at);
+    if (end == std::string::npos) end = list.size();
+    const std::string item = list.substr(at, end - at);
+    char *stop = nullptr;
+    const double v = strtod(item.c_str(), &stop);
+    if (item.empty() || *stop != 0) throw Exception("-p " + path + ": '" + item + "' is not a number");
+    axis.values.push_back(v);
+    at = end + 1;
+  }
+  if (axis.values.empty() || (!list.empty() && list.back() == ',')) throw Exception("-p " + path + ": empty value list (expected " + path + "=v1,v2,...)");
+  return axis;
+}
+} // namespace
+
 int main(int argc, char **argv)
 {
   RunOptions opt;
   int trials_override = -1;
   int gpus = 0;
   int c;
-  while ((c = getopt(argc, argv, "vs:r:t:lqc:g:")) != -1)
+  std::vector<std::string> sweep_args;
+  while ((c = getopt(argc, argv, "vs:r:t:lqc:g:p:n")) != -1)
   {
     switch (c)
     {
@@ -39,12 +77,14 @@ int main(int argc, char **argv)
       case 'q': opt.print_rows = false; break;
       case 'c': opt.table_log2_capacity = atoi(optarg); break;
       case 'g': gpus = atoi(optarg); break;
+      case 'p': sweep_args.push_back(optarg); break;
+      case 'n': opt.plan_only = true; break;
       default: return 1;
     }
   }
   if (optind > argc - 1)
   {
-    log(0, std::string("Usage: \n  ") + argv[0] + " [-v] [-s seed] [-r replicas] [-g gpus] [-t trials] [-l] [-q] <yaml file> [yaml file...]");
+    log(0, std::string("Usage: \n  ") + argv[0] + " [-v] [-s seed] [-r replicas] [-g gpus] [-t trials] [-l] [-q] [-p path=v1,v2,...]... [-n] <yaml file> [yaml file...]");
     return 1;
   }
   if (opt.seed == 0)
@@ -52,6 +92,36 @@ int main(int argc, char **argv)
     log(0, "seed 0 (time-based seeding) is not supported; pass -s <seed>");
     return 1;
   }
+  if (!sweep_args.empty())
+  { // the grid: point-major, the Cartesian product of the axes in the order given (last fastest), every point -r times
+    try
+    {
+      if (gpus > 1) throw Exception("-p: a parameter sweep runs on one GPU (-g " + std::to_string(gpus) + " is not built)");
+      if (opt.replicas < 2) throw Exception("-p: -r (repetitions per point) must be >= 2: the standard deviation per point divides by repetitions - 1");
+      std::vector<SweepAxis> axes;
+      size_t points = 1;
+      for (const std::string &a : sweep_args)
+      {
+        axes.push_back(parse_sweep_axis(a));
+        for (size_t k = 0; k + 1 < axes.size(); ++k)
+          if (axes[k].param == axes.back().param) throw Exception(std::string("-p: ") + kSweepPaths[axes.back().param] + " is given twice");
+        points *= axes.back().values.size();
+        if (points * (size_t)opt.replicas > (1u << 24)) throw Exception("-p: more than 2^24 clones");
+      }
+      const size_t R = (size_t)opt.replicas;
+      for (size_t point = 0; point < points; ++point)
+      {
+        size_t rest = point;
+        std::vector<size_t> at(axes.size());
+        for (size_t a = axes.size(); a-- > 0;) { at[a] = rest % axes[a].values.size(); rest /= axes[a].values.size(); }
+        for (size_t a = 0; a < axes.size(); ++a) opt.sweep[axes[a].param].insert(opt.sweep[axes[a].param].end(), R, axes[a].values[at[a]]);
+      }
+      opt.sweep_repetitions = opt.replicas;
+      opt.replicas = (int)(points * R);
+    }
+    catch (Exception &e) { log(0, e.what()); return 1; }
+  }
+  if (opt.plan_only) gpus = 0;        // the plan is printed by this process, before anything touches HIP
   std::string id_file;
   if (gpus < 0 || gpus > 64) { log(0, "-g: between 1 and 64 processes"); return 1; }
   if (gpus >= 1)

@@ -1059,6 +1059,8 @@ struct BatchLearningExperimentImpl : Experiment {
   std::vector<double> run(const RunOptions &opt) override
   {
     if (runs != 1) throw Exception(path() + ": runs > 1 (Experiment::reset between runs) is not built for the batch path");
+    if (opt.sweep_repetitions > 0 || opt.plan_only)
+      throw Exception(path() + ": a parameter sweep (-p) and its plan (-n) are built for experiment/online_learning, not for experiment/batch_learning");
     grlx_fqi_config c;
     lower(&c);
     c.n_replicas = opt.replicas;
@@ -1375,6 +1377,27 @@ struct OnlineLearningExperimentImpl : OnlineLearningExperiment, StepwiseExperime
     c.max_rows = (test_interval >= 0 ? trial_cap / (test_interval + 1) : trial_cap) + 1;
     if (opt.table_log2_capacity) c.table_log2_capacity = opt.table_log2_capacity;
     std::vector<double> curve;
+    const bool sweep = opt.sweep_repetitions > 0;
+    if (sweep)
+    {
+      if (steps > 0) throw Exception(path() + ": a parameter sweep (-p) is not built together with a steps budget (steps: " + std::to_string(steps) + ")");
+      if (opt.world > 1) throw Exception(path() + ": a parameter sweep (-p) runs on one GPU (-g " + std::to_string(opt.world) + " is not built)");
+      for (int k = 0; k < 4; ++k)
+        if (!opt.sweep[k].empty() && (int)opt.sweep[k].size() != opt.replicas) throw Exception(path() + ": a sweep needs one value per clone");
+    }
+    if (opt.plan_only)
+    { // one line per clone of this process: i seed alpha gamma lambda epsilon.  Nothing has touched the device yet.
+      const double shared[4] = {c.alpha, c.gamma, c.lambda, c.epsilon};
+      for (int i = 0; i < opt.replicas; ++i)
+      {
+        char line[256];
+        int at = snprintf(line, sizeof(line), "%d %lld", opt.rank * opt.replicas + i, (long long)(opt.seed + opt.rank * opt.replicas + i));
+        for (int k = 0; k < 4; ++k)
+          at += snprintf(line + at, sizeof(line) - (size_t)at, " %.17g", opt.sweep[k].empty() ? shared[k] : opt.sweep[k][(size_t)i]);
+        std::cout << line << std::endl;
+      }
+      return curve;
+    }
     int obs_dims = 0, state_dims = 0;
     grlx_env_dims(c.env, &state_dims, &obs_dims);
     if (exporter || env_exporter)
@@ -1401,6 +1424,23 @@ struct OnlineLearningExperimentImpl : OnlineLearningExperiment, StepwiseExperime
     for (int i = 0; i < opt.replicas; ++i) seeds[(size_t)i] = opt.seed + first_clone + i;
     grlx_ctx *ctx = nullptr;
     if (grlx_create(&c, seeds.data(), &ctx) != GRLX_OK) throw Exception(grlx_last_error());
+    if (sweep)
+    { // grlx_set_replica_params validates one parameter against the other three as they stand.  So that a grid whose final (gamma, lambda)
+      // pairs are all valid is never refused on the way there, lambda first goes to min(the yaml's, the grid's) -- a shorter trace is
+      // always valid --, then gamma, then lambda.
+      std::vector<std::pair<int, const double *>> calls;
+      std::vector<double> lambda_low;
+      if (!opt.sweep[GRLX_PARAM_GAMMA].empty() && !opt.sweep[GRLX_PARAM_LAMBDA].empty())
+      {
+        for (double v : opt.sweep[GRLX_PARAM_LAMBDA]) lambda_low.push_back(v < c.lambda ? v : c.lambda);
+        calls.push_back({GRLX_PARAM_LAMBDA, lambda_low.data()});
+      }
+      for (int k = 0; k < 4; ++k)
+        if (!opt.sweep[k].empty()) calls.push_back({k, opt.sweep[k].data()});
+      for (const auto &call : calls)
+        if (grlx_set_replica_params(ctx, call.first, call.second) != GRLX_OK)
+        { std::string e = grlx_last_error(); grlx_destroy(ctx); throw Exception(e); }
+    }
     for (int rr = run_offset; rr < runs + run_offset; ++rr)
     {
       // Load policy every run (online_learning.cpp:140-150 -> ParameterizedRepresentation {action: load},
@@ -1525,6 +1565,11 @@ struct OnlineLearningExperimentImpl : OnlineLearningExperiment, StepwiseExperime
       std::vector<int64_t> trial((size_t)n), stp((size_t)n);
       std::vector<double> reward((size_t)n);
       std::vector<double> episode_time((size_t)n);     // total_time: sum of tau = steps of the trial (discrete_time, modeled.cpp:209-212)
+      // a sweep: the "simple regret" of every clone (bin/grllib.py:71-75) -- the mean of the last len(rows) / 20 row rewards, read as the
+      // reference's workers read them: from the text of the clone's output (so the figures can be recomputed from the files)
+      std::vector<double> regret;
+      if (sweep && n / 20 == 0)
+      { grlx_destroy(ctx); throw Exception(path() + ": a sweep's simple regret needs at least 20 rows per run (this run wrote " + std::to_string(n) + ")"); }
       for (int i = 0; i < opt.replicas; ++i)
       {
         grlx_read_rows(ctx, i, 0, n, trial.data(), stp.data(), reward.data());
@@ -1548,6 +1593,43 @@ struct OnlineLearningExperimentImpl : OnlineLearningExperiment, StepwiseExperime
           if (i == 0 && opt.rank == 0 && opt.print_rows) std::cout << oss.str() << std::endl;
         }
         if (i == 0) curve = reward;
+        if (sweep)
+        {
+          const int sample = n / 20;
+          double sum = 0;
+          for (int k = n - sample; k < n; ++k)
+          { // the reward column as written above
+            std::ostringstream col;
+            if (opt.legacy_rows) col << reward[(size_t)k];
+            else col << std::setprecision(3) << std::fixed << reward[(size_t)k];
+            sum += strtod(col.str().c_str(), nullptr);
+          }
+          regret.push_back(sum / sample);
+        }
+      }
+      if (sweep && opt.rank == 0 && !output.empty())
+      { // bin/grlo:46-48 per point: avg, stddev (n - 1), stderr = stddev / sqrt(n); every sum left to right
+        std::ostringstream name;
+        name << output << "-" << rr << "-sweep.txt";
+        std::ofstream ofs(name.str());
+        const int R = opt.sweep_repetitions, points = opt.replicas / R;
+        const double shared[4] = {c.alpha, c.gamma, c.lambda, c.epsilon};
+        for (int pt = 0; pt < points; ++pt)
+        {
+          const double *res = regret.data() + (size_t)pt * (size_t)R;
+          double sum = 0;
+          for (int k = 0; k < R; ++k) sum += res[k];
+          const double avg = sum / R;
+          double sq = 0;
+          for (int k = 0; k < R; ++k) sq += (res[k] - avg) * (res[k] - avg);
+          const double stddev = std::sqrt(sq / (R - 1)), stderr_ = stddev / std::sqrt((double)R);
+          char line[384];
+          int at = snprintf(line, sizeof(line), "%d", pt);
+          for (int k = 0; k < 4; ++k)
+            at += snprintf(line + at, sizeof(line) - (size_t)at, " %.17g", opt.sweep[k].empty() ? shared[k] : opt.sweep[k][(size_t)pt * (size_t)R]);
+          snprintf(line + at, sizeof(line) - (size_t)at, " %d %.17g %.17g %.17g", R, avg, stddev, stderr_);
+          ofs << line << std::endl;
+        }
       }
       if (opt.reducer && n > 0)
       { // the learning curve over the clones of ALL ranks: per row {sum, sum of squares, count} of this device's replicas (grlx_curve_stats,
@@ -1619,6 +1701,8 @@ struct MultiExperiment : OnlineLearningExperiment {
   }
   std::vector<double> run(const RunOptions &opt) override
   {
+    if (opt.sweep_repetitions > 0)
+      throw Exception(path() + ": a parameter sweep (-p) lays out its own clones; it is not built together with experiment/multi");
     RunOptions clones = opt;
     clones.replicas = instances * std::max(1, opt.replicas);
     return prototype->run(clones);

@@ -18,6 +18,15 @@ struct RunOptions {
   int table_log2_capacity = 0;
   bool legacy_rows = false;     // 3-column rows as in the reference's committed golden files
   bool print_rows = true;
+  // `grlxd -p <path>=v1,v2,...`: a grid sweep over predictor alpha / gamma / lambda and the sampler's epsilon -- the study of the reference's
+  // bin/grlo (bin/optimize.yaml) as the replicas of ONE device context.  sweep[k] (k = GRLX_PARAM_*) is empty (the yaml's value for every
+  // clone) or holds the value of every clone; clone i = point * sweep_repetitions + k, the points being the Cartesian product of the
+  // axes in the order given, the last one fastest.  replicas = points * sweep_repetitions.  After every run rank 0 writes
+  // <output>-<run>-sweep.txt: per point its index, the four values, and n / avg / stddev / stderr of the clones' simple regret as
+  // bin/grlo prints them.
+  std::vector<double> sweep[4];
+  int sweep_repetitions = 0;    // > 0: a sweep
+  bool plan_only = false;       // `grlxd -n`: print one line per clone (i seed alpha gamma lambda epsilon) and run nothing
 };
 
 // Environment::step (environment.h:48-51 -> ModeledEnvironment::step, modeled.cpp:160-213) for a batch of instances:

@@ -62,6 +62,32 @@ def compass_walker_q_config(n_replicas=1, agent=capi.AGENT_Q, **overrides) -> ca
     return cfg
 
 
+def sweep_grid(repetitions, **axes):
+    """The replicas of a grid sweep: the Cartesian product of the axes in the order given, the last axis fastest, every point
+    repeated `repetitions` times -- replica i = point * repetitions + k.  Returns {axis: [value of replica i]} (plain lists,
+    ready for Runner.set_replica_params); `grlxd -p` lays its clones out in the same order."""
+    repetitions = int(repetitions)
+    if repetitions < 1:
+        raise ValueError("repetitions must be >= 1")
+    names = list(axes)
+    values = [list(axes[n]) for n in names]
+    if not names or any(len(v) == 0 for v in values):
+        raise ValueError("every axis needs at least one value")
+    points = 1
+    for v in values:
+        points *= len(v)
+    out = {n: [] for n in names}
+    for point in range(points):
+        rest = point
+        at = [0] * len(names)
+        for a in range(len(names) - 1, -1, -1):
+            at[a] = rest % len(values[a])
+            rest //= len(values[a])
+        for a, n in enumerate(names):
+            out[n].extend([float(values[a][at[a]])] * repetitions)
+    return out
+
+
 def _ptr(arr, ctype):
     return arr.ctypes.data_as(C.POINTER(ctype))
 
@@ -161,6 +187,74 @@ class Runner:
 
     def curve_stats(self, out_dev_ptr: int, first: int, count: int, stream: int = 0):
         capi.check(self.lib.grlx_curve_stats(self._ctx, first, count, C.c_void_p(out_dev_ptr), C.c_void_p(stream)))
+
+    def curve_stats_grouped(self, out_dev_ptr: int, first: int, count: int, group_size: int, stream: int = 0):
+        """grlx_curve_stats per group of `group_size` consecutive replicas (the repetitions of one sweep point):
+        device buffer out[count][n_replicas // group_size][3]."""
+        capi.check(self.lib.grlx_curve_stats_grouped(self._ctx, first, count, int(group_size), C.c_void_p(out_dev_ptr), C.c_void_p(stream)))
+
+    # ---- hyper-parameter sweep: alpha / gamma / lambda / epsilon per replica (include/grlx.h) ----
+    def set_replica_params(self, alpha=None, gamma=None, lambda_=None, epsilon=None):
+        """One value per replica for each parameter given (see sweep_grid); the others keep the configuration's value.
+        Only before the first run of the context; makes it a sweep context.
+
+        grlx_set_replica_params takes one parameter per call and validates it against the other three as they stand, so a grid
+        whose final (gamma, lambda) pairs are all valid could be refused on the way there (gamma = 0.99 beside the
+        configuration's lambda = 0.65, though its own lambda is 0.4).  With both given, lambda therefore first goes to
+        min(current, new) per replica -- a shorter trace is always valid -- then gamma, then lambda: every valid grid is
+        accepted in any order of values.  A refusal leaves all four parameters as they were before the call."""
+        given = {}
+        for name, values in (("alpha", alpha), ("gamma", gamma), ("lambda_", lambda_), ("epsilon", epsilon)):
+            if values is None:
+                continue
+            v = np.ascontiguousarray(values, dtype=np.float64)
+            if v.shape != (self.cfg.n_replicas,):
+                raise ValueError("need one value per replica")
+            given[name] = v
+        if not given:
+            return
+        before = self.replica_params()
+        applied = []
+        try:
+            for name in ("alpha", "epsilon"):
+                if name in given:
+                    self._set_param(name, given[name])
+                    applied.append(name)
+            if "gamma" in given and "lambda_" in given:
+                applied += ["gamma", "lambda_"]
+                self._set_gamma_lambda(before["lambda_"], given["gamma"], given["lambda_"])
+            else:
+                for name in ("gamma", "lambda_"):
+                    if name in given:
+                        self._set_param(name, given[name])
+            # (a single gamma or lambda_ that is refused was not applied)
+        except capi.GrlxError:
+            if "gamma" in applied:
+                self._set_gamma_lambda(self.replica_params()["lambda_"], before["gamma"], before["lambda_"])
+            for name in applied:
+                if name in ("alpha", "epsilon"):
+                    self._set_param(name, before[name])
+            raise
+
+    _PARAMS = {"alpha": capi.PARAM_ALPHA, "gamma": capi.PARAM_GAMMA, "lambda_": capi.PARAM_LAMBDA, "epsilon": capi.PARAM_EPSILON}
+
+    def _set_param(self, name, v):
+        v = np.ascontiguousarray(v, dtype=np.float64)
+        capi.check(self.lib.grlx_set_replica_params(self._ctx, self._PARAMS[name], _ptr(v, C.c_double)))
+
+    def _set_gamma_lambda(self, lambda_now, gamma, lambda_):
+        self._set_param("lambda_", np.minimum(lambda_now, lambda_))      # (a NaN stays a NaN and is refused here, by name)
+        self._set_param("gamma", gamma)
+        self._set_param("lambda_", lambda_)
+
+    def replica_params(self):
+        """dict(alpha, gamma, lambda_, epsilon) of float64[n_replicas]: what every replica runs with."""
+        out = {}
+        for name, param in (("alpha", capi.PARAM_ALPHA), ("gamma", capi.PARAM_GAMMA), ("lambda_", capi.PARAM_LAMBDA), ("epsilon", capi.PARAM_EPSILON)):
+            v = np.zeros(self.cfg.n_replicas, np.float64)
+            capi.check(self.lib.grlx_get_replica_params(self._ctx, param, _ptr(v, C.c_double)))
+            out[name] = v
+        return out
 
     def step_counts(self):
         a, b = C.c_uint64(), C.c_uint64()

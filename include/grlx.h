@@ -235,6 +235,30 @@ int  grlx_read_row_times(grlx_ctx *ctx, int replica, int first, int count, doubl
  * all-reduce of the multi-GPU path. */
 int  grlx_curve_stats(grlx_ctx *ctx, int first, int count, double *out_dev, void *stream);
 
+/* ... per group of group_size consecutive replicas: out[count][n_replicas / group_size][3], group q = the replicas
+ * [q * group_size, (q + 1) * group_size) -- the repetitions of one point of a sweep.  Same fixed order (every thread strided over its
+ * group, then the tree): with group_size == n_replicas the result equals grlx_curve_stats bit for bit.  n_replicas % group_size != 0
+ * is GRLX_ERR_INVALID. */
+int  grlx_curve_stats_grouped(grlx_ctx *ctx, int first, int count, int group_size, double *out_dev, void *stream);
+
+/* --- hyper-parameter sweep: one context, a different configuration per replica -------------------------------------------------
+ * The reference's study (bin/grlo over bin/optimize.yaml) varies predictor/alpha, predictor/gamma, predictor/lambda and
+ * sampler/epsilon and runs every (point, repetition) as a process of its own; here they are the replicas of one context.
+ * grlx_set_replica_params gives every replica its own value of ONE of the four (values[n_replicas]); parameters never set keep the
+ * configuration's value for every replica, and grlx_get_replica_params returns what holds (before any set: the configuration's).
+ * Allowed only between grlx_create and the first launch of the context (grlx_run, grlx_run_steps, a per-step call); persists
+ * across grlx_reset_run.  Every replica's values are validated as grlx_create validates the shared ones (finite; with a replacing
+ * trace gamma*lambda in (0,1) and its trace within the register trace's ten entries): a violation is GRLX_ERR_INVALID naming the
+ * replica and the value, and nothing is applied.
+ * The first set makes the context a SWEEP context.  Built for: SARSA / Q / Expected SARSA, a replacing trace or none, no target
+ * network, safe = 0, no taps, no diagnostics, not GRLX_ENV_EXTERNAL, replicas_per_wave 0, 4 or 8 (the automatic choice then never
+ * exceeds 8) -- otherwise GRLX_ERR_INVALID naming what is not built.  A sweep context runs the generic instantiation
+ * (grlx_last_kernel: GRLX_KERNEL_GENERIC) without the environment server; grlx_agent_*, grlx_env_start / _advance and
+ * grlx_set_diag(ctx, 1 | 2) return GRLX_ERR_INVALID on it, never a silent run on the shared values. */
+enum { GRLX_PARAM_ALPHA = 0, GRLX_PARAM_GAMMA = 1, GRLX_PARAM_LAMBDA = 2, GRLX_PARAM_EPSILON = 3 };
+int  grlx_set_replica_params(grlx_ctx *ctx, int param, const double *values /*[n_replicas]*/);
+int  grlx_get_replica_params(grlx_ctx *ctx, int param, double *values /*[n_replicas]*/);
+
 /* Which instantiation of the rollout kernel the last grlx_run launched (tests and benchmarks check that
  * the configuration they mean to measure takes the path they mean to measure). */
 enum { GRLX_KERNEL_NONE = 0,          /* nothing launched yet                                                  */

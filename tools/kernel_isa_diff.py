@@ -71,7 +71,8 @@ def main():
     n_diff = 0
     for k in names:
         if k not in a or k not in b:
-            print(f"| `{k}` | only in {'A' if k in a else 'B'} | | | | | |")
+            one = a[k] if k in a else b[k]                                   # a kernel of one build only: its own figures
+            print(f"| `{k}` | only in {'A' if k in a else 'B'} ({len(one[0])} instructions) | " + " | ".join(str(one[1].get(f)) for f in FIELDS) + " |")
             n_diff += 1
             continue
         same = a[k][0] == b[k][0]
