@@ -349,6 +349,14 @@ struct grlx_ctx {
   std::vector<double> sweep_host[4];
   SweepParams  *sweep_dev = nullptr;
   bool         sweep = false;
+  // A context WITHOUT a trace (GRLX_TRACE_NONE).  The deferred update stores p's weight straight into the table, behind the loads of the
+  // next step's weights that are already in flight, and no trace entry forwards it to them (p of consecutive steps is often the same
+  // slot); only the instantiations that load again after such an update, or that update in place, equal the reference there:
+  //   no_trace_td: SARSA / Q / Expected SARSA without target network and claim table run the sweep kernels on records that all hold the
+  //                configuration's values (sweep_dev, made at create): at most 8 replicas per wave, no environment server
+  //   no_trace_ac: the actor-critic runs the instantiation that updates the critic in place: 4 replicas per wave
+  // (QV, advantage learning, target networks, the claim table and the per-step entries update in place anyway.)
+  bool         no_trace_td = false, no_trace_ac = false;
   bool         launched = false;          // a rollout or per-step kernel has run in this context: its replicas' parameters are fixed
 };
 
@@ -576,6 +584,12 @@ int grlx_create(const grlx_config *cfg, const int64_t *seeds, grlx_ctx **out)
         (cfg->env == GRLX_ENV_ACROBOT || cfg->env == GRLX_ENV_COMPASS_WALKER) && (N + simds - 1) / simds >= 15)
       rpw = (cfg->env == GRLX_ENV_COMPASS_WALKER && (N + simds - 1) / simds >= 30) ? 32 : 16;
     if (!has_wide || P.tap_capacity > 0) rpw = 4;
+    // without a trace (see grlx_ctx): what runs is the sweep kernels' layouts (4, 8) or the in-place actor-critic kernel (4)
+    const bool td_agent = cfg->agent == GRLX_AGENT_SARSA || cfg->agent == GRLX_AGENT_Q || cfg->agent == GRLX_AGENT_EXPECTED_SARSA;
+    ctx->no_trace_td = cfg->trace == GRLX_TRACE_NONE && td_agent && cfg->target_interval == 0 && cfg->projector.safe == 0 && cfg->env != GRLX_ENV_EXTERNAL;
+    ctx->no_trace_ac = cfg->trace == GRLX_TRACE_NONE && cfg->agent == GRLX_AGENT_AC && cfg->env != GRLX_ENV_EXTERNAL;
+    if (ctx->no_trace_td && rpw > 8) rpw = 8;
+    if (ctx->no_trace_ac) rpw = 4;
     P.replicas_per_wave = rpw;
     P.wave_limit = cfg->wave_limit > 0 ? cfg->wave_limit : simds;      // these kernels hold a SIMD's whole register file: one wave per SIMD
   }
@@ -629,6 +643,14 @@ int grlx_create(const grlx_config *cfg, const int64_t *seeds, grlx_ctx **out)
     const size_t bytes = ((size_t)N * sizeof(double)) << logC;
     CTX_TRY(hipMalloc((void **)&ctx->tvals, bytes));
     CTX_TRY(hipMemset(ctx->tvals, 0xFF, bytes));                     // all ones = not materialised
+  }
+  if (ctx->no_trace_td)
+  { // the records of the sweep kernels, every replica with the configuration's values (grlx_set_replica_params overwrites them)
+    SweepParams w;
+    w.alpha = P.alpha; w.gamma = P.gamma; w.gl = P.gl; w.epsilon = P.epsilon;
+    std::vector<SweepParams> rec((size_t)N, w);
+    CTX_TRY(hipMalloc((void **)&ctx->sweep_dev, sizeof(SweepParams) * (size_t)N));
+    CTX_TRY(hipMemcpy(ctx->sweep_dev, rec.data(), sizeof(SweepParams) * (size_t)N, hipMemcpyHostToDevice));
   }
   if (P.tap_capacity > 0)
   {
@@ -721,6 +743,9 @@ int grlx_set_diag(grlx_ctx *ctx, int enable)
 {
   if (!ctx) return fail(GRLX_ERR_INVALID, "null ctx");
   if (enable && ctx->sweep) return fail(GRLX_ERR_INVALID, "diagnostics are not built for a sweep context (grlx_set_replica_params)");
+  if (enable == 2 && ctx->cfg.trace == GRLX_TRACE_NONE)
+    return fail(GRLX_ERR_INVALID, "stamps of the production ordering (grlx_set_diag 2) are not built for a context without a trace "
+                                  "(trace = GRLX_TRACE_NONE): use the in-place stamps (grlx_set_diag 1)");
   const size_t waves = ((size_t)ctx->P.n_replicas + kReplicasPerWave - 1) / kReplicasPerWave;
   if (enable && !ctx->diag)
   {
@@ -943,15 +968,17 @@ static int run_trials(grlx_ctx *ctx, int n_trials, uint64_t steps_budget, void *
       }
     }
     if (ctx->poison) HIP_TRY(launch_poison_registers(ctx->poison_pattern, (hipStream_t)stream));
+    // stamps and per-step taps are recorded by instantiations of their own, which a context without a trace may run as they are
+    const bool recorded = Pb.diag_out != nullptr || (Pb.tap_replica >= 0 && Pb.tap_capacity > 0);
     if (ctx->cfg.agent == GRLX_AGENT_AC)
-      HIP_TRY(launch_rollout_ac(Pb, n, (hipStream_t)stream, &ctx->last_kernel));
+      HIP_TRY(launch_rollout_ac(Pb, n, (hipStream_t)stream, &ctx->last_kernel, ctx->no_trace_ac));
     else if (ctx->cfg.agent == GRLX_AGENT_QV)
       HIP_TRY(launch_rollout_qv(Pb, n, (hipStream_t)stream, &ctx->last_kernel));
     else if (ctx->cfg.target_interval > 0 || ctx->cfg.projector.safe != 0)
       HIP_TRY(launch_rollout_tgt(Pb, n, (hipStream_t)stream, &ctx->last_kernel));
     else if (ctx->cfg.trace == GRLX_TRACE_ACCUMULATING)
       HIP_TRY(launch_rollout_acc(Pb, n, (hipStream_t)stream, &ctx->last_kernel));
-    else if (ctx->sweep)        // (without the environment server)
+    else if (ctx->sweep || (ctx->no_trace_td && !recorded))        // (without the environment server)
       HIP_TRY(launch_rollout(Pb, n, (hipStream_t)stream, &ctx->last_kernel, ctx->sweep_dev));
     else if (ctx->env_server && env_server_serves(Pb) && (size_t)ctx->P.n_replicas * env_server_mail_bytes(Pb) < (1ull << 31) && env_server_ready(ctx))
     { // the server's launch forks off the caller's stream and joins it again: for the caller, still one stream-ordered operation

@@ -164,7 +164,8 @@ hipError_t launch_rollout(const DevParams &P, int n_trials, hipStream_t stream, 
 bool       env_server_serves(const DevParams &P);                                   // is this context's rollout kernel one the environment server works for?
 size_t     env_server_mail_bytes(const DevParams &P);                               // ... and the size of a replica's mailbox there (0: not served)
 hipError_t launch_env_server(const DevParams &P, hipStream_t stream);
-hipError_t launch_rollout_ac(const DevParams &P, int n_trials, hipStream_t stream, int *variant);
+// in_place: the instantiation that updates the critic in place (a context without a trace, grlx_api.cpp; 4 replicas per wave)
+hipError_t launch_rollout_ac(const DevParams &P, int n_trials, hipStream_t stream, int *variant, bool in_place = false);
 hipError_t launch_rollout_qv(const DevParams &P, int n_trials, hipStream_t stream, int *variant);
 hipError_t launch_rollout_acc(const DevParams &P, int n_trials, hipStream_t stream, int *variant);
 hipError_t launch_rollout_tgt(const DevParams &P, int n_trials, hipStream_t stream, int *variant);

@@ -107,9 +107,11 @@ hipError_t launch_poison_registers(uint32_t pattern, hipStream_t stream)
 
 // ------------------------------------------------------------- launchers ---
 
-hipError_t launch_rollout_ac(const DevParams &P, int n_trials, hipStream_t stream, int *variant)
+hipError_t launch_rollout_ac(const DevParams &P, int n_trials, hipStream_t stream, int *variant, bool in_place)
 {
-  const bool taps = P.tap_replica >= 0 && P.tap_capacity > 0;          // recorded by the in-place instantiation
+  // taps are recorded by the in-place instantiation; a context without a trace runs it too (in_place): the deferred critic update
+  // stores p's weight behind the loads of V(s') already in flight, and without a trace nothing forwards it to them
+  const bool taps = in_place || (P.tap_replica >= 0 && P.tap_capacity > 0);
   if (variant) *variant = taps ? GRLX_KERNEL_IN_PLACE : GRLX_KERNEL_GENERIC;
   int waves = (P.n_replicas + kReplicasPerWave - 1) / kReplicasPerWave;
   if (!taps && P.replicas_per_wave >= 8)

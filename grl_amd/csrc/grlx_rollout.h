@@ -478,9 +478,11 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials, c
           up.dW = pd_dW;
           up.dT = pd_dT;
           td_update_lane<true>(tr, tab, up, pd_pos, pd_sh, pd_wp, g, j, sh_ppos, sh_fb, sh_fbflag, status, ev);
-          // a sweep context without a trace: the update stored p's weight straight into the table, behind the loads of Q(s', .)
-          // already in flight, and no trace entry forwards it (p of consecutive steps is often the same slot) -- load again below
-          if constexpr (SPEC::kPerReplica)
+          // without a trace the update stored p's weight straight into the table, behind the loads of Q(s', .) already in flight,
+          // and no trace entry forwards it (p of consecutive steps is often the same slot) -- load again below.  Built into the
+          // instantiations a context without a trace launches: the sweep kernels (grlx_api.cpp routes every plain one there) and the
+          // step-by-step records of this ordering (TAP with DEFER); the others are never launched without a trace.
+          if constexpr (SPEC::kPerReplica || TAP)
             if (!up.use_trace) ev.n = 2u;
           pd = false;
         }

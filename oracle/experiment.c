@@ -309,7 +309,7 @@ static double sarsa_update(orc_exp *e, const double *prev_obs, double prev_actio
   }
   double delta = target - lin_read(e, 0, &s->representation, &p);
   lin_write(e, 0, &s->representation, &p, target, s->alpha);
-  if (s->trace != ORC_TRACE_NONE)
+  if (s->trace != ORC_TRACE_NONE)                              /* sarsa.cpp:112-116 `if (trace_)` (no trace: the write at :110 with alpha is the whole update); finalize clears only `if (trace_)`, :130-131 */
   {
     double ee = orc_m_powtau(s, s->gamma * s->lambda, tau);
     lin_update_trace(e, 0, &s->representation, &e->trace, s->alpha * delta, ee);
@@ -355,7 +355,7 @@ static double expected_sarsa_update(orc_exp *e, const double *prev_obs, double p
     target += orc_m_powtau(s, s->gamma, tau) * expected_value(e, obs);
   double delta = target - lin_read(e, 0, &s->representation, &p);
   lin_write(e, 0, &s->representation, &p, target, s->alpha);
-  if (s->trace != ORC_TRACE_NONE)
+  if (s->trace != ORC_TRACE_NONE)                              /* sarsa.cpp:182-186 `if (trace_)` after the write at :181; finalize :200-201 */
   {
     double ee = orc_m_powtau(s, s->gamma * s->lambda, tau);
     lin_update_trace(e, 0, &s->representation, &e->trace, s->alpha * delta, ee);
@@ -389,7 +389,7 @@ static double q_update(orc_exp *e, const double *prev_obs, double prev_action, d
     project_sa(e, prev_obs, action, &pc);
   }
   lin_write(e, 0, &s->representation, &p, target, s->alpha);
-  if (s->trace != ORC_TRACE_NONE)
+  if (s->trace != ORC_TRACE_NONE)                              /* advantage.cpp:101-105 `if (trace_)` after the write at :98 (QPredictor); finalize :180-181 */
   {
     double ee = orc_m_powtau(s, s->gamma * s->lambda, tau);
     lin_update_trace(e, 0, &s->representation, &e->trace, s->alpha * delta, ee);
@@ -426,7 +426,7 @@ static double advantage_update(orc_exp *e, const double *prev_obs, double prev_a
   }
   double delta = target - a;
   lin_write(e, 0, &s->representation, &p, target, s->alpha);
-  if (s->trace != ORC_TRACE_NONE)
+  if (s->trace != ORC_TRACE_NONE)                              /* advantage.cpp:261-265 `if (trace_)` after the write at :258 (AdvantagePredictor); finalize :276-277 */
   {
     double ee = orc_m_powtau(s, s->gamma * s->lambda, tau);
     lin_update_trace(e, 0, &s->representation, &e->trace, s->alpha * delta, ee);
@@ -477,7 +477,7 @@ static double td_critic(orc_exp *e, const double *prev_obs, double tau, double r
   }
   double delta = target - lin_read(e, 0, &s->representation, &p);
   lin_write(e, 0, &s->representation, &p, target, s->alpha);
-  if (s->trace != ORC_TRACE_NONE)
+  if (s->trace != ORC_TRACE_NONE)                              /* predictors/td.cpp:82-86 `if (trace_)` after the write at :80; finalize :97-98 */
   {
     double ee = orc_m_powtau(s, s->gamma * s->lambda, tau);
     lin_update_trace(e, 0, &s->representation, &e->trace, s->alpha * delta, ee);
@@ -525,7 +525,7 @@ static double qv_update(orc_exp *e, const double *prev_obs, double prev_action, 
   double delta = target - lin_read(e, 1, &s->actor_representation, &vp);
   lin_write(e, 0, &s->representation, &qp, target, s->alpha);            /* Q update */
   lin_write(e, 1, &s->actor_representation, &vp, target, s->beta);       /* V update */
-  if (s->trace != ORC_TRACE_NONE)
+  if (s->trace != ORC_TRACE_NONE)                              /* qv.cpp:97-101 `if (trace_)` after the Q write (:92) and the V write (:95); finalize :113-114 */
   {
     double ee = orc_m_powtau(s, s->gamma * s->lambda, tau);
     lin_update_trace(e, 1, &s->actor_representation, &e->trace, s->beta * delta, ee);

@@ -46,10 +46,11 @@ def replica_spec(spec, params, k):
 _oracle_cache = {}      # every test runs clean and poisoned: the oracle's half is computed once
 
 
-def oracle_run(spec, seed, plan, memory):
+def oracle_run(spec, seed, plan, memory, tables=(0,)):
     """plan: a tuple of ("run", trials) | ("steps", budget) | ("reset",) applied in order; returns the rows of every run segment
-    (a list per reset-separated run), the RNG positions, the environment state, the weight slots and their values"""
-    key = (bytes(spec), int(seed), plan, int(memory))
+    (a list per reset-separated run), the RNG positions, the environment state, the weight slots and their values (`w`: table 0;
+    `w1`: the second table of a two-table agent, when `tables` names it)"""
+    key = (bytes(spec), int(seed), plan, int(memory), tuple(tables))
     if key not in _oracle_cache:
         e = ob.Experiment(spec, seed=int(seed))
         runs = [[]]
@@ -65,12 +66,16 @@ def oracle_run(spec, seed, plan, memory):
         slots = np.random.default_rng(11).integers(0, memory, 2000).astype(np.uint32)
         rows = [[(x.trial, x.steps, x.reward, x.time) for x in run] for run in runs]
         _oracle_cache[key] = dict(rows=rows, rng=list(e.rng())[:3], state=np.array(e.state()), slots=slots, w=np.array(e.weights(slots)))
+        for t in tables:
+            if t != 0:
+                _oracle_cache[key]["w%d" % t] = np.array(e.weights(slots, table=t))
         e.close()
     return _oracle_cache[key]
 
 
-def check_replica(r, k, want, what, memory):
-    """the last run of `want` against the rows the context holds now; streams, state and weights against the oracle's end"""
+def check_replica(r, k, want, what, memory, n_rng=3):
+    """the last run of `want` against the rows the context holds now; streams, state and weights (of every table `want` holds) against
+    the oracle's end.  n_rng: the streams the graph has (the actor-critic graph has no samplers: 2)"""
     rows = want["rows"][-1]
     t, s, rew = r.rows(k)
     assert len(rows) == r.replica_rows(k), f"{what}: row count"
@@ -78,9 +83,11 @@ def check_replica(r, k, want, what, memory):
     assert list(s) == [x[1] for x in rows], f"{what}: steps column"
     assert_bit_equal(rew, [x[2] for x in rows], f"{what}: returns")
     assert_bit_equal(r.row_times(k, 0, len(rows)), [x[3] for x in rows], f"{what}: episode times")
-    assert list(r.rng(k))[:3] == want["rng"], f"{what}: RNG positions"
+    assert list(r.rng(k))[:n_rng] == want["rng"][:n_rng], f"{what}: RNG positions"
     assert_bit_equal(r.env_state(k), want["state"], f"{what}: env state")
     assert_bit_equal(r.weights(k, want["slots"]), want["w"], f"{what}: weights")
+    if "w1" in want:
+        assert_bit_equal(r.weights(k, want["slots"], 1), want["w1"], f"{what}: weights of the second table")
 
 
 def sweep_vs_oracle(grlx, make, n, chunks, rpw, seeds=None, params=None, **over):

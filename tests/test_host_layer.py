@@ -257,3 +257,13 @@ def test_deployer_multi_gpu_ranks_fail_cleanly_without_devices(tmp_path):
     assert res.returncode == 1
     assert "2 of 2 ranks failed" in res.stderr + res.stdout and "multi-GPU" in res.stderr + res.stdout
     assert not list(tmp_path.glob("*.txt"))
+
+
+def test_a_predictor_without_a_trace_block_is_accepted(grlxd, tmp_path):
+    """`trace` is an optional parameter of the predictors (sarsa.cpp:45): without the block the host layer builds a configuration
+    with GRLX_TRACE_NONE (objects.cpp, `pred->trace ? ... : GRLX_TRACE_NONE`) instead of refusing the yaml.  `-n` stops after the
+    configuration is lowered, before anything touches a device; what such a context computes is tests/test_gpu_no_trace.py's."""
+    block = "      trace:\n        type: trace/enumerated/replacing\n"
+    res = run(grlxd, ["-s", "1", "-r", "2", "-n", _variant(tmp_path, block, "")], tmp_path)
+    assert res.returncode == 0, res.stderr
+    assert [ln.split()[:2] for ln in res.stdout.strip().split("\n")] == [["0", "1"], ["1", "2"]]
