@@ -75,6 +75,15 @@ __device__ __forceinline__ void unit_store(MailUnit *p, double v, unsigned long 
   // (s_nop: a store of more than 8 bytes reads its data registers a cycle late, and the assembler does not see into this string)
   asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(d) : "memory");
 }
+// server side: unit I of a candidate, at a constant offset from the candidate's first unit (the address is computed once for the five)
+template <int I>
+__device__ __forceinline__ void unit_store_at(MailUnit *p, double v, unsigned long long seq)
+{
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  mail_u32x4 d;
+  d.x = (unsigned)b; d.y = (unsigned)(b >> 32); d.z = (unsigned)seq; d.w = (unsigned)(seq >> 32);
+  asm volatile("global_store_dwordx4 %0, %1, off offset:%2 sc1\n\ts_nop 1" ::"v"(p), "v"(d), "n"(I * (int)sizeof(MailUnit)) : "memory");
+}
 // server side: the three units of a start state, all loads in flight together, then ONE wait; true when every unit carries `seq`
 // (inline assembly, waited for on the spot: nothing else is in flight in the server when it reads a start state)
 template <int N>
@@ -164,8 +173,13 @@ __device__ __forceinline__ bool mail_take(const DevParams &N, const MailBox &b, 
 // stream.  When the command "the step was taken with action a*" arrives, the three lanes (a*, .) hold what the rollout wave asks for next and
 // store it at once; only then do all nine integrate the level after it, each from the state lane (a*, its a) held.  The integration is off
 // the path between a command and its answer (two trips through memory), at the same number of instructions per step.
-// Registers: 48 (x 2: vector + accumulation) = 96 of a SIMD's 512, beside the 416 of rollout_served_kernel.  The constants of the dynamics
-// stay literals here (PIN = false).
+// Registers: 48 (x 2: vector + accumulation) = 96 of a SIMD's 512, beside the 416 of rollout_served_kernel (83-85 used).  The pair is bound by the
+// instructions its two waves issue, so what counts here is the length of the path of one command:
+//   * the constants of the dynamics are made ONCE, before the loop (Env::server_consts): literals, except the additive constant of each
+//     fma(z, k1, k0) of the sine's polynomials, which is held in a vector register -- an instruction reads one scalar operand, and
+//     with both constants scalar the compiler copied one into a vector register beside every use;
+//   * the five units of an answer are stored from one address (unit_store_at);
+//   * the handling of a command is flat (see the loop).
 template <int ENV, int NA, typename SPEC>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(48))) void env_server_kernel(DevParams P)
 {
@@ -189,6 +203,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(48))) void env_s
   unsigned idle = 0;
   bool seen = false;
   mail_setprio((P.env_tune >> 2) & 3u);
+  const typename Env<ENV>::ServerConsts ec = Env<ENV>::server_consts();     // once: eight register pairs for the whole launch
 #ifdef GRLX_ENV_SERVER_STATS
   unsigned long long t_begin = mail_clock(), t_busy = 0, n_cmd = 0, n_idle = 0, n_split = 0, n_batch = 0;
 #endif
@@ -226,65 +241,67 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(48))) void env_s
     if (!__all(ready || done)) ++n_split;
     ++n_batch;
 #endif
+    // (flat on purpose: every level of per-lane nesting around the integration costs a copy of the candidate per command)
+    bool step = false;                       // this lane has a command to answer: a step, or a reset whose start state has arrived
+    unsigned op = 0u;
     if (ready)
     {
-      unsigned op = (unsigned)(word & 0xFFu);
+      op = (unsigned)(word & 0xFFu);
       if (op == kMailExit)
       {
         done = true;
         progress = true;
       }
       else
-      {
-        bool have = true;
-        if (op == kMailReset)
-        { // a trial starts: the first level is integrated here, from the start state (every lane (., a2) the same f(start, a2));
-          // the lanes (0, .) then stand for "the action taken".  (A second copy of the integration: folding both levels into one loop
-          // costs registers the kernel does not have -- 102 and scratch, and with scratch the two kernels no longer share the SIMDs.)
-          double x[S];
-          have = units_load<3>(&m->reset[0], expect, x);      // (not there yet: the command is looked at again)
-          if (have)
-          {
-            double obs[D];
-            int terminal = 0;
-            uint32_t st = 0;
-#pragma unroll
-            for (int i = 0; i < S; ++i) cx[i] = x[i];
-            env_step<ENV, false>(N, cx, act, obs, creward, terminal, st);
-            cobs0 = obs[0];
-            op = 0u;
-          }
-        }
-        if (have)
-        { // the answer: what the action taken leaves, for every next action
-          if (worker && a == (int)op)
-          {
-            MailUnit *u = &m->cand[expect & 1u][a2][0];
-            unit_store(u + 0, cx[0], expect);
-            unit_store(u + 1, cx[1], expect);
-            unit_store(u + 2, cx[2], expect);
-            unit_store(u + 3, cobs0, expect);
-            unit_store(u + 4, creward, expect);
-          }
-          // the level after it: lane (a, a2) continues from the state the lane (action taken, a) holds
-          const int src = (lane & ~15) + (int)op * NA + (worker ? a : 0);
-          double x[S];
-#pragma unroll
-          for (int i = 0; i < S; ++i) x[i] = lane_fetch(cx[i], src);
+        step = true;
+    }
+    if (rarely(__any(step && op == kMailReset)))
+      if (step && op == kMailReset)
+      { // a trial starts: the first level is integrated here, from the start state (every lane (., a2) the same f(start, a2));
+        // the lanes (0, .) then stand for "the action taken".  (A second copy of the integration: folding both levels into one loop
+        // costs registers the kernel does not have -- 102 and scratch, and with scratch the two kernels no longer share the SIMDs.)
+        double x[S];
+        step = units_load<3>(&m->reset[0], expect, x);      // (not there yet: the command is looked at again)
+        if (step)
+        {
           double obs[D];
           int terminal = 0;
           uint32_t st = 0;
 #pragma unroll
           for (int i = 0; i < S; ++i) cx[i] = x[i];
-          env_step<ENV, false>(N, cx, act, obs, creward, terminal, st);
+          env_step_consts<ENV>(N, ec, cx, act, obs, creward, terminal, st);
           cobs0 = obs[0];
-          ++expect;
-          progress = true;
-#ifdef GRLX_ENV_SERVER_STATS
-          ++n_cmd;
-#endif
+          op = 0u;
         }
       }
+    if (step)
+    { // the answer: what the action taken leaves, for every next action
+      if (worker && a == (int)op)
+      {
+        MailUnit *u = &m->cand[expect & 1u][a2][0];
+        unit_store_at<0>(u, cx[0], expect);
+        unit_store_at<1>(u, cx[1], expect);
+        unit_store_at<2>(u, cx[2], expect);
+        unit_store_at<3>(u, cobs0, expect);
+        unit_store_at<4>(u, creward, expect);
+      }
+      // the level after it: lane (a, a2) continues from the state the lane (action taken, a) holds
+      const int src = (lane & ~15) + (int)op * NA + (worker ? a : 0);
+      double x[S];
+#pragma unroll
+      for (int i = 0; i < S; ++i) x[i] = lane_fetch(cx[i], src);
+      double obs[D];
+      int terminal = 0;
+      uint32_t st = 0;
+#pragma unroll
+      for (int i = 0; i < S; ++i) cx[i] = x[i];
+      env_step_consts<ENV>(N, ec, cx, act, obs, creward, terminal, st);
+      cobs0 = obs[0];
+      ++expect;
+      progress = true;
+#ifdef GRLX_ENV_SERVER_STATS
+      ++n_cmd;
+#endif
     }
     if (__any(progress)) idle = 0;
     else if (++idle > kServerIdlePolls) break;

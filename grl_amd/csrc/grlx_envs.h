@@ -32,7 +32,7 @@ template <> struct Env<GRLX_ENV_PENDULUM> {
   static constexpr int S = 3, D = 2;
   static constexpr bool kAbsorbing = false;      // can observe() report an absorbing state (terminal = 2)?
   // pendulum.cpp:40-49, 55-68; the constants are held in registers by the caller (rk4_step)
-  struct Consts { SinConsts k; double invJ, mgl, b, kkr, kr; };
+  struct Consts { SinConsts k; double invJ, mgl, b, kkr, kr; static constexpr bool kSignByAdd = false; };
   template <bool PIN> __device__ static __forceinline__ Consts consts()
   {
     const double J = 0.000191, m = 0.055, g = 9.81, l = 0.042, b = 0.000003, K = 0.0536, R = 9.5;
@@ -45,10 +45,20 @@ template <> struct Env<GRLX_ENV_PENDULUM> {
     c.kr = math_const<PIN>(K / R);
     return c;
   }
-  __device__ static __forceinline__ void eom(const Consts &c, const double *x, double u, double *xd)
+  // The environment server's (grlx_env_server.h): the same values; of the sine's constants the additive ones pinned (kPinAdditive,
+  // grlx_math.h), and the sine's sign set by an integer add (psin<true>) -- a type of its own, so that no other kernel's code changes.
+  struct ServerConsts : Consts { static constexpr bool kSignByAdd = true; };
+  __device__ static __forceinline__ ServerConsts server_consts()
+  {
+    ServerConsts c;
+    static_cast<Consts &>(c) = consts<false>();
+    c.k = sin_consts<kPinAdditive>();
+    return c;
+  }
+  template <typename C> __device__ static __forceinline__ void eom(const C &c, const double *x, double u, double *xd)
   {
     double a = x[0], ad = x[1];
-    double add = c.invJ * (c.mgl * psin(a, c.k) - c.b * ad - c.kkr * ad + c.kr * u);
+    double add = c.invJ * (c.mgl * psin<C::kSignByAdd>(a, c.k) - c.b * ad - c.kkr * ad + c.kr * u);
     xd[0] = ad;
     xd[1] = add;
     xd[2] = 1;
@@ -558,6 +568,7 @@ __device__ __forceinline__ void env_eom(const typename Env<ENV>::Consts &ec, con
     Env<ENV>::eom(ec, x, u, xd);
 }
 
+// (rk4_step_consts below is a COPY of this function for the environment server: a change here is a change there)
 template <int ENV, bool PIN, typename SH = NoShare>
 __device__ __forceinline__ void rk4_step(const DevParams &P, const double *x, double u, double *next, const SH &sh = SH())
 {
@@ -594,6 +605,7 @@ __device__ __forceinline__ void rk4_step(const DevParams &P, const double *x, do
 // PIN: hold the dynamics' constants in vector registers across the integration loop (pays at one
 // wave per SIMD, costs registers)
 // SH: NoShare, or a LaneShare when several lanes integrate the same replica (rollout kernels)
+// (env_step_consts below is a COPY of this function for the environment server: a change here is a change there)
 template <int ENV, bool PIN = true, typename SH = NoShare>
 __device__ __forceinline__ void env_step(const DevParams &P, double *x, double action, double *obs, double &reward, int &terminal, uint32_t &status,
                                          const SH &sh = SH())
@@ -607,6 +619,56 @@ __device__ __forceinline__ void env_step(const DevParams &P, double *x, double a
   terminal = Env<ENV>::observe(P, next, obs);
   reward = Env<ENV>::evaluate(P, x, action, next);
   // the branch-free sin/cos need |angle| < 2^20; 2^19 at step ends leaves room for the stages
+  if (!Env<ENV>::in_domain(next)) status |= ST_DOMAIN;
+#pragma unroll
+  for (int i = 0; i < S; ++i) x[i] = next[i];
+}
+
+
+// ---- the environment server's step (grlx_env_server.h): rk4_step and env_step above with the dynamics' constants made by the CALLER,
+// once, outside the loop it steps in.  Copies, not a shared body: the kernels that call rk4_step / env_step keep their machine code to
+// the instruction (a shared body moved a handful of instructions in every one of them), and these two are the only other users.
+template <int ENV, typename CONSTS>
+__device__ __forceinline__ void rk4_step_consts(const DevParams &P, const CONSTS &ec, const double *x, double u, double *next)
+{
+  constexpr int S = Env<ENV>::S, SD = S - 1;
+  const double h = P.h;
+  const double tinc = (((h + 2 * h) + 2 * h) + h) / 6;
+  double xd[S], k1[SD], k2[SD], k3[SD], k4[SD], t[S];
+#pragma unroll
+  for (int i = 0; i < S; ++i) { next[i] = x[i]; t[i] = x[i]; }
+  for (int ii = 0; ii < P.integration_steps; ++ii)
+  {
+    Env<ENV>::eom(ec, next, u, xd);
+#pragma unroll
+    for (int i = 0; i < SD; ++i) { k1[i] = h * xd[i]; t[i] = next[i] + k1[i] / 2; }
+    Env<ENV>::eom(ec, t, u, xd);
+#pragma unroll
+    for (int i = 0; i < SD; ++i) { k2[i] = h * xd[i]; t[i] = next[i] + k2[i] / 2; }
+    Env<ENV>::eom(ec, t, u, xd);
+#pragma unroll
+    for (int i = 0; i < SD; ++i) { k3[i] = h * xd[i]; t[i] = next[i] + k3[i]; }
+    Env<ENV>::eom(ec, t, u, xd);
+#pragma unroll
+    for (int i = 0; i < SD; ++i)
+    {
+      k4[i] = h * xd[i];
+      next[i] = next[i] + div6(k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]);
+    }
+    next[SD] = next[SD] + tinc;
+  }
+}
+
+template <int ENV, typename CONSTS>
+__device__ __forceinline__ void env_step_consts(const DevParams &P, const CONSTS &ec, double *x, double action, double *obs, double &reward,
+                                                int &terminal, uint32_t &status)
+{
+  static_assert(!HasCustomModel<ENV>::value, "a model that integrates itself makes its own constants");
+  constexpr int S = Env<ENV>::S;
+  double next[S];
+  rk4_step_consts<ENV>(P, ec, x, Env<ENV>::actuate(action), next);
+  terminal = Env<ENV>::observe(P, next, obs);
+  reward = Env<ENV>::evaluate(P, x, action, next);
   if (!Env<ENV>::in_domain(next)) status |= ST_DOMAIN;
 #pragma unroll
   for (int i = 0; i < S; ++i) x[i] = next[i];

@@ -116,11 +116,18 @@ struct SinConsts {
 __device__ __forceinline__ double math_pin(double v) { asm volatile("" : "+v"(v)); return v; }
 // PIN = false leaves the constants to the compiler (literals): the choice for kernels that run
 // several waves per SIMD, where registers are scarcer than scalar issue slots.
-template <bool PIN> __device__ __forceinline__ double math_const(double v) { return PIN ? math_pin(v) : v; }
+// PIN = kPinAdditive (the pendulum's environment server) pins only the ADDITIVE constant of each fma(z, k1, k0) of the two
+// polynomials: with both left as literals the instruction would read two scalar operands, a VALU instruction of this
+// architecture may read one, and the compiler copies the other into a vector register next to every use (18 + 7 moves per RK4
+// sub-step).  Eight register pairs instead of the twenty PIN = true takes.
+constexpr int kPinAdditive = 2;
+template <int PIN> __device__ __forceinline__ double math_const(double v) { return PIN == 1 ? math_pin(v) : v; }
+template <int PIN> __device__ __forceinline__ double math_const_additive(double v) { return PIN != 0 ? math_pin(v) : v; }
 
-template <bool PIN = true>
+template <int PIN = true>
 __device__ __forceinline__ SinConsts sin_consts()
 {
+  static_assert(PIN == 0 || PIN == 1 || PIN == kPinAdditive, "false, true or kPinAdditive");
   SinConsts k;
   k.invpio2 = math_const<PIN>(GRLX_INVPIO2);
   k.p1 = math_const<PIN>(GRLX_PIO2_1);
@@ -131,11 +138,26 @@ __device__ __forceinline__ SinConsts sin_consts()
   const double cv[8] = {0x1.5555555555555p-5, -0x1.6c16c16c16c17p-10, 0x1.a01a01a01a01ap-16, -0x1.27e4fb7789f5cp-22,
                         0x1.1eed8eff8d898p-29, -0x1.93974a8c07c9dp-37, 0x1.ae7f3e733b81fp-45, -0x1.6827863b97d97p-53};
 #pragma unroll
-  for (int i = 0; i < 8; ++i) { k.s[i] = math_const<PIN>(sv[i]); k.c[i] = math_const<PIN>(cv[i]); }
+  for (int i = 0; i < 8; i += 2)
+  {
+    k.s[i] = math_const_additive<PIN>(sv[i]); k.c[i] = math_const_additive<PIN>(cv[i]);
+    k.s[i + 1] = math_const<PIN>(sv[i + 1]); k.c[i + 1] = math_const<PIN>(cv[i + 1]);
+  }
   return k;
 }
 
+// -v where bit 1 of q is set, else v: the sign bit is the top bit of the high word, so adding bit 1 of q shifted there flips it
+// (the carry falls off) -- the bits (q & 2) ? -v : v gives, for every v, in two instructions instead of four
+__device__ __forceinline__ double math_negate_if_bit1(double v, int q)
+{
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  const unsigned hi = (unsigned)(b >> 32) + (((unsigned)q & 2u) << 30);
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | (b & 0xFFFFFFFFull)));
+}
+
 // psin with the constants supplied: the same operations as psin below, in the same order
+// (SIGN_BY_ADD: math_negate_if_bit1 for the last select; the environment server's)
+template <bool SIGN_BY_ADD = false>
 __device__ __forceinline__ double psin(double x, const SinConsts &k)
 {
   const double fn = __builtin_rint(x * k.invpio2);
@@ -163,6 +185,7 @@ __device__ __forceinline__ double psin(double x, const SinConsts &k)
   const double tail = (1.0 - w) - hz;
   const double cs = w + __builtin_fma(z2, Q, __builtin_fma(-r, t, tail));
   const double v = (q & 1) ? cs : sn;
+  if constexpr (SIGN_BY_ADD) return math_negate_if_bit1(v, q);
   return (q & 2) ? -v : v;
 }
 

@@ -477,7 +477,7 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials, c
         {
           up.dW = pd_dW;
           up.dT = pd_dT;
-          td_update_lane<true>(tr, tab, up, pd_pos, pd_sh, pd_wp, g, j, sh_ppos, sh_fb, sh_fbflag, status, ev);
+          td_update_lane<true, true>(tr, tab, up, pd_pos, pd_sh, pd_wp, g, j, sh_ppos, sh_fb, sh_fbflag, status, ev);
           // without a trace the update stored p's weight straight into the table, behind the loads of Q(s', .) already in flight,
           // and no trace entry forwards it (p of consecutive steps is often the same slot) -- load again below.  Built into the
           // instantiations a context without a trace launches: the sweep kernels (grlx_api.cpp routes every plain one there) and the
@@ -704,14 +704,14 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials, c
             pd_pos = p_pos;
             status |= (p_pos == kInvalidPos) ? ST_BAD_POS : 0u;      // assert: an update always follows an action taken
             pd_sh = p_sh;
-            pd_wp = wp;
+            pd_wp = wp;                                              // (forwarded above; the trace is next written by the update this feeds)
           }
           else
           {
             up.dW = dW;
             up.dT = dT;
             Evicted none;
-            td_update_lane<false>(tr, tab, up, p_pos, p_sh, wp, g, j, sh_ppos, sh_fb, sh_fbflag, status, none);
+            td_update_lane<false, true>(tr, tab, up, p_pos, p_sh, wp, g, j, sh_ppos, sh_fb, sh_fbflag, status, none);
             tr_len_ref = tr.len;
           }
         }

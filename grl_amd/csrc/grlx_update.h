@@ -94,9 +94,13 @@ __device__ __forceinline__ double add_clamped(const UpdateParams &u, double v, d
 // later; pos = kInvalidPos: nothing held); ev.n counts the write-backs of the call (n > 1, or a
 // path that does not count: n = 2, tells the caller that table values it loaded before this call
 // may be stale).
+// FORWARDED: the caller passes the wp that trace_forward(tr, p_pos, .) returned, and no td_update_lane ran on `tr` since.  Then the
+// aliased entry's weight is wp itself: trace_forward and the loop below pick the same entry (the last e with pos[e] == p_pos, over all
+// kMaxTrace entries), nothing but td_update_lane writes pos or val (trace_share_event sets wt only; a flush leaves no entry to alias),
+// and the loop leaves the val of an `own` entry alone.  So the chain of selects that carries it (a_val) is dead and is not built.
 struct Evicted { uint32_t n, pos; double val; };
 
-template <bool HOLD>
+template <bool HOLD, bool FORWARDED = false>
 __device__ __forceinline__ void td_update_lane(TraceRegs &tr, const Table &tab, const UpdateParams &u, uint32_t p_pos, bool p_sh, double wp,
                                                int g, int j, const uint32_t *sh_ppos, double *sh_fb, uint32_t *sh_fbflag, uint32_t &status,
                                                Evicted &ev)
@@ -148,7 +152,7 @@ __device__ __forceinline__ void td_update_lane(TraceRegs &tr, const Table &tab, 
         tr.val[e] = doit ? vv : tr.val[e];
         doitmask |= doit ? (1u << e) : 0u;
         ownmask |= own ? (1u << e) : 0u;
-        a_val = own ? tr.val[e] : a_val;
+        if (!FORWARDED) a_val = own ? tr.val[e] : a_val;
         a_de = own ? de : a_de;
         a_upd = own ? upd : a_upd;
         tr.pos[e] = own ? kInvalidPos : tr.pos[e];       // ssub: the slot leaves the trace
@@ -159,7 +163,7 @@ __device__ __forceinline__ void td_update_lane(TraceRegs &tr, const Table &tab, 
     const uint32_t stmask = doitmask & tr.wt;            // write-through entries that changed
     tr.wt &= ~ownmask;
     // p's write first, then the aliased entry's update (if it is still being updated)
-    const double base = aliased ? a_val : wp;
+    const double base = (!FORWARDED && aliased) ? a_val : wp;
     const double v1 = add_clamped(u, base, u.dW);
     const double v2 = add_clamped(u, v1, a_de);
     v = (aliased && a_upd) ? v2 : v1;
