@@ -137,7 +137,11 @@ _DIAG_SIGS = {
     "grlx_env_server_counts": (C.c_int, [C.c_void_p, _P(C.c_int), _P(C.c_int)]),
     "grlx_env_server_debug": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "grlx_fqi_debug_stamps": (C.c_int, [C.c_void_p, _P(C.c_ulonglong), C.c_int]),
+    "grlx_last_kernel_name": (C.c_char_p, [C.c_void_p]),
+    "grlx_kernel_plan": (C.c_int, [_P(Config), C.c_int, C.c_int, _P(C.c_int), _P(C.c_int), _P(C.c_int), C.c_char_p, C.c_char_p, C.c_size_t]),
 }
+# grlx_kernel_plan flags
+PLAN_STAMPS_IN_PLACE, PLAN_STAMPS_DEFERRED, PLAN_SWEEP, PLAN_SERVER_OFF, PLAN_WALKER_SERVER, PLAN_FITS_YES, PLAN_FITS_NO = 1, 2, 4, 8, 16, 32, 64
 ABI_VERSION = 2         # include/grlx.h: GRLX_ABI_VERSION
 
 
@@ -177,6 +181,8 @@ def load():
     _share_hip_runtime_with_torch()
     lib = C.CDLL(path)
     for name, (res, args) in list(_SIGS.items()) + list(_DIAG_SIGS.items()):
+        if name in _DIAG_SIGS and os.environ.get("GRLX_LIB") and not hasattr(lib, name):
+            continue                 # GRLX_LIB may name an older build (A/B timing): it has the boundary, not necessarily every diagnostic
         fn = getattr(lib, name)      # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -188,6 +194,15 @@ def load():
                           "exec-prologue filter and its kernels can read stale lanes (DESIGN.md 4.1f); run `python -m grl_amd._build`")
     _lib = lib
     return lib
+
+
+def kernel_plan(cfg, simds: int, flags: int = 0):
+    """grlx_kernel_plan (include/grlx_diag.h): (replicas per wave, rollout row, server row or "", GRLX_KERNEL_* variant, grid) of what a
+    context of `cfg` would launch on a device of `simds` SIMDs; needs no device.  Raises GrlxError where grlx_create would."""
+    rpw, variant, grid = C.c_int(0), C.c_int(0), C.c_int(0)
+    rollout, server = C.create_string_buffer(256), C.create_string_buffer(256)
+    check(load().grlx_kernel_plan(C.byref(cfg), simds, flags, C.byref(rpw), C.byref(variant), C.byref(grid), rollout, server, 256))
+    return rpw.value, rollout.value.decode(), server.value.decode(), variant.value, grid.value
 
 
 def check(code: int) -> int:

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 #include "grlx_internal.h"
+#include "../../include/grlx_diag.h"
 
 using namespace grlx;
 
@@ -125,24 +126,26 @@ int make_params(const grlx_config &c, DevParams *P)
     S = 0;
     D = (c.agent == GRLX_AGENT_AC) ? c.projector.dims : c.projector.dims - 1;
     if (D < 1 || D >= GRLX_MAX_DIMS) return fail(GRLX_ERR_INVALID, "projector/tile_coding:resolution (an external environment's observation has %d dimensions)", D);
-    if (c.agent != GRLX_AGENT_SARSA && c.agent != GRLX_AGENT_Q && c.agent != GRLX_AGENT_EXPECTED_SARSA && c.agent != GRLX_AGENT_AC)
+    if (!is_td_agent(c.agent) && c.agent != GRLX_AGENT_AC)
       return fail(GRLX_ERR_INVALID, "an external environment is served by the per-step agent entry points: SARSA / Q / Expected SARSA or actor-critic");
   }
   else if (env_dims(c.env, &S, &D) != GRLX_OK) return fail(GRLX_ERR_INVALID, "environment %d is not supported by the fused path", c.env);
-  if (c.agent != GRLX_AGENT_SARSA && c.agent != GRLX_AGENT_Q && c.agent != GRLX_AGENT_AC && c.agent != GRLX_AGENT_EXPECTED_SARSA &&
-      c.agent != GRLX_AGENT_ADVANTAGE && c.agent != GRLX_AGENT_QV) return fail(GRLX_ERR_INVALID, "agent %d is not supported by the fused path", c.agent);
+  if (!is_td_agent(c.agent) && c.agent != GRLX_AGENT_AC && c.agent != GRLX_AGENT_ADVANTAGE && c.agent != GRLX_AGENT_QV) return fail(GRLX_ERR_INVALID, "agent %d is not supported by the fused path", c.agent);
+  // "is it built?" is asked of the kernel table (kernel_built: a row with this key).  An external environment has no rollout kernel: its
+  // per-step entry points (grlx_step.h) take what the pendulum's rows take.
+  const int row_env = external ? GRLX_ENV_PENDULUM : c.env;
   if (c.agent == GRLX_AGENT_ADVANTAGE)
   {
     if (!(c.kappa > 0)) return fail(GRLX_ERR_INVALID, "predictor/critic/advantage:kappa");
-    if ((c.env != GRLX_ENV_PENDULUM && c.env != GRLX_ENV_ACROBOT) || c.action_steps != 3)
+    if (!kernel_built(FAM_TD, c.env, c.action_steps, 4, MODE_ADVANTAGE))
       return fail(GRLX_ERR_INVALID, "advantage learning is built for the pendulum and the acrobot with 3 actions");
   }
   const bool ac = c.agent == GRLX_AGENT_AC;
   const bool qv = c.agent == GRLX_AGENT_QV;
-  if (qv && ((c.env != GRLX_ENV_PENDULUM && c.env != GRLX_ENV_ACROBOT) || c.action_steps != 3))
+  if (qv && !kernel_built(FAM_QV, c.env, c.action_steps, 4, MODE_IN_PLACE))
     return fail(GRLX_ERR_INVALID, "predictor/critic/qv is built for the pendulum and the acrobot with 3 actions");
   if (qv && !(c.beta > 0)) return fail(GRLX_ERR_INVALID, "predictor/critic/qv:beta");
-  if (ac && !external && c.env != GRLX_ENV_CART_POLE && c.env != GRLX_ENV_PENDULUM) return fail(GRLX_ERR_INVALID, "actor-critic is built for cart-pole and pendulum");
+  if (ac && !external && !kernel_built(FAM_AC, c.env, 0, 4, MODE_DEFERRED)) return fail(GRLX_ERR_INVALID, "actor-critic is built for cart-pole and pendulum");
   if (!external)
   {
   if (c.discrete_time != 1) return fail(GRLX_ERR_INVALID, "environment/modeled:discrete_time must be 1");
@@ -162,18 +165,15 @@ int make_params(const grlx_config &c, DevParams *P)
   }
   if (!ac && (c.action_steps < 1 || c.action_steps > GRLX_MAX_ACTIONS)) return fail(GRLX_ERR_INVALID, "discretizer/uniform:steps (1..%d supported)", GRLX_MAX_ACTIONS);
   if (!ac && !qv && c.agent != GRLX_AGENT_ADVANTAGE && c.trace != GRLX_TRACE_ACCUMULATING && c.env != GRLX_ENV_CART_POLE_BALANCING)
-  { // the instantiations of rollout_kernel (launch_rollout): anything else has no kernel to run
-    const bool built = ((c.env == GRLX_ENV_PENDULUM || external) && (c.action_steps == 3 || c.action_steps == 5)) ||
-                       ((c.env == GRLX_ENV_ACROBOT || c.env == GRLX_ENV_CART_POLE || c.env == GRLX_ENV_COMPASS_WALKER) && c.action_steps == 3);
-    if (!built)
+  { // the instantiations of rollout_kernel: anything else has no kernel to run
+    if (!kernel_built(FAM_TD, row_env, c.action_steps, 4, MODE_DEFERRED))
       return fail(GRLX_ERR_INVALID, "discretizer/uniform:steps = %d is not built for this environment (pendulum: 3 or 5 actions; "
                                     "acrobot, cart-pole, compass walker: 3 actions)", c.action_steps);
   }
   if (ac && c.trace != GRLX_TRACE_REPLACING && c.trace != GRLX_TRACE_NONE) return fail(GRLX_ERR_INVALID, "trace type %d is not supported by the fused path", c.trace);
   if (c.trace == GRLX_TRACE_ACCUMULATING)
   { // its own (uncached, read-modify-write) kernel: SARSA / Q / Expected SARSA on the pendulum and the acrobot
-    if ((c.agent != GRLX_AGENT_SARSA && c.agent != GRLX_AGENT_Q && c.agent != GRLX_AGENT_EXPECTED_SARSA) ||
-        (c.env != GRLX_ENV_PENDULUM && c.env != GRLX_ENV_ACROBOT) || c.action_steps != 3)
+    if (!is_td_agent(c.agent) || !kernel_built(FAM_ACC, c.env, c.action_steps, 4, MODE_IN_PLACE))
       return fail(GRLX_ERR_INVALID, "trace/enumerated/accumulating is built for SARSA / Q / Expected SARSA on the pendulum and the acrobot with 3 actions");
   }
   else if (c.trace != GRLX_TRACE_NONE && c.trace != GRLX_TRACE_REPLACING) return fail(GRLX_ERR_INVALID, "trace type %d is not supported by the fused path", c.trace);
@@ -251,10 +251,10 @@ int make_params(const grlx_config &c, DevParams *P)
 
   if (c.projector.safe >= 1)
   { // claim table of the tile coding: its own (plain) kernel
-    if ((c.agent != GRLX_AGENT_SARSA && c.agent != GRLX_AGENT_Q) || c.env == GRLX_ENV_CART_POLE_BALANCING ||
-        c.action_steps != 3 || c.trace == GRLX_TRACE_ACCUMULATING)
+    if ((c.agent != GRLX_AGENT_SARSA && c.agent != GRLX_AGENT_Q) || !kernel_built(FAM_TGT, row_env, c.action_steps, 4, MODE_IN_PLACE, 0, 1) ||
+        c.trace == GRLX_TRACE_ACCUMULATING)
       return fail(GRLX_ERR_INVALID, "projector/tile_coding:safe >= 1 is built for predictor/critic/sarsa and predictor/critic/q with 3 actions, replacing or no trace");
-    if (c.env != GRLX_ENV_PENDULUM && c.target_interval > 0) return fail(GRLX_ERR_INVALID, "safe >= 1 together with a target network is built for the pendulum");
+    if (c.target_interval > 0 && !kernel_built(FAM_TGT, c.env, c.action_steps, 4, MODE_IN_PLACE, 1, 1)) return fail(GRLX_ERR_INVALID, "safe >= 1 together with a target network is built for the pendulum");
     P->tile_safe = c.projector.safe;         // 2: the policy's batch projections claim too
   }
   if ((ac || qv) && c.actor_projector.safe != 0) return fail(GRLX_ERR_INVALID, "projector/tile_coding:safe on the second table");
@@ -263,7 +263,7 @@ int make_params(const grlx_config &c, DevParams *P)
   { // target network of the Q table: its own (plain) kernel
     if (c.agent != GRLX_AGENT_SARSA && c.agent != GRLX_AGENT_Q)
       return fail(GRLX_ERR_INVALID, "representation/parameterized/linear:interval (a target network is built for predictor/critic/sarsa and predictor/critic/q)");
-    if (c.env == GRLX_ENV_CART_POLE_BALANCING || c.action_steps != 3 || c.trace == GRLX_TRACE_ACCUMULATING)
+    if (!kernel_built(FAM_TGT, row_env, c.action_steps, 4, MODE_IN_PLACE, 1, 0) || c.trace == GRLX_TRACE_ACCUMULATING)
       return fail(GRLX_ERR_INVALID, "representation/parameterized/linear:interval (built for 3 actions, replacing or no trace)");
     if (c.target_tau < 0 || c.target_tau > 1) return fail(GRLX_ERR_INVALID, "representation/parameterized/linear:tau");
     P->target_interval = c.target_interval;
@@ -327,12 +327,12 @@ struct grlx_ctx {
   bool         run_pending = false;       // ... with work possibly still in flight on it
   int          n_tables = 1;
   int64_t      trials_run = 0;
-  int          last_kernel = GRLX_KERNEL_NONE;
+  const KernelRow *last_row = nullptr;    // the row of the kernel table launched last
   bool         poison = false;            // GRLX_POISON_REGISTERS=<pattern>: diagnostic, see launch_poison_registers
   uint32_t     poison_pattern = 0;
   // the environment server of the pendulum rollout kernels (grlx_env_server.h): mailboxes, its stream, and the fork / join events
   int          env_server = 1;            // GRLX_ENV_SERVER=0 turns it off
-  void         *park = nullptr;           // rotating actor-critic kernel: parked lane state of the third sub-batch, per wave
+  void         *park = nullptr;           // 32-replica waves of the compass walker: parked lane state of the sub-batches beyond the third, per wave
   EnvMail      *env_mail = nullptr;
   size_t       env_mail_bytes = 0;        // per replica: kEnvMailBytes (pendulum kernels) or kWideMailBytes (wide kernels)
   hipStream_t  srv_stream = nullptr;
@@ -345,7 +345,7 @@ struct grlx_ctx {
   int32_t      *stage_i32 = nullptr;      // [N] active | [N] terminal
   uint64_t     step_calls = 0;            // agent calls since the last look at the tables' load
   // hyper-parameter sweep (grlx_set_replica_params): the per-replica values as given ([GRLX_PARAM_*][replica]; empty = none set: not a
-  // sweep context) and their device records, handed to launch_rollout once the context is a sweep context
+  // sweep context) and their device records, handed to the SpecSweep rows once the context is a sweep context
   std::vector<double> sweep_host[4];
   SweepParams  *sweep_dev = nullptr;
   bool         sweep = false;
@@ -503,34 +503,42 @@ int grlx_env_dims(int env, int *state_dims, int *obs_dims)
   return GRLX_OK;
 }
 
+// Everything grlx_create refuses before it looks for a device.  P: the parameter block, without device pointers, sizes and layout.
+static int admit(const grlx_config *cfg, DevParams *P)
+{
+  if (cfg->n_replicas < 1) return fail(GRLX_ERR_INVALID, "n_replicas must be >= 1");
+  if (cfg->max_rows < 1) return fail(GRLX_ERR_INVALID, "max_rows must be >= 1");
+  // more than 8 replicas per wave: 12 and 16 for the actor-critic; for the TD agents the layouts rollout_wide_kernel is built in (16: four
+  // sub-batches, the acrobot and the compass walker with three actions; 32: eight, the compass walker)
+  const int rpw = cfg->replicas_per_wave;
+  if (rpw != 0 && rpw != 4 && rpw != 8 && !((rpw == 12 || rpw == 16) && cfg->agent == GRLX_AGENT_AC) &&
+      !(is_td_agent(cfg->agent) && kernel_built(FAM_TD, cfg->env, cfg->action_steps, rpw, MODE_DEFERRED)))
+    return fail(GRLX_ERR_INVALID, "replicas_per_wave must be 0 (automatic), 4 or 8 (12: actor-critic only; 16: actor-critic, and the TD agents on the acrobot / the compass walker with 3 actions; 32: the TD agents on the compass walker)");
+  if (cfg->wave_limit < 0) return fail(GRLX_ERR_INVALID, "wave_limit must be 0 (automatic) or positive");
+  if (cfg->tap_deferred && cfg->tap_replica >= 0 && cfg->tap_capacity > 0 &&
+      (!is_td_agent(cfg->agent) || cfg->trace == GRLX_TRACE_ACCUMULATING || !kernel_built(FAM_TD, cfg->env, cfg->action_steps, 4, MODE_TAPPED)))
+    return fail(GRLX_ERR_INVALID, "tap_deferred is built for SARSA / Q / Expected SARSA on the pendulum (3 or 5 actions) and the acrobot (3 actions)");
+  int rc = make_params(*cfg, P);
+  if (rc != GRLX_OK) return rc;
+  if (cfg->env == GRLX_ENV_CART_POLE_BALANCING)
+    return fail(GRLX_ERR_INVALID, "task/cart_pole/balancing is served by grlx_env_step only (no fused TD rollout is built for it)");
+  P->n_replicas = cfg->n_replicas;
+  P->max_rows = cfg->max_rows;
+  P->no_specialisation = cfg->force_generic;
+  P->tap_replica = cfg->tap_replica;
+  P->tap_capacity = cfg->tap_replica >= 0 ? cfg->tap_capacity : 0;
+  P->tap_starts = cfg->tap_starts != 0 ? 1 : 0;
+  P->tap_deferred = (cfg->tap_deferred != 0 && P->tap_capacity > 0) ? 1 : 0;
+  return GRLX_OK;
+}
+
 int grlx_create(const grlx_config *cfg, const int64_t *seeds, grlx_ctx **out)
 {
   if (!cfg || !seeds || !out) return fail(GRLX_ERR_INVALID, "null argument");
   *out = nullptr;
-  if (cfg->n_replicas < 1) return fail(GRLX_ERR_INVALID, "n_replicas must be >= 1");
-  if (cfg->max_rows < 1) return fail(GRLX_ERR_INVALID, "max_rows must be >= 1");
-  // 16 for the TD agents: the four-sub-batch instantiations of rollout_wide_kernel (the acrobot and the compass walker, three actions)
-  const bool td16 = cfg->replicas_per_wave == 16 && (cfg->env == GRLX_ENV_ACROBOT || cfg->env == GRLX_ENV_COMPASS_WALKER) && cfg->action_steps == 3 &&
-                    (cfg->agent == GRLX_AGENT_SARSA || cfg->agent == GRLX_AGENT_Q || cfg->agent == GRLX_AGENT_EXPECTED_SARSA);
-  // 32: the eight-sub-batch instantiation (the compass walker: two lanes per replica suffice for its environment phase)
-  const bool td32 = cfg->replicas_per_wave == 32 && cfg->env == GRLX_ENV_COMPASS_WALKER && cfg->action_steps == 3 &&
-                    (cfg->agent == GRLX_AGENT_SARSA || cfg->agent == GRLX_AGENT_Q || cfg->agent == GRLX_AGENT_EXPECTED_SARSA);
-  if (cfg->replicas_per_wave != 0 && cfg->replicas_per_wave != 4 && cfg->replicas_per_wave != 8 && !td16 && !td32 &&
-      !((cfg->replicas_per_wave == 12 || cfg->replicas_per_wave == 16) && cfg->agent == GRLX_AGENT_AC))
-    return fail(GRLX_ERR_INVALID, "replicas_per_wave must be 0 (automatic), 4 or 8 (12: actor-critic only; 16: actor-critic, and the TD agents on the acrobot / the compass walker with 3 actions; 32: the TD agents on the compass walker)");
-  if (cfg->wave_limit < 0) return fail(GRLX_ERR_INVALID, "wave_limit must be 0 (automatic) or positive");
-  if (cfg->tap_deferred && cfg->tap_replica >= 0 && cfg->tap_capacity > 0)
-  {
-    const bool td = (cfg->agent == GRLX_AGENT_SARSA || cfg->agent == GRLX_AGENT_Q || cfg->agent == GRLX_AGENT_EXPECTED_SARSA);
-    const bool built = (cfg->env == GRLX_ENV_PENDULUM && (cfg->action_steps == 3 || cfg->action_steps == 5)) || (cfg->env == GRLX_ENV_ACROBOT && cfg->action_steps == 3);
-    if (!td || cfg->trace == GRLX_TRACE_ACCUMULATING || !built)
-      return fail(GRLX_ERR_INVALID, "tap_deferred is built for SARSA / Q / Expected SARSA on the pendulum (3 or 5 actions) and the acrobot (3 actions)");
-  }
   DevParams P;
-  int rc = make_params(*cfg, &P);
+  int rc = admit(cfg, &P);
   if (rc != GRLX_OK) return rc;
-  if (cfg->env == GRLX_ENV_CART_POLE_BALANCING)
-    return fail(GRLX_ERR_INVALID, "task/cart_pole/balancing is served by grlx_env_step only (no fused TD rollout is built for it)");
   if (!have_device()) return fail(GRLX_ERR_NO_DEVICE, "no HIP device: grlx has no CPU fallback");
 
   grlx_ctx *ctx = new grlx_ctx();
@@ -549,49 +557,17 @@ int grlx_create(const grlx_config *cfg, const int64_t *seeds, grlx_ctx **out)
   if (cfg->table_log2_max != 0 && (cfg->table_log2_max < (int)logC || cfg->table_log2_max > 26))
   { delete ctx; return fail(GRLX_ERR_INVALID, "table_log2_max must be 0 or in table_log2_capacity..26"); }
   ctx->logC_max = cfg->table_log2_max ? (uint32_t)cfg->table_log2_max : 26u;
-  P.n_replicas = N;
   P.logC = logC;
-  P.max_rows = cfg->max_rows;
-  P.no_specialisation = cfg->force_generic;
-  P.tap_replica = cfg->tap_replica;
-  P.tap_capacity = cfg->tap_replica >= 0 ? cfg->tap_capacity : 0;
-  P.tap_starts = cfg->tap_starts != 0 ? 1 : 0;
-  P.tap_deferred = (cfg->tap_deferred != 0 && P.tap_capacity > 0) ? 1 : 0;
-  { // replicas per wave: wide waves once the batch outnumbers the SIMDs four to one (taps and stamps: always 4)
-    const bool has_wide = cfg->target_interval == 0 && cfg->projector.safe == 0 && (cfg->agent == GRLX_AGENT_SARSA || cfg->agent == GRLX_AGENT_Q || cfg->agent == GRLX_AGENT_EXPECTED_SARSA ||
-                           cfg->agent == GRLX_AGENT_AC) && cfg->trace != GRLX_TRACE_ACCUMULATING;
-    int rpw = cfg->replicas_per_wave;
+  {
     hipDeviceProp_t prop;
     int dev = 0;
     int simds = 1024;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) simds = 4 * prop.multiProcessorCount;
-    // 8 once the 4-replica waves outnumber the SIMDs.  (Round 2's 16-slot actor-critic kernel parked four sub-batches in 66 KB of LDS,
-    // two waves per CU: 213 M vs 329 M env-steps/s at 16384 cart-pole replicas.  Since round 3 the sub-batches beyond the second park in
-    // device memory)
-    if (rpw == 0) rpw = ((N + kReplicasPerWave - 1) / kReplicasPerWave > simds) ? 8 : 4;
-    // actor-critic, more than 8 replicas per SIMD: more slots per wave share one environment phase (grlx_rollout_ac_wide.h; 16384 cart-pole
-    // replicas: 373 M env-steps/s with 8 slots, 405 M with 12, 425 M with 16).  16 slots for 15 or more replicas per SIMD; 12, rotated
-    // trial by trial over the wave's own replicas, for 9 to 14 (13 replicas keep 12 slots busier than 16).
-    if (cfg->replicas_per_wave == 0 && cfg->agent == GRLX_AGENT_AC && rpw == 8 && cfg->wave_limit == 0)
-    {
-      const int per_simd = (N + simds - 1) / simds;
-      if (per_simd >= 15) rpw = 16;
-      else if (per_simd >= 9) rpw = 12;
-    }
-    // TD agents on the acrobot / the compass walker (the environment phase is half of a pass), 15 or more replicas per SIMD: four sub-batches
-    // per wave share one environment phase (rollout_wide_kernel<., 3, 4, .>)
-    if (cfg->replicas_per_wave == 0 && cfg->agent != GRLX_AGENT_AC && rpw == 8 && cfg->action_steps == 3 &&
-        (cfg->env == GRLX_ENV_ACROBOT || cfg->env == GRLX_ENV_COMPASS_WALKER) && (N + simds - 1) / simds >= 15)
-      rpw = (cfg->env == GRLX_ENV_COMPASS_WALKER && (N + simds - 1) / simds >= 30) ? 32 : 16;
-    if (!has_wide || P.tap_capacity > 0) rpw = 4;
-    // without a trace (see grlx_ctx): what runs is the sweep kernels' layouts (4, 8) or the in-place actor-critic kernel (4)
-    const bool td_agent = cfg->agent == GRLX_AGENT_SARSA || cfg->agent == GRLX_AGENT_Q || cfg->agent == GRLX_AGENT_EXPECTED_SARSA;
-    ctx->no_trace_td = cfg->trace == GRLX_TRACE_NONE && td_agent && cfg->target_interval == 0 && cfg->projector.safe == 0 && cfg->env != GRLX_ENV_EXTERNAL;
-    ctx->no_trace_ac = cfg->trace == GRLX_TRACE_NONE && cfg->agent == GRLX_AGENT_AC && cfg->env != GRLX_ENV_EXTERNAL;
-    if (ctx->no_trace_td && rpw > 8) rpw = 8;
-    if (ctx->no_trace_ac) rpw = 4;
-    P.replicas_per_wave = rpw;
-    P.wave_limit = cfg->wave_limit > 0 ? cfg->wave_limit : simds;      // these kernels hold a SIMD's whole register file: one wave per SIMD
+    const Layout L = choose_layout(*cfg, simds);
+    ctx->no_trace_td = L.no_trace_td;
+    ctx->no_trace_ac = L.no_trace_ac;
+    P.replicas_per_wave = L.replicas_per_wave;
+    P.wave_limit = L.wave_limit;
   }
 
   const size_t n_tables = (cfg->agent == GRLX_AGENT_AC || cfg->agent == GRLX_AGENT_QV) ? 2 : 1;
@@ -880,11 +856,11 @@ int grlx_reset_run(grlx_ctx *ctx)
 
 // Mailboxes, stream and events of the environment server, created at the first launch that wants them.  The server is an optimisation: when
 // its 1 KB per replica (or a stream, or an event) cannot be had, the context goes on without it.
-static bool env_server_ready(grlx_ctx *ctx)
+static bool env_server_ready(grlx_ctx *ctx, size_t mail_bytes)
 {
   if (ctx->env_mail) return true;
-  ctx->env_mail_bytes = env_server_mail_bytes(ctx->P);
-  bool ok = ctx->env_mail_bytes != 0 && hipMalloc((void **)&ctx->env_mail, (size_t)ctx->P.n_replicas * ctx->env_mail_bytes) == hipSuccess;
+  ctx->env_mail_bytes = mail_bytes;
+  bool ok = mail_bytes != 0 && hipMalloc((void **)&ctx->env_mail, (size_t)ctx->P.n_replicas * ctx->env_mail_bytes) == hipSuccess;
   ok = ok && hipStreamCreateWithFlags(&ctx->srv_stream, hipStreamNonBlocking) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->srv_go, hipEventDisableTiming) == hipSuccess;
   ok = ok && hipEventCreateWithFlags(&ctx->srv_done, hipEventDisableTiming) == hipSuccess;
@@ -969,18 +945,20 @@ static int run_trials(grlx_ctx *ctx, int n_trials, uint64_t steps_budget, void *
     }
     if (ctx->poison) HIP_TRY(launch_poison_registers(ctx->poison_pattern, (hipStream_t)stream));
     // stamps and per-step taps are recorded by instantiations of their own, which a context without a trace may run as they are
-    const bool recorded = Pb.diag_out != nullptr || (Pb.tap_replica >= 0 && Pb.tap_capacity > 0);
-    if (ctx->cfg.agent == GRLX_AGENT_AC)
-      HIP_TRY(launch_rollout_ac(Pb, n, (hipStream_t)stream, &ctx->last_kernel, ctx->no_trace_ac));
-    else if (ctx->cfg.agent == GRLX_AGENT_QV)
-      HIP_TRY(launch_rollout_qv(Pb, n, (hipStream_t)stream, &ctx->last_kernel));
-    else if (ctx->cfg.target_interval > 0 || ctx->cfg.projector.safe != 0)
-      HIP_TRY(launch_rollout_tgt(Pb, n, (hipStream_t)stream, &ctx->last_kernel));
-    else if (ctx->cfg.trace == GRLX_TRACE_ACCUMULATING)
-      HIP_TRY(launch_rollout_acc(Pb, n, (hipStream_t)stream, &ctx->last_kernel));
-    else if (ctx->sweep || (ctx->no_trace_td && !recorded))        // (without the environment server)
-      HIP_TRY(launch_rollout(Pb, n, (hipStream_t)stream, &ctx->last_kernel, ctx->sweep_dev));
-    else if (ctx->env_server && env_server_serves(Pb) && (size_t)ctx->P.n_replicas * env_server_mail_bytes(Pb) < (1ull << 31) && env_server_ready(ctx))
+    PlanFacts facts;
+    facts.sweep = ctx->sweep || (ctx->no_trace_td && !records(Pb));        // (without the environment server)
+    facts.ac_in_place = ctx->no_trace_ac;
+    facts.server = ctx->env_server != 0;
+    const char *walker = getenv("GRLX_ENV_SERVER_WALKER");
+    facts.walker_server = walker && atoi(walker) != 0;
+    facts.fits = waves_fit_together;
+    KernelPlan plan = plan_rollout(Pb, facts);
+    if (plan.server && !((size_t)ctx->P.n_replicas * plan.row->mail_bytes < (1ull << 31) && env_server_ready(ctx, plan.row->mail_bytes)))
+    { // the server is an optimisation: without its mailboxes the launch is planned again without it
+      facts.server = false;
+      plan = plan_rollout(Pb, facts);
+    }
+    if (plan.server)
     { // the server's launch forks off the caller's stream and joins it again: for the caller, still one stream-ordered operation
       Pb.env_mail = ctx->env_mail;
       Pb.env_tune = 3u;        // the rollout wave is the critical path: it issues first, the server fills its gaps (+0.7 %)
@@ -988,13 +966,14 @@ static int run_trials(grlx_ctx *ctx, int n_trials, uint64_t steps_budget, void *
       HIP_TRY(hipMemsetAsync(ctx->env_mail, 0, (size_t)ctx->P.n_replicas * ctx->env_mail_bytes, (hipStream_t)stream));
       HIP_TRY(hipEventRecord(ctx->srv_go, (hipStream_t)stream));
       HIP_TRY(hipStreamWaitEvent(ctx->srv_stream, ctx->srv_go, 0));
-      HIP_TRY(launch_env_server(Pb, ctx->srv_stream));
-      HIP_TRY(launch_rollout(Pb, n, (hipStream_t)stream, &ctx->last_kernel));
+    }
+    HIP_TRY(launch_plan(plan, Pb, n, ctx->sweep_dev, (hipStream_t)stream, ctx->srv_stream));
+    ctx->last_row = plan.row;
+    if (plan.server)
+    {
       HIP_TRY(hipEventRecord(ctx->srv_done, ctx->srv_stream));
       HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, ctx->srv_done, 0));
     }
-    else
-      HIP_TRY(launch_rollout(Pb, n, (hipStream_t)stream, &ctx->last_kernel));
   }
   HIP_TRY(launch_max_load(ctx->P, ctx->n_tables, ctx->max_load, (hipStream_t)stream));
   ctx->trials_run += n_trials;
@@ -1113,7 +1092,8 @@ int grlx_read_rows(grlx_ctx *ctx, int replica, int first, int count, int64_t *tr
   return GRLX_OK;
 }
 
-int grlx_last_kernel(grlx_ctx *ctx) { return ctx ? ctx->last_kernel : GRLX_KERNEL_NONE; }
+int grlx_last_kernel(grlx_ctx *ctx) { return ctx && ctx->last_row ? ctx->last_row->variant : GRLX_KERNEL_NONE; }
+const char *grlx_last_kernel_name(grlx_ctx *ctx) { return ctx && ctx->last_row ? ctx->last_row->name : ""; }
 int grlx_replicas_per_wave(grlx_ctx *ctx) { return ctx ? ctx->P.replicas_per_wave : 0; }
 
 int grlx_read_row_times(grlx_ctx *ctx, int replica, int first, int count, double *episode_time)
@@ -1154,24 +1134,64 @@ double sweep_config_value(const grlx_ctx *ctx, int param)
 }
 
 // what a sweep context is built for; the message names what is not
-int sweep_admits(const grlx_ctx *ctx)
+int sweep_admits(const grlx_config &c, const DevParams &P)
 {
-  const grlx_config &c = ctx->cfg;
   if (c.env == GRLX_ENV_EXTERNAL)
     return fail(GRLX_ERR_INVALID, "per-replica parameters are not built for GRLX_ENV_EXTERNAL (the per-step entry points read the shared values)");
-  if (c.agent != GRLX_AGENT_SARSA && c.agent != GRLX_AGENT_Q && c.agent != GRLX_AGENT_EXPECTED_SARSA)
+  if (!is_td_agent(c.agent))
     return fail(GRLX_ERR_INVALID, "per-replica parameters are built for the agents SARSA, Q and Expected SARSA (agent %d is not)", c.agent);
   if (c.trace != GRLX_TRACE_REPLACING && c.trace != GRLX_TRACE_NONE)
     return fail(GRLX_ERR_INVALID, "per-replica parameters are built for a replacing trace or none (an accumulating trace is not)");
   if (c.target_interval > 0) return fail(GRLX_ERR_INVALID, "per-replica parameters are not built with a target network (representation interval > 0)");
   if (c.projector.safe != 0) return fail(GRLX_ERR_INVALID, "per-replica parameters are not built with projector/tile_coding:safe");
-  if (ctx->P.tap_capacity > 0) return fail(GRLX_ERR_INVALID, "per-replica parameters are not built with taps");
-  if (ctx->P.diag_out) return fail(GRLX_ERR_INVALID, "per-replica parameters are not built with diagnostics (grlx_set_diag)");
+  if (P.tap_capacity > 0) return fail(GRLX_ERR_INVALID, "per-replica parameters are not built with taps");
+  if (P.diag_out) return fail(GRLX_ERR_INVALID, "per-replica parameters are not built with diagnostics (grlx_set_diag)");
   if (c.replicas_per_wave != 0 && c.replicas_per_wave != 4 && c.replicas_per_wave != 8)
     return fail(GRLX_ERR_INVALID, "per-replica parameters are built for replicas_per_wave 0, 4 or 8 (%d is not)", c.replicas_per_wave);
   return GRLX_OK;
 }
 } // namespace
+
+// diagnostic (include/grlx_diag.h): what a context of this configuration would launch on a device of `simds` SIMDs -- the validation of
+// grlx_create, the layout choice and plan_rollout, without a device
+int grlx_kernel_plan(const grlx_config *cfg, int simds, int flags, int *replicas_per_wave, int *variant, int *grid, char *rollout_name,
+                     char *server_name, size_t name_cap)
+{
+  if (!cfg || simds < 1) return fail(GRLX_ERR_INVALID, "bad argument");
+  DevParams P;
+  int rc = admit(cfg, &P);
+  if (rc != GRLX_OK) return rc;
+  const Layout L = choose_layout(*cfg, simds);
+  P.replicas_per_wave = L.replicas_per_wave;
+  P.wave_limit = L.wave_limit;
+  const int stamps = flags & (GRLX_PLAN_STAMPS_IN_PLACE | GRLX_PLAN_STAMPS_DEFERRED);
+  if (stamps == GRLX_PLAN_STAMPS_DEFERRED && cfg->trace == GRLX_TRACE_NONE)
+    return fail(GRLX_ERR_INVALID, "stamps of the production ordering are not built for a context without a trace");
+  static unsigned long long no_stamps_here;          // grlx_set_diag: the plan only asks whether the pointer is set
+  if (stamps) P.diag_out = &no_stamps_here;
+  P.diag_deferred = stamps == GRLX_PLAN_STAMPS_DEFERRED ? 1 : 0;
+  if (flags & GRLX_PLAN_SWEEP)
+  { // grlx_set_replica_params
+    if ((rc = sweep_admits(*cfg, P)) != GRLX_OK) return rc;
+    if (P.replicas_per_wave > 8) P.replicas_per_wave = 8;
+  }
+  PlanFacts facts;
+  facts.sweep = (flags & GRLX_PLAN_SWEEP) || (L.no_trace_td && !records(P));
+  facts.ac_in_place = L.no_trace_ac;
+  facts.server = !(flags & GRLX_PLAN_SERVER_OFF);
+  facts.walker_server = (flags & GRLX_PLAN_WALKER_SERVER) != 0;
+  facts.fits = (flags & GRLX_PLAN_FITS_YES) ? +[](const KernelRow &) { return true; } :
+               (flags & GRLX_PLAN_FITS_NO) ? +[](const KernelRow &) { return false; } : waves_fit_together;
+  if (cfg->env == GRLX_ENV_EXTERNAL) return fail(GRLX_ERR_INVALID, "this context has no environment (GRLX_ENV_EXTERNAL): it launches no rollout kernel");
+  const KernelPlan plan = plan_rollout(P, facts);
+  if (!plan.row) return fail(GRLX_ERR_INVALID, "no rollout kernel is built for this launch");
+  if (replicas_per_wave) *replicas_per_wave = P.replicas_per_wave;
+  if (variant) *variant = plan.row->variant;
+  if (grid) *grid = (int)plan.grid;
+  if (rollout_name && name_cap) snprintf(rollout_name, name_cap, "%s", plan.row->name);
+  if (server_name && name_cap) snprintf(server_name, name_cap, "%s", plan.server ? plan.row->server_name : "");
+  return GRLX_OK;
+}
 
 int grlx_get_replica_params(grlx_ctx *ctx, int param, double *values)
 {
@@ -1187,7 +1207,7 @@ int grlx_set_replica_params(grlx_ctx *ctx, int param, const double *values)
   if (!ctx || !values) return fail(GRLX_ERR_INVALID, "null argument");
   if (param < 0 || param > 3) return fail(GRLX_ERR_INVALID, "param %d is not one of GRLX_PARAM_*", param);
   if (ctx->launched) return fail(GRLX_ERR_INVALID, "grlx_set_replica_params is allowed only before the first launch of the context");
-  int rc = sweep_admits(ctx);
+  int rc = sweep_admits(ctx->cfg, ctx->P);
   if (rc != GRLX_OK) return rc;
   const size_t N = (size_t)ctx->P.n_replicas;
   // the four values of every replica with this call applied, validated as make_params validates the shared ones
@@ -1514,7 +1534,7 @@ int grlx_env_advance(grlx_ctx *ctx, const int32_t *active, const double *action,
 static int agent_ready(grlx_ctx *ctx)
 {
   const grlx_config &c = ctx->cfg;
-  const bool td = c.agent == GRLX_AGENT_SARSA || c.agent == GRLX_AGENT_Q || c.agent == GRLX_AGENT_EXPECTED_SARSA;
+  const bool td = is_td_agent(c.agent);
   if (!(td || c.agent == GRLX_AGENT_AC) || c.trace == GRLX_TRACE_ACCUMULATING || c.target_interval > 0 || c.projector.safe != 0 ||
       (td && c.action_steps != 3 && c.action_steps != 5))
     return fail(GRLX_ERR_INVALID, "the per-step agent entry points are built for agent/td with predictor/critic/{sarsa, q, expected_sarsa} (3 or 5 actions, "

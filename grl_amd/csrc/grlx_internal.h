@@ -16,6 +16,7 @@ constexpr int kMaxTrace = 10;            // replacing trace: (gamma*lambda)^n < 
 constexpr int kMaxActions = GRLX_MAX_ACTIONS;
 constexpr uint32_t kInvalidPos = 0xFFFFFFFFu;
 constexpr int kMaxProbe = 2048;
+constexpr int kAcOwnedMax = 64;      // replicas a wave of the rotating (B = 3) actor-critic kernel can own (grlx_rollout_ac_wide.h)
 
 // status bits (sticky, per replica)
 enum : uint32_t { ST_TABLE_FULL = 1u, ST_DOMAIN = 2u, ST_ROWS_FULL = 4u, ST_TRACE_OVERFLOW = 8u,
@@ -136,7 +137,7 @@ struct DevParams {
   uint64_t steps_budget;
   uint32_t env_tune;            // experiments (GRLX_ENV_SERVER_TUNE): bits 0-1 s_setprio of the rollout wave, 2-3 of the server wave, 4 no prefetch;
                                 // tests: bit 6 the server leaves at once (every replica falls back to integrating itself)
-  void    *park;                // rotating actor-critic kernel (12 slots): lane state of the third sub-batch, kAcParkBytes per wave
+  void    *park;                // 32-replica waves of the compass walker: lane state of the sub-batches beyond the third, 5 x kAcParkBytes per wave
   struct EnvMail *env_mail;     // mailboxes of the environment server ([replica], grlx_env_server.h); null = the rollout kernel integrates itself
   int32_t  test_trials;         // experiment/online_learning:test_trials (>= 1): greedy episodes per test trial, averaged in the row
   // Actor-critic with EQUAL tile codings for actor and critic (cfg/cart_pole/ac_tc.yaml: the critic copies resolution and memory):
@@ -156,19 +157,51 @@ struct DevParams {
   uint32_t *agent_lane;         // [replica][16 lanes][2]: reference slots of project(prev_obs, prev_action) / critic's and actor's project(prev_obs)
 };
 
+inline bool is_td_agent(int agent) { return agent == GRLX_AGENT_SARSA || agent == GRLX_AGENT_Q || agent == GRLX_AGENT_EXPECTED_SARSA; }
+inline bool tapped(const DevParams &P) { return P.tap_replica >= 0 && P.tap_capacity > 0; }
+inline bool records(const DevParams &P) { return P.diag_out != nullptr || tapped(P); }      // stamps or per-step taps are written
+
 // ---------------------------------------------------------------------------
-// launchers implemented in grlx_kernels.hip
-// *variant (optional) receives the GRLX_KERNEL_* instantiation that was launched
-// sweep (optional): the per-replica learning parameters of a sweep context; set, the SpecSweep instantiations are launched
-hipError_t launch_rollout(const DevParams &P, int n_trials, hipStream_t stream, int *variant, const SweepParams *sweep = nullptr);
-bool       env_server_serves(const DevParams &P);                                   // is this context's rollout kernel one the environment server works for?
-size_t     env_server_mail_bytes(const DevParams &P);                               // ... and the size of a replica's mailbox there (0: not served)
-hipError_t launch_env_server(const DevParams &P, hipStream_t stream);
-// in_place: the instantiation that updates the critic in place (a context without a trace, grlx_api.cpp; 4 replicas per wave)
-hipError_t launch_rollout_ac(const DevParams &P, int n_trials, hipStream_t stream, int *variant, bool in_place = false);
-hipError_t launch_rollout_qv(const DevParams &P, int n_trials, hipStream_t stream, int *variant);
-hipError_t launch_rollout_acc(const DevParams &P, int n_trials, hipStream_t stream, int *variant);
-hipError_t launch_rollout_tgt(const DevParams &P, int n_trials, hipStream_t stream, int *variant);
+// The rollout instantiations: ONE table (grlx_kernel_table.h, in the translation unit that instantiates them), one row per kernel, in
+// precedence order.  plan_rollout (grlx_plan.cpp) takes the first row whose key and `matches` fit; admission at create asks the same table.
+enum KernelFamily : int { FAM_TD, FAM_AC, FAM_QV, FAM_ACC, FAM_TGT };
+// what a row is for.  DEFERRED: the production ordering, nothing recorded (the only rows whose key has a layout other than 4, with SWEEP
+// and SERVED); IN_PLACE: the instantiation that updates in place and records taps / stamps; the others as named.
+enum KernelMode : int { MODE_SWEEP, MODE_SERVED, MODE_STAMPED, MODE_TAPPED, MODE_ADVANTAGE, MODE_DEFERRED, MODE_IN_PLACE };
+struct KernelRow {
+  int family, env, actions, replicas_per_wave, mode;
+  int target, safe;                                   // FAM_TGT: the (target network, claim table) pair of the instantiation
+  bool (*matches)(const DevParams &);                 // Spec...::matches; null for SpecNone
+  int variant;                                        // GRLX_KERNEL_* reported by grlx_last_kernel
+  const char *name; const void *kernel;               // the instantiation as spelled in the table, and its address
+  const char *server_name; const void *server;        // the environment server that goes with it (null: none) ...
+  size_t mail_bytes;                                  // ... and the size of a replica's mailbox there
+};
+const KernelRow *kernel_rows(int *count);
+hipError_t launch_set_u32(uint32_t *p, uint32_t v, hipStream_t stream);                // the queue word of the wide actor-critic kernels
+
+// grlx_plan.cpp.  What a launch needs to know besides its parameters, passed in explicitly so that the plan is a pure function.
+struct PlanFacts {
+  bool sweep;                                         // the SpecSweep rows run: a sweep context, or a TD context without a trace that records nothing
+  bool ac_in_place;                                   // an actor-critic context without a trace
+  bool server;                                        // the environment server is on (GRLX_ENV_SERVER)
+  bool walker_server;                                 // ... for the compass walker too (GRLX_ENV_SERVER_WALKER)
+  bool (*fits)(const KernelRow &);                    // do a wave of the row's kernel and one of its server fit one SIMD?
+};
+struct KernelPlan {
+  const KernelRow *row;                               // null: nothing is built for this launch
+  unsigned grid;                                      // waves of the rollout kernel (and blocks of the server)
+  bool set_queue; uint32_t queue_word;                // wide actor-critic kernels: the next unstarted replica, set before the launch
+  bool server;                                        // launch row->server beside it
+};
+KernelPlan plan_rollout(const DevParams &P, const PlanFacts &facts);
+bool kernel_built(int family, int env, int actions, int replicas_per_wave, int mode, int target = 0, int safe = 0);
+bool waves_fit_together(const KernelRow &row);        // asks the runtime, once per row
+// the layout a context gets: replicas per wave from (config, SIMD count), and the two no-trace routings (see grlx_ctx)
+struct Layout { int replicas_per_wave, wave_limit; bool no_trace_td, no_trace_ac; };
+Layout choose_layout(const grlx_config &cfg, int simds);
+// `server`: the stream of the server's launch when the plan has one
+hipError_t launch_plan(const KernelPlan &plan, const DevParams &P, int n_trials, const SweepParams *sweep, hipStream_t stream, hipStream_t server);
 // diagnostic: overwrite the whole vector register file (512 registers per lane) and the user SGPRs of every SIMD with
 // `pattern`, so that a kernel launched next on `stream` that reads a register it never wrote computes with that
 // pattern instead of with whatever the previous wave left (GRLX_POISON_REGISTERS)

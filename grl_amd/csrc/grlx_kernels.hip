@@ -14,6 +14,7 @@
 //    four entries, grlx_table.h), lazily initialised to the value the reference's
 //    8,388,608-draw initialisation gives that slot (LCG jump-ahead, grlx_rng.h).
 //  * the TD update of a step is applied one pass later, under the next step's loads.
+//  * which instantiation a launch runs is decided in one place: the rows of grlx_kernel_table.h (included last), read by grlx_plan.cpp.
 //  * what a trial, a counted step, a tap record and a result row are is the same in every four-replica
 //    kernel: grlx_frame.h (included after grlx_update.h, before the first rollout header).
 //  * sums over the 16 tilings are taken in the reference's serial order
@@ -105,389 +106,10 @@ hipError_t launch_poison_registers(uint32_t pattern, hipStream_t stream)
   return hipGetLastError();
 }
 
-// ------------------------------------------------------------- launchers ---
-
-hipError_t launch_rollout_ac(const DevParams &P, int n_trials, hipStream_t stream, int *variant, bool in_place)
+hipError_t launch_set_u32(uint32_t *p, uint32_t v, hipStream_t stream)
 {
-  // taps are recorded by the in-place instantiation; a context without a trace runs it too (in_place): the deferred critic update
-  // stores p's weight behind the loads of V(s') already in flight, and without a trace nothing forwards it to them
-  const bool taps = in_place || (P.tap_replica >= 0 && P.tap_capacity > 0);
-  if (variant) *variant = taps ? GRLX_KERNEL_IN_PLACE : GRLX_KERNEL_GENERIC;
-  int waves = (P.n_replicas + kReplicasPerWave - 1) / kReplicasPerWave;
-  if (!taps && P.replicas_per_wave >= 8)
-  { // two (four) sub-batches per wave share one environment phase (grlx_rollout_ac_wide.h); at most wave_limit waves, the
-    // replicas beyond their first load are handed out by a device-side counter as slots fall idle
-    int R = P.replicas_per_wave;
-    int all_waves = (P.n_replicas + R - 1) / R;
-    int wwaves = all_waves < P.wave_limit ? all_waves : P.wave_limit;
-    // 12 slots: every wave owns ceil(n / waves) consecutive replicas and rotates them through its slots (no device-wide queue); a batch
-    // that would give a wave more than kAcOwnedMax runs in the 8-slot kernel
-    if (R == 12 && (P.n_replicas + wwaves - 1) / wwaves > kAcOwnedMax)
-    {
-      R = 8;
-      all_waves = (P.n_replicas + R - 1) / R;
-      wwaves = all_waves < P.wave_limit ? all_waves : P.wave_limit;
-    }
-    if (R == 12)
-    { // (with K = ceil(n / waves) replicas per wave the last waves may own none: launch only the ones that own some)
-      const int k = (P.n_replicas + wwaves - 1) / wwaves;
-      wwaves = (P.n_replicas + k - 1) / k;
-    }
-    hipLaunchKernelGGL(set_u32_kernel, dim3(1), dim3(1), 0, stream, P.queue, (uint32_t)wwaves * (uint32_t)R);
-#define GRLX_LAUNCH_AC_WIDE(NB)                                                                                                  \
-    if (P.env == GRLX_ENV_CART_POLE && !P.no_specialisation && SpecCartPoleAc::matches(P))                                       \
-    {                                                                                                                            \
-      if (variant) *variant = GRLX_KERNEL_SPECIALISED;                                                                           \
-      hipLaunchKernelGGL((rollout_ac_wide_kernel<GRLX_ENV_CART_POLE, NB, SpecCartPoleAc>), dim3(wwaves), dim3(64), 0, stream, P, n_trials); \
-    }                                                                                                                            \
-    else if (P.env == GRLX_ENV_CART_POLE)                                                                                        \
-      hipLaunchKernelGGL((rollout_ac_wide_kernel<GRLX_ENV_CART_POLE, NB, SpecNone>), dim3(wwaves), dim3(64), 0, stream, P, n_trials); \
-    else if (P.env == GRLX_ENV_PENDULUM)                                                                                         \
-      hipLaunchKernelGGL((rollout_ac_wide_kernel<GRLX_ENV_PENDULUM, NB, SpecNone>), dim3(wwaves), dim3(64), 0, stream, P, n_trials); \
-    else                                                                                                                         \
-      return hipErrorInvalidValue;
-    if (R == 16) { GRLX_LAUNCH_AC_WIDE(4) }
-    else if (R == 12) { GRLX_LAUNCH_AC_WIDE(3) }
-    else { GRLX_LAUNCH_AC_WIDE(2) }
-#undef GRLX_LAUNCH_AC_WIDE
-    return hipGetLastError();
-  }
-  switch (P.env)
-  {
-    case GRLX_ENV_CART_POLE:
-      if (taps)
-        hipLaunchKernelGGL((rollout_ac_kernel<GRLX_ENV_CART_POLE, SpecNone, false>), dim3(waves), dim3(64), 0, stream, P, n_trials);
-      else if (!P.no_specialisation && SpecCartPoleAc::matches(P))
-      {
-        if (variant) *variant = GRLX_KERNEL_SPECIALISED;
-        hipLaunchKernelGGL((rollout_ac_kernel<GRLX_ENV_CART_POLE, SpecCartPoleAc, true>), dim3(waves), dim3(64), 0, stream, P, n_trials);
-      }
-      else
-        hipLaunchKernelGGL((rollout_ac_kernel<GRLX_ENV_CART_POLE, SpecNone, true>), dim3(waves), dim3(64), 0, stream, P, n_trials);
-      break;
-    case GRLX_ENV_PENDULUM:
-      if (taps)
-        hipLaunchKernelGGL((rollout_ac_kernel<GRLX_ENV_PENDULUM, SpecNone, false>), dim3(waves), dim3(64), 0, stream, P, n_trials);
-      else
-        hipLaunchKernelGGL((rollout_ac_kernel<GRLX_ENV_PENDULUM, SpecNone, true>), dim3(waves), dim3(64), 0, stream, P, n_trials);
-      break;
-    default:
-      return hipErrorInvalidValue;
-  }
+  hipLaunchKernelGGL(set_u32_kernel, dim3(1), dim3(1), 0, stream, p, v);
   return hipGetLastError();
-}
-
-// The environment server works for the deferred-update pendulum instantiations of rollout_kernel with three actions (EXT in grlx_rollout.h),
-// and -- its own kernel, grlx_env_server_wide.h -- for the wide kernels of the acrobot and the compass walker (8 replicas per wave, three actions).
-// do a wave of the rollout kernel and a wave of its server fit on one SIMD together (512 registers)?  asked of the runtime once per pair
-template <typename KA, typename KB>
-static bool waves_fit_together(KA rollout, KB server)
-{
-  hipFuncAttributes a, b;
-  if (hipFuncGetAttributes(&a, reinterpret_cast<const void *>(rollout)) != hipSuccess || hipFuncGetAttributes(&b, reinterpret_cast<const void *>(server)) != hipSuccess)
-  {
-    (void)hipGetLastError();
-    return false;
-  }
-  const int gran = 8;                                  // allocation granule of the unified register file
-  const int ra = (a.numRegs + gran - 1) / gran * gran, rb = (b.numRegs + gran - 1) / gran * gran;
-  if (getenv("GRLX_ENV_SERVER_DEBUG"))
-    fprintf(stderr, "grlx: rollout wave %d registers (%zu B scratch, %zu B LDS) + server wave %d registers (%zu B scratch): %s\n", a.numRegs, a.localSizeBytes,
-            a.sharedSizeBytes, b.numRegs, b.localSizeBytes, ra + rb <= 512 ? "resident together" : "do not fit one SIMD");
-  return ra + rb <= 512;
-}
-static bool env_server_wide(const DevParams &P)
-{
-  const bool inplace = P.diag_out != nullptr || (P.tap_replica >= 0 && P.tap_capacity > 0);
-  const bool td = P.agent == GRLX_AGENT_SARSA || P.agent == GRLX_AGENT_Q || P.agent == GRLX_AGENT_EXPECTED_SARSA;
-  if (!(!inplace && P.replicas_per_wave == 8 && (P.env == GRLX_ENV_ACROBOT || P.env == GRLX_ENV_COMPASS_WALKER) && P.A == 3 && td &&
-        P.trace_kind != GRLX_TRACE_ACCUMULATING && P.target_interval == 0 && P.tile_safe == 0))
-    return false;
-  // The walker's server is built and tested but NOT the default: beside the 346-register rollout wave it has 160 registers, too few to hold
-  // the sine's constants and the integrator's stages, and the code it becomes issues more vector instructions than the SIMD has slots left
-  // (measured: 180-213 M env-steps/s with it against 220 M without).  GRLX_ENV_SERVER_WALKER=1 turns it on.
-  if (P.env == GRLX_ENV_COMPASS_WALKER)
-  {
-    const char *w = getenv("GRLX_ENV_SERVER_WALKER");
-    if (!w || atoi(w) == 0) return false;
-  }
-  // a server that cannot be resident beside its rollout wave would only be waited for in vain (8000 polls at the first step)
-  static const bool fit_walker_spec = waves_fit_together(rollout_wide_served_kernel<GRLX_ENV_COMPASS_WALKER, SpecWalkerQ>, env_server_walker_kernel<SpecWalkerQ>);
-  static const bool fit_acrobot_spec = waves_fit_together(rollout_wide_served_kernel<GRLX_ENV_ACROBOT, SpecAcrobotQ>, env_server_acrobot_pinned_kernel<SpecAcrobotQ>);
-  static const bool fit_walker = waves_fit_together(rollout_wide_served_kernel<GRLX_ENV_COMPASS_WALKER, SpecNone>, env_server_walker_kernel<SpecNone>);
-  static const bool fit_acrobot = waves_fit_together(rollout_wide_served_kernel<GRLX_ENV_ACROBOT, SpecNone>, env_server_acrobot_kernel<SpecNone>);
-  if (!P.no_specialisation && SpecWalkerQ::matches(P)) return fit_walker_spec;
-  if (!P.no_specialisation && SpecAcrobotQ::matches(P)) return fit_acrobot_spec;
-  return P.env == GRLX_ENV_ACROBOT ? fit_acrobot : fit_walker;
-}
-bool env_server_serves(const DevParams &P)
-{
-  const bool inplace = P.diag_out != nullptr || (P.tap_replica >= 0 && P.tap_capacity > 0);
-  if (env_server_wide(P)) return true;
-  return !inplace && P.replicas_per_wave == 4 && P.env == GRLX_ENV_PENDULUM && P.A == 3 && P.agent != GRLX_AGENT_ADVANTAGE;
-}
-size_t env_server_mail_bytes(const DevParams &P)
-{
-  return env_server_wide(P) ? kWideMailBytes : env_server_serves(P) ? kEnvMailBytes : 0;
-}
-
-// One block per rollout wave, with the numeric parameters of the instantiation launch_rollout picks (same constants, same folding).
-hipError_t launch_env_server(const DevParams &P, hipStream_t stream)
-{
-  if (!P.env_mail || !env_server_serves(P)) return hipErrorInvalidValue;
-  if (env_server_wide(P))
-  { // one block per wide rollout wave (8 replicas), with the numeric parameters of the instantiation launch_rollout picks
-    const int wwaves = (P.n_replicas + 7) / 8;
-    if (!P.no_specialisation && SpecWalkerQ::matches(P))
-      hipLaunchKernelGGL((env_server_walker_kernel<SpecWalkerQ>), dim3(wwaves), dim3(64), 0, stream, P);
-    else if (!P.no_specialisation && SpecAcrobotQ::matches(P))
-      hipLaunchKernelGGL((env_server_acrobot_pinned_kernel<SpecAcrobotQ>), dim3(wwaves), dim3(64), 0, stream, P);
-    else if (P.env == GRLX_ENV_ACROBOT)
-      hipLaunchKernelGGL((env_server_acrobot_kernel<SpecNone>), dim3(wwaves), dim3(64), 0, stream, P);
-    else
-      hipLaunchKernelGGL((env_server_walker_kernel<SpecNone>), dim3(wwaves), dim3(64), 0, stream, P);
-    return hipGetLastError();
-  }
-  const int waves = (P.n_replicas + kReplicasPerWave - 1) / kReplicasPerWave;
-#define GRLX_LAUNCH_SERVER(AGENT)                                                                                      \
-  if (!P.no_specialisation && SpecPendulumTcA<AGENT>::matches(P))                                                    \
-  {                                                                                                                  \
-    hipLaunchKernelGGL((env_server_kernel<GRLX_ENV_PENDULUM, 3, SpecPendulumTcA<AGENT>>), dim3(waves), dim3(64), 0, stream, P); \
-    return hipGetLastError();                                                                                        \
-  }
-  GRLX_LAUNCH_SERVER(GRLX_AGENT_SARSA)
-  GRLX_LAUNCH_SERVER(GRLX_AGENT_Q)
-  GRLX_LAUNCH_SERVER(GRLX_AGENT_EXPECTED_SARSA)
-#undef GRLX_LAUNCH_SERVER
-  hipLaunchKernelGGL((env_server_kernel<GRLX_ENV_PENDULUM, 3, SpecNone>), dim3(waves), dim3(64), 0, stream, P);
-  return hipGetLastError();
-}
-
-hipError_t launch_rollout(const DevParams &P, int n_trials, hipStream_t stream, int *variant, const SweepParams *sweep)
-{
-  if (variant) *variant = GRLX_KERNEL_GENERIC;
-  int waves = (P.n_replicas + kReplicasPerWave - 1) / kReplicasPerWave;
-  if (sweep)
-  { // a hyper-parameter sweep (grlx_set_replica_params): the production ordering with the learning parameters of every replica its own.
-    // What grlx_api.cpp admits as a sweep context has one of these instantiations; anything else is an error, never the shared values.
-    const bool inplace = P.diag_out != nullptr || (P.tap_replica >= 0 && P.tap_capacity > 0);
-    const bool td = P.agent == GRLX_AGENT_SARSA || P.agent == GRLX_AGENT_Q || P.agent == GRLX_AGENT_EXPECTED_SARSA;
-    if (inplace || !td || P.env_mail || P.trace_kind == GRLX_TRACE_ACCUMULATING || P.target_interval != 0 || P.tile_safe != 0 ||
-        (P.replicas_per_wave != 4 && P.replicas_per_wave != 8))
-      return hipErrorInvalidValue;
-    const int wwaves = (P.n_replicas + 7) / 8;
-#define GRLX_LAUNCH_SWEEP(ENVID, NACT)                                                                                \
-    if (P.env == ENVID && P.A == NACT)                                                                              \
-    {                                                                                                               \
-      if (P.replicas_per_wave == 8)                                                                                 \
-        hipLaunchKernelGGL((rollout_wide_sweep_kernel<ENVID, NACT>), dim3(wwaves), dim3(64), 0, stream, P, n_trials, sweep); \
-      else                                                                                                          \
-        hipLaunchKernelGGL((rollout_sweep_kernel<ENVID, NACT>), dim3(waves), dim3(64), 0, stream, P, n_trials, sweep);    \
-      return hipGetLastError();                                                                                     \
-    }
-    GRLX_LAUNCH_SWEEP(GRLX_ENV_PENDULUM, 3)
-    GRLX_LAUNCH_SWEEP(GRLX_ENV_PENDULUM, 5)
-    GRLX_LAUNCH_SWEEP(GRLX_ENV_ACROBOT, 3)
-    GRLX_LAUNCH_SWEEP(GRLX_ENV_CART_POLE, 3)
-    GRLX_LAUNCH_SWEEP(GRLX_ENV_COMPASS_WALKER, 3)
-#undef GRLX_LAUNCH_SWEEP
-    return hipErrorInvalidValue;
-  }
-  if (P.env_mail && env_server_wide(P))
-  { // the wide kernels' environment server (launch_env_server picks the same numeric parameters)
-    const int wwaves = (P.n_replicas + 7) / 8;
-#define GRLX_LAUNCH_WSERVED(SPECQ)                                                                                     \
-    if (!P.no_specialisation && SPECQ::matches(P))                                                                   \
-    {                                                                                                                \
-      if (variant) *variant = GRLX_KERNEL_SPECIALISED;                                                               \
-      hipLaunchKernelGGL((rollout_wide_served_kernel<SPECQ::kEnv, SPECQ>), dim3(wwaves), dim3(64), 0, stream, P, n_trials); \
-      return hipGetLastError();                                                                                      \
-    }
-    GRLX_LAUNCH_WSERVED(SpecWalkerQ)
-    GRLX_LAUNCH_WSERVED(SpecAcrobotQ)
-#undef GRLX_LAUNCH_WSERVED
-    if (P.env == GRLX_ENV_ACROBOT)
-      hipLaunchKernelGGL((rollout_wide_served_kernel<GRLX_ENV_ACROBOT, SpecNone>), dim3(wwaves), dim3(64), 0, stream, P, n_trials);
-    else
-      hipLaunchKernelGGL((rollout_wide_served_kernel<GRLX_ENV_COMPASS_WALKER, SpecNone>), dim3(wwaves), dim3(64), 0, stream, P, n_trials);
-    return hipGetLastError();
-  }
-  if (P.env_mail)
-  { // with the environment server (launch_env_server picks the same numeric parameters)
-    if (!env_server_serves(P)) return hipErrorInvalidValue;
-#define GRLX_LAUNCH_SERVED(AGENT)                                                                                      \
-    if (!P.no_specialisation && SpecPendulumTcA<AGENT>::matches(P))                                                  \
-    {                                                                                                                \
-      if (variant) *variant = GRLX_KERNEL_SPECIALISED;                                                               \
-      hipLaunchKernelGGL((rollout_served_kernel<3, SpecPendulumTcA<AGENT>>), dim3(waves), dim3(64), 0, stream, P, n_trials); \
-      return hipGetLastError();                                                                                      \
-    }
-    GRLX_LAUNCH_SERVED(GRLX_AGENT_SARSA)
-    GRLX_LAUNCH_SERVED(GRLX_AGENT_Q)
-    GRLX_LAUNCH_SERVED(GRLX_AGENT_EXPECTED_SARSA)
-#undef GRLX_LAUNCH_SERVED
-    hipLaunchKernelGGL((rollout_served_kernel<3, SpecNone>), dim3(waves), dim3(64), 0, stream, P, n_trials);
-    return hipGetLastError();
-  }
-  // stamps and per-step taps are recorded by the instantiation that updates in place
-#ifdef GRLX_WIDE_STAMPS
-  const bool inplace = P.tap_replica >= 0 && P.tap_capacity > 0;      // stamped wide build: diag_out feeds the wide kernel
-#else
-  const bool inplace = P.diag_out != nullptr || (P.tap_replica >= 0 && P.tap_capacity > 0);
-#endif
-  if (P.diag_out && P.diag_deferred && P.env == GRLX_ENV_PENDULUM && P.A == 3 && !(P.tap_replica >= 0 && P.tap_capacity > 0))
-  {
-    if (variant) *variant = GRLX_KERNEL_GENERIC;
-    hipLaunchKernelGGL((rollout_kernel<GRLX_ENV_PENDULUM, 3, true, SpecNone, true>), dim3(waves), dim3(64), 0, stream, P, n_trials);
-    return hipGetLastError();
-  }
-  if (P.tap_deferred && P.tap_replica >= 0 && P.tap_capacity > 0 && !P.diag_out && P.agent != GRLX_AGENT_ADVANTAGE)
-  { // per-step records of the production ordering (tests): generic instantiation, deferred update, taps
-    if (variant) *variant = GRLX_KERNEL_GENERIC;
-#define GRLX_LAUNCH_TAPDEF(ENVID, NACT)                                                                               \
-    if (P.env == ENVID && P.A == NACT)                                                                              \
-    {                                                                                                               \
-      hipLaunchKernelGGL((rollout_kernel<ENVID, NACT, false, SpecNone, true, false, true>), dim3(waves), dim3(64), 0, stream, P, n_trials); \
-      return hipGetLastError();                                                                                     \
-    }
-    GRLX_LAUNCH_TAPDEF(GRLX_ENV_PENDULUM, 3)
-    GRLX_LAUNCH_TAPDEF(GRLX_ENV_PENDULUM, 5)
-    GRLX_LAUNCH_TAPDEF(GRLX_ENV_ACROBOT, 3)
-#undef GRLX_LAUNCH_TAPDEF
-    return hipErrorInvalidValue;
-  }
-#define GRLX_LAUNCH(ENVID, NACT)                                                                              \
-  if (P.env == ENVID && P.A == NACT)                                                                        \
-  {                                                                                                         \
-    if (variant && inplace) *variant = GRLX_KERNEL_IN_PLACE;                                                \
-    if (inplace)                                                                                            \
-      hipLaunchKernelGGL((rollout_kernel<ENVID, NACT, true, SpecNone>), dim3(waves), dim3(64), 0, stream, P, n_trials); \
-    else                                                                                                    \
-      hipLaunchKernelGGL((rollout_kernel<ENVID, NACT, false, SpecNone>), dim3(waves), dim3(64), 0, stream, P, n_trials); \
-    return hipGetLastError();                                                                               \
-  }
-  if (P.agent == GRLX_AGENT_ADVANTAGE)
-  { // advantage learning: its own in-place instantiation (taps included)
-    if (variant) *variant = GRLX_KERNEL_IN_PLACE;
-#define GRLX_LAUNCH_ADV(ENVID, NACT)                                                                                  \
-    if (P.env == ENVID && P.A == NACT)                                                                              \
-    {                                                                                                               \
-      hipLaunchKernelGGL((rollout_kernel<ENVID, NACT, true, SpecNone, false, true>), dim3(waves), dim3(64), 0, stream, P, n_trials); \
-      return hipGetLastError();                                                                                     \
-    }
-    GRLX_LAUNCH_ADV(GRLX_ENV_PENDULUM, 3)
-    GRLX_LAUNCH_ADV(GRLX_ENV_ACROBOT, 3)
-#undef GRLX_LAUNCH_ADV
-    return hipErrorInvalidValue;
-  }
-  if (!inplace && P.replicas_per_wave == 32)
-  { // 30 or more compass walkers per SIMD: EIGHT sub-batches per wave (two lanes per replica in the environment phase: the walker's two sines);
-    // the sub-batches beyond the fourth park in P.park
-    const int wwaves = (P.n_replicas + 31) / 32;
-    if (!P.park || P.env != GRLX_ENV_COMPASS_WALKER || P.A != 3) return hipErrorInvalidValue;
-    if (!P.no_specialisation && SpecWalkerQ::matches(P))
-    {
-      if (variant) *variant = GRLX_KERNEL_SPECIALISED;
-      hipLaunchKernelGGL((rollout_wide_kernel<GRLX_ENV_COMPASS_WALKER, 3, 8, SpecWalkerQ>), dim3(wwaves), dim3(64), 0, stream, P, n_trials);
-      return hipGetLastError();
-    }
-    hipLaunchKernelGGL((rollout_wide_kernel<GRLX_ENV_COMPASS_WALKER, 3, 8, SpecNone>), dim3(wwaves), dim3(64), 0, stream, P, n_trials);
-    return hipGetLastError();
-  }
-  if (!inplace && P.replicas_per_wave == 16)
-  { // 15 or more replicas per SIMD: FOUR sub-batches per wave share one environment phase (E + 4 T per 16 replicas instead of 2 (E + 2 T));
-    // instantiated where the environment phase is half of a pass: the acrobot and the compass walker with three actions
-    const int wwaves = (P.n_replicas + 15) / 16;
-#define GRLX_LAUNCH_WIDE4_SPECQ(SPECQ)                                                                                \
-    if (!P.no_specialisation && SPECQ::matches(P))                                                                  \
-    {                                                                                                               \
-      if (variant) *variant = GRLX_KERNEL_SPECIALISED;                                                              \
-      hipLaunchKernelGGL((rollout_wide_kernel<SPECQ::kEnv, 3, 4, SPECQ>), dim3(wwaves), dim3(64), 0, stream, P, n_trials); \
-      return hipGetLastError();                                                                                     \
-    }
-    GRLX_LAUNCH_WIDE4_SPECQ(SpecWalkerQ)
-    GRLX_LAUNCH_WIDE4_SPECQ(SpecAcrobotQ)
-#undef GRLX_LAUNCH_WIDE4_SPECQ
-    if (P.env == GRLX_ENV_ACROBOT && P.A == 3)
-    {
-      hipLaunchKernelGGL((rollout_wide_kernel<GRLX_ENV_ACROBOT, 3, 4, SpecNone>), dim3(wwaves), dim3(64), 0, stream, P, n_trials);
-      return hipGetLastError();
-    }
-    if (P.env == GRLX_ENV_COMPASS_WALKER && P.A == 3)
-    {
-      hipLaunchKernelGGL((rollout_wide_kernel<GRLX_ENV_COMPASS_WALKER, 3, 4, SpecNone>), dim3(wwaves), dim3(64), 0, stream, P, n_trials);
-      return hipGetLastError();
-    }
-    return hipErrorInvalidValue;
-  }
-  if (!inplace && P.replicas_per_wave == 8)
-  { // more replicas than 4 x SIMDs: two sub-batches per wave share one environment phase (grlx_rollout_wide.h)
-    const int wwaves = (P.n_replicas + 7) / 8;
-#define GRLX_LAUNCH_WIDE(ENVID, NACT)                                                                                 \
-    if (P.env == ENVID && P.A == NACT)                                                                              \
-    {                                                                                                               \
-      hipLaunchKernelGGL((rollout_wide_kernel<ENVID, NACT, 2, SpecNone>), dim3(wwaves), dim3(64), 0, stream, P, n_trials); \
-      return hipGetLastError();                                                                                     \
-    }
-#define GRLX_LAUNCH_WIDE_SPEC(AGENT)                                                                                  \
-    if (!P.no_specialisation && SpecPendulumTcA<AGENT>::matches(P))                                                 \
-    {                                                                                                               \
-      if (variant) *variant = GRLX_KERNEL_SPECIALISED;                                                              \
-      hipLaunchKernelGGL((rollout_wide_kernel<GRLX_ENV_PENDULUM, 3, 2, SpecPendulumTcA<AGENT>>), dim3(wwaves), dim3(64), 0, stream, P, n_trials); \
-      return hipGetLastError();                                                                                     \
-    }
-    GRLX_LAUNCH_WIDE_SPEC(GRLX_AGENT_SARSA)
-    GRLX_LAUNCH_WIDE_SPEC(GRLX_AGENT_Q)
-#define GRLX_LAUNCH_WIDE_SPECQ(SPECQ)                                                                                 \
-    if (!P.no_specialisation && SPECQ::matches(P))                                                                  \
-    {                                                                                                               \
-      if (variant) *variant = GRLX_KERNEL_SPECIALISED;                                                              \
-      hipLaunchKernelGGL((rollout_wide_kernel<SPECQ::kEnv, 3, 2, SPECQ>), dim3(wwaves), dim3(64), 0, stream, P, n_trials); \
-      return hipGetLastError();                                                                                     \
-    }
-    GRLX_LAUNCH_WIDE_SPECQ(SpecWalkerQ)
-    GRLX_LAUNCH_WIDE_SPECQ(SpecAcrobotQ)
-#undef GRLX_LAUNCH_WIDE_SPECQ
-    GRLX_LAUNCH_WIDE(GRLX_ENV_PENDULUM, 3)
-    GRLX_LAUNCH_WIDE(GRLX_ENV_PENDULUM, 5)
-    GRLX_LAUNCH_WIDE(GRLX_ENV_ACROBOT, 3)
-    GRLX_LAUNCH_WIDE(GRLX_ENV_CART_POLE, 3)
-    GRLX_LAUNCH_WIDE(GRLX_ENV_COMPASS_WALKER, 3)
-#undef GRLX_LAUNCH_WIDE
-#undef GRLX_LAUNCH_WIDE_SPEC
-    return hipErrorInvalidValue;
-  }
-  if (!inplace && !P.no_specialisation)
-  { // compile-time specialised instantiations of the reference's cfg/pendulum/{sarsa,q}_tc.yaml family
-#define GRLX_LAUNCH_SPEC(AGENT)                                                                                        \
-    if (SpecPendulumTcA<AGENT>::matches(P))                                                                            \
-    {                                                                                                                  \
-      if (variant) *variant = GRLX_KERNEL_SPECIALISED;                                                                 \
-      hipLaunchKernelGGL((rollout_kernel<GRLX_ENV_PENDULUM, 3, false, SpecPendulumTcA<AGENT>>), dim3(waves), dim3(64), 0, stream, P, n_trials); \
-      return hipGetLastError();                                                                                        \
-    }
-    GRLX_LAUNCH_SPEC(GRLX_AGENT_SARSA)
-    GRLX_LAUNCH_SPEC(GRLX_AGENT_Q)
-    GRLX_LAUNCH_SPEC(GRLX_AGENT_EXPECTED_SARSA)
-#undef GRLX_LAUNCH_SPEC
-#define GRLX_LAUNCH_SPECQ(SPECQ)                                                                                       \
-    if (SPECQ::matches(P))                                                                                             \
-    {                                                                                                                  \
-      if (variant) *variant = GRLX_KERNEL_SPECIALISED;                                                                 \
-      hipLaunchKernelGGL((rollout_kernel<SPECQ::kEnv, 3, false, SPECQ>), dim3(waves), dim3(64), 0, stream, P, n_trials); \
-      return hipGetLastError();                                                                                        \
-    }
-    GRLX_LAUNCH_SPECQ(SpecWalkerQ)
-    GRLX_LAUNCH_SPECQ(SpecAcrobotQ)
-#undef GRLX_LAUNCH_SPECQ
-  }
-  GRLX_LAUNCH(GRLX_ENV_PENDULUM, 3)
-  GRLX_LAUNCH(GRLX_ENV_PENDULUM, 5)
-  GRLX_LAUNCH(GRLX_ENV_ACROBOT, 3)
-  GRLX_LAUNCH(GRLX_ENV_CART_POLE, 3)
-  GRLX_LAUNCH(GRLX_ENV_COMPASS_WALKER, 3)
-#undef GRLX_LAUNCH
-  return hipErrorInvalidValue;
 }
 
 // -------------------------------------------------- fine-grained kernels ---
@@ -1005,3 +627,5 @@ hipError_t launch_remap_positions(const DevParams &P, const uint32_t *remap_dev,
 }
 
 } // namespace grlx
+
+#include "grlx_kernel_table.h"      // last: every rollout kernel is instantiated by its row

@@ -19,7 +19,6 @@
 
 namespace grlx {
 
-constexpr int kAcOwnedMax = 64;      // replicas a wave of the rotating (B = 3) kernel can own
 
 // WideRep slots reused: S1 holds the bits of ActionPolicy::n_ (ac_noise), eps_decay holds ActionPolicy::decay_ (ac_decay).
 template <int ENV, int B, typename SPEC>

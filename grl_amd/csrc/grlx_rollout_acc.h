@@ -409,31 +409,5 @@ __global__ __launch_bounds__(64) void rollout_acc_kernel(DevParams P, int n_tria
   store_status(RS, ids, run.status);
 }
 
-hipError_t launch_rollout_acc(const DevParams &P, int n_trials, hipStream_t stream, int *variant)
-{
-  if (variant) *variant = GRLX_KERNEL_IN_PLACE;
-  int waves = (P.n_replicas + kReplicasPerWave - 1) / kReplicasPerWave;
-  if (!P.no_specialisation && !(P.tap_replica >= 0 && P.tap_capacity > 0))
-  {
-#define GRLX_LAUNCH_ACC_SPEC(AGENT)                                                                                              \
-    if (SpecPendulumAcc<AGENT>::matches(P))                                                                                      \
-    {                                                                                                                            \
-      if (variant) *variant = GRLX_KERNEL_SPECIALISED;                                                                           \
-      hipLaunchKernelGGL((rollout_acc_kernel<GRLX_ENV_PENDULUM, 3, SpecPendulumAcc<AGENT>>), dim3(waves), dim3(64), 0, stream, P, n_trials); \
-      return hipGetLastError();                                                                                                  \
-    }
-    GRLX_LAUNCH_ACC_SPEC(GRLX_AGENT_SARSA)
-    GRLX_LAUNCH_ACC_SPEC(GRLX_AGENT_Q)
-#undef GRLX_LAUNCH_ACC_SPEC
-  }
-  if (P.env == GRLX_ENV_PENDULUM && P.A == 3)
-    hipLaunchKernelGGL((rollout_acc_kernel<GRLX_ENV_PENDULUM, 3>), dim3(waves), dim3(64), 0, stream, P, n_trials);
-  else if (P.env == GRLX_ENV_ACROBOT && P.A == 3)
-    hipLaunchKernelGGL((rollout_acc_kernel<GRLX_ENV_ACROBOT, 3>), dim3(waves), dim3(64), 0, stream, P, n_trials);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
-}
-
 
 } // namespace grlx

@@ -285,18 +285,5 @@ __global__ __launch_bounds__(64) void rollout_qv_kernel(DevParams P, int n_trial
   store_status(RS, ids, status);
 }
 
-hipError_t launch_rollout_qv(const DevParams &P, int n_trials, hipStream_t stream, int *variant)
-{
-  if (variant) *variant = GRLX_KERNEL_IN_PLACE;
-  int waves = (P.n_replicas + kReplicasPerWave - 1) / kReplicasPerWave;
-  if (P.env == GRLX_ENV_PENDULUM && P.A == 3)
-    hipLaunchKernelGGL((rollout_qv_kernel<GRLX_ENV_PENDULUM, 3>), dim3(waves), dim3(64), 0, stream, P, n_trials);
-  else if (P.env == GRLX_ENV_ACROBOT && P.A == 3)
-    hipLaunchKernelGGL((rollout_qv_kernel<GRLX_ENV_ACROBOT, 3>), dim3(waves), dim3(64), 0, stream, P, n_trials);
-  else
-    return hipErrorInvalidValue;
-  return hipGetLastError();
-}
-
 
 } // namespace grlx

@@ -508,31 +508,6 @@ __global__ __launch_bounds__(64) void rollout_tgt_kernel(DevParams P, int n_tria
   store_status(RS, ids, run.status);
 }
 
-hipError_t launch_rollout_tgt(const DevParams &P, int n_trials, hipStream_t stream, int *variant)
-{
-  if (variant) *variant = GRLX_KERNEL_IN_PLACE;
-  int waves = (P.n_replicas + kReplicasPerWave - 1) / kReplicasPerWave;
-  const bool target = P.target_interval > 0, safe = P.tile_safe != 0;
-#define GRLX_LAUNCH_PLAIN(ENVID, TG, SF)                                                                              \
-  if (P.env == ENVID && P.A == 3 && target == TG && safe == SF)                                                     \
-  {                                                                                                                 \
-    hipLaunchKernelGGL((rollout_tgt_kernel<ENVID, 3, TG, SF>), dim3(waves), dim3(64), 0, stream, P, n_trials);      \
-    return hipGetLastError();                                                                                       \
-  }
-  GRLX_LAUNCH_PLAIN(GRLX_ENV_PENDULUM, true, false)
-  GRLX_LAUNCH_PLAIN(GRLX_ENV_PENDULUM, false, true)
-  GRLX_LAUNCH_PLAIN(GRLX_ENV_PENDULUM, true, true)
-  GRLX_LAUNCH_PLAIN(GRLX_ENV_ACROBOT, true, false)
-  GRLX_LAUNCH_PLAIN(GRLX_ENV_ACROBOT, false, true)
-  // round 3: the other two environments of the path (a discretised cart-pole; cfg/compass_walker/qlearning_walk.yaml)
-  GRLX_LAUNCH_PLAIN(GRLX_ENV_CART_POLE, true, false)
-  GRLX_LAUNCH_PLAIN(GRLX_ENV_CART_POLE, false, true)
-  GRLX_LAUNCH_PLAIN(GRLX_ENV_COMPASS_WALKER, true, false)
-  GRLX_LAUNCH_PLAIN(GRLX_ENV_COMPASS_WALKER, false, true)
-#undef GRLX_LAUNCH_PLAIN
-  return hipErrorInvalidValue;
-}
-
 // current target-network value of reference slots (no insertion)
 __global__ void get_target_weights_kernel(DevParams P, int replica, const uint32_t *slots, int n, double *out)
 {

@@ -165,6 +165,10 @@ class Runner:
         """capi GRLX_KERNEL_*: 1 generic, 2 specialised (compile-time instantiation), 3 diagnostic in-place."""
         return self.lib.grlx_last_kernel(self._ctx)
 
+    def last_kernel_name(self) -> str:
+        """The row of the kernel table the context launched last, as spelled there ("" before the first launch) -- diagnostic export."""
+        return self.lib.grlx_last_kernel_name(self._ctx).decode()
+
     def env_server_counts(self):
         """(replicas served by the environment server to the end of the last launch that had it, replicas that fell back to integrating
         themselves); (0, 0) when no launch of this context had it -- diagnostic export, not part of include/grlx.h"""

@@ -20,6 +20,24 @@ int grlx_env_server_debug(grlx_ctx *ctx, void *out, size_t bytes);
 /* Shader-clock stamps of the LAST fqi_epochs_kernel launch (GRLX_FQI_STAMPS=1 at grlx_fqi_create): count = n_replicas * 16 * 4 * 8. */
 int grlx_fqi_debug_stamps(grlx_fqi_ctx *ctx, unsigned long long *out, int count);
 
+/* Which kernel runs.  Every rollout instantiation is one row of the kernel table (grl_amd/csrc/grlx_kernel_table.h); a row's name is the
+ * instantiation as spelled there, e.g. "rollout_wide_kernel<GRLX_ENV_ACROBOT, 3, 4, SpecAcrobotQ>".
+ * grlx_last_kernel_name: the row the context launched last ("" before the first launch).
+ * grlx_kernel_plan: what a context of this configuration would launch on a device of `simds` SIMDs, WITHOUT a device: the validation of
+ * grlx_create (its error codes and messages), the layout choice and the plan of one launch.  Out (each optional): the replicas per wave,
+ * the GRLX_KERNEL_* variant, the grid, the rollout row's name and the server row's name ("" when the launch has no environment server),
+ * each name truncated to name_cap bytes. */
+#define GRLX_PLAN_STAMPS_IN_PLACE 1   /* as after grlx_set_diag(ctx, 1) */
+#define GRLX_PLAN_STAMPS_DEFERRED 2   /* as after grlx_set_diag(ctx, 2) */
+#define GRLX_PLAN_SWEEP           4   /* as after grlx_set_replica_params */
+#define GRLX_PLAN_SERVER_OFF      8   /* GRLX_ENV_SERVER=0 */
+#define GRLX_PLAN_WALKER_SERVER  16   /* GRLX_ENV_SERVER_WALKER=1 */
+#define GRLX_PLAN_FITS_YES       32   /* a rollout wave and its server wave fit one SIMD: yes / no; neither flag: ask the runtime */
+#define GRLX_PLAN_FITS_NO        64
+const char *grlx_last_kernel_name(grlx_ctx *ctx);
+int grlx_kernel_plan(const grlx_config *cfg, int simds, int flags, int *replicas_per_wave, int *variant, int *grid, char *rollout_name,
+                     char *server_name, size_t name_cap);
+
 #ifdef __cplusplus
 }
 #endif
