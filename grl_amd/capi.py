@@ -63,6 +63,15 @@ class Tap(C.Structure):
                 ("q", C.c_double * MAX_ACTIONS), ("p_idx", C.c_uint32 * 32), ("state", C.c_double * MAX_STATE)]
 
 
+class SnapshotInfo(C.Structure):
+    """grlx_snapshot_info_t (include/grlx.h)"""
+    _fields_ = [("format_version", C.c_uint32), ("n_replicas", C.c_uint32), ("n_tables", C.c_uint32), ("table_log2", C.c_uint32),
+                ("is_sweep", C.c_uint32), ("has_trace", C.c_uint32), ("has_target", C.c_uint32), ("twin_tables", C.c_uint32),
+                ("rows", C.c_uint32), ("record_bytes", C.c_uint32), ("trials_run", C.c_int64),
+                ("total_bytes", C.c_uint64), ("header_bytes", C.c_uint64), ("n_records", C.c_uint64), ("checksum", C.c_uint64),
+                ("section_bytes", C.c_uint64 * 5), ("config", Config)]
+
+
 class GrlxError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"grlx error {code}: {msg}")
@@ -107,6 +116,10 @@ _SIGS = {
     "grlx_get_target_weights": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_uint32), C.c_int, _P(C.c_double), _P(C.c_uint32)]),
     "grlx_export_weights": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P(C.c_double)]),
     "grlx_load_weights": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_double), C.c_uint64]),
+    "grlx_snapshot_size": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
+    "grlx_snapshot_save": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_uint64)]),
+    "grlx_snapshot_load": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "grlx_snapshot_info": (C.c_int, [C.c_void_p, C.c_uint64, _P(SnapshotInfo)]),
     "grlx_read_taps": (C.c_int, [C.c_void_p, _P(Tap), C.c_int, _P(C.c_int)]),
     "grlx_env_start": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_int32), _P(C.c_double)]),
     "grlx_env_advance": (C.c_int, [C.c_void_p, _P(C.c_int32), _P(C.c_double), _P(C.c_double), _P(C.c_double), _P(C.c_int32)]),
@@ -139,7 +152,12 @@ _DIAG_SIGS = {
     "grlx_fqi_debug_stamps": (C.c_int, [C.c_void_p, _P(C.c_ulonglong), C.c_int]),
     "grlx_last_kernel_name": (C.c_char_p, [C.c_void_p]),
     "grlx_kernel_plan": (C.c_int, [_P(Config), C.c_int, C.c_int, _P(C.c_int), _P(C.c_int), _P(C.c_int), C.c_char_p, C.c_char_p, C.c_size_t]),
+    "grlx_snapshot_timing": (C.c_int, [C.c_void_p, _P(C.c_double), _P(C.c_double)]),
+    "grlx_snapshot_naive_copy": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_double), _P(C.c_double)]),
 }
+# entry points of include/grlx.h that a library named by GRLX_LIB may predate (A/B timing of an older build against this binding); the
+# library in the tree must export every one of them, as it must every other symbol of _SIGS
+_NEWER_SIGS = ("grlx_snapshot_size", "grlx_snapshot_save", "grlx_snapshot_load", "grlx_snapshot_info")
 # grlx_kernel_plan flags
 PLAN_STAMPS_IN_PLACE, PLAN_STAMPS_DEFERRED, PLAN_SWEEP, PLAN_SERVER_OFF, PLAN_WALKER_SERVER, PLAN_FITS_YES, PLAN_FITS_NO = 1, 2, 4, 8, 16, 32, 64
 ABI_VERSION = 2         # include/grlx.h: GRLX_ABI_VERSION
@@ -181,8 +199,9 @@ def load():
     _share_hip_runtime_with_torch()
     lib = C.CDLL(path)
     for name, (res, args) in list(_SIGS.items()) + list(_DIAG_SIGS.items()):
-        if name in _DIAG_SIGS and os.environ.get("GRLX_LIB") and not hasattr(lib, name):
-            continue                 # GRLX_LIB may name an older build (A/B timing): it has the boundary, not necessarily every diagnostic
+        if (name in _DIAG_SIGS or name in _NEWER_SIGS) and os.environ.get("GRLX_LIB") and not hasattr(lib, name):
+            continue                 # GRLX_LIB may name an older build (A/B timing): it has the boundary it was built with, not necessarily every
+                                     # diagnostic or the entry points added since (calling a missing one raises AttributeError: never a fallback)
         fn = getattr(lib, name)      # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -4,6 +4,8 @@
 // -p <path>=v1,v2,... (repeatable): a grid sweep over predictor alpha / gamma / lambda and the sampler's epsilon, the study of the reference's
 // bin/grlo as the clones of one run: -r is then the repetitions per point, clone i = point * repetitions + k (points: the Cartesian product
 // in the order of the -p options, the last fastest) with seed + i and identity "@i"; <output>-<run>-sweep.txt holds the statistics per point,
+// -k FILE: write a snapshot of the whole context (grlx_snapshot_save) when the trial loop of the run ends; -K FILE: start from one and continue
+// its trial loop up to trials: / -t -- the output files are those of the uninterrupted run, byte for byte,
 // -n: print the plan (one line per clone: i seed alpha gamma lambda epsilon) and exit before anything touches HIP, and
 // -g N: one process per GPU (rank r on the r-th visible device, started before anything touches HIP), every rank running -r replicas
 // (clones r * replicas ..., seeds and "@i" identities counted over the whole job), the learning curves reduced with one RCCL all-reduce
@@ -65,7 +67,7 @@ int main(int argc, char **argv)
   int gpus = 0;
   int c;
   std::vector<std::string> sweep_args;
-  while ((c = getopt(argc, argv, "vs:r:t:lqc:g:p:n")) != -1)
+  while ((c = getopt(argc, argv, "vs:r:t:lqc:g:p:nk:K:")) != -1)
   {
     switch (c)
     {
@@ -79,12 +81,14 @@ int main(int argc, char **argv)
       case 'g': gpus = atoi(optarg); break;
       case 'p': sweep_args.push_back(optarg); break;
       case 'n': opt.plan_only = true; break;
+      case 'k': opt.snapshot_save = optarg; break;
+      case 'K': opt.snapshot_load = optarg; break;
       default: return 1;
     }
   }
   if (optind > argc - 1)
   {
-    log(0, std::string("Usage: \n  ") + argv[0] + " [-v] [-s seed] [-r replicas] [-g gpus] [-t trials] [-l] [-q] [-p path=v1,v2,...]... [-n] <yaml file> [yaml file...]");
+    log(0, std::string("Usage: \n  ") + argv[0] + " [-v] [-s seed] [-r replicas] [-g gpus] [-t trials] [-l] [-q] [-p path=v1,v2,...]... [-n] [-k snapshot] [-K snapshot] <yaml file> [yaml file...]");
     return 1;
   }
   if (opt.seed == 0)
@@ -118,6 +122,15 @@ int main(int argc, char **argv)
       }
       opt.sweep_repetitions = opt.replicas;
       opt.replicas = (int)(points * R);
+    }
+    catch (Exception &e) { log(0, e.what()); return 1; }
+  }
+  if (!opt.snapshot_save.empty() || !opt.snapshot_load.empty())
+  {
+    try
+    {
+      if (!opt.snapshot_load.empty() && !sweep_args.empty()) throw Exception("-K together with -p: the per-replica values come from the snapshot");
+      if (gpus > 1) throw Exception("-k / -K: a snapshot is one context on one GPU (-g " + std::to_string(gpus) + " is not built)");
     }
     catch (Exception &e) { log(0, e.what()); return 1; }
   }

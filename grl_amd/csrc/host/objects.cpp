@@ -1061,6 +1061,8 @@ struct BatchLearningExperimentImpl : Experiment {
     if (runs != 1) throw Exception(path() + ": runs > 1 (Experiment::reset between runs) is not built for the batch path");
     if (opt.sweep_repetitions > 0 || opt.plan_only)
       throw Exception(path() + ": a parameter sweep (-p) and its plan (-n) are built for experiment/online_learning, not for experiment/batch_learning");
+    if (!opt.snapshot_save.empty() || !opt.snapshot_load.empty())
+      throw Exception(path() + ": a snapshot (-k / -K) is built for experiment/online_learning, not for experiment/batch_learning");
     grlx_fqi_config c;
     lower(&c);
     c.n_replicas = opt.replicas;
@@ -1361,6 +1363,7 @@ struct OnlineLearningExperimentImpl : OnlineLearningExperiment, StepwiseExperime
       }
   }
 
+  static constexpr int kSnapshotRows = 4096;      // test rows a run with -k reserves at least: room for its continuation's rows
   std::vector<double> run(const RunOptions &opt) override
   {
     if (trials <= 0 && steps <= 0) throw Exception(path() + ": trials or steps must be > 0 (the reference's trials: 0, steps: 0 runs forever)");
@@ -1376,6 +1379,32 @@ struct OnlineLearningExperimentImpl : OnlineLearningExperiment, StepwiseExperime
     c.n_replicas = opt.replicas;
     c.max_rows = (test_interval >= 0 ? trial_cap / (test_interval + 1) : trial_cap) + 1;
     if (opt.table_log2_capacity) c.table_log2_capacity = opt.table_log2_capacity;
+    // exact resume: -k reserves rows for a continuation; -K takes the snapshot's reservation, which the load compares
+    const bool snap_save = !opt.snapshot_save.empty(), snap_load = !opt.snapshot_load.empty();
+    std::vector<char> snapshot;
+    grlx_snapshot_info_t snap_info;
+    if (snap_save || snap_load)
+    {
+      if (runs > 1) throw Exception(path() + ": a snapshot (-k / -K) is not built together with runs: " + std::to_string(runs) + " (one run per command)");
+      if (steps > 0) throw Exception(path() + ": a snapshot (-k / -K) is not built together with a steps budget (steps: " + std::to_string(steps) + ")");
+    }
+    const int rows_needed = c.max_rows;
+    if (snap_save && c.max_rows < kSnapshotRows) c.max_rows = kSnapshotRows;
+    if (snap_load && !opt.plan_only)
+    {
+      std::ifstream f(opt.snapshot_load, std::ios::binary | std::ios::ate);
+      if (!f) throw Exception("-K: could not open the snapshot '" + opt.snapshot_load + "'");
+      snapshot.resize((size_t)f.tellg());
+      f.seekg(0);
+      if (!f.read(snapshot.data(), (std::streamsize)snapshot.size())) throw Exception("-K: could not read the snapshot '" + opt.snapshot_load + "'");
+      if (grlx_snapshot_info(snapshot.data(), snapshot.size(), &snap_info) != GRLX_OK) throw Exception("-K " + opt.snapshot_load + ": " + grlx_last_error());
+      if (snap_info.trials_run > trials)
+        throw Exception("-K " + opt.snapshot_load + ": the snapshot has run " + std::to_string(snap_info.trials_run) + " trials, this run asks for " + std::to_string(trials));
+      if (snap_info.config.max_rows < rows_needed)
+        throw Exception("-K " + opt.snapshot_load + ": the snapshot reserves " + std::to_string(snap_info.config.max_rows) + " test rows, " + std::to_string(trials) +
+                        " trials need " + std::to_string(rows_needed));
+      c.max_rows = snap_info.config.max_rows;
+    }
     std::vector<double> curve;
     const bool sweep = opt.sweep_repetitions > 0;
     if (sweep)
@@ -1441,6 +1470,14 @@ struct OnlineLearningExperimentImpl : OnlineLearningExperiment, StepwiseExperime
         if (grlx_set_replica_params(ctx, call.first, call.second) != GRLX_OK)
         { std::string e = grlx_last_error(); grlx_destroy(ctx); throw Exception(e); }
     }
+    int first_trial = 0;             // -K: the trial loop continues where the snapshot's stopped
+    if (snap_load)
+    {
+      if (grlx_snapshot_load(ctx, snapshot.data(), snapshot.size()) != GRLX_OK)
+      { std::string e = grlx_last_error(); grlx_destroy(ctx); throw Exception("-K " + opt.snapshot_load + ": " + e); }
+      first_trial = (int)snap_info.trials_run;
+      std::vector<char>().swap(snapshot);
+    }
     for (int rr = run_offset; rr < runs + run_offset; ++rr)
     {
       // Load policy every run (online_learning.cpp:140-150 -> ParameterizedRepresentation {action: load},
@@ -1473,7 +1510,7 @@ struct OnlineLearningExperimentImpl : OnlineLearningExperiment, StepwiseExperime
       int rc = GRLX_OK;
       if (!by_trial)
       {
-        rc = grlx_run(ctx, trials, nullptr);
+        rc = grlx_run(ctx, trials - first_trial, nullptr);
         if (rc == GRLX_OK) rc = grlx_sync(ctx, nullptr);
       }
       else
@@ -1481,7 +1518,7 @@ struct OnlineLearningExperimentImpl : OnlineLearningExperiment, StepwiseExperime
         uint64_t learn0 = 0, test0 = 0;
         grlx_step_counts(ctx, &learn0, &test0);
         uint64_t ss = 0;
-        for (int tt = 0; (trials <= 0 || tt < trials) && (steps <= 0 || ss < (uint64_t)steps) && rc == GRLX_OK; ++tt)
+        for (int tt = first_trial; (trials <= 0 || tt < trials) && (steps <= 0 || ss < (uint64_t)steps) && rc == GRLX_OK; ++tt)
         {
           rc = grlx_run(ctx, 1, nullptr);
           if (rc == GRLX_OK) rc = grlx_sync(ctx, nullptr);
@@ -1499,6 +1536,17 @@ struct OnlineLearningExperimentImpl : OnlineLearningExperiment, StepwiseExperime
         }
       }
       if (rc != GRLX_OK) { std::string e = grlx_last_error(); grlx_destroy(ctx); throw Exception(e); }
+      if (snap_save)
+      { // the whole context, as it stands at the end of the trial loop
+        uint64_t bytes = 0, written = 0;
+        std::vector<char> buf;
+        if (grlx_snapshot_size(ctx, &bytes) == GRLX_OK) buf.resize((size_t)bytes);
+        if (buf.empty() || grlx_snapshot_save(ctx, buf.data(), bytes, &written) != GRLX_OK)
+        { std::string e = grlx_last_error(); grlx_destroy(ctx); throw Exception("-k " + opt.snapshot_save + ": " + e); }
+        std::ofstream f(opt.snapshot_save, std::ios::binary | std::ios::trunc);
+        if (!f.write(buf.data(), (std::streamsize)written) || !f.flush())
+        { grlx_destroy(ctx); throw Exception("-k: could not write the snapshot '" + opt.snapshot_save + "'"); }
+      }
       double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count();
 
       std::vector<grlx_tap> taps;
@@ -1703,6 +1751,8 @@ struct MultiExperiment : OnlineLearningExperiment {
   {
     if (opt.sweep_repetitions > 0)
       throw Exception(path() + ": a parameter sweep (-p) lays out its own clones; it is not built together with experiment/multi");
+    if (!opt.snapshot_save.empty() || !opt.snapshot_load.empty())
+      throw Exception(path() + ": a snapshot (-k / -K) is not built together with experiment/multi (use -r for the clones)");
     RunOptions clones = opt;
     clones.replicas = instances * std::max(1, opt.replicas);
     return prototype->run(clones);

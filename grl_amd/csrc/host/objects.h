@@ -1,6 +1,7 @@
 // objects.h -- what the deployer needs to know about the experiment object.
 #pragma once
 #include <cstdint>
+#include <string>
 #include <vector>
 #include "configurable.h"
 
@@ -27,6 +28,10 @@ struct RunOptions {
   std::vector<double> sweep[4];
   int sweep_repetitions = 0;    // > 0: a sweep
   bool plan_only = false;       // `grlxd -n`: print one line per clone (i seed alpha gamma lambda epsilon) and run nothing
+  // exact resume (grlx_snapshot_save / _load): `grlxd -k FILE` writes the context's snapshot when the trial loop of the run ends (and reserves
+  // at least kSnapshotRows test rows, so that a continuation has room for its own); `grlxd -K FILE` starts from one: the trial loop continues at
+  // the snapshot's trial count up to `trials:` / -t, and the output files are written whole -- the rows are in the snapshot
+  std::string snapshot_save, snapshot_load;
 };
 
 // Environment::step (environment.h:48-51 -> ModeledEnvironment::step, modeled.cpp:160-213) for a batch of instances:

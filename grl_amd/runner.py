@@ -88,6 +88,18 @@ def sweep_grid(repetitions, **axes):
     return out
 
 
+def snapshot_info(src) -> capi.SnapshotInfo:
+    """grlx_snapshot_info of a snapshot file (a path) or of its bytes: the header's fields and the grlx_config; needs no device."""
+    if isinstance(src, (bytes, bytearray, memoryview)):
+        data = bytes(src)
+    else:
+        with open(src, "rb") as f:
+            data = f.read()
+    info = capi.SnapshotInfo()
+    capi.check(capi.load().grlx_snapshot_info(data, len(data), C.byref(info)))
+    return info
+
+
 def _ptr(arr, ctype):
     return arr.ctypes.data_as(C.POINTER(ctype))
 
@@ -111,6 +123,57 @@ class Runner:
             sd, od = C.c_int(), C.c_int()
             capi.check(self.lib.grlx_env_dims(cfg.env, C.byref(sd), C.byref(od)))
             self.state_dims, self.obs_dims = sd.value, od.value
+
+    # ---- exact resume: the whole context as one byte string (include/grlx.h: grlx_snapshot_*) ----
+    def snapshot_size(self) -> int:
+        n = C.c_uint64(0)
+        capi.check(self.lib.grlx_snapshot_size(self._ctx, C.byref(n)))
+        return n.value
+
+    def _snapshot_view(self, cap=None) -> memoryview:
+        cap = self.snapshot_size() if cap is None else int(cap)
+        buf = (C.c_ubyte * max(cap, 1))()
+        n = C.c_uint64(0)
+        capi.check(self.lib.grlx_snapshot_save(self._ctx, buf, cap, C.byref(n)))
+        return memoryview(buf)[: n.value]
+
+    def snapshot(self, cap: int = None) -> bytes:
+        """The context's snapshot (waits for what is in flight; the context is left as it was).  cap: the buffer handed to the
+        library, by default exactly grlx_snapshot_size."""
+        return bytes(self._snapshot_view(cap))
+
+    def load_snapshot(self, data: bytes):
+        """Continue from a snapshot: allowed before the first launch of the context; a refusal leaves the context as it was."""
+        data = bytes(data)
+        capi.check(self.lib.grlx_snapshot_load(self._ctx, data, len(data)))
+
+    def save_state(self, path):
+        with open(path, "wb") as f:
+            f.write(self._snapshot_view())          # straight from the buffer the library filled: one copy of a snapshot in memory
+
+    def load_state(self, path):
+        with open(path, "rb") as f:
+            self.load_snapshot(f.read())
+
+    @classmethod
+    def from_state(cls, path, **layout):
+        """A context continued from the snapshot in `path`: the configuration is the snapshot's, with `layout` overriding the fields results
+        do not depend on (replicas_per_wave, wave_limit, force_generic, table_log2_capacity, table_log2_max).  The seeds given to grlx_create
+        do not matter: every state is overwritten by the load."""
+        info = snapshot_info(path)
+        cfg = capi.Config.from_buffer_copy(info.config)
+        allowed = ("replicas_per_wave", "wave_limit", "force_generic", "table_log2_capacity", "table_log2_max")
+        for k, v in layout.items():
+            if k not in allowed:
+                raise ValueError(f"{k} is not a layout field: a continued context keeps the snapshot's {k}")
+            setattr(cfg, k, v)
+        r = cls(cfg, np.zeros(cfg.n_replicas, np.int64))
+        try:
+            r.load_state(path)
+        except Exception:
+            r.close()
+            raise
+        return r
 
     def close(self):
         if self._ctx:

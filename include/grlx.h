@@ -326,6 +326,46 @@ int  grlx_load_weights(grlx_ctx *ctx, int table, int first_replica, int n_replic
  * parameter vector double[memory] of one replica's table, little-endian as grl's .dat files hold it
  * (untouched slots carry their lazily computed initial value).  out: host buffer of `memory` doubles. */
 int  grlx_export_weights(grlx_ctx *ctx, int table, int replica, double *out);
+
+/* --- exact resume: a whole context as one byte string -------------------------------------------------------------------------
+ * A snapshot holds everything a context carries from one launch to the next: the replicas' random streams, environment state,
+ * exploration decay, trial / step counters, the rows written so far, the actor-critic's persisted critic trace, the occupied entries
+ * of the sparse tables with their claim words and positions, the target network's values and synchronisation counts, the base of
+ * the lazy initialisation, a sweep context's per-replica values -- and the grlx_config it was created with.  A context that loads
+ * it and runs b trials gives the bits of the one that ran on for b trials: in another process, on another device of the same kind.
+ * One self-describing little-endian byte string in the caller's host buffer (layout: grl_amd/csrc/grlx_snapshot_format.h); canonical:
+ * two contexts in the same state give the same bytes.  No device pointer, nothing that lives inside one launch only.
+ *
+ * grlx_snapshot_size: waits for the context's work; the exact size of a snapshot taken now.
+ * grlx_snapshot_save: waits likewise, writes the snapshot into buf[cap] (*written = its size; cap too small: GRLX_ERR_INVALID) and leaves
+ *   the context exactly as it was.  NOT BUILT (GRLX_ERR_INVALID, "not built"): a context that holds a loaded policy (grlx_load_weights), one
+ *   on which a per-step entry point has run, GRLX_ENV_EXTERNAL, taps or grlx_set_diag.
+ * grlx_snapshot_load: allowed on a context that has launched nothing yet.  The context's configuration must equal the snapshot's except in
+ *   replicas_per_wave, wave_limit, force_generic, table_log2_capacity, table_log2_max (layout and sizing: results do not depend on them) and
+ *   the tap fields (a context with taps is refused); a difference elsewhere is GRLX_ERR_INVALID naming the field and both values.  The tables
+ *   are re-allocated at the snapshot's capacity (beyond the context's table_log2_max: GRLX_ERR_INVALID; no memory: GRLX_ERR_OOM).  Everything
+ *   is validated, and everything allocated, before the context is touched: a refused load leaves a context that runs as a fresh one.  After
+ *   a successful load the context counts as launched (grlx_set_replica_params is refused); a snapshot of a sweep context makes it one.
+ * grlx_snapshot_info: host only, needs no device: the header's fields and the configuration; `bytes` may cover the header alone. */
+typedef struct {
+  uint32_t format_version;
+  uint32_t n_replicas, n_tables;
+  uint32_t table_log2;                /* entries per replica and table = 2^this            */
+  uint32_t is_sweep, has_trace, has_target, twin_tables;
+  uint32_t rows;                      /* largest row count of a replica                    */
+  uint32_t record_bytes;              /* one table record: 24, or 32 with a target network */
+  int64_t  trials_run;
+  uint64_t total_bytes, header_bytes;
+  uint64_t n_records;                 /* occupied table entries, all tables and replicas   */
+  uint64_t checksum;                  /* FNV-1a 64 over everything after the header        */
+  uint64_t section_bytes[5];          /* states, rows, trace, sweep, records               */
+  grlx_config config;
+} grlx_snapshot_info_t;
+int  grlx_snapshot_size(grlx_ctx *ctx, uint64_t *bytes);
+int  grlx_snapshot_save(grlx_ctx *ctx, void *buf, uint64_t cap, uint64_t *written);
+int  grlx_snapshot_load(grlx_ctx *ctx, const void *buf, uint64_t bytes);
+int  grlx_snapshot_info(const void *buf, uint64_t bytes, grlx_snapshot_info_t *out);
+
 int  grlx_read_taps(grlx_ctx *ctx, grlx_tap *out, int cap, int *n);
 
 /* --- fine-grained batched operators (host pointers; each call copies in, runs a

@@ -38,6 +38,16 @@ const char *grlx_last_kernel_name(grlx_ctx *ctx);
 int grlx_kernel_plan(const grlx_config *cfg, int simds, int flags, int *replicas_per_wave, int *variant, int *grid, char *rollout_name,
                      char *server_name, size_t name_cap);
 
+
+/* Snapshots (grlx_snapshot_save / _load), for tools/snapshot_throughput.py.
+ * grlx_snapshot_timing: milliseconds (events on the device) that snapshot_pack_kernel took in the context's last grlx_snapshot_save and
+ * snapshot_unpack_kernel in its grlx_snapshot_load; negative where none has run.
+ * grlx_snapshot_naive_copy: the naive snapshot as a baseline -- hipMemcpy of the context's OWN raw arrays (tables, target values, states,
+ * rows, trace) to one freshly allocated pageable host buffer of their total size and back again (the context is left as it was): the
+ * bytes and the milliseconds of both directions.  GRLX_ERR_OOM when the host has no such buffer. */
+int grlx_snapshot_timing(grlx_ctx *ctx, double *pack_ms, double *unpack_ms);
+int grlx_snapshot_naive_copy(grlx_ctx *ctx, uint64_t *bytes, double *out_ms, double *back_ms);
+
 #ifdef __cplusplus
 }
 #endif
