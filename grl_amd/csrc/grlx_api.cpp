@@ -662,7 +662,11 @@ int grlx_create(const grlx_config *cfg, const int64_t *seeds, grlx_ctx **out)
     s.ac_decay = 1;
     s.tr_len = 0;
     s.tr_total = 1;
-    if (cfg->agent == GRLX_AGENT_AC) s.G = h_next(h_seed((long)seeds[r]));   // no samplers: only the thread-local seed is drawn
+    if (cfg->agent == GRLX_AGENT_AC)
+    { // no samplers: only the thread-local seed is drawn, and grlx_get_rng reports the two streams the graph does not have as 0
+      s.G = h_next(h_seed((long)seeds[r]));
+      s.S1 = s.S2 = 0;
+    }
   }
   CTX_TRY(hipMemcpy(ctx->states, hs.data(), sizeof(ReplicaState) * (size_t)N, hipMemcpyHostToDevice));
 #undef CTX_TRY

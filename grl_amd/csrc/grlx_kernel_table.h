@@ -1,6 +1,7 @@
 // grlx_kernel_table.h -- every rollout instantiation of the library, one row each (KernelRow, grlx_internal.h).
 //
-// Included at the end of grlx_kernels.hip: taking a kernel's address here is what instantiates it.  To add an instantiation, add its row;
+// Included at the end of grlx_kernels.hip: taking a kernel's address here is what instantiates it.  To add an instantiation, add its row
+// and its case in tests/kernel_plan_cases.py (a launched case is held to the oracle's bits by tests/test_gpu_kernel_plan_parity.py);
 // plan_rollout (grlx_plan.cpp) takes the FIRST row whose key -- family, environment, actions, replicas per wave, mode, and for FAM_TGT the
 // (target, safe) pair -- and whose `matches` fit the launch, so the rows stand in precedence order:
 //   sweep -> wide served -> served -> stamped deferred -> tapped deferred -> advantage -> 32 -> 16 -> 8 -> specialised 4 -> generic 4

@@ -284,7 +284,7 @@ int  grlx_read_diag(grlx_ctx *ctx, uint64_t *out /*[waves][8] cycle sums*/, int 
 
 /* --- state inspection (parity tests) ------------------------------------ */
 int  grlx_get_env_state(grlx_ctx *ctx, int replica, double *state /*[GRLX_MAX_STATE]*/);
-int  grlx_get_rng(grlx_ctx *ctx, int replica, uint64_t out[4] /* G, TL, S1, S2 */);
+int  grlx_get_rng(grlx_ctx *ctx, int replica, uint64_t out[4] /* G, TL, S1, S2; a sampler stream the graph does not have (actor-critic: both) is 0 */);
 /* Replaces reading LinearRepresentation::params_ (linear.cpp; .dat dump
  * representation.h:201-263): current weights of the given reference slots. */
 int  grlx_get_weights(grlx_ctx *ctx, int table, int replica, const uint32_t *slots, int n, double *out);

@@ -76,6 +76,31 @@ def cart_pole_ac(grlx, n, **over):
     return cfg, spec
 
 
+def pendulum_ac(grlx, n, **over):
+    """The actor-critic block of cfg/cart_pole/ac_tc.yaml over the pendulum's two observations (the wrapped angle comes first):
+    dynamics/pendulum + task/pendulum/swingup as in cfg/pendulum/sarsa_tc.yaml, torques in [-3, 3] under the yaml's sigma of 5."""
+    res, wrap = [0.31415, 3.1415], [6.283, 0]
+    cfg = None
+    if grlx is not None:
+        cfg = grlx.cart_pole_ac_config(n, **over)
+        cfg.env, cfg.control_step, cfg.timeout, cfg.action_min, cfg.action_max = 0, 0.03, 2.99, -3.0, 3.0
+        for ts in (cfg.projector, cfg.actor_projector):
+            _set_tile(ts, 16, 8388608, res, wrap)
+            ts.resolution[2] = ts.resolution[3] = 0.0
+        cfg.actor_representation.output_min, cfg.actor_representation.output_max = -3.0, 3.0
+    spec = cart_pole_ac(None, n, **over)[1]
+    spec.env = 0
+    spec.control_step, spec.integration_steps, spec.timeout = 0.03, 5, 2.99
+    spec.action_min, spec.action_max = -3.0, 3.0
+    for ts in (spec.projector, spec.actor_projector):
+        for i in range(8):
+            ts.resolution[i] = 0.0
+            ts.wrapping[i] = 0.0
+        _set_tile(ts, 16, 8388608, res, wrap)
+    spec.actor_representation.output_min, spec.actor_representation.output_max = -3.0, 3.0
+    return cfg, spec
+
+
 def compass_walker(grlx, n, agent=1, **over):
     """cfg/compass_walker/qlearning_walk.yaml: model/compass_walker + task/compass_walker/walk, Q-learning."""
     res = [0.0838, 0.1047, 0.1111, 0.2222, 10, 1.2]
@@ -104,6 +129,20 @@ def pendulum_qv(grlx, n, **over):
         _set_tile(cfg.actor_projector, 16, 8388608, [0.31415, 3.1415], [6.283, 0])
         cr = cfg.actor_representation
         cr.init_min, cr.init_max, cr.output_min, cr.output_max, cr.limit = 0.0, 1.0, -DBL_MAX, DBL_MAX, 1
+    return cfg, spec
+
+
+def acrobot_qv(grlx, n, **over):
+    """predictor/critic/qv (cfg/pendulum/qv_tc.yaml's agent block, beta = 0.1) on the acrobot of `acrobot`: the state-value table V
+    (table 1) over the four observations at the Q table's state resolution; V's representation is the Q table's."""
+    res, wrap = [0.05, 0.05, 0.2, 0.4], [0] * 4
+    cfg, spec = acrobot(grlx, n, agent=ob.AGENT_QV, beta=0.1, **over)
+    spec.beta = 0.1
+    _set_tile(spec.actor_projector, 16, 8388608, res, wrap)
+    spec.actor_representation = spec.representation
+    if cfg is not None:
+        _set_tile(cfg.actor_projector, 16, 8388608, res, wrap)
+        cfg.actor_representation = cfg.representation
     return cfg, spec
 
 

@@ -1,5 +1,6 @@
-"""Which kernel runs: one table of cases shared by tests/test_kernel_plan.py (grlx_kernel_plan, no device) and
-tests/test_gpu_kernel_plan.py (what a context launches).  The expected values are literals: they state what the launch ladders chose
+"""Which kernel runs: one table of cases shared by tests/test_kernel_plan.py (grlx_kernel_plan, no device),
+tests/test_gpu_kernel_plan.py (what a context launches) and tests/test_gpu_kernel_plan_parity.py (what that launch computes, against the
+oracle built from the same case: build_pair).  The expected values are literals: they state what the launch ladders chose
 before the kernel table replaced them (profiles/kernel_plan_ab.md has the kernel traces of both builds).
 
 A case: (id, builder, n_replicas, config overrides, flags, simds, gpu, (replicas per wave, rollout row, server row, variant)).
@@ -17,43 +18,59 @@ TAPDEF = dict(tap_replica=0, tap_capacity=64, tap_deferred=1)
 SARSA, Q, ES, ADV = capi.AGENT_SARSA, capi.AGENT_Q, capi.AGENT_EXPECTED_SARSA, capi.AGENT_ADVANTAGE
 
 
-def build(grlx, builder, n, over):
-    """The grlx_config of a case (`safe` is the projector's)."""
+BUILDERS = {"pendulum": "pendulum", "acrobot": "acrobot", "walker": "compass_walker", "cart_pole_q": "cart_pole_q", "cart_pole_ac": "cart_pole_ac",
+            "pendulum_ac": "pendulum_ac", "pendulum_qv": "pendulum_qv", "acrobot_qv": "acrobot_qv"}      # case builder -> tests/configs.py
+# Every override key of a case is in exactly one of these lists; build_pair refuses any other, so a case cannot run against an oracle
+# that silently lacks one of its overrides.
+RESULT_KEYS = ["agent", "alpha", "gamma", "epsilon", "timeout", "sigma", "kappa", "trace", "action_steps", "target_interval", "target_tau",
+               "safe"]                                        # they change results: the oracle's spec gets them too
+KERNEL_KEYS = ["replicas_per_wave", "force_generic", "wave_limit", "tap_replica", "tap_capacity", "tap_deferred",
+               "table_log2_capacity"]                         # they only choose a kernel or size its buffers: the spec never sees them
+
+
+def build_pair(grlx, builder, n, over):
+    """(grlx_config, oracle spec) of a case, the overrides applied to both halves (`safe` is the projector's in the config).
+    grlx = None: the oracle half only (a cart-pole spec then has the task's penalties off instead of its config's: tests/configs.py)."""
+    from tests import configs
+    unknown = [k for k in over if k not in RESULT_KEYS and k not in KERNEL_KEYS]
+    if unknown:
+        raise KeyError(f"override keys {unknown} are neither in RESULT_KEYS nor in KERNEL_KEYS (tests/kernel_plan_cases.py)")
     over = dict(over)
     safe = over.pop("safe", 0)
-    cfg = _build(grlx, builder, n, over)
-    cfg.projector.safe = safe
-    return cfg
+    cfg, spec = getattr(configs, BUILDERS[builder])(grlx, n, **over)
+    if cfg is not None:
+        cfg.projector.safe = safe
+    spec.safe = safe
+    for k in RESULT_KEYS:
+        if k in over:
+            setattr(spec, k, over[k])
+    return cfg, spec
 
 
-def _build(grlx, builder, n, over):
-    from tests import configs
-    if builder == "pendulum":
-        return configs.pendulum(grlx, n, **over)[0]
-    if builder == "acrobot":
-        return configs.acrobot(grlx, n, **over)[0]
-    if builder == "walker":
-        return configs.compass_walker(grlx, n, **over)[0]
-    if builder == "cart_pole_q":
-        return configs.cart_pole_q(grlx, n, **over)[0]
-    if builder == "cart_pole_ac":
-        return grlx.cart_pole_ac_config(n, **over)
-    if builder == "pendulum_ac":       # the actor-critic block of cfg/cart_pole/ac_tc.yaml over the pendulum's two observations
-        cfg = grlx.cart_pole_ac_config(n, **over)
-        cfg.env, cfg.control_step, cfg.timeout, cfg.action_min, cfg.action_max = capi.ENV_PENDULUM, 0.03, 2.99, -3.0, 3.0
-        for ts in (cfg.projector, cfg.actor_projector):
-            configs._set_tile(ts, 16, 8388608, [0.31415, 3.1415], [6.283, 0])
-            ts.resolution[2] = ts.resolution[3] = 0.0
-        cfg.actor_representation.output_min, cfg.actor_representation.output_max = -3.0, 3.0
-        return cfg
-    if builder == "pendulum_qv":
-        return configs.pendulum_qv(grlx, n, **over)[0]
-    if builder == "acrobot_qv":
-        cfg = configs.acrobot(grlx, n, agent=capi.AGENT_QV, beta=0.1, **over)[0]
-        configs._set_tile(cfg.actor_projector, 16, 8388608, [0.05, 0.05, 0.2, 0.4], [0] * 4)
-        cfg.actor_representation = cfg.representation
-        return cfg
-    raise KeyError(builder)
+def build(grlx, builder, n, over):
+    """The grlx_config of a case."""
+    return build_pair(grlx, builder, n, over)[0]
+
+
+def open_runner(grlx, monkeypatch, case, cfg):
+    """What a launched case does before its first run: the environment-server switches of its flags, the context with seeds 1..n, the
+    per-replica alphas of a sweep case, the stamps of a stamped one.  Returns (runner, alpha of every replica or None)."""
+    import numpy as np
+    n, flags = case[2], case[4]
+    monkeypatch.setenv("GRLX_ENV_SERVER", "0" if flags & OFF else "1")
+    monkeypatch.setenv("GRLX_ENV_SERVER_WALKER", "1" if flags & WALKER else "0")
+    r = grlx.Runner(cfg, np.arange(1, n + 1))
+    alphas = None
+    try:
+        if flags & SWEEP:
+            alphas = [0.1 + 0.01 * k for k in range(n)]
+            r.set_replica_params(alpha=alphas)
+        if flags & (STAMPS1 | STAMPS2):
+            r.set_diag(2 if flags & STAMPS2 else 1)
+    except Exception:
+        r.close()
+        raise
+    return r, alphas
 
 
 CASES = [
@@ -269,6 +286,9 @@ CASES = [
     ("auto-walker-30", "walker", 30, dict(), OFF, 1, False, (32, "rollout_wide_kernel<GRLX_ENV_COMPASS_WALKER, 3, 8, SpecWalkerQ>", "", SPECIALISED)),
     ("auto-target-network-stays-4", "pendulum", 30, dict(target_interval=5, target_tau=0.5), OFF, 1, False, (4, "rollout_tgt_kernel<GRLX_ENV_PENDULUM, 3, true, false>", "", IN_PLACE)),
 ]
+
+# the cases a device launches: tests/test_gpu_kernel_plan.py (which row ran) and tests/test_gpu_kernel_plan_parity.py (with the oracle's bits)
+LAUNCHED = [c for c in CASES if c[6]]
 
 # the grid of the two 12-slot cases (one wave each) is asserted too
 GRIDS = {"ac-12-one-wave-owns-64": 1, "ac-12-one-wave-cannot-own-65": 1, "ac-12": 2, "pend-sarsa-served": 2, "walker-32": 2, "acrobot-8-served": 2}
