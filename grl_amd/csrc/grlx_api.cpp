@@ -1748,7 +1748,10 @@ int grlx_update(grlx_ctx *ctx, int table, const int32_t *replica, const uint32_t
 
 int grlx_math(int op, const double *x, const double *y, int n, double *out)
 {
-  if (!x || !out || n < 0 || op < 0 || op > 8 || (op == 3 && !y)) return fail(GRLX_ERR_INVALID, "bad argument");
+  if (!x || !out || n < 0 || op < 0 || op > 13 || (op == 3 && !y)) return fail(GRLX_ERR_INVALID, "bad argument");
+  if (op >= 9 && op <= 12)      // the unchecked forms: nothing outside their domain reaches them (!(a < b) refuses a NaN too)
+    for (int i = 0; i < n; ++i)
+      if (!(std::fabs(x[i]) < 0x1p20)) return fail(GRLX_ERR_INVALID, "grlx_math ops 9 to 12 are the unchecked sin/cos forms: every argument must satisfy |x| < 2^20");
   if (!have_device()) return fail(GRLX_ERR_NO_DEVICE, "no HIP device: grlx has no CPU fallback");
   if (n == 0) return GRLX_OK;
   DevBuf dx, dy, dout;

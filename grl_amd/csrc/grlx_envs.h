@@ -73,6 +73,8 @@ template <> struct Env<GRLX_ENV_PENDULUM> {
   }
   __device__ static __forceinline__ double actuate(double a) { return fmin(fmax(a, -3.0), 3.0); }   // :105-109
   __device__ static __forceinline__ bool in_domain(const double *x) { return __builtin_fabs(x[0]) < 0x1p19; }
+  // every sin/cos argument eom() forms from x inside the sine's domain?  (env_step_kernel's second pass, grlx_kernels.hip; no rollout kernel calls it)
+  __device__ static __forceinline__ bool arguments_in_domain(const double *x) { return __builtin_fabs(x[0]) < 0x1p20; }
   __device__ static __forceinline__ int observe(const DevParams &P, const double *x, double *obs)
   { // :111-129
     double a = pfmod(x[0] + GRLX_PI, GRLX_2PI);
@@ -213,6 +215,11 @@ template <> struct Env<GRLX_ENV_ACROBOT> {
   }
   __device__ static __forceinline__ double actuate(double a) { return a; }                  // Task::actuate default (environment.h:94)
   __device__ static __forceinline__ bool in_domain(const double *x) { return __builtin_fabs(x[0]) < 0x1p18 && __builtin_fabs(x[1]) < 0x1p18; }
+  // every sin/cos argument eom() forms from x inside the sine's domain?  (env_step_kernel's second pass, grlx_kernels.hip; no rollout kernel calls it)
+  __device__ static __forceinline__ bool arguments_in_domain(const double *x)
+  {
+    return __builtin_fabs(x[1]) < 0x1p20 && __builtin_fabs(x[0] + x[1] - GRLX_PI / 2) < 0x1p20 && __builtin_fabs(x[0] - GRLX_PI / 2) < 0x1p20;
+  }
   __device__ static __forceinline__ int observe(const DevParams &, const double *x, double *obs)
   { // :109-125
 #pragma unroll
@@ -278,6 +285,8 @@ template <> struct Env<GRLX_ENV_CART_POLE> {
   }
   __device__ static __forceinline__ double actuate(double a) { return a; }                  // Task::actuate default (environment.h:94)
   __device__ static __forceinline__ bool in_domain(const double *x) { return __builtin_fabs(x[1]) < 0x1p19; }
+  // every sin/cos argument eom() forms from x inside the sine's domain?  (env_step_kernel's second pass, grlx_kernels.hip; no rollout kernel calls it)
+  __device__ static __forceinline__ bool arguments_in_domain(const double *x) { return __builtin_fabs(x[1]) < 0x1p20; }
   __device__ static __forceinline__ int observe(const DevParams &P, const double *x, double *obs)
   { // :166-190
     double a = pfmod(x[1] + GRLX_PI, GRLX_2PI);
@@ -568,7 +577,8 @@ __device__ __forceinline__ void env_eom(const typename Env<ENV>::Consts &ec, con
     Env<ENV>::eom(ec, x, u, xd);
 }
 
-// (rk4_step_consts below is a COPY of this function for the environment server: a change here is a change there)
+// (rk4_step_consts below is a COPY of this function for the environment server, and stage_arguments_in_domain in grlx_kernels.hip
+// walks the same stages, operation for operation, to look at the sines' arguments: a change here is a change in both)
 template <int ENV, bool PIN, typename SH = NoShare>
 __device__ __forceinline__ void rk4_step(const DevParams &P, const double *x, double u, double *next, const SH &sh = SH())
 {
@@ -618,7 +628,11 @@ __device__ __forceinline__ void env_step(const DevParams &P, double *x, double a
     rk4_step<ENV, PIN, SH>(P, x, Env<ENV>::actuate(action), next, sh);
   terminal = Env<ENV>::observe(P, next, obs);
   reward = Env<ENV>::evaluate(P, x, action, next);
-  // the branch-free sin/cos need |angle| < 2^20; 2^19 at step ends leaves room for the stages
+  // the branch-free sin/cos need |angle| < 2^20; 2^19 at step ends leaves room for the stages at the rates the runs reach.
+  // NOT for every accepted state: the cart-pole's dtheta quirk (eom above) accelerates the pole by
+  // ~0.035 theta^2 sin(2 theta), and from |theta| > 2^17 a stage can pass 2^20 and the step still end below 2^19
+  // (tests/test_gpu_env_domain.py).  grlx_env_step, which takes any state, checks the stage arguments themselves:
+  // env_step_kernel, grlx_kernels.hip.
   if (!Env<ENV>::in_domain(next)) status |= ST_DOMAIN;
 #pragma unroll
   for (int i = 0; i < S; ++i) x[i] = next[i];

@@ -131,6 +131,43 @@ hipError_t launch_project(const TileParams &tp, const double *in_dev, int n, uin
   return hipGetLastError();
 }
 
+// Does every sin/cos evaluation of one control step get an argument inside its domain (|x| < 2^20)?  The caller of grlx_env_step may
+// hand in ANY state; in_domain() looks at step ends only, and a state it accepts can take an RK4 stage beyond 2^20 and come back
+// (the cart-pole from |theta| > 2^17: see env_step, grlx_envs.h), where the unchecked psin / pcos return unspecified values.  A
+// second pass over the stages of rk4_step -- the same operations on the same values, hence the same stage states -- that looks at
+// the arguments and keeps nothing else.  The compass walker integrates itself and is not covered (its own rates carry the angles
+// out of in_domain() long before a stage leaves the sine's domain).
+template <int ENV>
+__device__ bool stage_arguments_in_domain(const DevParams &P, const double *x, double u)
+{
+  constexpr int S = Env<ENV>::S, SD = S - 1;
+  const double h = P.h;
+  double xd[S], k1[SD], k2[SD], k3[SD], k4[SD], t[S], next[S];
+  for (int i = 0; i < S; ++i) { next[i] = x[i]; t[i] = x[i]; }
+  const typename Env<ENV>::Consts ec = Env<ENV>::template consts<false>();
+  bool ok = true;
+  for (int ii = 0; ii < P.integration_steps; ++ii)
+  {
+    ok = ok && Env<ENV>::arguments_in_domain(next);
+    Env<ENV>::eom(ec, next, u, xd);
+    for (int i = 0; i < SD; ++i) { k1[i] = h * xd[i]; t[i] = next[i] + k1[i] / 2; }
+    ok = ok && Env<ENV>::arguments_in_domain(t);
+    Env<ENV>::eom(ec, t, u, xd);
+    for (int i = 0; i < SD; ++i) { k2[i] = h * xd[i]; t[i] = next[i] + k2[i] / 2; }
+    ok = ok && Env<ENV>::arguments_in_domain(t);
+    Env<ENV>::eom(ec, t, u, xd);
+    for (int i = 0; i < SD; ++i) { k3[i] = h * xd[i]; t[i] = next[i] + k3[i]; }
+    ok = ok && Env<ENV>::arguments_in_domain(t);
+    Env<ENV>::eom(ec, t, u, xd);
+    for (int i = 0; i < SD; ++i)
+    {
+      k4[i] = h * xd[i];
+      next[i] = next[i] + div6(k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]);
+    }
+  }
+  return ok;
+}
+
 // Environment::step, batched: one lane per environment instance
 template <int ENV>
 __global__ void env_step_kernel(DevParams P, double *state, const double *action, int n,
@@ -144,6 +181,8 @@ __global__ void env_step_kernel(DevParams P, double *state, const double *action
   for (int k = 0; k < S; ++k) x[k] = state[(size_t)i * S + k];
   uint32_t st = 0;
   if (!Env<ENV>::in_domain(x)) st |= ST_DOMAIN;
+  if constexpr (!HasCustomModel<ENV>::value)
+    if (!stage_arguments_in_domain<ENV>(P, x, Env<ENV>::actuate(action[i]))) st |= ST_DOMAIN;
   env_step<ENV>(P, x, action[i], o, rw, term, st);
   for (int k = 0; k < S; ++k) state[(size_t)i * S + k] = x[k];
   for (int k = 0; k < D; ++k) obs[(size_t)i * D + k] = o[k];
@@ -339,6 +378,12 @@ __global__ void math_kernel(int op, const double *x, const double *y, int n, dou
     case 6: r = psin_s(v, sin_consts<false>()); break;       // small-angle-aware forms (whole waves of small arguments take the short path)
     case 7: r = pcos_s(v, sin_consts<false>()); break;
     case 8: { double sn, cs; psincos_s(v, sin_consts<false>(), sn, cs); r = sn + cs; break; }
+    // the forms the rollout kernels and the environment servers call, with their constants: unchecked, the host refuses |x| >= 2^20
+    case 9: r = psin<false>(v, sin_consts<true>()); break;
+    case 10: r = psin<true>(v, sin_consts<kPinAdditive>()); break;       // the served pendulum's: sign by integer add
+    case 11: r = pcos(v, sin_consts<true>()); break;
+    case 12: { double sn, cs; psincos(v, sin_consts<true>(), sn, cs); r = sn + cs; break; }
+    case 13: r = pexp(v); break;
     default: r = __builtin_sqrt(v); break;
   }
   out[i] = r;

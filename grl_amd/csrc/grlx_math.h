@@ -9,8 +9,9 @@
 // translation unit MUST be compiled with -ffp-contract=off so that nothing but
 // the explicit __builtin_fma calls is fused.
 //
-// Specification (checked bit for bit against an independent CPU restatement in
-// tests/test_gpu_math.py):
+// Specification (checked bit for bit against an independent CPU restatement, oracle/portable_math.c, in
+// tests/test_gpu_math.py -- every form below, over the whole domain and on the doubles next to k*pi/2; that
+// restatement is held to the exact functions in tests/test_oracle_math.py):
 //   reduce(x): fn = rint(x*INVPIO2); r0 = fma(-fn,P1,x)  (exact for |x| < 2^20)
 //              p = fn*P2; pl = fma(fn,P2,-p); r = r0-p; e = (r0-r)-p   [Fast2Sum]
 //              t = (e-pl) - fn*P3; reduced argument = r + t, NOT renormalised (the
@@ -24,7 +25,11 @@
 // wave per SIMD, where a dependent f64 operation costs ~19 cycles.
 // Constants are Taylor coefficients 1/k! and a three-double split of pi/2, all
 // correctly rounded from exact rationals (tools/gen_math_constants.py).
-// Accuracy: <= 1 ulp from glibc on 3 % of arguments, identical elsewhere.
+// Accuracy (measured against 240-bit values, tests/test_oracle_math.py; table in DESIGN.md section 2): psin / pcos below
+// 0.77 ulp over the whole domain (more than 1/2 ulp off at 3.1 % of arguments; 0.50 ulp on the doubles nearest k*pi/2, where
+// the result is as small as 6e-19); plog below 0.76 ulp on the drand48 lattice j*2^-48 the kernels feed it, but up to 1.50 ulp
+// for general arguments just above 1 (no kernel evaluates it there); pexp below 0.95 ulp.  Against glibc 2.35: psin / pcos
+// differ in the last bit at 3.1 % of arguments, plog on the lattice at 5.1 %, never by more than one ulp.
 // No tiny-argument shortcut (the general path returns x resp. 1; sin(-0) = +0).
 // Domain: |x| < 2^20: psin/pcos are branch-free and unchecked, psin_checked/pcos_checked
 // return NaN outside; the rollout kernel checks its states once per step (GRLX_ERR_DOMAIN).
@@ -356,7 +361,7 @@ __device__ __forceinline__ double pcos_checked(double x) { return (__builtin_fab
 // is either exact or 1/3 resp. 2/3 of an ulp beyond a representable number -- never within
 // 2^-54 ulp of a rounding midpoint -- so the perturbation cannot change the rounding:
 // the result equals the IEEE division bit for bit (checked against v_div on random and
-// structured inputs in tests/test_gpu_parity.py).  Tiny |x| takes the true division.
+// structured inputs in tests/test_gpu_math.py).  Tiny |x| takes the true division.
 __device__ __forceinline__ double div6(double x)
 {
   const double c = 0x1.5555555555555p-3;        // RN(1/6)
@@ -447,6 +452,11 @@ __device__ __forceinline__ double pexp(double x)
 // fmod(x, y) for finite x, y > 0: exact by definition (IEEE remainder toward
 // zero); long division by exactly representable multiples of y.  Each
 // subtraction is exact (Sterbenz), so the result equals libm's fmod bit for bit.
+// Domain: any finite x; any y > 0, infinity included (a subnormal y, or x/y beyond 2^1000, goes to the library's fmod); NaN for a
+// non-finite x, a NaN, or y <= 0 (C's fmod takes |y|: this one does not).  The kernels call it with y = 2 pi and |x| < 2^19 + pi
+// only; tests/test_gpu_math.py covers that range densely (the doubles next to every kind of k * 2 pi, |x| < y, x = +-y, +-0),
+// other divisors at random, and the ends of this domain one by one (the largest double, subnormal and smallest normal divisors,
+// exponent differences on both sides of 1000, every NaN case).
 __device__ __forceinline__ double pfmod(double x, double y)
 {
   double ax = __builtin_fabs(x);

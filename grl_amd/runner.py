@@ -566,7 +566,10 @@ def env_step(cfg: capi.Config, state, action):
     return state, obs, reward, terminal
 
 
-MATH_SIN, MATH_COS, MATH_LOG, MATH_FMOD, MATH_SQRT = 0, 1, 2, 3, 4
+MATH_SIN, MATH_COS, MATH_LOG, MATH_FMOD, MATH_SQRT, MATH_DIV6 = 0, 1, 2, 3, 4, 5
+MATH_SIN_SMALL, MATH_COS_SMALL, MATH_SINCOS_SMALL = 6, 7, 8                 # psin_s, pcos_s, psincos_s (sine + cosine)
+# the unchecked forms the rollout kernels and the environment servers call (|x| < 2^20, else GRLX_ERR_INVALID), and pexp
+MATH_SIN_PINNED, MATH_SIN_SERVER, MATH_COS_PINNED, MATH_SINCOS_PINNED, MATH_EXP = 9, 10, 11, 12, 13
 
 
 def device_math(op: int, x, y=None):

@@ -424,7 +424,11 @@ int  grlx_agent_end(grlx_ctx *ctx, int test, const int32_t *active, double tau, 
 
 /* device math used by the environments (bit-identical to the documented
  * portable specification): op 0 sin, 1 cos, 2 log, 3 fmod(x, y[i]), 4 sqrt, 5 x/6 (the 3-operation exact form used by RK4),
- * 6 / 7 / 8 the small-angle-aware sin, cos and sin+cos the compass walker uses (bitwise equal to 0 / 1 / their sum) */
+ * 6 / 7 / 8 the small-angle-aware sin, cos and sin+cos the compass walker uses (bitwise equal to 0 / 1 / their sum),
+ * 9 / 10 / 11 / 12 the UNCHECKED forms the rollout kernels and the environment servers call, with their constants held in
+ * registers: sin, sin with the sign set by an integer add (the served pendulum's), cos, sin+cos of one reduction (bitwise equal
+ * to 0 / 0 / 1 / their sum on |x| < 2^20; an argument outside, or not finite, is GRLX_ERR_INVALID and nothing is launched),
+ * 13 exp (the batch path's logistic; NaN -> NaN, x > 709.782712893384 -> +inf, x < -745.2 -> +0) */
 int  grlx_math(int op, const double *x, const double *y, int n, double *out);
 
 /* Rand / RandGen streams (utils.h:84-137) evaluated on the device:

@@ -111,6 +111,9 @@ static void acrobot_eom(const orc_spec *s, const double *x, double u, double *xd
                 (m1*lc1+m2*l1)*g*orc_m_cos(s, theta1-M_PI/2)+phi2;
   double d2 = m2*(lc2*lc2+l1*lc2*cos2)+I2;
   double d1 = m1*lc1*lc1 + m2*(l1*l1+lc2*lc2+2*l1*lc2*cos2)+I1+I2;
+  /* QUIRK reproduced from the source text (acrobot.cpp:63), like cart_pole.cpp:65 below: thetad2*thetad2 where the textbook
+   * model has thetad1*thetad1.  Energy is not conserved in the reference either (0.15 J in 1 s; 1e-11 with thetad1): physical
+   * invariants cannot pin these dynamics. */
   double thetadd2 = (tau+d2*phi1/d1-m2*l1*lc2*thetad2*thetad2*sin2-phi2)/
                     (m2*lc2*lc2+I2-d2*d2/d1);
   double thetadd1 = -(d2*thetadd2+phi1)/d1;

@@ -25,60 +25,7 @@ def assert_bit_equal(a, b, what=""):
 
 
 # ---------------------------------------------------------------- math -----
-@pytest.mark.parametrize("op,name,lo,hi", [(0, "orc_psin", -200.0, 200.0), (1, "orc_pcos", -200.0, 200.0),
-                                           (2, "orc_plog", 1e-300, 1e3)])
-def test_device_math_bit_exact(grlx, oracle, op, name, lo, hi):
-    rng = np.random.default_rng(op)
-    x = np.concatenate([rng.uniform(lo, hi, 200000), rng.uniform(-1e-3, 1e-3, 20000) if op < 2 else rng.uniform(0, 1, 20000) ** 8,
-                        np.array([0.0, -0.0, 1e-30, 0.5, 1.0, np.pi, -np.pi, 2 * np.pi, 1e5, -1e5, 1048575.0])])
-    if op == 2:
-        x = np.abs(x) + 1e-308
-    got = grlx.runner.device_math(op, x)
-    f = getattr(oracle, name)
-    want = np.array([f(float(v)) for v in x])
-    assert_bit_equal(got, want, name)
-
-
-def test_small_angle_forms_equal_the_general_ones(grlx, oracle):
-    """psin_s / pcos_s / psincos_s take a short path when every lane of a wave has |x| within a quarter turn: it
-    must give the bits of the general path.  Whole waves of small arguments, mixed waves, boundaries, zeros."""
-    rng = np.random.default_rng(12)
-    small = rng.uniform(-0.78, 0.78, 64 * 300)
-    edge = np.concatenate([np.full(64, 0.0), np.full(64, -0.0), np.full(64, 0.7853981633974483), np.full(64, -0.7853981633974483),
-                           np.full(64, 0.7853981633974484), np.full(64, 0.78539816339744828), np.full(64, 1e-300), np.full(64, -5e-324)])
-    mixed = rng.uniform(-7, 7, 64 * 200)
-    tiny = rng.uniform(-1e-9, 1e-9, 64 * 20)
-    x = np.concatenate([small, edge, mixed, tiny, np.nextafter(0.7853981633974483, [0.0, 1.0] * 32)])
-    want_s = np.array([oracle.orc_psin(float(v)) for v in x])
-    want_c = np.array([oracle.orc_pcos(float(v)) for v in x])
-    assert_bit_equal(grlx.runner.device_math(6, x), want_s, "psin_s")
-    assert_bit_equal(grlx.runner.device_math(7, x), want_c, "pcos_s")
-    assert_bit_equal(grlx.runner.device_math(8, x), want_s + want_c, "psincos_s")
-
-
-def test_device_fmod_sqrt_exact(grlx):
-    rng = np.random.default_rng(5)
-    x = np.concatenate([rng.uniform(-500, 500, 100000), rng.uniform(-7, 7, 100000), [0.0, -0.0, 2 * np.pi, -2 * np.pi, 1e15]])
-    y = np.full_like(x, 2 * np.pi)
-    assert_bit_equal(grlx.runner.device_math(3, x, y), np.fmod(x, y), "fmod")
-    y2 = rng.uniform(1e-3, 50, x.size)
-    assert_bit_equal(grlx.runner.device_math(3, x, y2), np.fmod(x, y2), "fmod general")
-    z = rng.uniform(0, 1e6, 100000)
-    assert_bit_equal(grlx.runner.device_math(4, z), np.sqrt(z), "sqrt")
-
-
-def test_div6_equals_ieee_division(grlx):
-    """RK4's (k1+2k2+2k3+k4)/6 (modeled.cpp:272) uses a 3-operation form proven to be correctly
-    rounded; check it against the true division on random, structured and extreme inputs."""
-    rng = np.random.default_rng(9)
-    m = rng.integers(1 << 52, 1 << 53, 400000).astype(np.float64)          # every mantissa pattern class
-    e = rng.integers(-300, 300, m.size)
-    x = np.concatenate([np.ldexp(m, e - 52) * rng.choice([-1.0, 1.0], m.size), rng.uniform(-1e3, 1e3, 200000),
-                        np.arange(-3000, 3000, dtype=np.float64), np.arange(1, 4000, dtype=np.float64) * (2.0 ** -60),
-                        [0.0, -0.0, 1e-310, -1e-310, 5e-324, 1e308, -1e308, 6.0, 3.0, 1.0 / 3.0]])
-    assert_bit_equal(grlx.runner.device_math(5, x), x / 6.0, "x/6")
-
-
+# (the device math against its specification: tests/test_gpu_math.py)
 def test_rand48_jump_on_device(grlx, oracle):
     skip = np.array([0, 1, 2, 1000, 8388607, 8388608, 8388609, 2**33 + 5, 2**47 - 1], dtype=np.uint64)
     for seed in (1, 77, 2**31 - 1):
@@ -712,16 +659,6 @@ def test_cart_pole_env_step_bit_exact(grlx):
             state = gs
         if esp:
             assert 2 in set(np.unique(gterm))
-
-
-def test_device_log_sqrt_for_box_muller(grlx, oracle):
-    """Rand::getNormal (utils.h:120-125) = sqrt(-2 log U1) cos(2 pi U2): log on drand48 values k * 2^-48"""
-    rng = np.random.default_rng(17)
-    u = np.concatenate([rng.integers(1, 1 << 48, 200000).astype(np.float64) * 2.0 ** -48, [2.0 ** -48, 1 - 2.0 ** -48, 0.5]])
-    got = grlx.runner.device_math(2, u)
-    want = np.array([oracle.orc_plog(float(v)) for v in u])
-    assert_bit_equal(got, want, "plog on uniform draws")
-    assert_bit_equal(grlx.runner.device_math(4, -2 * want), np.sqrt(-2 * want), "sqrt")
 
 
 @pytest.mark.parametrize("over", [dict(), dict(end_stop_penalty=1, ac_update_method=1, ac_step_limit=0.5)])
