@@ -148,6 +148,7 @@ _SIGS = {
 # include/grlx_diag.h: diagnostic exports (tools, tests, bench.py), not part of the boundary
 _DIAG_SIGS = {
     "grlx_env_server_counts": (C.c_int, [C.c_void_p, _P(C.c_int), _P(C.c_int)]),
+    "grlx_uniform_pass_counts": (C.c_int, [C.c_void_p, _P(C.c_ulonglong), C.c_int]),
     "grlx_env_server_debug": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "grlx_fqi_debug_stamps": (C.c_int, [C.c_void_p, _P(C.c_ulonglong), C.c_int]),
     "grlx_last_kernel_name": (C.c_char_p, [C.c_void_p]),

@@ -1018,6 +1018,20 @@ int grlx_env_server_counts(grlx_ctx *ctx, int *served, int *fell_back)
   return GRLX_OK;
 }
 
+// diagnostic (not part of include/grlx.h): per replica, the passes its wave took in the wave-uniform loop of rollout_served_kernel
+// (grlx_rollout.h) in the last launch that had the environment server; zeros when no launch of this context had it
+int grlx_uniform_pass_counts(grlx_ctx *ctx, unsigned long long *out, int count)
+{
+  if (!ctx || !out || count < 0) return fail(GRLX_ERR_INVALID, "bad argument");
+  const int n = count < ctx->P.n_replicas ? count : ctx->P.n_replicas;
+  for (int i = 0; i < count; ++i) out[i] = 0;
+  if (!ctx->env_mail || n == 0) return GRLX_OK;
+  DRAIN(ctx);
+  HIP_TRY(hipMemcpy2D(out, sizeof(unsigned long long), (const char *)ctx->env_mail + kEnvMailUniformOffset, ctx->env_mail_bytes,
+                      sizeof(unsigned long long), (size_t)n, hipMemcpyDeviceToHost));
+  return GRLX_OK;
+}
+
 int grlx_run(grlx_ctx *ctx, int n_trials, void *stream) { return run_trials(ctx, n_trials, 0, stream); }
 
 // The trial loop of OnlineLearningExperiment::run with both of its bounds (online_learning.cpp:154):

@@ -23,6 +23,9 @@
 // and the action), the replica tells the server to stop and integrates by itself for the rest of the launch.  The server leaves when every
 // replica of its block has sent kExit (or has gone on without it), or after kServerStartPolls polls without a first command /
 // kServerIdlePolls polls (or iterations that consume no command) without a further one.  Neither side can hang the other.
+// The pass of the rollout wave exists twice (rollout_body, grlx_rollout.h): a full wave whose four replicas are all served and in mid-episode
+// takes its answers with ONE vote of the whole wave (mail_take_wave) in a loop of straight-line passes; a take that runs into its bound
+// there changes nothing and leaves that loop, and the general pass takes the same step again with mail_take, per replica, as described above.
 #pragma once
 
 namespace grlx {
@@ -33,18 +36,22 @@ struct __attribute__((aligned(1024))) EnvMail {
   unsigned long long cmd[4];                    //   0
   MailUnit reset[3];                            //  32
   unsigned long long pad0[6];                   //  80
-  unsigned long long stats[16];                 // 128  ([15]: served to the end 1 / fell back 2; the rest: GRLX_ENV_SERVER_STATS builds)
+  unsigned long long stats[16];                 // 128  ([15]: served to the end 1 / fell back 2; [14]: passes of the replica's wave in the
+                                                //       wave-uniform loop; the rest: GRLX_ENV_SERVER_STATS builds)
   MailUnit cand[2][3][kCandUnits];              // 256 .. 736
   unsigned long long pad1[36];
 };
 static_assert(sizeof(EnvMail) == kEnvMailBytes, "one mailbox = kEnvMailBytes");
 static_assert(offsetof(EnvMail, stats) + 15 * sizeof(unsigned long long) == kEnvMailFlagOffset, "the flag grlx_env_server_counts reads");
+static_assert(offsetof(EnvMail, stats) + 14 * sizeof(unsigned long long) == kEnvMailUniformOffset, "the count grlx_uniform_pass_counts reads");
 
 typedef __attribute__((address_space(1))) unsigned long long env_gu64;
 typedef unsigned int mail_u32x4 __attribute__((ext_vector_type(4)));
 #define GRLX_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 constexpr unsigned kMailReset = 3u, kMailExit = 4u;
-constexpr unsigned kFetchPolls = 400u;              // x (one round trip through memory) = ~0.5 ms: the server is not there
+constexpr unsigned kFetchPolls = 400u;              // x (one round trip through memory) = ~0.4 ms: the server is not there.  (A take that
+                                                    //   gives up inside the wave-uniform pass, mail_take_wave, is repeated by the general pass:
+                                                    //   for that ONE pass the bound on a missing server doubles, to about 0.8 ms)
 constexpr unsigned kFirstFetchPolls = 8000u;        // the first answer of a launch: the two kernels start on two streams, and the first
                                                     //   launch of a kernel in a process may wait for its scratch to be set up
 constexpr unsigned kServerStartPolls = 20000u;      // x (s_sleep + one round trip) = tens of ms without a first command: the rollout kernel is
@@ -108,15 +115,31 @@ __device__ __forceinline__ bool units_load(const MailUnit *p, unsigned long long
   return ok;
 }
 
+// rollout side: a replica's mailbox as {all mailboxes (wave-uniform), replica}.  The address is made where it is used: held as a pointer
+// per lane it is a register pair for the whole launch (and a pair more for every field address the compiler derives from it ahead of
+// the loops) -- registers the pass loop of rollout_served_kernel does not have.  (in_reg, grlx_policy.h, keeps the few address
+// instructions at the use: the compiler would otherwise move them out of every loop again.)
+struct MailRef {
+  EnvMail *all;
+  uint32_t r;
+  __device__ __forceinline__ EnvMail *get() const { return all + in_reg(r); }
+  __device__ __forceinline__ EnvMail *operator->() const { return get(); }
+};
 // rollout side, ONE lane of the replica's group
 __device__ __forceinline__ void mail_send(EnvMail *m, unsigned long long seq, unsigned op) { mail_store(&m->cmd[seq & 3u], (seq << 8) | op); }
 __device__ __forceinline__ void mail_send_reset(EnvMail *m, unsigned long long seq, const double *x)
 {
-  unit_store(&m->reset[0], x[0], seq);
-  unit_store(&m->reset[1], x[1], seq);
-  unit_store(&m->reset[2], x[2], seq);
+  // (from the mailbox's own address with immediate offsets: three addresses of their own were three register pairs that the compiler
+  //  kept for the whole launch -- registers the pass loop of rollout_served_kernel does not have)
+  static_assert(offsetof(EnvMail, reset) == 2 * sizeof(MailUnit), "reset[i] is unit 2 + i of the mailbox");
+  MailUnit *u = reinterpret_cast<MailUnit *>(m);
+  unit_store_at<2>(u, x[0], seq);
+  unit_store_at<3>(u, x[1], seq);
+  unit_store_at<4>(u, x[2], seq);
   mail_send(m, seq, kMailReset);
 }
+__device__ __forceinline__ void mail_send(const MailRef &m, unsigned long long seq, unsigned op) { mail_send(m.get(), seq, op); }
+__device__ __forceinline__ void mail_send_reset(const MailRef &m, unsigned long long seq, const double *x) { mail_send_reset(m.get(), seq, x); }
 
 // rollout side, all 16 lanes of the replica's group: what command `seq` followed by action `a` leaves.  Lane j < 5 loads unit j (4 registers
 // instead of 20), the group agrees on whether all five were the ones of `seq`, and the values are handed round.  The load is a buffer
@@ -155,6 +178,40 @@ __device__ __forceinline__ bool mail_take(const DevParams &N, const MailBox &b, 
   }
   if (polled) *polled += polls;
   if (!ok) return false;
+  const double v = __longlong_as_double((long long)(((unsigned long long)d.y << 32) | d.x));
+  const int base = g * 16;
+  x[0] = lane_fetch(v, base + 0);
+  x[1] = lane_fetch(v, base + 1);
+  x[2] = lane_fetch(v, base + 2);
+  obs[0] = lane_fetch(v, base + 3);
+  obs[1] = x[1];
+  reward = lane_fetch(v, base + 4);
+  terminal = x[2] > N.timeout ? 1 : 0;                            // Env::observe
+  if (!Env<ENV>::in_domain(x)) status |= ST_DOMAIN;             // env_step
+  return true;
+}
+// The same take for a wave whose FOUR groups are all served and all mid-episode (the wave-uniform pass of rollout_body): the vote is over
+// the whole wave -- while any group's five units are not yet those of `seq`, every lane polls again -- so the loop is one scalar branch
+// and nothing around it is per lane.  A unit that carries `seq` is final, so polling a group that already had its answer reads the same
+// values again: same bits as mail_take.  On running into kFetchPolls NOTHING is changed (x, obs, reward, terminal, status as they were):
+// the caller leaves its loop and the general pass takes this step with mail_take, falling back per replica there.
+template <int ENV>
+__device__ __forceinline__ bool mail_take_wave(const DevParams &N, const MailBox &b, mail_u32x4 d, unsigned long long seq, int a, int g,
+                                               double *x, double *obs, double &reward, int &terminal, uint32_t &status,
+                                               unsigned long long *polled = nullptr)
+{
+  static_assert(ENV == GRLX_ENV_PENDULUM, "the pendulum's mailbox");
+  unsigned polls = 0;
+  while (!__all((((unsigned long long)d.w << 32) | d.z) == seq))
+  {
+    if (++polls > kFetchPolls)
+    {
+      if (polled) *polled += polls;
+      return false;
+    }
+    d = mail_prefetch(b, seq, a);
+  }
+  if (polled) *polled += polls;
   const double v = __longlong_as_double((long long)(((unsigned long long)d.y << 32) | d.x));
   const int base = g * 16;
   x[0] = lane_fetch(v, base + 0);

@@ -9,7 +9,8 @@ namespace grlx {
 constexpr int kLanesPerReplica = 16;     // one lane per tiling
 constexpr size_t kEnvMailBytes = 1024;    // sizeof(EnvMail), grlx_env_server.h
 constexpr size_t kEnvMailFlagOffset = 128 + 15 * 8;   // offsetof(EnvMail, stats[15]): served to the end 1 / fell back 2
-constexpr size_t kWideMailBytes = 2048;   // >= sizeof(WideMail<ENV>), grlx_env_server_wide.h (the wide kernels' environment server)
+constexpr size_t kEnvMailUniformOffset = 128 + 14 * 8;   // offsetof(EnvMail, stats[14]): passes the replica's wave took in the wave-uniform loop
+constexpr size_t kWideMailBytes = 2048;  // >= sizeof(WideMail<ENV>), grlx_env_server_wide.h (the wide kernels' environment server)
 constexpr size_t kAcParkBytes = 12 * 64 * 16 + 3 * 64 * 4;     // grlx_rollout_ac_wide.h: kWideQuads quads + three counters per lane
 constexpr int kReplicasPerWave = 4;      // per sub-batch; a wide wave carries 4*B (grlx_rollout_wide.h)
 constexpr int kMaxTrace = 10;            // replacing trace: (gamma*lambda)^n < 0.01 must hold for n <= 10

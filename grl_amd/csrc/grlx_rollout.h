@@ -228,6 +228,8 @@ struct SpecSweep {
 #define GRLX_ROLLOUT_OCCUPANCY
 #endif
 // SERVED: the environment steps come from the environment server (grlx_env_server.h) -- its own kernel, rollout_served_kernel below.
+// Only there, the pass of a learning episode in mid-flight exists a second time, as a wave-uniform loop of straight-line passes at the
+// top of the pass loop (profiles/served_uniform_pass_ab.md); the other instantiations are the same code with or without it.
 template <int ENV, int NA, bool DIAG, typename SPEC, bool DEFER, bool ADV, bool TAP, bool SERVED>
 __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials, const SweepParams *sweep = nullptr)
 {
@@ -304,9 +306,10 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials, c
   // the environment server (grlx_env_server.h): this replica's mailbox, the number of commands sent, and whether the server still answers
   constexpr bool EXT = SERVED;
   static_assert(!SERVED || (DEFER && !DIAG && !TAP && !ADV && ENV == GRLX_ENV_PENDULUM && NA == 3), "what the environment server works for");
-  EnvMail *mail = nullptr;
+  MailRef mail = {nullptr, 0u};
   unsigned long long mseq = 0;
   bool srv = false;
+  unsigned n_uniform = 0;                  // passes this wave took in the wave-uniform loop (one scalar add each; mail->stats[14])
 #ifdef GRLX_ENV_SERVER_STATS
   unsigned long long st_wait = 0, st_polls = 0, st_fetch = 0, st_begin = mail_clock();
 #endif
@@ -315,7 +318,7 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials, c
   if constexpr (EXT)
   {
     srv = live && P.env_mail != nullptr;
-    mail = P.env_mail + r;
+    mail = MailRef{P.env_mail, (uint32_t)r};
     mbox = mailbox_of(P, r, j);
     mail_setprio(P.env_tune & 3u);
   }
@@ -380,6 +383,207 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials, c
 
     for (;;)
     {
+      // -------- SERVED: the wave-uniform pass.  From its third pass on, a learning episode of a full wave whose four replicas are all
+      // served runs the SAME pass for every lane: running, not the first pass, an update pending, the step taken from the server, Q(s', .)
+      // looked up (has_next is a compile-time `true` for the pendulum), a TD update queued.  That pass is restated here straight-line,
+      // in a loop whose test is one scalar branch: written as per-lane regions (the general pass below) the register allocator parks
+      // every value that lives across the pass in accumulation registers at the head of the loop and fetches it back inside each
+      // region, a few hundred moves per pass that compute nothing.  Same helpers on the same arguments in the same order as the general
+      // pass, so the same bits; each block names the block of the general pass it restates, and a change to one is made to both.
+      // Everything else -- the start pass and the second, the tail with only `pd` set, test episodes, a ragged last wave, a wave in which
+      // a replica fell back, a take that ran into its bound -- runs the general pass.
+      if constexpr (SERVED)
+      {
+        static_assert(!Env<ENV>::kAbsorbing, "has_next is taken as true");
+        if (__all(live && running && !first && srv && !test && pd) && !(P.env_tune & 16u))
+        {
+          do
+          {
+            DIAG_STAMP(0)
+            // [environment step] the candidate of the action taken; the vote is the whole wave's.  Not there within the bound: nothing has
+            // changed, the general pass takes this step (polls again, falls back per replica)
+#ifdef GRLX_ENV_SERVER_STATS
+            const unsigned long long tf0 = mail_clock();
+            const bool stepped = mail_take_wave<ENV>(N, mbox, mpre, mseq - 1, action_index, g, x, obs, reward, terminal, status, &st_polls);
+            st_wait += mail_clock() - tf0;
+            ++st_fetch;
+#else
+            const bool stepped = mail_take_wave<ENV>(N, mbox, mpre, mseq - 1, action_index, g, x, obs, reward, terminal, status);
+#endif
+            if (!stepped) break;
+            ++n_uniform;
+            total_reward += reward;                                          // :202
+            time += 1;                                                       // tau = 1
+            DIAG_STAMP(1)
+
+            // [policy: projections]
+            uint32_t slot[NA];
+            Lookup lk[NA];
+            BucketRegs br[NA];
+            {
+              uint32_t hpre = 449u ^ (uint32_t)(D + 2);                          // tile_slots_obs_actions
+#pragma unroll
+              for (int i = 0; i < D; ++i)
+                hpre = murmur_mix(hpre, tile_coord<T>(N.tile, i, tile_quant(N.tile, i, obs[i]), j));
+              const uint32_t hpm = hpre * 0x5bd1e995u;                           // shared by the NA projections
+#pragma unroll
+              for (int a = 0; a < NA; ++a)
+              {
+                uint32_t h = hpm ^ key_act[a];                                   // murmur_mix(hpre, coordinate of action a)
+                h = murmur_absorb(h, key_j);                                     // murmur_mix(h, j)
+                const uint32_t hm = murmur_final(h), mem = (uint32_t)N.tile.memory;
+                slot[a] = ((mem & (mem - 1u)) == 0u) ? (hm & (mem - 1u)) : (hm % mem);
+              }
+            }
+            DIAG_STAMP(2)
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+            DIAG_STAMP(6)
+            // [weights of project(s, a); home buckets of Q(s', .)]
+            double wp = wp_seen;
+            table_issue<NA>(tab, slot, lk, br);
+
+            // [the PREVIOUS step's predictor update] (pending in every lane)
+            Evicted ev;
+            ev.n = 0u; ev.pos = kInvalidPos; ev.val = 0;
+            DIAG_STAMP(7)
+            sh_ppos[g * 16 + j] = pd_pos;
+            sh_fbflag[j * 4 + g] = 0u;
+            wave_sync();
+            up.dW = pd_dW;
+            up.dT = pd_dT;
+            td_update_lane<true, true>(tr, tab, up, pd_pos, pd_sh, pd_wp, g, j, sh_ppos, sh_fb, sh_fbflag, status, ev);
+            DIAG_STAMP(5)
+
+            // [table_get_finish and the reload after a sharing event]
+            double q[NA];
+            uint32_t pos[NA];
+            double w[NA];
+            bool sh[NA];
+#pragma unroll
+            for (int a = 0; a < NA; ++a) { q[a] = 0; pos[a] = kInvalidPos; w[a] = 0; sh[a] = false; }
+            bool shared_event = false;
+            table_get_finish<NA>(tab, N.lin, RSc, 0, slot, lk, br, pos, w, sh, g, j, gmask, sh_mb, sh_ms, sh_mail, sh_jump, status, inserted,
+                                 [&](uint32_t mp) {
+                                   if (ev.pos != kInvalidPos && ev.pos == mp) value_store(tab, mp, ev.val);
+                                   trace_share_event(tr, tab, mp);
+                                   if (p_pos == mp) p_sh = true;
+                                   shared_event = true;
+                                 });
+            DIAG_STAMP(7)
+            if (rarely(__any(shared_event))) wp = value_load(tab, p_pos);
+            // [values that the deferred update may have made stale: the `risky` reload, then the held eviction]
+            {
+              bool risky = ev.n > 1u || p_sh;
+#pragma unroll
+              for (int a = 0; a < NA; ++a) risky = risky || sh[a];
+              if (rarely(__any(risky)))
+              {
+#pragma unroll
+                for (int a = 0; a < NA; ++a) w[a] = value_load(tab, pos[a]);
+                wp = value_load(tab, p_pos);
+              }
+              const bool held = ev.pos != kInvalidPos;
+#pragma unroll
+              for (int a = 0; a < NA; ++a) w[a] = (held && pos[a] == ev.pos) ? ev.val : w[a];
+              wp = (held && p_pos == ev.pos) ? ev.val : wp;
+            }
+            // [trace_forward, the LDS rows]
+#pragma unroll
+            for (int a = 0; a < NA; ++a)
+            {
+              w[a] = trace_forward(tr, pos[a], w[a]);
+              SHW(a, j, g) = w[a];
+            }
+            wp = trace_forward(tr, p_pos, wp);
+            SHW(NA, j, g) = wp;
+            DIAG_STAMP(3)
+            wave_sync();
+            // [sum_rows]
+            {
+              const int row = (j < NROWS) ? j : 0;
+              double sum = 0;
+#pragma unroll
+              for (int k = 0; k < 16; ++k) sum += SHW(row, k, g);
+              sum /= 16;
+              sh_res[g * 16 + j] = sum;
+            }
+            wave_sync();
+#pragma unroll
+            for (int a = 0; a < NA; ++a) q[a] = clampd(sh_res[g * 16 + a], up.out_min, up.out_max);
+            const double qsa = clampd(sh_res[g * 16 + NA], up.out_min, up.out_max);
+
+            // [sampler] of a learning episode; `time` is at least 1 here, so the decay at time 0 has nothing to do
+            int a_next = 0;
+            int mai = 0, man = 1;
+            double best = 0;
+            findmax<NA>(q, mai, man, best);
+            S1 = lcg_next(S1);
+            const double rnd = lcg_double(S1);
+            if (rnd < eps_decay * SPEC::epsilon(N, rep))
+            {
+              G = lcg_next(G);
+              a_next = (int)(lcg_long(G) % (uint32_t)NA);
+            }
+            else
+              a_next = (man > 1) ? tie_break<NA>(q, best, man, G) : mai;
+            // [the command] (per lane: a side-effect guard, no state lives in it)
+            if (!terminal)
+            {
+              ++mseq;
+              if (j == 0) mail_send(mail, mseq, (unsigned)a_next);
+              mpre = mail_prefetch(mbox, mseq - 1, a_next);
+            }
+
+            DIAG_STAMP(4)
+            // [predictor update: the target, queued for the next pass]
+            {
+              double target = reward;
+              if (SPEC::agent(P) == GRLX_AGENT_SARSA)
+                target += SPEC::gamma(N, rep) * pick<double, NA>(q, a_next);
+              else if (SPEC::agent(P) == GRLX_AGENT_EXPECTED_SARSA)
+              { // QPolicy::value (q.cpp:60-73) = sum_a Q(s',a) * EpsilonGreedySampler::distribution (greedy.cpp:220-238)
+                const double de = eps_decay * SPEC::epsilon(N, rep);
+                double v = 0;
+#pragma unroll
+                for (int kk = 0; kk < NA; ++kk)
+                {
+                  double d = (q[kk] == best) ? 1. / man : 0.;
+                  if (d == 1) d = 1 - de;
+                  d += de / NA;
+                  v += q[kk] * d;
+                }
+                target += SPEC::gamma(N, rep) * v;
+              }
+              else
+              {
+                double v = -__builtin_inf();
+#pragma unroll
+                for (int kk = 0; kk < NA; ++kk) v = fmax(v, q[kk]);
+                target += SPEC::gamma(N, rep) * v;
+              }
+              const double delta = target - qsa;
+              pd_dW = SPEC::alpha(N, rep) * (target - qsa);                    // LinearRepresentation::write (linear.cpp:186-196)
+              pd_dT = SPEC::alpha(N, rep) * delta;                             // VectorConstructor(alpha_*delta)
+              pd_pos = p_pos;
+              status |= (p_pos == kInvalidPos) ? ST_BAD_POS : 0u;
+              pd_sh = p_sh;
+              pd_wp = wp;
+            }
+            DIAG_STAMP(5)
+            // [bookkeeping]
+            ss++;                                                              // online_learning.cpp:218
+            action_index = a_next;                                             // (`action` itself: after the loop; p_slot: taps only)
+            p_pos = pick<uint32_t, NA>(pos, a_next);
+            p_sh = pick<bool, NA>(sh, a_next);
+            wp_seen = pick<double, NA>(w, a_next);
+            if (terminal) running = false;                                     // (per lane; ends this loop at its next test)
+            // [the eviction held back by the deferred update]
+            if (ev.pos != kInvalidPos) value_store(tab, ev.pos, ev.val);
+          } while (__all(running));
+          // only the general pass reads the torque itself (its fall-back integrator): discretizer_->at(index), uniform.cpp:140-151
+          action = pick<double, NA>(acts, action_index);
+        }
+      }
       if (!__any(running || pd)) break;
       // state that lives across the deferred-update site
       uint32_t slot[NA];
@@ -815,7 +1019,11 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials, c
       for (int k = 0; k < 8; ++k) mail->pad1[k] = diag_sum[k];
     }
 #endif
-    if (live && j == 0 && P.env_mail) mail->stats[15] = srv ? 1u : 2u;     // (grlx_env_server_counts: served to the end / fell back)
+    if (live && j == 0 && P.env_mail)
+    {
+      mail->stats[14] = n_uniform;          // (grlx_uniform_pass_counts: the passes this replica's wave took in the wave-uniform loop)
+      mail->stats[15] = srv ? 1u : 2u;      // (grlx_env_server_counts: served to the end / fell back)
+    }
     if (srv)
     { // no further command in this launch
       ++mseq;

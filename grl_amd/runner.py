@@ -239,6 +239,13 @@ class Runner:
         capi.check(self.lib.grlx_env_server_counts(self._ctx, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def uniform_pass_counts(self):
+        """Per replica, the passes its wave took in the wave-uniform loop of rollout_served_kernel in the last launch that had the
+        environment server (zeros when none had it) -- diagnostic export, not part of include/grlx.h"""
+        out = np.zeros(self.cfg.n_replicas, dtype=np.uint64)
+        capi.check(self.lib.grlx_uniform_pass_counts(self._ctx, _ptr(out, C.c_ulonglong), out.size))
+        return out
+
     def replicas_per_wave(self) -> int:
         """4: one replica per 16 lanes; 8: two sub-batches per wave sharing the environment phase (wide kernels); 12 / 16: three / four
         sub-batches (actor-critic only; 12 rotates the wave's own replicas through its slots trial by trial)."""

@@ -14,6 +14,11 @@ extern "C" {
  * it, how many replicas took every environment step from it and how many gave up waiting and integrated themselves; both 0 when no
  * launch of this context had it. */
 int grlx_env_server_counts(grlx_ctx *ctx, int *served, int *fell_back);
+/* The wave-uniform pass of rollout_served_kernel (grl_amd/csrc/grlx_rollout.h): out[r], r < min(count, replicas), = the passes the wave of
+ * replica r took in that loop in the last launch of the context that had the environment server (the four replicas of a wave report the
+ * same number; a ragged wave, a wave without the server and the wide kernels report 0); the rest of out, and all of it when no launch of
+ * this context had the server, is 0. */
+int grlx_uniform_pass_counts(grlx_ctx *ctx, unsigned long long *out, int count);
 /* The raw mailboxes of the environment server after the last launch (1 KB per replica; GRLX_ENV_SERVER_STATS builds leave cycle counts
  * in them): at most `bytes` bytes to `out`. */
 int grlx_env_server_debug(grlx_ctx *ctx, void *out, size_t bytes);
