@@ -132,6 +132,9 @@ _SIGS = {
     "grlx_read": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_int32), _P(C.c_uint32), C.c_int, _P(C.c_double)]),
     "grlx_write": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_int32), _P(C.c_uint32), C.c_int, _P(C.c_double), C.c_double]),
     "grlx_update": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_int32), _P(C.c_uint32), C.c_int, _P(C.c_double)]),
+    "grlx_query_q": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P(C.c_double), C.c_int, _P(C.c_double), _P(C.c_double), _P(C.c_int32), _P(C.c_int32)]),
+    "grlx_query_state": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_double), C.c_int, _P(C.c_double)]),
+    "grlx_query_ensemble": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_double), C.c_int, _P(C.c_double)]),
     "grlx_math": (C.c_int, [C.c_int, _P(C.c_double), _P(C.c_double), C.c_int, _P(C.c_double)]),
     "grlx_rand48_at": (C.c_int, [C.c_int64, _P(C.c_uint64), C.c_int, _P(C.c_double)]),
     "grlx_fqi_config_pendulum": (None, [_P(FqiConfig)]),
@@ -143,6 +146,7 @@ _SIGS = {
     "grlx_fqi_get_params": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_double), C.c_int]),
     "grlx_fqi_get_transitions": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_double), _P(C.c_double), _P(C.c_double), _P(C.c_double)]),
     "grlx_fqi_info": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_int64), _P(C.c_double), _P(C.c_int32), _P(C.c_double), _P(C.c_uint64)]),
+    "grlx_fqi_query": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P(C.c_double), C.c_int, _P(C.c_double)]),
 }
 
 # include/grlx_diag.h: diagnostic exports (tools, tests, bench.py), not part of the boundary
@@ -155,10 +159,12 @@ _DIAG_SIGS = {
     "grlx_kernel_plan": (C.c_int, [_P(Config), C.c_int, C.c_int, _P(C.c_int), _P(C.c_int), _P(C.c_int), C.c_char_p, C.c_char_p, C.c_size_t]),
     "grlx_snapshot_timing": (C.c_int, [C.c_void_p, _P(C.c_double), _P(C.c_double)]),
     "grlx_snapshot_naive_copy": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_double), _P(C.c_double)]),
+    "grlx_set_query_chunk_bytes": (C.c_int, [C.c_uint64]),
 }
 # entry points of include/grlx.h that a library named by GRLX_LIB may predate (A/B timing of an older build against this binding); the
 # library in the tree must export every one of them, as it must every other symbol of _SIGS
-_NEWER_SIGS = ("grlx_snapshot_size", "grlx_snapshot_save", "grlx_snapshot_load", "grlx_snapshot_info")
+_NEWER_SIGS = ("grlx_snapshot_size", "grlx_snapshot_save", "grlx_snapshot_load", "grlx_snapshot_info",
+               "grlx_query_q", "grlx_query_state", "grlx_query_ensemble", "grlx_fqi_query")
 # grlx_kernel_plan flags
 PLAN_STAMPS_IN_PLACE, PLAN_STAMPS_DEFERRED, PLAN_SWEEP, PLAN_SERVER_OFF, PLAN_WALKER_SERVER, PLAN_FITS_YES, PLAN_FITS_NO = 1, 2, 4, 8, 16, 32, 64
 ABI_VERSION = 2         # include/grlx.h: GRLX_ABI_VERSION

@@ -15,6 +15,7 @@
 #include <vector>
 #include "grlx_internal.h"
 #include "grlx_snapshot.h"
+#include "grlx_query.h"
 #include "../../include/grlx_diag.h"
 
 using namespace grlx;
@@ -37,6 +38,7 @@ int fail(int code, const char *fmt, ...)
 } // namespace
 namespace grlx {
 void set_last_error(const char *msg) { g_err = msg; }     // other translation units of the library (grlx_fqi.hip)
+void set_fqi_query_chunk_bytes(uint64_t bytes);            // grlx_fqi.hip: the staging bound of grlx_fqi_query
 }
 namespace {
 #define HIP_TRY(expr)                                                                   \
@@ -1758,6 +1760,147 @@ int grlx_update(grlx_ctx *ctx, int table, const int32_t *replica, const uint32_t
 {
   if (!delta) return fail(GRLX_ERR_INVALID, "bad argument");
   return table_op(ctx, table, 2, replica, idx, n, delta, 0, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------- policy queries ---
+} // extern "C"
+namespace {
+
+constexpr uint64_t kQueryChunkDefault = 256ull << 20;
+uint64_t g_query_chunk_bytes = kQueryChunkDefault;
+
+bool q_agent(int agent) { return agent != GRLX_AGENT_AC; }      // every other agent acts through a policy/discrete/q on table 0
+
+// what every query checks before it touches the device; tp: the projector of the table read, obs_dims: its share of the observation
+int query_admit(grlx_ctx *ctx, const char *who, int first_replica, int n_replicas, const double *obs, int n_obs, const TileParams &tp, int obs_dims)
+{
+  if (ctx->P.tile_safe >= 1)
+    return fail(GRLX_ERR_INVALID, "%s is not built for projector/tile_coding:safe >= 1 (a read would have to walk the claim table without claiming)", who);
+  if (n_obs < 0) return fail(GRLX_ERR_INVALID, "%s: n_obs = %d", who, n_obs);
+  if (first_replica < 0 || n_replicas < 0 || (int64_t)first_replica + n_replicas > ctx->P.n_replicas)
+    return fail(GRLX_ERR_INVALID, "%s: replica range [%d, %lld) is outside the context's %d replicas", who, first_replica,
+                (long long)first_replica + n_replicas, ctx->P.n_replicas);
+  if (!obs) return fail(GRLX_ERR_INVALID, "%s: obs is null", who);
+  for (int o = 0; o < n_obs; ++o)
+    for (int i = 0; i < obs_dims; ++i)
+    { // tile_quant casts floor(x * scaling) to int (tile_coding.cpp:121-125)
+      const double x = obs[(size_t)o * obs_dims + i];
+      if (!std::isfinite(x)) return fail(GRLX_ERR_INVALID, "%s: observation row %d, dimension %d is not finite (%g)", who, o, i, x);
+      if (!(fabs(x * tp.scaling[i]) < 1073741824.))
+        return fail(GRLX_ERR_INVALID, "%s: observation row %d, dimension %d (%g) is out of range: |x * scaling| reaches 2^30", who, o, i, x);
+    }
+  return GRLX_OK;
+}
+
+// observations per chunk so that one chunk's device arrays stay within the bound; at least one
+int query_chunk(int n_obs, size_t bytes_per_obs)
+{
+  const uint64_t fit = g_query_chunk_bytes / (bytes_per_obs ? bytes_per_obs : 1);
+  return (int)(fit < 1 ? 1 : fit > (uint64_t)n_obs ? (uint64_t)n_obs : fit);
+}
+
+// rows [n_replicas] of `width` bytes each: device [r][chunk] -> host [r][n_obs] at observation o0
+hipError_t query_copy_out(void *host, const void *dev, size_t elem, int n_replicas, int n_obs, int o0, int nc)
+{
+  return hipMemcpy2D((char *)host + (size_t)o0 * elem, (size_t)n_obs * elem, dev, (size_t)nc * elem, (size_t)nc * elem, (size_t)n_replicas,
+                     hipMemcpyDeviceToHost);
+}
+
+int query_q_impl(grlx_ctx *ctx, const char *who, int first_replica, int n_replicas, int group_size, const double *obs, int n_obs,
+                 double *q, double *value, int32_t *greedy, int32_t *n_max, double *ensemble)
+{
+  if (!ctx) return fail(GRLX_ERR_INVALID, "bad argument");
+  if (!q_agent(ctx->cfg.agent)) return fail(GRLX_ERR_INVALID, "%s serves agents with a policy/discrete/q; the actor-critic's tables are read by grlx_query_state", who);
+  const int NA = ctx->P.A, D = ctx->P.tile.D - 1;
+  if (NA != 3 && NA != 5) return fail(GRLX_ERR_INVALID, "%s is not built for %d actions (3 or 5)", who, NA);
+  int rc = query_admit(ctx, who, first_replica, n_replicas, obs, n_obs, ctx->P.tile, D);
+  if (rc != GRLX_OK) return rc;
+  if (ensemble && (group_size < 1 || n_replicas % group_size != 0))
+    return fail(GRLX_ERR_INVALID, "%s: group_size %d does not divide the %d replicas", who, group_size, n_replicas);
+  if (n_obs == 0 || n_replicas == 0) return GRLX_OK;
+  DRAIN(ctx);
+  const int n_groups = ensemble ? n_replicas / group_size : 0, cols = 2 + 2 * NA;
+  const size_t per_pair = sizeof(double) * (size_t)NA + sizeof(double) + 2 * sizeof(int32_t);
+  const int chunk = query_chunk(n_obs, sizeof(double) * (size_t)D + per_pair * (size_t)n_replicas + sizeof(double) * (size_t)cols * (size_t)n_groups);
+  DevBuf dobs, dq, dv, dg, dn, de;
+  const size_t pairs = (size_t)n_replicas * (size_t)chunk;
+  HIP_TRY(dobs.alloc(sizeof(double) * (size_t)chunk * D));
+  if (q || ensemble) HIP_TRY(dq.alloc(sizeof(double) * pairs * NA));
+  if (value || ensemble) HIP_TRY(dv.alloc(sizeof(double) * pairs));
+  if (greedy || ensemble) HIP_TRY(dg.alloc(sizeof(int32_t) * pairs));
+  if (n_max) HIP_TRY(dn.alloc(sizeof(int32_t) * pairs));
+  if (ensemble) HIP_TRY(de.alloc(sizeof(double) * (size_t)n_groups * chunk * cols));
+  for (int o0 = 0; o0 < n_obs; o0 += chunk)
+  {
+    const int nc = n_obs - o0 < chunk ? n_obs - o0 : chunk;
+    HIP_TRY(hipMemcpy(dobs.p, obs + (size_t)o0 * D, sizeof(double) * (size_t)nc * D, hipMemcpyHostToDevice));
+    QueryArgs A;
+    A.first_replica = first_replica; A.n_replicas = n_replicas; A.n_obs = nc;
+    A.obs = dobs.as<double>(); A.q = dq.as<double>(); A.value = dv.as<double>(); A.greedy = dg.as<int32_t>(); A.n_max = dn.as<int32_t>();
+    if (ctx->poison) HIP_TRY(launch_poison_registers(ctx->poison_pattern, nullptr));
+    HIP_TRY(launch_query_q(ctx->P, A, nullptr));
+    if (ensemble)
+    {
+      HIP_TRY(launch_query_reduce(NA, n_groups, group_size, nc, A.q, A.value, A.greedy, de.as<double>(), nullptr));
+      HIP_TRY(query_copy_out(ensemble, de.p, sizeof(double) * cols, n_groups, n_obs, o0, nc));
+    }
+    if (q) HIP_TRY(query_copy_out(q, dq.p, sizeof(double) * NA, n_replicas, n_obs, o0, nc));
+    if (value) HIP_TRY(query_copy_out(value, dv.p, sizeof(double), n_replicas, n_obs, o0, nc));
+    if (greedy) HIP_TRY(query_copy_out(greedy, dg.p, sizeof(int32_t), n_replicas, n_obs, o0, nc));
+    if (n_max) HIP_TRY(query_copy_out(n_max, dn.p, sizeof(int32_t), n_replicas, n_obs, o0, nc));
+  }
+  return GRLX_OK;
+}
+
+} // namespace
+extern "C" {
+
+int grlx_set_query_chunk_bytes(uint64_t bytes)
+{
+  g_query_chunk_bytes = bytes ? bytes : kQueryChunkDefault;
+  set_fqi_query_chunk_bytes(bytes);
+  return GRLX_OK;
+}
+
+int grlx_query_q(grlx_ctx *ctx, int first_replica, int n_replicas, const double *obs, int n_obs, double *q, double *value, int32_t *greedy, int32_t *n_max)
+{
+  return query_q_impl(ctx, "grlx_query_q", first_replica, n_replicas, 0, obs, n_obs, q, value, greedy, n_max, nullptr);
+}
+
+int grlx_query_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, const double *obs, int n_obs, double *out)
+{
+  if (!out) return fail(GRLX_ERR_INVALID, "bad argument");
+  return query_q_impl(ctx, "grlx_query_ensemble", first_replica, n_replicas, group_size, obs, n_obs, nullptr, nullptr, nullptr, nullptr, out);
+}
+
+int grlx_query_state(grlx_ctx *ctx, int table, int first_replica, int n_replicas, const double *obs, int n_obs, double *out)
+{
+  if (!ctx || !out) return fail(GRLX_ERR_INVALID, "bad argument");
+  if (table < 0 || table >= ctx->n_tables) return fail(GRLX_ERR_INVALID, "grlx_query_state: table %d (the context has %d)", table, ctx->n_tables);
+  if (table == 0 && q_agent(ctx->cfg.agent))
+    return fail(GRLX_ERR_INVALID, "grlx_query_state: table 0 of a Q agent takes (observation, action): use grlx_query_q");
+  const TileParams &tp = table == 1 ? ctx->P.tile_actor : ctx->P.tile;
+  int rc = query_admit(ctx, "grlx_query_state", first_replica, n_replicas, obs, n_obs, tp, tp.D);
+  if (rc != GRLX_OK) return rc;
+  if (n_obs == 0 || n_replicas == 0) return GRLX_OK;
+  DRAIN(ctx);
+  const int D = tp.D;
+  const int chunk = query_chunk(n_obs, sizeof(double) * (size_t)D + sizeof(double) * (size_t)n_replicas);
+  DevBuf dobs, dv;
+  HIP_TRY(dobs.alloc(sizeof(double) * (size_t)chunk * D));
+  HIP_TRY(dv.alloc(sizeof(double) * (size_t)n_replicas * (size_t)chunk));
+  for (int o0 = 0; o0 < n_obs; o0 += chunk)
+  {
+    const int nc = n_obs - o0 < chunk ? n_obs - o0 : chunk;
+    HIP_TRY(hipMemcpy(dobs.p, obs + (size_t)o0 * D, sizeof(double) * (size_t)nc * D, hipMemcpyHostToDevice));
+    QueryArgs A;
+    A.first_replica = first_replica; A.n_replicas = n_replicas; A.n_obs = nc;
+    A.obs = dobs.as<double>(); A.q = nullptr; A.value = dv.as<double>(); A.greedy = nullptr; A.n_max = nullptr;
+    if (ctx->poison) HIP_TRY(launch_poison_registers(ctx->poison_pattern, nullptr));
+    HIP_TRY(launch_query_state(ctx->P, table, A, nullptr));
+    HIP_TRY(query_copy_out(out, dv.p, sizeof(double), n_replicas, n_obs, o0, nc));
+  }
+  return GRLX_OK;
 }
 
 int grlx_math(int op, const double *x, const double *y, int n, double *out)

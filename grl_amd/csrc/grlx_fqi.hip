@@ -1047,3 +1047,81 @@ int grlx_fqi_info(grlx_fqi_ctx *ctx, int replica, int64_t *n_transitions, double
 }
 
 } // extern "C"
+
+// ------------------------------------------------------------------------------------------- policy query ---
+// grlx_fqi_query: the batch path's Q(s, a_k) at observations of the caller's choice -- the projector's normalisation and the network's
+// forward pass on the replica's CURRENT parameters, the operations of fqi_test_kernel's policy.  Reads F.net only: nothing of the
+// context changes.  Appended after everything else of the unit: the kernels above keep their instruction streams.
+namespace grlx {
+
+// one thread per (replica, observation), looping over the actions; q[(replica - first_replica) * n_obs + observation][F.A]
+template <int H>
+__global__ __launch_bounds__(64) void fqi_query_kernel(FqiParams F, int first_replica, int n_replicas, const double *obs, int n_obs, double *q)
+{
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)n_replicas * n_obs) return;
+  const int rl = (int)(i / n_obs), o = (int)(i - (long long)rl * n_obs);
+  const double *net = F.net + (size_t)(first_replica + rl) * 4 * F.P;
+  double ob[kFqiD];
+#pragma unroll
+  for (int d = 0; d < kFqiD; ++d) ob[d] = obs[(size_t)o * kFqiD + d];
+  for (int k = 0; k < F.A; ++k)
+  {
+    double in[kFqiNIn];
+    fqi_normalise(F, ob, F.actions[k], in);
+    q[(size_t)i * F.A + k] = ann_forward<H>(net, in, nullptr);
+  }
+}
+
+} // namespace grlx
+
+namespace {
+uint64_t g_fqi_query_chunk_bytes = 256ull << 20;      // device staging one query holds at most
+}
+namespace grlx { void set_fqi_query_chunk_bytes(uint64_t bytes) { g_fqi_query_chunk_bytes = bytes ? bytes : (256ull << 20); } }     // grlx_set_query_chunk_bytes
+
+extern "C" int grlx_fqi_query(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, const double *obs, int n_obs, double *q)
+{
+  if (!ctx || !q) return ffail(GRLX_ERR_INVALID, "bad argument");
+  if (!obs) return ffail(GRLX_ERR_INVALID, "grlx_fqi_query: obs is null");
+  if (n_obs < 0) return ffail(GRLX_ERR_INVALID, "grlx_fqi_query: n_obs = %d", n_obs);
+  if (first_replica < 0 || n_replicas < 0 || (int64_t)first_replica + n_replicas > ctx->F.R)
+    return ffail(GRLX_ERR_INVALID, "grlx_fqi_query: replica range [%d, %lld) is outside the context's %d replicas", first_replica,
+                 (long long)first_replica + n_replicas, ctx->F.R);
+  for (int o = 0; o < n_obs; ++o)
+    for (int d = 0; d < kFqiD; ++d)
+      if (!std::isfinite(obs[(size_t)o * kFqiD + d]))
+        return ffail(GRLX_ERR_INVALID, "grlx_fqi_query: observation row %d, dimension %d is not finite", o, d);
+  if (n_obs == 0 || n_replicas == 0) return GRLX_OK;
+  FQI_TRY(hipDeviceSynchronize());
+  const int A = ctx->F.A;
+  const uint64_t per_obs = sizeof(double) * kFqiD + sizeof(double) * (uint64_t)A * (uint64_t)n_replicas;
+  const uint64_t fit = g_fqi_query_chunk_bytes / per_obs;
+  const int chunk = (int)(fit < 1 ? 1 : fit > (uint64_t)n_obs ? (uint64_t)n_obs : fit);
+  double *dobs = nullptr, *dq = nullptr;
+  if (hipMalloc((void **)&dobs, sizeof(double) * kFqiD * (size_t)chunk) != hipSuccess ||
+      hipMalloc((void **)&dq, sizeof(double) * (size_t)A * (size_t)n_replicas * (size_t)chunk) != hipSuccess)
+  {
+    if (dobs) (void)hipFree(dobs);
+    return ffail(GRLX_ERR_OOM, "grlx_fqi_query: out of device memory");
+  }
+  hipError_t err = hipSuccess;
+  for (int o0 = 0; o0 < n_obs && err == hipSuccess; o0 += chunk)
+  {
+    const int nc = n_obs - o0 < chunk ? n_obs - o0 : chunk;
+    const long long pairs = (long long)n_replicas * nc;
+    err = hipMemcpy(dobs, obs + (size_t)o0 * kFqiD, sizeof(double) * kFqiD * (size_t)nc, hipMemcpyHostToDevice);
+    if (err != hipSuccess) break;
+    FQI_FOR_H(ctx->F.H, hipLaunchKernelGGL(fqi_query_kernel<HH>, dim3((unsigned)((pairs + 63) / 64)), dim3(64), 0, nullptr, ctx->F, first_replica,
+                                           n_replicas, dobs, nc, dq));
+    err = hipGetLastError();
+    if (err != hipSuccess) break;
+    const size_t elem = sizeof(double) * (size_t)A;                       // device [replica][nc][A] -> host [replica][n_obs][A] at o0
+    err = hipMemcpy2D((char *)q + (size_t)o0 * elem, (size_t)n_obs * elem, dq, (size_t)nc * elem, (size_t)nc * elem, (size_t)n_replicas,
+                      hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(dobs);
+  (void)hipFree(dq);
+  if (err != hipSuccess) return ffail(GRLX_ERR_HIP, "grlx_fqi_query failed: %s", hipGetErrorString(err));
+  return GRLX_OK;
+}

@@ -6,6 +6,8 @@
 // in the order of the -p options, the last fastest) with seed + i and identity "@i"; <output>-<run>-sweep.txt holds the statistics per point,
 // -k FILE: write a snapshot of the whole context (grlx_snapshot_save) when the trial loop of the run ends; -K FILE: start from one and continue
 // its trial loop up to trials: / -t -- the output files are those of the uninterrupted run, byte for byte,
+// -Q FILE: after the last trial of every run, query the policy at the observations of FILE (one per line) over the clones and write
+// <output>-<run>-policy.txt: observation, mean and standard deviation (n - 1) of the value, votes per action, the majority action (objects.h),
 // -n: print the plan (one line per clone: i seed alpha gamma lambda epsilon) and exit before anything touches HIP, and
 // -g N: one process per GPU (rank r on the r-th visible device, started before anything touches HIP), every rank running -r replicas
 // (clones r * replicas ..., seeds and "@i" identities counted over the whole job), the learning curves reduced with one RCCL all-reduce
@@ -67,7 +69,7 @@ int main(int argc, char **argv)
   int gpus = 0;
   int c;
   std::vector<std::string> sweep_args;
-  while ((c = getopt(argc, argv, "vs:r:t:lqc:g:p:nk:K:")) != -1)
+  while ((c = getopt(argc, argv, "vs:r:t:lqc:g:p:nk:K:Q:")) != -1)
   {
     switch (c)
     {
@@ -83,12 +85,13 @@ int main(int argc, char **argv)
       case 'n': opt.plan_only = true; break;
       case 'k': opt.snapshot_save = optarg; break;
       case 'K': opt.snapshot_load = optarg; break;
+      case 'Q': opt.query_file = optarg; break;
       default: return 1;
     }
   }
   if (optind > argc - 1)
   {
-    log(0, std::string("Usage: \n  ") + argv[0] + " [-v] [-s seed] [-r replicas] [-g gpus] [-t trials] [-l] [-q] [-p path=v1,v2,...]... [-n] [-k snapshot] [-K snapshot] <yaml file> [yaml file...]");
+    log(0, std::string("Usage: \n  ") + argv[0] + " [-v] [-s seed] [-r replicas] [-g gpus] [-t trials] [-l] [-q] [-p path=v1,v2,...]... [-n] [-k snapshot] [-K snapshot] [-Q observations] <yaml file> [yaml file...]");
     return 1;
   }
   if (opt.seed == 0)
@@ -131,6 +134,15 @@ int main(int argc, char **argv)
     {
       if (!opt.snapshot_load.empty() && !sweep_args.empty()) throw Exception("-K together with -p: the per-replica values come from the snapshot");
       if (gpus > 1) throw Exception("-k / -K: a snapshot is one context on one GPU (-g " + std::to_string(gpus) + " is not built)");
+    }
+    catch (Exception &e) { log(0, e.what()); return 1; }
+  }
+  if (!opt.query_file.empty())
+  { // the observation file is read, and -g refused, before any process is forked or any device looked for
+    try
+    {
+      if (gpus > 1) throw Exception("-Q: a policy query runs on one GPU (-g " + std::to_string(gpus) + " is not built)");
+      read_query_file(&opt);
     }
     catch (Exception &e) { log(0, e.what()); return 1; }
   }

@@ -1063,6 +1063,8 @@ struct BatchLearningExperimentImpl : Experiment {
       throw Exception(path() + ": a parameter sweep (-p) and its plan (-n) are built for experiment/online_learning, not for experiment/batch_learning");
     if (!opt.snapshot_save.empty() || !opt.snapshot_load.empty())
       throw Exception(path() + ": a snapshot (-k / -K) is built for experiment/online_learning, not for experiment/batch_learning");
+    if (!opt.query_file.empty())
+      throw Exception(path() + ": a policy query (-Q) is built for experiment/online_learning, not for experiment/batch_learning");
     grlx_fqi_config c;
     lower(&c);
     c.n_replicas = opt.replicas;
@@ -1407,6 +1409,18 @@ struct OnlineLearningExperimentImpl : OnlineLearningExperiment, StepwiseExperime
     }
     std::vector<double> curve;
     const bool sweep = opt.sweep_repetitions > 0;
+    const bool query = !opt.query_file.empty();
+    if (query)
+    { // everything that can be refused is refused here: nothing has touched the device yet
+      if (opt.world > 1) throw Exception(path() + ": a policy query (-Q) runs on one GPU (-g " + std::to_string(opt.world) + " is not built)");
+      if (c.agent == GRLX_AGENT_AC)
+        throw Exception(path() + ": a policy query (-Q) is built for agents with a policy/discrete/q; ensemble statistics for the actor-critic are not built");
+      if ((sweep ? opt.sweep_repetitions : opt.replicas) < 2)
+        throw Exception(path() + ": -Q: -r must be >= 2: the standard deviation over the clones divides by n - 1");
+      if (opt.query_cols != c.projector.dims - 1)
+        throw Exception("-Q " + opt.query_file + ": " + std::to_string(opt.query_cols) + " columns, the agent's observation has " + std::to_string(c.projector.dims - 1));
+      if (output.empty()) throw Exception(path() + ": -Q writes <output>-<run>-policy.txt: the experiment has no output");
+    }
     if (sweep)
     {
       if (steps > 0) throw Exception(path() + ": a parameter sweep (-p) is not built together with a steps budget (steps: " + std::to_string(steps) + ")");
@@ -1679,6 +1693,32 @@ struct OnlineLearningExperimentImpl : OnlineLearningExperiment, StepwiseExperime
           ofs << line << std::endl;
         }
       }
+      if (query && opt.rank == 0)
+      { // the policy after the last trial of the run: grlx_query_ensemble over the clones (a sweep: over the repetitions of every point)
+        const int G = sweep ? opt.sweep_repetitions : opt.replicas, groups = opt.replicas / G, A = c.action_steps, cols = 2 + 2 * A;
+        std::vector<double> ens((size_t)groups * (size_t)opt.query_rows * (size_t)cols);
+        if (grlx_query_ensemble(ctx, 0, opt.replicas, G, opt.query_obs.data(), opt.query_rows, ens.data()) != GRLX_OK)
+        { std::string e = grlx_last_error(); grlx_destroy(ctx); throw Exception("-Q " + opt.query_file + ": " + e); }
+        std::ostringstream name;
+        name << output << "-" << rr << "-policy.txt";
+        std::ofstream ofs(name.str());
+        double delta = (c.action_max - c.action_min) / ((double)A - 1);     // UniformDiscretizer::configure (uniform.cpp:60-95)
+        if (std::isnan(delta)) delta = 0.;
+        for (int g = 0; g < groups; ++g)
+          for (int o = 0; o < opt.query_rows; ++o)
+          {
+            const double *e = ens.data() + ((size_t)g * (size_t)opt.query_rows + (size_t)o) * (size_t)cols;
+            const double mean = e[0] / G, var = (e[1] - e[0] * e[0] / G) / (G - 1);
+            int majority = 0;                                               // the lowest index wins a tie
+            for (int a = 1; a < A; ++a)
+              if (e[2 + A + a] > e[2 + A + majority]) majority = a;
+            if (sweep) ofs << std::setw(15) << g;
+            for (int i = 0; i < opt.query_cols; ++i) ofs << std::setw(15) << opt.query_obs[(size_t)o * (size_t)opt.query_cols + (size_t)i];
+            ofs << std::setw(15) << mean << std::setw(15) << std::sqrt(var > 0 ? var : 0.);
+            for (int a = 0; a < A; ++a) ofs << std::setw(15) << (long long)e[2 + A + a];
+            ofs << std::setw(15) << c.action_min + delta * majority << std::endl;
+          }
+      }
       if (opt.reducer && n > 0)
       { // the learning curve over the clones of ALL ranks: per row {sum, sum of squares, count} of this device's replicas (grlx_curve_stats,
         // fixed reduction order), ONE all-reduce over the ranks, mean and standard deviation on rank 0.  (Trial-bounded runs write the same
@@ -1760,4 +1800,41 @@ struct MultiExperiment : OnlineLearningExperiment {
 };
 GRLX_REGISTER(MultiExperiment)
 
+} // namespace grlx_host
+
+namespace grlx_host {
+void read_query_file(RunOptions *opt)
+{
+  std::ifstream f(opt->query_file);
+  if (!f) throw Exception("-Q: could not open the observation file '" + opt->query_file + "'");
+  std::string line;
+  int line_no = 0;
+  opt->query_obs.clear();
+  opt->query_rows = opt->query_cols = 0;
+  while (std::getline(f, line))
+  {
+    line_no++;
+    const size_t hash = line.find('#');
+    if (hash != std::string::npos) line.erase(hash);
+    std::istringstream in(line);
+    std::string tok;
+    int n = 0;
+    while (in >> tok)
+    {
+      char *stop = nullptr;
+      const double v = strtod(tok.c_str(), &stop);
+      if (*stop != 0 || !std::isfinite(v))
+        throw Exception("-Q " + opt->query_file + ": line " + std::to_string(line_no) + ": '" + tok + "' is not a finite number");
+      opt->query_obs.push_back(v);
+      n++;
+    }
+    if (n == 0) continue;
+    if (opt->query_rows > 0 && n != opt->query_cols)
+      throw Exception("-Q " + opt->query_file + ": line " + std::to_string(line_no) + " has " + std::to_string(n) + " columns, the lines before it " +
+                      std::to_string(opt->query_cols));
+    opt->query_cols = n;
+    opt->query_rows++;
+  }
+  if (opt->query_rows == 0) throw Exception("-Q " + opt->query_file + ": no observations");
+}
 } // namespace grlx_host

@@ -32,7 +32,18 @@ struct RunOptions {
   // at least kSnapshotRows test rows, so that a continuation has room for its own); `grlxd -K FILE` starts from one: the trial loop continues at
   // the snapshot's trial count up to `trials:` / -t, and the output files are written whole -- the rows are in the snapshot
   std::string snapshot_save, snapshot_load;
+  // `grlxd -Q FILE`: after the last trial of every run of an experiment/online_learning with a Q agent, the policy is queried at the
+  // observations of FILE (one per line, whitespace-separated numbers, `#` comments; read by read_query_file before any device is looked
+  // for) with grlx_query_ensemble and rank 0 writes <output>-<run>-policy.txt: per observation its coordinates, mean and standard deviation
+  // (n - 1) of QPolicy::value over the clones, the votes per action and the majority action's value (the lowest index wins a tie), in the
+  // stream format of the rows files.  With -p: one line per (point, observation), the point's index first, the groups being the repetitions.
+  std::string query_file;
+  std::vector<double> query_obs;    // [query_rows][query_cols]
+  int query_rows = 0, query_cols = 0;
 };
+// fills opt.query_obs / _rows / _cols from opt.query_file; Exception for a missing or empty file, a token that is no finite number, rows of
+// different lengths
+void read_query_file(RunOptions *opt);
 
 // Environment::step (environment.h:48-51 -> ModeledEnvironment::step, modeled.cpp:160-213) for a batch of instances:
 // state[n][S] is advanced in place; obs[n][D], reward[n], terminal[n].  Forwards to grlx_env_step (HIP kernel).

@@ -481,6 +481,108 @@ class Runner:
         delta = np.ascontiguousarray(delta, dtype=np.float64)
         capi.check(self.lib.grlx_update(self._ctx, table, _ptr(replica, C.c_int32), _ptr(idx, C.c_uint32), replica.size, _ptr(delta, C.c_double)))
 
+    # ---- policy queries: the read side of the policies at observations of the caller's choice (include/grlx.h: grlx_query_*).
+    # A query changes nothing in the context.  replicas: None = all, else a range(first, end) or a (first, count) pair.
+    def _replica_range(self, replicas):
+        if replicas is None:
+            return 0, self.cfg.n_replicas
+        if isinstance(replicas, range):
+            if replicas.step != 1:
+                raise ValueError("replicas: a contiguous range")
+            return replicas.start, len(replicas)
+        first, count = replicas
+        return int(first), int(count)
+
+    def _obs_rows(self, obs):
+        obs = np.ascontiguousarray(obs, dtype=np.float64)
+        if obs.ndim != 2 or obs.shape[1] != self.obs_dims:
+            raise ValueError(f"expected observations of shape (n, {self.obs_dims}), got {obs.shape}")
+        return obs
+
+    def query_q(self, obs, replicas=None):
+        """(q[replica][obs][action], value[replica][obs], greedy, n_max) of the Q agents: QPolicy::values, QPolicy::value under the greedy
+        sampler, and GreedySampler::findmax's first maximum and number of maxima (a tie is reported, not broken)."""
+        obs = self._obs_rows(obs)
+        first, count = self._replica_range(replicas)
+        n, na = obs.shape[0], max(int(self.cfg.action_steps), 0)
+        q = np.zeros((count, n, na), np.float64)
+        value = np.zeros((count, n), np.float64)
+        greedy = np.zeros((count, n), np.int32)
+        n_max = np.zeros((count, n), np.int32)
+        capi.check(self.lib.grlx_query_q(self._ctx, first, count, _ptr(obs, C.c_double), n, _ptr(q, C.c_double), _ptr(value, C.c_double),
+                                         _ptr(greedy, C.c_int32), _ptr(n_max, C.c_int32)))
+        return q, value, greedy, n_max
+
+    def query_state(self, obs, table, replicas=None):
+        """out[replica][obs]: the read of a table over the observation alone -- actor-critic: 0 the critic's V(s), 1 ActionPolicy::read;
+        QV: 1 = V(s)."""
+        obs = self._obs_rows(obs)
+        first, count = self._replica_range(replicas)
+        out = np.zeros((count, obs.shape[0]), np.float64)
+        capi.check(self.lib.grlx_query_state(self._ctx, int(table), first, count, _ptr(obs, C.c_double), obs.shape[0], _ptr(out, C.c_double)))
+        return out
+
+    def policy_action(self, obs, replicas=None):
+        """The greedy action [replica][obs]: the discretizer's action at `greedy` for the Q agents (the first maximum: ties are not
+        broken), the actor's read clipped to the action range for the actor-critic."""
+        if self.cfg.agent == capi.AGENT_AC:
+            return np.minimum(np.maximum(self.query_state(obs, 1, replicas), self.cfg.action_min), self.cfg.action_max)
+        greedy = self.query_q(obs, replicas)[2]
+        # UniformDiscretizer::configure (uniform.cpp:60-95), as grlx_create builds the action list
+        delta = (self.cfg.action_max - self.cfg.action_min) / (float(self.cfg.action_steps) - 1) if self.cfg.action_steps != 1 else 0.0
+        if math.isnan(delta):
+            delta = 0.0
+        actions = np.array([self.cfg.action_min + delta * k for k in range(self.cfg.action_steps)], np.float64)
+        return actions[greedy]
+
+    def query_ensemble_raw(self, obs, group_size=None, replicas=None):
+        """grlx_query_ensemble as it is: out[group][obs][2 + 2A] = {sum value, sum value^2, sum q[0..A), votes[0..A)}, every sum over the
+        group's replicas in ascending order."""
+        obs = self._obs_rows(obs)
+        first, count = self._replica_range(replicas)
+        group_size = count if group_size is None else int(group_size)
+        groups = count // group_size if group_size > 0 else 0
+        out = np.zeros((groups, obs.shape[0], 2 + 2 * int(self.cfg.action_steps)), np.float64)
+        capi.check(self.lib.grlx_query_ensemble(self._ctx, first, count, group_size, _ptr(obs, C.c_double), obs.shape[0], _ptr(out, C.c_double)))
+        return out
+
+    def query_ensemble(self, obs, group_size=None, replicas=None):
+        """Ensemble statistics per group of `group_size` consecutive replicas (default: one group of all) and observation."""
+        first, count = self._replica_range(replicas)
+        group_size = count if group_size is None else int(group_size)
+        return EnsembleResult(self.query_ensemble_raw(obs, group_size, replicas), group_size, int(self.cfg.action_steps))
+
+
+class EnsembleResult:
+    """What Runner.query_ensemble returns, each [group][obs] (mean_q and votes: [group][obs][action]): mean_value and var_value (n - 1;
+    NaN for groups of one) of QPolicy::value over the group's replicas, mean_q, votes (replicas whose greedy action is a) and majority
+    (the action with most votes, the lowest index winning a tie).  `raw` holds the sums they are formed from."""
+
+    def __init__(self, raw, group_size, n_actions):
+        n = float(group_size)
+        self.raw, self.group_size = raw, group_size
+        s, ss = raw[..., 0], raw[..., 1]
+        self.mean_value = s / n
+        with np.errstate(divide="ignore", invalid="ignore"):
+            self.var_value = (ss - s * s / n) / (n - 1.0) if group_size > 1 else np.full(s.shape, np.nan)
+        self.mean_q = raw[..., 2:2 + n_actions] / n
+        self.votes = raw[..., 2 + n_actions:2 + 2 * n_actions].astype(np.int64)
+        self.majority = np.argmax(self.votes, axis=-1)          # argmax: the first of equal counts
+
+
+def observation_grid(lo, hi, points):
+    """The cartesian grid over [lo[i], hi[i]] with points[i] values per dimension (end points included), row-major -- the last
+    dimension fastest: float64[prod(points)][len(lo)], ready for the query calls.  Pure numpy."""
+    lo, hi = np.atleast_1d(np.asarray(lo, np.float64)), np.atleast_1d(np.asarray(hi, np.float64))
+    points = np.atleast_1d(np.asarray(points, np.int64))
+    if not (lo.shape == hi.shape == points.shape) or lo.ndim != 1:
+        raise ValueError("lo, hi and points need one entry per dimension")
+    if np.any(points < 1):
+        raise ValueError("points must be >= 1")
+    axes = [np.linspace(lo[i], hi[i], int(points[i])) for i in range(lo.size)]
+    mesh = np.meshgrid(*axes, indexing="ij")
+    return np.ascontiguousarray(np.stack([m.reshape(-1) for m in mesh], axis=1))
+
 
 def pendulum_fqi_config(n_replicas=1, **overrides) -> capi.FqiConfig:
     """Config of the reference's tests/pendulum-fqi-ann.yaml (experiment/batch_learning + predictor/fqi + ANN)."""
@@ -540,6 +642,22 @@ class FqiRunner:
         capi.check(self.lib.grlx_fqi_get_transitions(self._ctx, replica, first, count, _ptr(inp, C.c_double), _ptr(nobs, C.c_double),
                                                      _ptr(rew, C.c_double), _ptr(tgt, C.c_double)))
         return inp, nobs, rew, tgt
+
+    def query(self, obs, replicas=None):
+        """q[replica][obs][action]: the batch path's Q(s, a_k) on every replica's current parameters (grlx_fqi_query); replicas: None =
+        all, else a range(first, end) or a (first, count) pair.  Changes nothing in the context."""
+        obs = np.ascontiguousarray(obs, dtype=np.float64)
+        if obs.ndim != 2 or obs.shape[1] != 2:
+            raise ValueError(f"expected observations of shape (n, 2), got {obs.shape}")
+        if replicas is None:
+            first, count = 0, self.cfg.n_replicas
+        elif isinstance(replicas, range):
+            first, count = replicas.start, len(replicas)
+        else:
+            first, count = (int(x) for x in replicas)
+        q = np.zeros((count, obs.shape[0], self.cfg.action_steps), np.float64)
+        capi.check(self.lib.grlx_fqi_query(self._ctx, first, count, _ptr(obs, C.c_double), obs.shape[0], _ptr(q, C.c_double)))
+        return q
 
     def info(self, replica: int):
         n = C.c_int64(); md = C.c_double(); it = C.c_int32(); err = C.c_double(); rng = (C.c_uint64 * 2)()

@@ -390,6 +390,47 @@ int  grlx_write(grlx_ctx *ctx, int table, const int32_t *replica, const uint32_t
 int  grlx_update(grlx_ctx *ctx, int table, const int32_t *replica, const uint32_t *idx, int n,
                  const double *delta);
 
+/* --- policy queries: what the replicas have learned at observations of the caller's choice ------------------------------------
+ * The read side of the policies (the reference's value / policy field plots and mapping/policy/<...> are built on it), for the replicas
+ * [first_replica, first_replica + n_replicas) at obs[n_obs][obs_dims]; obs_dims = the projector's input dimensions, minus the action's
+ * for the Q agents (GRLX_ENV_EXTERNAL included).  Host pointers; each call waits for the stream of the context's last grlx_run, copies
+ * in, runs HIP kernels and copies out, in chunks of observations so that no call holds more than 256 MiB of device scratch (results do
+ * not depend on the chunking).
+ * A QUERY CHANGES NOTHING: no table entry is created (grlx_read creates the entries it reads; these do not) -- a slot never touched
+ * contributes the value the reference's dense initialisation gave it, or a loaded image's (grlx_load_weights); table occupancy, random
+ * streams, traces, per-step agent state and the target network are untouched, a snapshot taken after a query holds the bytes of one
+ * taken before.  A query before the first launch is allowed and does not count as one (grlx_set_replica_params and grlx_snapshot_load
+ * stay allowed).  The MAIN parameters are read, never a target network's (q.cpp:106 reads representation_; the target's values stay
+ * behind grlx_get_target_weights).
+ * Validated on the host before anything is launched (GRLX_ERR_INVALID, nothing written): null obs, n_obs < 0, a replica range outside
+ * the context, an observation that is not finite or whose |x * scaling[i]| reaches 2^30 (TileCodingProjector casts to int,
+ * tile_coding.cpp:121-125) -- the message names row and dimension.  n_obs == 0 or n_replicas == 0: GRLX_OK, nothing written.
+ * NOT BUILT (GRLX_ERR_INVALID, "not built"): projector/tile_coding:safe >= 1 (a read would have to walk the claim table without
+ * claiming). */
+
+/* Replaces QPolicy::values (q.cpp:94-107), QPolicy::value (q.cpp:56-68) and QPolicy::act(in, out) const (q.cpp:129-141) under the
+ * greedy sampler, for agents with a policy/discrete/q (SARSA, Q, Expected SARSA, advantage, QV: its table 0); 3 or 5 actions.
+ *   q[n_replicas][n_obs][action_steps]   representation_->read(project(obs, action a)): ((w0 + w1) + ... + w15) / 16, clamped to
+ *                                        output_min / output_max (linear.cpp:136-184)
+ *   greedy, n_max [n_replicas][n_obs]    mai and man of GreedySampler::findmax (greedy.cpp:47-61): the first maximum and the number
+ *                                        of maxima.  No random draw: a tie is reported, not broken.
+ *   value[n_replicas][n_obs]             v = 0; for every action in order: v += q[a] * dist[a], dist[a] = 1. / man at the maxima and 0
+ *                                        elsewhere (q.cpp:56-68 over GreedySampler::distribution, greedy.cpp:88-98)
+ * Any output may be NULL. */
+int  grlx_query_q(grlx_ctx *ctx, int first_replica, int n_replicas, const double *obs /*[n_obs][obs_dims]*/, int n_obs,
+                  double *q, double *value, int32_t *greedy, int32_t *n_max);
+/* The read of a table whose projector takes the observation alone: out[n_replicas][n_obs].  Actor-critic: table 0 = the critic's V(s),
+ * table 1 = ActionPolicy::read (action.cpp:99-112) -- the greedy action of ActionPolicy::act(in, out) const (action.cpp:160-...) is
+ * fmin(fmax(out, action_min), action_max).  QV: table 1 = V(s) (qv.cpp:74-108).  Table 0 of a Q agent takes (observation, action):
+ * refused, use grlx_query_q. */
+int  grlx_query_state(grlx_ctx *ctx, int table, int first_replica, int n_replicas, const double *obs, int n_obs, double *out);
+/* Q agents: grlx_query_q reduced on the device per group of group_size consecutive replicas (the repetitions of one point of a sweep,
+ * as in grlx_curve_stats_grouped) and per observation to raw sums: out[n_replicas / group_size][n_obs][2 + 2 * action_steps] =
+ * { sum value, sum value * value, sum q[0 .. A), votes[0 .. A) }, votes[a] = the number of replicas whose greedy is a (as a double).
+ * Every sum runs over the group's replicas in ascending order into one accumulator (no tree): that order is the specification.
+ * n_replicas % group_size != 0 is GRLX_ERR_INVALID. */
+int  grlx_query_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, const double *obs, int n_obs, double *out);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * The per-step plug-in interfaces on the replicas of a context: one call of the reference's interface for EVERY replica per
  * call, for graphs in which only one side of the loop of OnlineLearningExperiment::run (online_learning.cpp:172-213) lives on the
@@ -480,6 +521,13 @@ int  grlx_fqi_get_transitions(grlx_fqi_ctx *ctx, int replica, int first, int cou
 /* state of a replica after the last batch: transitions stored, L-infinity target change and iteration count of the last
  * rebuild (fqi.cpp:213), mean squared error of its last epoch (ann.cpp:201), RNG streams {global, thread-local} */
 int  grlx_fqi_info(grlx_fqi_ctx *ctx, int replica, int64_t *n_transitions, double *maxdelta, int32_t *iterations, double *error, uint64_t rng[2]);
+/* The batch path's policy query (see the policy queries of the online path above): q[n_replicas][n_obs][action_steps] = Q(s, a_k) of
+ * the replicas [first_replica, first_replica + n_replicas) at obs[n_obs][2] -- the projector's normalisation (normalizing.cpp:78-87) and
+ * ANNRepresentation::read (ann.cpp:133-160) on the replica's CURRENT parameters, as QPolicy::values forms them (q.cpp:94-107).  Waits
+ * for the device; changes nothing in the context.  Validated before anything is launched: null obs, n_obs < 0, the replica range, an
+ * observation that is not finite (row and dimension named); n_obs == 0 or n_replicas == 0: GRLX_OK, nothing written.  Staged in
+ * chunks of observations like the online queries. */
+int  grlx_fqi_query(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, const double *obs /*[n_obs][2]*/, int n_obs, double *q);
 
 #ifdef __cplusplus
 }

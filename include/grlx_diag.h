@@ -53,6 +53,10 @@ int grlx_kernel_plan(const grlx_config *cfg, int simds, int flags, int *replicas
 int grlx_snapshot_timing(grlx_ctx *ctx, double *pack_ms, double *unpack_ms);
 int grlx_snapshot_naive_copy(grlx_ctx *ctx, uint64_t *bytes, double *out_ms, double *back_ms);
 
+/* Policy queries (grlx_query_q / _state / _ensemble, grlx_fqi_query): the bound on the device scratch one call holds, process-wide; 0 = the default,
+ * 256 MiB.  A chunk never has less than one observation.  For tests: a small value forces several chunks at a small shape. */
+int grlx_set_query_chunk_bytes(uint64_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,7 +42,7 @@ def kernels(lib):
                     body[name] = []
                     continue
                 ins = ln.split("//")[0].strip()
-                if name is None or not ins:
+                if name is None or not ins or ins == "...":               # "...": objdump's elision of the zero padding up to the next symbol's alignment
                     continue
                 # pc-relative addresses of other symbols move with every other kernel's size: not part of this kernel's code
                 getpc = 3 if ins.startswith("s_getpc_b64") else getpc - 1
