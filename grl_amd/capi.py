@@ -153,7 +153,8 @@ _SIGS = {
 _DIAG_SIGS = {
     "grlx_env_server_counts": (C.c_int, [C.c_void_p, _P(C.c_int), _P(C.c_int)]),
     "grlx_uniform_pass_counts": (C.c_int, [C.c_void_p, _P(C.c_ulonglong), C.c_int]),
-    "grlx_env_server_debug": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "grlx_env_server_flags": (C.c_int, [C.c_void_p, _P(C.c_int32), C.c_int]),
+    "grlx_env_server_debug": (C.c_int,[C.c_void_p, C.c_void_p, C.c_size_t]),
     "grlx_fqi_debug_stamps": (C.c_int, [C.c_void_p, _P(C.c_ulonglong), C.c_int]),
     "grlx_last_kernel_name": (C.c_char_p, [C.c_void_p]),
     "grlx_kernel_plan": (C.c_int, [_P(Config), C.c_int, C.c_int, _P(C.c_int), _P(C.c_int), _P(C.c_int), C.c_char_p, C.c_char_p, C.c_size_t]),

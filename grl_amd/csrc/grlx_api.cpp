@@ -1034,6 +1034,22 @@ int grlx_uniform_pass_counts(grlx_ctx *ctx, unsigned long long *out, int count)
   return GRLX_OK;
 }
 
+// diagnostic (not part of include/grlx.h): per replica, the word grlx_env_server_counts sums -- 1 served to the end of the last launch
+// that had the environment server, 2 fell back; zeros when no launch of this context had it
+int grlx_env_server_flags(grlx_ctx *ctx, int32_t *out, int count)
+{
+  if (!ctx || !out || count < 0) return fail(GRLX_ERR_INVALID, "bad argument");
+  const int n = count < ctx->P.n_replicas ? count : ctx->P.n_replicas;
+  for (int i = 0; i < count; ++i) out[i] = 0;
+  if (!ctx->env_mail || n == 0) return GRLX_OK;
+  DRAIN(ctx);
+  std::vector<unsigned long long> flag((size_t)n);
+  HIP_TRY(hipMemcpy2D(flag.data(), sizeof(unsigned long long), (const char *)ctx->env_mail + kEnvMailFlagOffset, ctx->env_mail_bytes,
+                      sizeof(unsigned long long), (size_t)n, hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; ++i) out[i] = (int32_t)flag[(size_t)i];
+  return GRLX_OK;
+}
+
 int grlx_run(grlx_ctx *ctx, int n_trials, void *stream) { return run_trials(ctx, n_trials, 0, stream); }
 
 // The trial loop of OnlineLearningExperiment::run with both of its bounds (online_learning.cpp:154):

@@ -265,11 +265,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(48))) void env_s
   unsigned long long t_begin = mail_clock(), t_busy = 0, n_cmd = 0, n_idle = 0, n_split = 0, n_batch = 0;
 #endif
   // (tests: bits 8-23 of env_tune = the server leaves, unannounced, once it has answered that many commands of a replica -- a fetch in
-  //  MID-episode then runs into its bound and the rollout wave goes on by itself from there)
+  //  MID-episode then runs into its bound and the rollout wave goes on by itself from there.  Bits 24-31 = which replicas of the block it
+  //  leaves: bit 24 + q stands for replica q (here q < 4: bits 24-27), 0 = all of them; the others are served to the end of the launch,
+  //  so that ONE 16-lane group of a rollout wave falls back while its neighbours stay served.  A bit that names a dead slot of a ragged
+  //  wave changes nothing: that slot is `done` from the start.)
   const unsigned long long quit_after = (P.env_tune >> 8) & 0xFFFFu;
+  const unsigned quit_mask = P.env_tune >> 24;
+  const bool leaves = quit_after != 0u && (quit_mask == 0u || ((quit_mask >> q) & 1u) != 0u);
   for (;;)
   {
-    if (quit_after != 0u && expect > quit_after) done = true;
+    if (leaves && expect > quit_after) done = true;
     if (__all(done)) break;
     unsigned long long word = 0;
     bool ready = false;

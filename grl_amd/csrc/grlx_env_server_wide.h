@@ -159,10 +159,15 @@ __device__ __forceinline__ void env_server_wide_body(const DevParams &P)
   unsigned idle = 0;
   bool seen = false;
   mail_setprio((P.env_tune >> 2) & 3u);
-  const unsigned long long quit_after = (P.env_tune >> 8) & 0xFFFFu;      // (tests: the server leaves, unannounced, after that many passes)
+  // (tests: bits 8-23 of env_tune = the server leaves, unannounced, after that many passes; bits 24-31 = which replicas of the block it
+  //  leaves, bit 24 + q for replica q, 0 = all of them: the others are served to the end of the launch, a left replica counts as `done`
+  //  in every later pass of the block.  A bit that names a dead slot of a ragged wave changes nothing.)
+  const unsigned long long quit_after = (P.env_tune >> 8) & 0xFFFFu;
+  const unsigned quit_mask = P.env_tune >> 24;
+  const bool leaves = quit_after != 0u && (quit_mask == 0u || ((quit_mask >> q) & 1u) != 0u);
   for (;;)
   {
-    if (quit_after != 0u && expect > quit_after) done = true;
+    if (leaves && expect > quit_after) done = true;
     if (__all(done)) break;
     unsigned long long word = 0;
     bool ready = false;

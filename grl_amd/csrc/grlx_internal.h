@@ -137,7 +137,10 @@ struct DevParams {
   // (ReplicaState::ss) have reached this budget; 0 = none.  Honoured by rollout_kernel, rollout_wide_kernel and the actor-critic kernels.
   uint64_t steps_budget;
   uint32_t env_tune;            // experiments (GRLX_ENV_SERVER_TUNE): bits 0-1 s_setprio of the rollout wave, 2-3 of the server wave, 4 no prefetch;
-                                // tests: bit 6 the server leaves at once (every replica falls back to integrating itself)
+                                // tests: bit 6 the server leaves at once (every replica falls back to integrating itself); bits 8-23 the
+                                // server leaves, unannounced, once it has answered that many commands of a replica (0 = never); bits 24-31
+                                // which replicas of a server block it leaves then, bit 24 + q for replica q of the block (q = lane >> 4 in
+                                // env_server_kernel: bits 24-27; q = lane & 7 in the wide servers), 0 = all of them
   void    *park;                // 32-replica waves of the compass walker: lane state of the sub-batches beyond the third, 5 x kAcParkBytes per wave
   struct EnvMail *env_mail;     // mailboxes of the environment server ([replica], grlx_env_server.h); null = the rollout kernel integrates itself
   int32_t  test_trials;         // experiment/online_learning:test_trials (>= 1): greedy episodes per test trial, averaged in the row

@@ -246,6 +246,13 @@ class Runner:
         capi.check(self.lib.grlx_uniform_pass_counts(self._ctx, _ptr(out, C.c_ulonglong), out.size))
         return out
 
+    def env_server_flags(self):
+        """Per replica, what env_server_counts sums: 1 served by the environment server to the end of the last launch that had it, 2 fell
+        back to integrating itself (zeros when no launch had it) -- diagnostic export, not part of include/grlx.h"""
+        out = np.zeros(self.cfg.n_replicas, dtype=np.int32)
+        capi.check(self.lib.grlx_env_server_flags(self._ctx, _ptr(out, C.c_int32), out.size))
+        return out
+
     def replicas_per_wave(self) -> int:
         """4: one replica per 16 lanes; 8: two sub-batches per wave sharing the environment phase (wide kernels); 12 / 16: three / four
         sub-batches (actor-critic only; 12 rotates the wave's own replicas through its slots trial by trial)."""

@@ -19,6 +19,10 @@ int grlx_env_server_counts(grlx_ctx *ctx, int *served, int *fell_back);
  * same number; a ragged wave, a wave without the server and the wide kernels report 0); the rest of out, and all of it when no launch of
  * this context had the server, is 0. */
 int grlx_uniform_pass_counts(grlx_ctx *ctx, unsigned long long *out, int count);
+/* Which replicas grlx_env_server_counts counted: out[r], r < min(count, replicas), = 1 when replica r was served to the end of the last
+ * launch of the context that had the environment server, 2 when it fell back to integrating itself; the rest of out, and all of it when
+ * no launch of this context had the server, is 0. */
+int grlx_env_server_flags(grlx_ctx *ctx, int32_t *out, int count);
 /* The raw mailboxes of the environment server after the last launch (1 KB per replica; GRLX_ENV_SERVER_STATS builds leave cycle counts
  * in them): at most `bytes` bytes to `out`. */
 int grlx_env_server_debug(grlx_ctx *ctx, void *out, size_t bytes);

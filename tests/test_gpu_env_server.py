@@ -1,7 +1,10 @@
 """The environment server of the pendulum rollout kernels (grl_amd/csrc/grlx_env_server.h): the integration of the next step moves to a
 second kernel that shares the SIMDs with the rollout waves.  Same operations on the same arguments, so every result must be the one of
 the kernel that integrates itself (GRLX_ENV_SERVER=0) -- and the one of the oracle, which the rest of the GPU suite checks with the server on
-by default.  Also: a server that is not there (every replica gives up waiting and integrates itself), ragged waves, chunked launches."""
+by default.  Also: a server that is not there (every replica gives up waiting and integrates itself), ragged waves, chunked launches.
+The wide servers (acrobot, compass walker) follow, and at the end the MIXED wide wave: GRLX_ENV_SERVER_TUNE bits 24-31 make the server
+leave only some replicas of a block, so that the per-replica fallback of wide_mail_take runs beside served neighbours; those cases hold
+the run to the one without the server (and to the oracle) and the per-replica flags (Runner.env_server_flags) to the mask, exactly."""
 import numpy as np
 import pytest
 
@@ -196,7 +199,8 @@ def _wide_snapshot(grlx, env, seeds, chunks, budget=0, **over):
     r.sync()
     rng = np.random.default_rng(5)
     slots = rng.integers(0, cfg.projector.memory, 3000).astype(np.uint32)
-    out = {"counts": r.env_server_counts(), "kernel": r.last_kernel(), "rpw": r.replicas_per_wave(), "rows": [], "state": [], "rng": [], "w": [], "load": []}
+    out = {"counts": r.env_server_counts(), "flags": [int(f) for f in r.env_server_flags()], "kernel": r.last_kernel(), "rpw": r.replicas_per_wave(),
+           "rows": [], "state": [], "rng": [], "w": [], "load": []}
     for k in range(len(seeds)):
         t, s, rew = r.rows(k)
         out["rows"].append((list(t), list(s), np.asarray(rew, dtype=np.float64).view(np.uint64).tolist(),
@@ -353,3 +357,85 @@ def test_a_wide_server_that_leaves_in_mid_episode(grlx, monkeypatch, env, quit_a
     on = _wide_snapshot(grlx, env, seeds, chunks)
     assert on["counts"][1] > 0, on["counts"]      # (a replica whose last launch had fewer passes than that was served to its end)
     _same_wide(on, off)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# A mixed wide wave: GRLX_ENV_SERVER_TUNE bits 24-31 restrict the "server leaves" hook of bits 8-23 to some replicas of every server
+# block (bit 24 + q: replica q = lane & 7 of the block), the others are served to the end of the launch.  On the rollout side this is the
+# per-replica `ok = (bad & mine) == 0` of wide_mail_take and the `sh_srv[eq] = 0` that follows (grlx_rollout_wide.h): the left replicas
+# integrate in the wave's own environment phase, under a partial exec mask, beside neighbours that keep fetching their candidates.
+
+_WIDE_LAUNCHES = [11, 11]     # trial indices 10 and 21 are test trials: two rows, the second launch holds the learning trials 11 .. 20
+_wide_off, _wide_oracle = {}, {}
+
+
+def _wide_off_run(grlx, monkeypatch, env, n):
+    """the run without the server, once per (environment, replicas)"""
+    if (env, n) not in _wide_off:
+        monkeypatch.setenv("GRLX_ENV_SERVER", "0")
+        _wide_off[(env, n)] = _wide_snapshot(grlx, env, np.arange(3, 3 + n), _WIDE_LAUNCHES)
+        monkeypatch.delenv("GRLX_ENV_SERVER")
+        assert _wide_off[(env, n)]["counts"] == (0, 0) and _wide_off[(env, n)]["flags"] == [0] * n
+    return _wide_off[(env, n)]
+
+
+def _wide_oracle_run(env, seed):
+    """the oracle's run of one replica, once per (environment, seed): steps and returns of the rows, streams, state"""
+    from tests import configs
+    if (env, seed) not in _wide_oracle:
+        spec = (configs.acrobot if env == "acrobot" else configs.compass_walker)(None, 1)[1]
+        e = ob.Experiment(spec, seed=int(seed))
+        rows, _ = e.run(sum(_WIDE_LAUNCHES))
+        _wide_oracle[(env, seed)] = ([x.steps for x in rows], np.asarray([x.reward for x in rows]).view(np.uint64).tolist(), list(e.rng())[:3],
+                                     np.asarray(e.state()).view(np.uint64).tolist())
+        e.close()
+    return _wide_oracle[(env, seed)]
+
+
+@pytest.mark.parametrize("env,quit_after,n,mask", [("acrobot", 45, 8, 0x01), ("acrobot", 45, 8, 0x80), ("acrobot", 45, 8, 0x5A), ("acrobot", 45, 13, 0x90),
+                                                   ("walker", 29, 8, 0x24), ("walker", 29, 13, 0x24)])
+def test_some_replicas_of_a_wide_wave_lose_their_server(grlx, monkeypatch, env, quit_after, n, mask):
+    """One full wave (8) and a full wave beside a ragged one (13 = 8 + 5: 0x90 names replicas 4 and 7 of the first wave, replica 12 of the
+    second and a dead slot of it; 0x24 names 2 and 5, 10 and a dead slot).  Episodes end at steps of their own, so steps, resets and skips
+    of served replicas share a server pass with replicas the server has left.  Same bits as with the server off, for 8 replicas also as
+    the oracle.  The flags are exact: a replica takes the answer of server pass p - 2 in pass p, so one that still takes a step after pass
+    quit_after + 2 of its last launch must fall back, and steps are a lower bound on passes -- the precondition is read from the run
+    WITHOUT the server (the learning steps between its two rows: trials 11 .. 20, all in the last launch) and asserted."""
+    seeds = np.arange(3, 3 + n)
+    off = _wide_off_run(grlx, monkeypatch, env, n)
+    for k in range(n):
+        t, s = off["rows"][k][0], off["rows"][k][1]
+        assert len(s) == 2 and s[1] - s[0] > quit_after + 2, f"replica {k}: rows at trials {t}, learning steps {s}: too few steps in the last launch for this case"
+    monkeypatch.setenv("GRLX_ENV_SERVER_TUNE", str((mask << 24) | (quit_after << 8)))
+    on = _wide_snapshot(grlx, env, seeds, _WIDE_LAUNCHES)
+    what = f"{env}, {n} replicas, mask {mask:#04x}, quit_after {quit_after}: server {on['counts']}, flags {on['flags']}"
+    print(what)
+    assert on["kernel"] == 2 and on["rpw"] == 8 and on["counts"][0] > 0, what
+    _same_wide(on, off)
+    assert on["flags"] == [2 if (mask >> (k % 8)) & 1 else 1 for k in range(n)], what
+    if n == 8:
+        for k in range(n):
+            steps, rew, rng, state = _wide_oracle_run(env, seeds[k])
+            assert on["rows"][k][1] == steps and on["rows"][k][2] == rew, f"{what}: replica {k}: rows against the oracle"
+            assert on["rng"][k][:3] == rng and on["state"][k] == state, f"{what}: replica {k}: streams and state against the oracle"
+
+
+def test_env_server_flags(grlx):
+    """Runner.env_server_flags: zeros before any served launch, afterwards per replica what env_server_counts sums; replicas beyond the
+    context read 0."""
+    import ctypes as C
+    n = 5
+    cfg = grlx.pendulum_sarsa_config(n, max_rows=4)
+    r = grlx.Runner(cfg, np.arange(1, n + 1))
+    assert list(r.env_server_flags()) == [0] * n and r.env_server_counts() == (0, 0)
+    r.run(2); r.sync()
+    flags = [int(f) for f in r.env_server_flags()]
+    served, fell_back = r.env_server_counts()
+    assert served > 0 and (flags.count(1), flags.count(2)) == (served, fell_back) and served + fell_back == n, (flags, served, fell_back)
+    out = np.full(n + 3, -1, dtype=np.int32)
+    assert r.lib.grlx_env_server_flags(r._ctx, out.ctypes.data_as(C.POINTER(C.c_int32)), out.size) == 0
+    assert out.tolist() == flags + [0] * 3
+    out[:] = -1
+    assert r.lib.grlx_env_server_flags(r._ctx, out.ctypes.data_as(C.POINTER(C.c_int32)), 2) == 0
+    assert out.tolist() == flags[:2] + [-1] * (n + 1)             # no more than `count` words are written
+    r.close()
