@@ -1,0 +1,27 @@
+// grlx_evaluate.h -- greedy evaluation episodes (grlx_evaluate): what grlx_api.cpp hands to the kernels of grlx_evaluate.hip.
+// Included by those two only: no rollout kernel sees it, the kernels have no row in the kernel table and DevParams does not grow.
+#pragma once
+#include "grlx_internal.h"
+
+namespace grlx {
+
+// One chunk of start states for a range of replicas; every pointer is a device pointer.  A pair is (replica, start state) with the
+// index (replica - first_replica) * n_starts + start: the layout of every per-pair array.
+struct EvaluateArgs {
+  int32_t            first_replica, n_replicas;
+  int32_t            n_starts;      // start states of this chunk
+  int32_t            max_steps;     // 1 ... GRLX_MAX_EPISODE_STEPS: no episode runs further, whatever its state says
+  const double      *states;        // [n_starts][model state dimensions]
+  const SweepParams *sweep;         // [replica of the context]: the replica's own gamma; null = DevParams::gamma
+  double            *ret, *disc;    // [pair]
+  int32_t           *steps, *terminal, *ties;   // [pair]
+  double            *final_state;   // [pair][model state dimensions]
+};
+
+// terminal code of an episode that left the portable math's domain (Env::in_domain at a step end); 0 / 1 / 2 are the task's
+constexpr int kEvaluateDomain = 3;
+
+bool evaluate_built(int agent, int env, int actions);      // is there an instantiation for this context?
+hipError_t launch_evaluate(const DevParams &P, const EvaluateArgs &A, hipStream_t stream);
+
+} // namespace grlx

@@ -1,0 +1,253 @@
+// grlx_evaluate.hip -- greedy evaluation episodes (grlx_evaluate): for every (replica, start state) pair one episode of the test agent
+// (agent/fixed over the learned tables) from a model state of the caller's choice to its end, in one launch.  Reference: the test
+// branch of OnlineLearningExperiment::run (online_learning.cpp:172-213) for one episode with the caller's state in place of Task::start;
+// QPolicy::act const under GreedySampler::findmax (q.cpp:129-141, greedy.cpp:47-61), ActionPolicy::act(in, out) const (action.cpp).
+//
+// An evaluation writes to nothing but its own output arrays.  Every step is the body of query_q_kernel / query_state_kernel
+// (grlx_query.hip: peek-only probes through query_weights, slots without an entry contribute initial_weight(); no entry is created, no
+// counter, stream, trace, key bit or sticky status is touched) followed by the environment step of the rollout kernels
+// (env_step<ENV, false, NoShare>, grlx_envs.h).
+//
+// Layout: the queries'.  A 16-lane group serves one (replica, start state) pair, lane = tiling, four pairs per wave, four waves per block
+// (no wave waits for another: every LDS region belongs to one wave).  Pair = replica * n_starts + start, so the groups of a wave mostly
+// probe one replica's table and mostly run episodes of similar length.  All 16 lanes of a group integrate the same state redundantly: the
+// bits are identical in every lane and the environment needs no cross-lane traffic.
+//
+// The episode loop is wave-uniform: it runs while a ballot finds an active group and the step counter is below max_steps -- the bound
+// that keeps a caller-made state from becoming a hang.  Finished and dead groups skip loads, LDS stores, the environment step and the
+// sums under a predicate; every lane reaches every wave_sync.  Lane 0 of a group writes the pair's outputs once, after the loop.
+//
+// LDS: the weight tile of grlx_query.hip (rows kRowStride = 66 doubles apart, see the bank argument there), the group's Q-values, and
+// two words per group by which lane 0 hands findmax's result (the actor-critic: the action) back to the 16 lanes.
+//
+// Compiled with -ffp-contract=off like every unit: g * reward is a plain product, the sums plain additions.
+#include "grlx_internal.h"
+#include "grlx_math.h"
+#include "grlx_rng.h"
+#include "grlx_tile.h"
+#include "grlx_table.h"
+#include "grlx_envs.h"
+#include "grlx_query_weights.h"
+#include "grlx_evaluate.h"
+
+namespace grlx {
+
+// what a group carries through the loop besides the model state
+struct EpisodeSums {
+  double ret, disc, g;
+  int steps, code, ties;
+};
+
+// one step's bookkeeping (online_learning.cpp:202; disc += g * reward; g = g * gamma); returns whether the episode goes on
+__device__ __forceinline__ bool episode_account(EpisodeSums &e, double reward, double gamma, int terminal, uint32_t status, bool tie)
+{
+  e.ret += reward;
+  e.disc += e.g * reward;
+  e.g = e.g * gamma;
+  e.steps++;
+  e.ties += tie ? 1 : 0;
+  e.code = (status & ST_DOMAIN) ? kEvaluateDomain : terminal;
+  return e.code == 0;
+}
+
+template <int S>
+__device__ __forceinline__ void episode_store(const EvaluateArgs &A, long long pair, const EpisodeSums &e, const double (&x)[S])
+{
+  A.ret[pair] = e.ret;
+  A.disc[pair] = e.disc;
+  A.steps[pair] = e.steps;
+  A.terminal[pair] = e.code;
+  A.ties[pair] = e.ties;
+#pragma unroll
+  for (int i = 0; i < S; ++i) A.final_state[(size_t)pair * S + i] = x[i];
+}
+
+// Q agents: actions[first maximum of Q(obs, .)] at every step
+template <int ENV, int NA>
+__global__ __launch_bounds__(kQueryWaves * 64) void evaluate_q_kernel(DevParams P, EvaluateArgs A)
+{
+  constexpr int T = kLanesPerReplica, S = Env<ENV>::S, D = Env<ENV>::D;
+  __shared__ double sh_w[kQueryWaves][NA * kRowStride];
+  __shared__ double sh_q[kQueryWaves][4 * 8];
+  __shared__ int32_t sh_a[kQueryWaves][4 * 2];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, j = lane & 15;
+  const long long n_pairs = (long long)A.n_replicas * A.n_starts;
+  const long long pair = ((long long)blockIdx.x * kQueryWaves + wave) * 4 + g;
+  const bool live = pair < n_pairs;                    // dead groups of the last wave neither load nor store
+  double *W = sh_w[wave], *Q = sh_q[wave];
+  int32_t *M = sh_a[wave];
+
+  const int rl = live ? (int)(pair / A.n_starts) : 0, s = live ? (int)(pair - (long long)rl * A.n_starts) : 0;
+  const int r = A.first_replica + rl;
+  const Table tab = table_of(P, 0, r);
+  const ReplicaState &rs = P.states[r];
+  const double gamma = A.sweep ? A.sweep[r].gamma : P.gamma;
+  double x[S], obs[D];
+#pragma unroll
+  for (int i = 0; i < S; ++i) x[i] = live ? A.states[(size_t)s * S + i] : 0.;
+  (void)Env<ENV>::observe(P, x, obs);                  // the start state's terminal code is ignored, as Environment::start has none
+
+  EpisodeSums e;
+  e.ret = 0; e.disc = 0; e.g = 1; e.steps = 0; e.code = 0; e.ties = 0;
+  bool active = live;
+  for (int step = 0; step < A.max_steps; ++step)
+  {
+    if (__ballot(active) == 0ull) break;               // wave-uniform
+    if (active)
+    { // project(obs, a_k), k < NA: the hash of the observation once, then the action's coordinate and the tiling (tile_coding.cpp:103-149)
+      uint32_t hpre = 449u ^ (uint32_t)(D + 2);
+#pragma unroll
+      for (int i = 0; i < D; ++i)
+        hpre = murmur_mix(hpre, tile_coord<T>(P.tile, i, tile_quant(P.tile, i, obs[i]), j));
+      uint32_t slot[NA];
+#pragma unroll
+      for (int a = 0; a < NA; ++a)
+      {
+        uint32_t h = murmur_mix(hpre, tile_coord<T>(P.tile, D, tile_quant(P.tile, D, P.actions[a]), j));
+        h = murmur_mix(h, j);
+        slot[a] = murmur_final(h) % (uint32_t)P.tile.memory;
+      }
+      double w[NA];
+      query_weights<NA>(tab, rs, 0, P.lin, slot, w);
+#pragma unroll
+      for (int a = 0; a < NA; ++a) W[a * kRowStride + lane] = w[a];
+    }
+    wave_sync();
+    if (active && j < NA)
+    { // LinearRepresentation::read (linear.cpp:136-184): serial sum over the 16 tilings, mean, clamp
+      double sum = 0;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) sum += W[j * kRowStride + g * 16 + k];
+      sum /= 16;
+      Q[g * 8 + j] = query_clamp(sum, P.lin.out_min, P.lin.out_max);
+    }
+    wave_sync();
+    if (active && j == 0)
+    { // greedy.cpp:47-61
+      int mai = 0, man = 1;
+      double best = Q[g * 8];
+#pragma unroll
+      for (int a = 1; a < NA; ++a)
+      {
+        const double q = Q[g * 8 + a];
+        if (q > best) { best = q; mai = a; man = 1; }
+        else if (q == best) man++;
+      }
+      M[g * 2] = mai;
+      M[g * 2 + 1] = man;
+    }
+    wave_sync();
+    if (active)
+    {
+      const int mai = M[g * 2], man = M[g * 2 + 1];
+      double action = P.actions[0];                    // selects, not an indexed read of the parameter block: no scratch copy of it
+#pragma unroll
+      for (int a = 1; a < NA; ++a) action = (mai == a) ? P.actions[a] : action;
+      double reward = 0;
+      int terminal = 0;
+      uint32_t status = 0;
+      env_step<ENV, false, NoShare>(P, x, action, obs, reward, terminal, status);
+      active = episode_account(e, reward, gamma, terminal, status, man > 1);
+    }
+  }
+  if (live && j == 0) episode_store<S>(A, pair, e, x);
+}
+
+// actor-critic: the noise-free actor, fmin(fmax(read(actor table, obs), action_min), action_max) (ActionPolicy::act(in, out) const)
+template <int ENV>
+__global__ __launch_bounds__(kQueryWaves * 64) void evaluate_ac_kernel(DevParams P, EvaluateArgs A)
+{
+  constexpr int S = Env<ENV>::S, D = Env<ENV>::D;
+  __shared__ double sh_w[kQueryWaves][64];
+  __shared__ double sh_act[kQueryWaves][4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, j = lane & 15;
+  const long long n_pairs = (long long)A.n_replicas * A.n_starts;
+  const long long pair = ((long long)blockIdx.x * kQueryWaves + wave) * 4 + g;
+  const bool live = pair < n_pairs;
+  double *W = sh_w[wave], *ACT = sh_act[wave];
+
+  const int rl = live ? (int)(pair / A.n_starts) : 0, s = live ? (int)(pair - (long long)rl * A.n_starts) : 0;
+  const int r = A.first_replica + rl;
+  const Table tab = table_of(P, 1, r);                 // twin tables: each holds its own keys
+  const ReplicaState &rs = P.states[r];
+  const double gamma = A.sweep ? A.sweep[r].gamma : P.gamma;
+  double x[S], obs[D];
+#pragma unroll
+  for (int i = 0; i < S; ++i) x[i] = live ? A.states[(size_t)s * S + i] : 0.;
+  (void)Env<ENV>::observe(P, x, obs);
+
+  EpisodeSums e;
+  e.ret = 0; e.disc = 0; e.g = 1; e.steps = 0; e.code = 0; e.ties = 0;
+  bool active = live;
+  for (int step = 0; step < A.max_steps; ++step)
+  {
+    if (__ballot(active) == 0ull) break;
+    if (active)
+    {
+      // project(obs) of the actor's projector (tile_coding.cpp:103-149), unrolled over the observation: tile_slot_generic's loop
+      // indexes obs by a run-time counter, which puts obs into scratch
+      uint32_t h = 449u ^ (uint32_t)(D + 1);
+#pragma unroll
+      for (int i = 0; i < D; ++i)
+        h = murmur_mix(h, tile_coord<kLanesPerReplica>(P.tile_actor, i, tile_quant(P.tile_actor, i, obs[i]), j));
+      h = murmur_mix(h, j);
+      uint32_t slot[1] = {murmur_final(h) % (uint32_t)P.tile_actor.memory};
+      double w[1];
+      query_weights<1>(tab, rs, 1, P.lin_actor, slot, w);
+      W[lane] = w[0];
+    }
+    wave_sync();
+    if (active && j == 0)
+    { // ActionPolicy::read (action.cpp:99-112) over LinearRepresentation::read, then the clip of act
+      double sum = 0;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) sum += W[g * 16 + k];
+      sum /= 16;
+      sum = query_clamp(sum, P.lin_actor.out_min, P.lin_actor.out_max);
+      ACT[g] = query_clamp(sum, P.action_min, P.action_max);
+    }
+    wave_sync();
+    if (active)
+    {
+      const double action = ACT[g];
+      double reward = 0;
+      int terminal = 0;
+      uint32_t status = 0;
+      env_step<ENV, false, NoShare>(P, x, action, obs, reward, terminal, status);
+      active = episode_account(e, reward, gamma, terminal, status, false);
+    }
+  }
+  if (live && j == 0) episode_store<S>(A, pair, e, x);
+}
+
+// The instantiations: the (environment, action count) pairs grlx_create admits for the Q agents, and the actor-critic's two environments
+bool evaluate_built(int agent, int env, int actions)
+{
+  if (agent == GRLX_AGENT_AC) return env == GRLX_ENV_CART_POLE || env == GRLX_ENV_PENDULUM;
+  if (env == GRLX_ENV_PENDULUM) return actions == 3 || actions == 5;
+  return (env == GRLX_ENV_ACROBOT || env == GRLX_ENV_CART_POLE || env == GRLX_ENV_COMPASS_WALKER) && actions == 3;
+}
+
+hipError_t launch_evaluate(const DevParams &P, const EvaluateArgs &A, hipStream_t stream)
+{
+  const long long pairs = (long long)A.n_replicas * A.n_starts;
+  const unsigned blocks = (unsigned)((pairs + 4 * kQueryWaves - 1) / (4 * kQueryWaves));
+  if (blocks == 0) return hipSuccess;
+  if (!evaluate_built(P.agent, P.env, P.A) || A.max_steps < 1) return hipErrorInvalidValue;
+  const dim3 grid(blocks), block(kQueryWaves * 64);
+  if (P.agent == GRLX_AGENT_AC)
+  {
+    if (P.env == GRLX_ENV_CART_POLE) hipLaunchKernelGGL(evaluate_ac_kernel<GRLX_ENV_CART_POLE>, grid, block, 0, stream, P, A);
+    else hipLaunchKernelGGL(evaluate_ac_kernel<GRLX_ENV_PENDULUM>, grid, block, 0, stream, P, A);
+  }
+  else if (P.env == GRLX_ENV_PENDULUM && P.A == 3) hipLaunchKernelGGL((evaluate_q_kernel<GRLX_ENV_PENDULUM, 3>), grid, block, 0, stream, P, A);
+  else if (P.env == GRLX_ENV_PENDULUM) hipLaunchKernelGGL((evaluate_q_kernel<GRLX_ENV_PENDULUM, 5>), grid, block, 0, stream, P, A);
+  else if (P.env == GRLX_ENV_ACROBOT) hipLaunchKernelGGL((evaluate_q_kernel<GRLX_ENV_ACROBOT, 3>), grid, block, 0, stream, P, A);
+  else if (P.env == GRLX_ENV_CART_POLE) hipLaunchKernelGGL((evaluate_q_kernel<GRLX_ENV_CART_POLE, 3>), grid, block, 0, stream, P, A);
+  else hipLaunchKernelGGL((evaluate_q_kernel<GRLX_ENV_COMPASS_WALKER, 3>), grid, block, 0, stream, P, A);
+  return hipGetLastError();
+}
+
+} // namespace grlx

@@ -8,6 +8,9 @@
 // its trial loop up to trials: / -t -- the output files are those of the uninterrupted run, byte for byte,
 // -Q FILE: after the last trial of every run, query the policy at the observations of FILE (one per line) over the clones and write
 // <output>-<run>-policy.txt: observation, mean and standard deviation (n - 1) of the value, votes per action, the majority action (objects.h),
+// -E FILE: after the last trial of every run, one greedy episode per (clone, start state) from the model states of FILE (one per line) with
+// grlx_evaluate, and <output>-<run>-returns.txt: mean and standard deviation (n - 1) of the return, mean steps, the count of every terminal
+// code and the summed ties over the clones (objects.h),
 // -n: print the plan (one line per clone: i seed alpha gamma lambda epsilon) and exit before anything touches HIP, and
 // -g N: one process per GPU (rank r on the r-th visible device, started before anything touches HIP), every rank running -r replicas
 // (clones r * replicas ..., seeds and "@i" identities counted over the whole job), the learning curves reduced with one RCCL all-reduce
@@ -69,7 +72,7 @@ int main(int argc, char **argv)
   int gpus = 0;
   int c;
   std::vector<std::string> sweep_args;
-  while ((c = getopt(argc, argv, "vs:r:t:lqc:g:p:nk:K:Q:")) != -1)
+  while ((c = getopt(argc, argv, "vs:r:t:lqc:g:p:nk:K:Q:E:")) != -1)
   {
     switch (c)
     {
@@ -86,12 +89,13 @@ int main(int argc, char **argv)
       case 'k': opt.snapshot_save = optarg; break;
       case 'K': opt.snapshot_load = optarg; break;
       case 'Q': opt.query_file = optarg; break;
+      case 'E': opt.evaluate_file = optarg; break;
       default: return 1;
     }
   }
   if (optind > argc - 1)
   {
-    log(0, std::string("Usage: \n  ") + argv[0] + " [-v] [-s seed] [-r replicas] [-g gpus] [-t trials] [-l] [-q] [-p path=v1,v2,...]... [-n] [-k snapshot] [-K snapshot] [-Q observations] <yaml file> [yaml file...]");
+    log(0, std::string("Usage: \n  ") + argv[0] + " [-v] [-s seed] [-r replicas] [-g gpus] [-t trials] [-l] [-q] [-p path=v1,v2,...]... [-n] [-k snapshot] [-K snapshot] [-Q observations] [-E states] <yaml file> [yaml file...]");
     return 1;
   }
   if (opt.seed == 0)
@@ -143,6 +147,17 @@ int main(int argc, char **argv)
     {
       if (gpus > 1) throw Exception("-Q: a policy query runs on one GPU (-g " + std::to_string(gpus) + " is not built)");
       read_query_file(&opt);
+    }
+    catch (Exception &e) { log(0, e.what()); return 1; }
+  }
+  if (!opt.evaluate_file.empty())
+  { // likewise: the state file is read, and -g and -r 1 refused, before any process is forked or any device looked for
+    try
+    {
+      if (gpus > 1) throw Exception("-E: a policy evaluation runs on one GPU (-g " + std::to_string(gpus) + " is not built)");
+      if ((sweep_args.empty() ? opt.replicas : opt.sweep_repetitions) < 2)
+        throw Exception("-E: -r must be >= 2: the standard deviation over the clones divides by n - 1");
+      read_evaluate_file(&opt);
     }
     catch (Exception &e) { log(0, e.what()); return 1; }
   }

@@ -1065,6 +1065,8 @@ struct BatchLearningExperimentImpl : Experiment {
       throw Exception(path() + ": a snapshot (-k / -K) is built for experiment/online_learning, not for experiment/batch_learning");
     if (!opt.query_file.empty())
       throw Exception(path() + ": a policy query (-Q) is built for experiment/online_learning, not for experiment/batch_learning");
+    if (!opt.evaluate_file.empty())
+      throw Exception(path() + ": a policy evaluation (-E) is built for experiment/online_learning, not for experiment/batch_learning");
     grlx_fqi_config c;
     lower(&c);
     c.n_replicas = opt.replicas;
@@ -1421,6 +1423,19 @@ struct OnlineLearningExperimentImpl : OnlineLearningExperiment, StepwiseExperime
         throw Exception("-Q " + opt.query_file + ": " + std::to_string(opt.query_cols) + " columns, the agent's observation has " + std::to_string(c.projector.dims - 1));
       if (output.empty()) throw Exception(path() + ": -Q writes <output>-<run>-policy.txt: the experiment has no output");
     }
+    const bool evaluate = !opt.evaluate_file.empty();
+    if (evaluate)
+    { // ... and so is everything about -E (grlx_evaluate validates the states themselves, and what it is built for, before it launches)
+      if (opt.world > 1) throw Exception(path() + ": a policy evaluation (-E) runs on one GPU (-g " + std::to_string(opt.world) + " is not built)");
+      if ((sweep ? opt.sweep_repetitions : opt.replicas) < 2)
+        throw Exception(path() + ": -E: -r must be >= 2: the standard deviation over the clones divides by n - 1");
+      int state_dims = 0;
+      if (grlx_env_dims(c.env, &state_dims, nullptr) != GRLX_OK) throw Exception(path() + ": -E: " + grlx_last_error());
+      if (opt.evaluate_cols != state_dims)
+        throw Exception("-E " + opt.evaluate_file + ": " + std::to_string(opt.evaluate_cols) + " columns, the model's state has " + std::to_string(state_dims) +
+                        " (the time included)");
+      if (output.empty()) throw Exception(path() + ": -E writes <output>-<run>-returns.txt: the experiment has no output");
+    }
     if (sweep)
     {
       if (steps > 0) throw Exception(path() + ": a parameter sweep (-p) is not built together with a steps budget (steps: " + std::to_string(steps) + ")");
@@ -1719,6 +1734,44 @@ struct OnlineLearningExperimentImpl : OnlineLearningExperiment, StepwiseExperime
             ofs << std::setw(15) << c.action_min + delta * majority << std::endl;
           }
       }
+      if (evaluate && opt.rank == 0)
+      { // greedy episodes from the start states of the file, after the last trial of the run; the statistics on the host, ascending clones
+        const int G = sweep ? opt.sweep_repetitions : opt.replicas, groups = opt.replicas / G, NS = opt.evaluate_rows;
+        const size_t pairs = (size_t)opt.replicas * (size_t)NS;
+        std::vector<double> ret(pairs);
+        std::vector<int32_t> esteps(pairs), eterm(pairs), eties(pairs);
+        if (grlx_evaluate(ctx, 0, opt.replicas, opt.evaluate_states.data(), NS, 0, ret.data(), nullptr, esteps.data(), eterm.data(), eties.data(), nullptr) != GRLX_OK)
+        { std::string e = grlx_last_error(); grlx_destroy(ctx); throw Exception("-E " + opt.evaluate_file + ": " + e); }
+        std::ostringstream name;
+        name << output << "-" << rr << "-returns.txt";
+        std::ofstream ofs(name.str());
+        for (int g = 0; g < groups; ++g)
+          for (int s = 0; s < NS; ++s)
+          {
+            double sum = 0, step_sum = 0;
+            long long codes[4] = {0, 0, 0, 0}, tie_sum = 0;
+            for (int k = 0; k < G; ++k)
+            {
+              const size_t at = ((size_t)g * (size_t)G + (size_t)k) * (size_t)NS + (size_t)s;
+              sum += ret[at];
+              step_sum += (double)esteps[at];
+              codes[eterm[at] & 3]++;
+              tie_sum += eties[at];
+            }
+            const double mean = sum / G;
+            double sq = 0;
+            for (int k = 0; k < G; ++k)
+            {
+              const double d = ret[((size_t)g * (size_t)G + (size_t)k) * (size_t)NS + (size_t)s] - mean;
+              sq += d * d;
+            }
+            char line[384];
+            int at = sweep ? snprintf(line, sizeof(line), "%d ", g) : 0;
+            snprintf(line + at, sizeof(line) - (size_t)at, "%.17g %.17g %.17g %lld %lld %lld %lld %lld", mean, std::sqrt(sq / (G - 1)), step_sum / G, codes[0],
+                     codes[1], codes[2], codes[3], tie_sum);
+            ofs << line << std::endl;
+          }
+      }
       if (opt.reducer && n > 0)
       { // the learning curve over the clones of ALL ranks: per row {sum, sum of squares, count} of this device's replicas (grlx_curve_stats,
         // fixed reduction order), ONE all-reduce over the ranks, mean and standard deviation on rank 0.  (Trial-bounded runs write the same
@@ -1803,14 +1856,16 @@ GRLX_REGISTER(MultiExperiment)
 } // namespace grlx_host
 
 namespace grlx_host {
-void read_query_file(RunOptions *opt)
+namespace {
+// rows of whitespace-separated finite numbers, `#` comments, every row as long as the first: flag = "-Q" / "-E", what = "observation" / "state"
+void read_number_file(const std::string &flag, const std::string &file, const std::string &what, std::vector<double> *out, int *rows, int *cols)
 {
-  std::ifstream f(opt->query_file);
-  if (!f) throw Exception("-Q: could not open the observation file '" + opt->query_file + "'");
+  std::ifstream f(file);
+  if (!f) throw Exception(flag + ": could not open the " + what + " file '" + file + "'");
   std::string line;
   int line_no = 0;
-  opt->query_obs.clear();
-  opt->query_rows = opt->query_cols = 0;
+  out->clear();
+  *rows = *cols = 0;
   while (std::getline(f, line))
   {
     line_no++;
@@ -1824,17 +1879,24 @@ void read_query_file(RunOptions *opt)
       char *stop = nullptr;
       const double v = strtod(tok.c_str(), &stop);
       if (*stop != 0 || !std::isfinite(v))
-        throw Exception("-Q " + opt->query_file + ": line " + std::to_string(line_no) + ": '" + tok + "' is not a finite number");
-      opt->query_obs.push_back(v);
+        throw Exception(flag + " " + file + ": line " + std::to_string(line_no) + ": '" + tok + "' is not a finite number");
+      out->push_back(v);
       n++;
     }
     if (n == 0) continue;
-    if (opt->query_rows > 0 && n != opt->query_cols)
-      throw Exception("-Q " + opt->query_file + ": line " + std::to_string(line_no) + " has " + std::to_string(n) + " columns, the lines before it " +
-                      std::to_string(opt->query_cols));
-    opt->query_cols = n;
-    opt->query_rows++;
+    if (*rows > 0 && n != *cols)
+      throw Exception(flag + " " + file + ": line " + std::to_string(line_no) + " has " + std::to_string(n) + " columns, the lines before it " +
+                      std::to_string(*cols));
+    *cols = n;
+    (*rows)++;
   }
-  if (opt->query_rows == 0) throw Exception("-Q " + opt->query_file + ": no observations");
+  if (*rows == 0) throw Exception(flag + " " + file + ": no " + what + "s");
+}
+} // namespace
+
+void read_query_file(RunOptions *opt) { read_number_file("-Q", opt->query_file, "observation", &opt->query_obs, &opt->query_rows, &opt->query_cols); }
+void read_evaluate_file(RunOptions *opt)
+{
+  read_number_file("-E", opt->evaluate_file, "state", &opt->evaluate_states, &opt->evaluate_rows, &opt->evaluate_cols);
 }
 } // namespace grlx_host

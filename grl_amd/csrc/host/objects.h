@@ -40,7 +40,19 @@ struct RunOptions {
   std::string query_file;
   std::vector<double> query_obs;    // [query_rows][query_cols]
   int query_rows = 0, query_cols = 0;
+  // `grlxd -E FILE`: after the last trial of every run of an experiment/online_learning, one greedy episode per (clone, start state) with
+  // grlx_evaluate from the MODEL states of FILE (one per line, as many columns as grlx_env_dims reports state dimensions -- the time
+  // included --, `#` comments; read by read_evaluate_file before any device is looked for), and rank 0 writes <output>-<run>-returns.txt:
+  // per start state one line "mean sd mean_steps n0 n1 n2 n3 ties" (%.17g) -- mean and standard deviation (n - 1, two passes) of the return
+  // and the mean number of steps over the clones, the number of clones whose episode ended with terminal code 0 (cut at
+  // GRLX_MAX_EPISODE_STEPS), 1 (timed out), 2 (absorbing), 3 (left the math domain), and the summed ties; every sum on the host in
+  // ascending clone order.  With -p: one line per (point, start state), the point's index first, over the repetitions of the point.
+  std::string evaluate_file;
+  std::vector<double> evaluate_states;    // [evaluate_rows][evaluate_cols]
+  int evaluate_rows = 0, evaluate_cols = 0;
 };
+// ... the same for opt.evaluate_file -> opt.evaluate_states / _rows / _cols (messages begin with -E)
+void read_evaluate_file(RunOptions *opt);
 // fills opt.query_obs / _rows / _cols from opt.query_file; Exception for a missing or empty file, a token that is no finite number, rows of
 // different lengths
 void read_query_file(RunOptions *opt);

@@ -1,6 +1,7 @@
 """Thin Python host over the C ABI: one `Runner` = one grlx context = the
 replicas of one GPU.  All computation happens in the HIP kernels behind
 include/grlx.h; this file only marshals arguments."""
+import collections
 import ctypes as C
 import math
 
@@ -558,6 +559,28 @@ class Runner:
         first, count = self._replica_range(replicas)
         group_size = count if group_size is None else int(group_size)
         return EnsembleResult(self.query_ensemble_raw(obs, group_size, replicas), group_size, int(self.cfg.action_steps))
+
+    def evaluate(self, states, replicas=None, max_steps=0):
+        """One greedy episode of the test agent per (replica, start state) pair, on the device, from states[n][state_dims] (the MODEL's
+        state, time included: what get_env_state and the taps give) to its end or to max_steps (0 = GRLX_MAX_EPISODE_STEPS):
+        Evaluation(ret, disc, steps, terminal, ties, final_state), each [replica][start] (final_state: [replica][start][state_dims]).
+        terminal: 1 timed out, 2 absorbing, 0 cut at max_steps, 3 left the portable math's domain.  ties: steps at which the Q agents'
+        maximum was not unique (the first maximum acts; no random draw).  The context is not changed (include/grlx.h: grlx_evaluate)."""
+        states = np.ascontiguousarray(states, dtype=np.float64)
+        if states.ndim != 2 or states.shape[1] != self.state_dims:
+            raise ValueError(f"expected states of shape (n, {self.state_dims}), got {states.shape}")
+        first, count = self._replica_range(replicas)
+        n = states.shape[0]
+        ret, disc = np.zeros((count, n), np.float64), np.zeros((count, n), np.float64)
+        steps, terminal, ties = np.zeros((count, n), np.int32), np.zeros((count, n), np.int32), np.zeros((count, n), np.int32)
+        final_state = np.zeros((count, n, self.state_dims), np.float64)
+        capi.check(self.lib.grlx_evaluate(self._ctx, first, count, _ptr(states, C.c_double), n, int(max_steps), _ptr(ret, C.c_double),
+                                          _ptr(disc, C.c_double), _ptr(steps, C.c_int32), _ptr(terminal, C.c_int32), _ptr(ties, C.c_int32),
+                                          _ptr(final_state, C.c_double)))
+        return Evaluation(ret, disc, steps, terminal, ties, final_state)
+
+
+Evaluation = collections.namedtuple("Evaluation", "ret disc steps terminal ties final_state")
 
 
 class EnsembleResult:

@@ -431,6 +431,41 @@ int  grlx_query_state(grlx_ctx *ctx, int table, int first_replica, int n_replica
  * n_replicas % group_size != 0 is GRLX_ERR_INVALID. */
 int  grlx_query_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, const double *obs, int n_obs, double *out);
 
+/* --- policy evaluation: greedy episodes from start states of the caller's choice -------------------------------------------------
+ * For every (replica, start state) pair one episode of the TEST agent (agent/fixed over the learned tables) on the replica's current
+ * parameters, from that model state to its end, on the device, in one launch: the test branch of OnlineLearningExperiment::run
+ * (online_learning.cpp:172-213) for one episode with states[s] in place of Task::start.  Replicas [first_replica, first_replica +
+ * n_replicas); states[n_starts][state_dims], state_dims the MODEL's (grlx_env_dims: pendulum 3, cart-pole and acrobot 5, walker 11).
+ * The state carries the time, and the walker's its timeout and step flag, so a state from grlx_get_env_state or a tap continues exactly.
+ *   The loop.   Observe the start state -- its terminal code is ignored, as the reference's start ignores it: an episode has at least
+ *               one step -- then act, step, add the reward, until the step's terminal code is non-zero or max_steps steps have run.
+ *   The action. Q agents (SARSA, Q, Expected SARSA, advantage, QV's table 0; accumulating trace and target network included: the MAIN
+ *               parameters are read, as by the queries): actions[mai], mai the FIRST maximum of GreedySampler::findmax (greedy.cpp:
+ *               47-61).  No random draw is made; `ties` counts the steps at which there was more than one maximum.  With ties == 0
+ *               the episode is the reference's test episode from that state, bit for bit.  Actor-critic: fmin(fmax(read(actor table,
+ *               obs), action_min), action_max) (ActionPolicy::act(in, out) const); ties = 0.
+ *   ret         ret = 0; ret += reward in step order (online_learning.cpp:202)
+ *   disc        g = 1; disc = 0; per step disc += g * reward; g = g * gamma (plain products; the replica's own gamma in a sweep context)
+ *   steps       steps taken
+ *   terminal    1 timed out, 2 absorbing, 0 cut at max_steps, 3 the step ended outside the portable math's domain (what the rollout
+ *               kernels flag and grlx_sync reports as GRLX_ERR_DOMAIN: the step is counted, the episode stops there, no sticky flag is set)
+ *   final_state [n_replicas][n_starts][state_dims] the model state after the last step
+ * ret, disc, steps, terminal, ties: [n_replicas][n_starts].  Host pointers; any output may be NULL.
+ * max_steps: 1 ... GRLX_MAX_EPISODE_STEPS, 0 = that cap.  The kernel never iterates further, whatever time or timeout the state carries.
+ * AN EVALUATION CHANGES NOTHING in the context, like a query (above): tables, streams, counters, rows, the environment states and the
+ * sticky status are untouched; it is allowed before the first launch and does not count as one; it waits for the stream of the last
+ * grlx_run and stages in chunks of start states under the queries' bound (grlx_set_query_chunk_bytes).
+ * Validated on the host before anything is launched (GRLX_ERR_INVALID, nothing written; row and component named): null states,
+ * n_starts < 0, the replica range, max_steps out of range, a state component that is not finite or reaches 2^17 in magnitude (below it
+ * the RK4 stages of a step stay inside the branch-free sine's domain at the rates the tasks reach; a hand-made RATE near the bound can
+ * still carry an angle out within one step -- the acrobot's does -- which ends the episode with code 3 after that step, its sums and
+ * final state then being those of sines taken outside their domain), GRLX_ENV_EXTERNAL (no environment), projector/tile_coding:safe >= 1
+ * ("not built"), an (environment, action count) pair without an instantiation (built: pendulum x {3, 5} actions, acrobot, cart-pole and
+ * walker x 3; actor-critic: cart-pole and pendulum).  n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
+ * NOT BUILT: per-step trajectories, the epsilon-greedy learning policy, acting on the target network, ensemble votes, the batch path. */
+int  grlx_evaluate(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][state_dims]*/, int n_starts,
+                   int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * The per-step plug-in interfaces on the replicas of a context: one call of the reference's interface for EVERY replica per
  * call, for graphs in which only one side of the loop of OnlineLearningExperiment::run (online_learning.cpp:172-213) lives on the
