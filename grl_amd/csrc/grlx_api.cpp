@@ -1921,33 +1921,42 @@ int grlx_query_state(grlx_ctx *ctx, int table, int first_replica, int n_replicas
 }
 
 // ---- policy evaluation: greedy episodes from start states of the caller's choice (grlx_evaluate.hip) -----------------------------------
-int grlx_evaluate(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, double *ret, double *disc,
-                  int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state)
+// what both evaluations check before they touch the device
+static int evaluate_admit(grlx_ctx *ctx, const char *who, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps)
 {
   if (!ctx) return fail(GRLX_ERR_INVALID, "bad argument");
   if (ctx->cfg.env == GRLX_ENV_EXTERNAL)
-    return fail(GRLX_ERR_INVALID, "grlx_evaluate: the context has no environment (GRLX_ENV_EXTERNAL): there is nothing to step");
+    return fail(GRLX_ERR_INVALID, "%s: the context has no environment (GRLX_ENV_EXTERNAL): there is nothing to step", who);
   if (ctx->P.tile_safe >= 1)
-    return fail(GRLX_ERR_INVALID, "grlx_evaluate is not built for projector/tile_coding:safe >= 1 (a read would have to walk the claim table without claiming)");
+    return fail(GRLX_ERR_INVALID, "%s is not built for projector/tile_coding:safe >= 1 (a read would have to walk the claim table without claiming)", who);
   if (!evaluate_built(ctx->cfg.agent, ctx->cfg.env, ctx->P.A))
-    return fail(GRLX_ERR_INVALID, "grlx_evaluate is not built for environment %d with %d actions (Q agents: pendulum x {3, 5}, acrobot, cart-pole, walker x 3; actor-critic: cart-pole, pendulum)",
+    return fail(GRLX_ERR_INVALID, "%s is not built for environment %d with %d actions (Q agents: pendulum x {3, 5}, acrobot, cart-pole, walker x 3; actor-critic: cart-pole, pendulum)", who,
                 ctx->cfg.env, ctx->cfg.agent == GRLX_AGENT_AC ? 0 : ctx->P.A);
-  if (n_starts < 0) return fail(GRLX_ERR_INVALID, "grlx_evaluate: n_starts = %d", n_starts);
+  if (n_starts < 0) return fail(GRLX_ERR_INVALID, "%s: n_starts = %d", who, n_starts);
   if (first_replica < 0 || n_replicas < 0 || (int64_t)first_replica + n_replicas > ctx->P.n_replicas)
-    return fail(GRLX_ERR_INVALID, "grlx_evaluate: replica range [%d, %lld) is outside the context's %d replicas", first_replica,
+    return fail(GRLX_ERR_INVALID, "%s: replica range [%d, %lld) is outside the context's %d replicas", who, first_replica,
                 (long long)first_replica + n_replicas, ctx->P.n_replicas);
-  if (!states) return fail(GRLX_ERR_INVALID, "grlx_evaluate: states is null");
+  if (!states) return fail(GRLX_ERR_INVALID, "%s: states is null", who);
   if (max_steps < 0 || max_steps > GRLX_MAX_EPISODE_STEPS)
-    return fail(GRLX_ERR_INVALID, "grlx_evaluate: max_steps = %d is outside 1 ... GRLX_MAX_EPISODE_STEPS (%d; 0 = that cap)", max_steps, GRLX_MAX_EPISODE_STEPS);
-  if (max_steps == 0) max_steps = GRLX_MAX_EPISODE_STEPS;
+    return fail(GRLX_ERR_INVALID, "%s: max_steps = %d is outside 1 ... GRLX_MAX_EPISODE_STEPS (%d; 0 = that cap)", who, max_steps, GRLX_MAX_EPISODE_STEPS);
   const int S = ctx->S;
   for (int s = 0; s < n_starts; ++s)
     for (int i = 0; i < S; ++i)
     { // below 2^17 the RK4 stages of one step stay inside the branch-free sine's domain (the cart-pole's case)
       const double v = states[(size_t)s * S + i];
-      if (!std::isfinite(v)) return fail(GRLX_ERR_INVALID, "grlx_evaluate: state row %d, component %d is not finite (%g)", s, i, v);
-      if (!(fabs(v) < 0x1p17)) return fail(GRLX_ERR_INVALID, "grlx_evaluate: state row %d, component %d (%g) is out of range: its magnitude reaches 2^17", s, i, v);
+      if (!std::isfinite(v)) return fail(GRLX_ERR_INVALID, "%s: state row %d, component %d is not finite (%g)", who, s, i, v);
+      if (!(fabs(v) < 0x1p17)) return fail(GRLX_ERR_INVALID, "%s: state row %d, component %d (%g) is out of range: its magnitude reaches 2^17", who, s, i, v);
     }
+  return GRLX_OK;
+}
+
+int grlx_evaluate(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, double *ret, double *disc,
+                  int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state)
+{
+  int rc = evaluate_admit(ctx, "grlx_evaluate", first_replica, n_replicas, states, n_starts, max_steps);
+  if (rc != GRLX_OK) return rc;
+  if (max_steps == 0) max_steps = GRLX_MAX_EPISODE_STEPS;
+  const int S = ctx->S;
   if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
   DRAIN(ctx);
   const size_t per_pair = 2 * sizeof(double) + 3 * sizeof(int32_t) + sizeof(double) * (size_t)S;
@@ -1980,6 +1989,66 @@ int grlx_evaluate(grlx_ctx *ctx, int first_replica, int n_replicas, const double
     if (terminal) HIP_TRY(query_copy_out(terminal, dterm.p, sizeof(int32_t), n_replicas, n_starts, s0, nc));
     if (ties) HIP_TRY(query_copy_out(ties, dties.p, sizeof(int32_t), n_replicas, n_starts, s0, nc));
     if (final_state) HIP_TRY(query_copy_out(final_state, dfin.p, sizeof(double) * (size_t)S, n_replicas, n_starts, s0, nc));
+    HIP_TRY(hipDeviceSynchronize());               // every output may be NULL: the next chunk's copy-in must not overtake this launch
+  }
+  return GRLX_OK;
+}
+
+// ---- ensemble evaluation: one episode per (group of consecutive replicas, start state) on the group's vote or mean Q ----------------------
+int grlx_evaluate_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule, const double *states, int n_starts,
+                           int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, int64_t *member_ties,
+                           int64_t *agreement, double *final_state)
+{
+  const char *who = "grlx_evaluate_ensemble";
+  int rc = evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps);
+  if (rc != GRLX_OK) return rc;
+  if (!q_agent(ctx->cfg.agent))
+    return fail(GRLX_ERR_INVALID, "%s is not built for the actor-critic agent (a vote over continuous actions is mapping/policy/multi's); it serves agents with a policy/discrete/q", who);
+  if (group_size < 1) return fail(GRLX_ERR_INVALID, "%s: group_size = %d is below 1", who, group_size);
+  if (n_replicas % group_size != 0) return fail(GRLX_ERR_INVALID, "%s: group_size %d does not divide the %d replicas", who, group_size, n_replicas);
+  if (rule != GRLX_ENSEMBLE_VOTE && rule != GRLX_ENSEMBLE_MEAN_Q)
+    return fail(GRLX_ERR_INVALID, "%s: unknown rule %d (GRLX_ENSEMBLE_VOTE = 0, GRLX_ENSEMBLE_MEAN_Q = 1)", who, rule);
+  if (max_steps == 0) max_steps = GRLX_MAX_EPISODE_STEPS;
+  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
+  DRAIN(ctx);
+  const int S = ctx->S, n_groups = n_replicas / group_size;
+  const size_t per_pair = 2 * sizeof(double) + 3 * sizeof(int32_t) + 2 * sizeof(int64_t) + sizeof(double) * (size_t)S;
+  int chunk = query_chunk(n_starts, sizeof(double) * (size_t)S + per_pair * (size_t)n_groups);
+  if ((int64_t)chunk * n_groups > 0x7fffffff) chunk = 0x7fffffff / n_groups;      // one block per pair: the grid's bound
+  const size_t pairs = (size_t)n_groups * (size_t)chunk;
+  DevBuf dst, dret, ddisc, dsteps, dterm, dties, dmt, dag, dfin;
+  HIP_TRY(dst.alloc(sizeof(double) * (size_t)chunk * S));
+  HIP_TRY(dret.alloc(sizeof(double) * pairs));
+  HIP_TRY(ddisc.alloc(sizeof(double) * pairs));
+  HIP_TRY(dsteps.alloc(sizeof(int32_t) * pairs));
+  HIP_TRY(dterm.alloc(sizeof(int32_t) * pairs));
+  HIP_TRY(dties.alloc(sizeof(int32_t) * pairs));
+  HIP_TRY(dmt.alloc(sizeof(int64_t) * pairs));
+  HIP_TRY(dag.alloc(sizeof(int64_t) * pairs));
+  HIP_TRY(dfin.alloc(sizeof(double) * pairs * S));
+  for (int s0 = 0; s0 < n_starts; s0 += chunk)
+  {
+    const int nc = n_starts - s0 < chunk ? n_starts - s0 : chunk;
+    HIP_TRY(hipMemcpy(dst.p, states + (size_t)s0 * S, sizeof(double) * (size_t)nc * S, hipMemcpyHostToDevice));
+    EnsembleArgs A;
+    A.first_replica = first_replica; A.n_replicas = n_replicas; A.group_size = group_size; A.rule = rule;
+    A.n_starts = nc; A.max_steps = max_steps;
+    A.states = dst.as<double>();
+    A.sweep = ctx->sweep ? ctx->sweep_dev : nullptr;
+    A.ret = dret.as<double>(); A.disc = ddisc.as<double>();
+    A.steps = dsteps.as<int32_t>(); A.terminal = dterm.as<int32_t>(); A.ties = dties.as<int32_t>();
+    A.member_ties = dmt.as<int64_t>(); A.agreement = dag.as<int64_t>();
+    A.final_state = dfin.as<double>();
+    if (ctx->poison) HIP_TRY(launch_poison_registers(ctx->poison_pattern, nullptr));
+    HIP_TRY(launch_evaluate_ensemble(ctx->P, A, nullptr));
+    if (ret) HIP_TRY(query_copy_out(ret, dret.p, sizeof(double), n_groups, n_starts, s0, nc));
+    if (disc) HIP_TRY(query_copy_out(disc, ddisc.p, sizeof(double), n_groups, n_starts, s0, nc));
+    if (steps) HIP_TRY(query_copy_out(steps, dsteps.p, sizeof(int32_t), n_groups, n_starts, s0, nc));
+    if (terminal) HIP_TRY(query_copy_out(terminal, dterm.p, sizeof(int32_t), n_groups, n_starts, s0, nc));
+    if (ties) HIP_TRY(query_copy_out(ties, dties.p, sizeof(int32_t), n_groups, n_starts, s0, nc));
+    if (member_ties) HIP_TRY(query_copy_out(member_ties, dmt.p, sizeof(int64_t), n_groups, n_starts, s0, nc));
+    if (agreement) HIP_TRY(query_copy_out(agreement, dag.p, sizeof(int64_t), n_groups, n_starts, s0, nc));
+    if (final_state) HIP_TRY(query_copy_out(final_state, dfin.p, sizeof(double) * (size_t)S, n_groups, n_starts, s0, nc));
     HIP_TRY(hipDeviceSynchronize());               // every output may be NULL: the next chunk's copy-in must not overtake this launch
   }
   return GRLX_OK;

@@ -21,7 +21,23 @@ struct EvaluateArgs {
 // terminal code of an episode that left the portable math's domain (Env::in_domain at a step end); 0 / 1 / 2 are the task's
 constexpr int kEvaluateDomain = 3;
 
+// grlx_evaluate_ensemble: one chunk of start states for a range of replicas in groups of group_size consecutive ones; every pointer is
+// a device pointer.  A pair is (group, start state) with the index group * n_starts + start.
+struct EnsembleArgs {
+  int32_t            first_replica, n_replicas;
+  int32_t            group_size;    // divides n_replicas
+  int32_t            rule;          // GRLX_ENSEMBLE_VOTE / GRLX_ENSEMBLE_MEAN_Q
+  int32_t            n_starts, max_steps;
+  const double      *states;        // [n_starts][model state dimensions]
+  const SweepParams *sweep;         // the gamma of a group's FIRST replica; null = DevParams::gamma
+  double            *ret, *disc;    // [pair]
+  int32_t           *steps, *terminal, *ties;   // [pair]
+  int64_t           *member_ties, *agreement;   // [pair]
+  double            *final_state;   // [pair][model state dimensions]
+};
+
 bool evaluate_built(int agent, int env, int actions);      // is there an instantiation for this context?
 hipError_t launch_evaluate(const DevParams &P, const EvaluateArgs &A, hipStream_t stream);
+hipError_t launch_evaluate_ensemble(const DevParams &P, const EnsembleArgs &A, hipStream_t stream);    // Q agents only
 
 } // namespace grlx

@@ -20,6 +20,9 @@
 // LDS: the weight tile of grlx_query.hip (rows kRowStride = 66 doubles apart, see the bank argument there), the group's Q-values, and
 // two words per group by which lane 0 hands findmax's result (the actor-critic: the action) back to the 16 lanes.
 //
+// evaluate_ensemble_kernel (grlx_evaluate_ensemble): the same episode for a GROUP of consecutive replicas that share one environment state
+// and act on their vote or their summed Q; its layout is described at the kernel.
+//
 // Compiled with -ffp-contract=off like every unit: g * reward is a plain product, the sums plain additions.
 #include "grlx_internal.h"
 #include "grlx_math.h"
@@ -60,6 +63,69 @@ __device__ __forceinline__ void episode_store(const EvaluateArgs &A, long long p
   A.ties[pair] = e.ties;
 #pragma unroll
   for (int i = 0; i < S; ++i) A.final_state[(size_t)pair * S + i] = x[i];
+}
+
+// The probe of one member by its 16-lane group, evaluate_q_kernel's written as a function for evaluate_ensemble_kernel: project(obs, a_k),
+// k < NA -- the hash of the observation once, then the action's coordinate and the tiling (tile_coding.cpp:103-149) --, query_weights,
+// the lane's NA weights into its column of the wave's tile.  evaluate_q_kernel keeps its own copy of these lines, and of findmax and
+// action_of below: calling any of the three from it changed its machine code (instruction counts, on the walker the registers), and
+// the existing kernels stay the code they were.  member_q is shared: it leaves evaluate_q_kernel instruction for instruction the same.
+template <int ENV, int NA>
+__device__ __forceinline__ void member_probe(const DevParams &P, const Table &tab, const ReplicaState &rs,
+                                             const double (&obs)[Env<ENV>::D], int j, int lane, double *W)
+{
+  constexpr int T = kLanesPerReplica, D = Env<ENV>::D;
+  uint32_t hpre = 449u ^ (uint32_t)(D + 2);
+#pragma unroll
+  for (int i = 0; i < D; ++i)
+    hpre = murmur_mix(hpre, tile_coord<T>(P.tile, i, tile_quant(P.tile, i, obs[i]), j));
+  uint32_t slot[NA];
+#pragma unroll
+  for (int a = 0; a < NA; ++a)
+  {
+    uint32_t h = murmur_mix(hpre, tile_coord<T>(P.tile, D, tile_quant(P.tile, D, P.actions[a]), j));
+    h = murmur_mix(h, j);
+    slot[a] = murmur_final(h) % (uint32_t)P.tile.memory;
+  }
+  double w[NA];
+  query_weights<NA>(tab, rs, 0, P.lin, slot, w);
+#pragma unroll
+  for (int a = 0; a < NA; ++a) W[a * kRowStride + lane] = w[a];
+}
+
+// LinearRepresentation::read (linear.cpp:136-184) by lane j < NA of group g: serial sum over the 16 tilings, mean, clamp
+__device__ __forceinline__ double member_q(const DevParams &P, const double *W, int g, int j)
+{
+  double sum = 0;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) sum += W[j * kRowStride + g * 16 + k];
+  sum /= 16;
+  return query_clamp(sum, P.lin.out_min, P.lin.out_max);
+}
+
+// GreedySampler::findmax (greedy.cpp:47-61): the first maximum and the number of maxima
+template <int NA, class V>
+__device__ __forceinline__ void findmax(const V *v, int &mai, int &man)
+{
+  mai = 0; man = 1;
+  V best = v[0];
+#pragma unroll
+  for (int a = 1; a < NA; ++a)
+  {
+    const V q = v[a];
+    if (q > best) { best = q; mai = a; man = 1; }
+    else if (q == best) man++;
+  }
+}
+
+// actions[mai] by selects, not an indexed read of the parameter block: no scratch copy of it
+template <int NA>
+__device__ __forceinline__ double action_of(const DevParams &P, int mai)
+{
+  double action = P.actions[0];
+#pragma unroll
+  for (int a = 1; a < NA; ++a) action = (mai == a) ? P.actions[a] : action;
+  return action;
 }
 
 // Q agents: actions[first maximum of Q(obs, .)] at every step
@@ -114,14 +180,7 @@ __global__ __launch_bounds__(kQueryWaves * 64) void evaluate_q_kernel(DevParams 
       for (int a = 0; a < NA; ++a) W[a * kRowStride + lane] = w[a];
     }
     wave_sync();
-    if (active && j < NA)
-    { // LinearRepresentation::read (linear.cpp:136-184): serial sum over the 16 tilings, mean, clamp
-      double sum = 0;
-#pragma unroll
-      for (int k = 0; k < 16; ++k) sum += W[j * kRowStride + g * 16 + k];
-      sum /= 16;
-      Q[g * 8 + j] = query_clamp(sum, P.lin.out_min, P.lin.out_max);
-    }
+    if (active && j < NA) Q[g * 8 + j] = member_q(P, W, g, j);
     wave_sync();
     if (active && j == 0)
     { // greedy.cpp:47-61
@@ -152,6 +211,108 @@ __global__ __launch_bounds__(kQueryWaves * 64) void evaluate_q_kernel(DevParams 
     }
   }
   if (live && j == 0) episode_store<S>(A, pair, e, x);
+}
+
+// Ensembles of Q agents: one episode per (group of G consecutive replicas, start state); at every step the members' first maxima are
+// counted (votes) and their Q-values summed, both over the members in ASCENDING order, and the episode acts on the first maximum of
+// the votes (GRLX_ENSEMBLE_VOTE) or of the sums (GRLX_ENSEMBLE_MEAN_Q).  Reference: MultiDiscretePolicy::act (multi_discrete.cpp:
+// 120-235) under policy_strategy_majority_voting_prob / _add_prob; see include/grlx.h for what differs.
+//
+// Layout: one block of kQueryWaves waves serves one episode; its 16 lane groups serve 16 members per round, ceil(G / 16) rounds per step.
+// Per round: member_probe, the wave's barrier, member_q by lanes j < NA into the member's slot of sh_m, then the block's barrier, after
+// which EVERY thread continues the same votes / sumq accumulators over the round's slots in ascending member order -- broadcast LDS
+// reads, identical bits in every thread, so no result is handed back.  All 256 threads integrate the same state redundantly: the
+// episode's end is block-uniform by construction, and every thread reaches every barrier.
+//
+// sh_m is double-buffered by the parity of a round counter that runs through the episode.  A thread that writes buffer p in round k + 2
+// has passed the block barrier of round k + 1, which every thread reaches only after its reads of round k (buffer p) are done.  The
+// wave's tile W is written again only after that block barrier too, which orders it after the wave's own reads of the round before.
+// Dead member slots (member >= G) skip loads and stores; nobody reads their slots.
+template <int ENV, int NA>
+__global__ __launch_bounds__(kQueryWaves * 64) void evaluate_ensemble_kernel(DevParams P, EnsembleArgs A)
+{
+  constexpr int S = Env<ENV>::S, D = Env<ENV>::D, kSlots = kQueryWaves * 4;
+  __shared__ double sh_w[kQueryWaves][NA * kRowStride];
+  __shared__ double sh_m[2][kSlots][8];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, j = lane & 15;
+  const int slot = wave * 4 + g;                       // the member of a round this lane group serves
+  const int G = A.group_size;
+  const int grp = (int)(blockIdx.x / (unsigned)A.n_starts), s = (int)(blockIdx.x - (unsigned)grp * (unsigned)A.n_starts);
+  const int r0 = A.first_replica + grp * G;
+  double *W = sh_w[wave];
+
+  const double gamma = A.sweep ? A.sweep[r0].gamma : P.gamma;      // the group's first replica's
+  double x[S], obs[D];
+#pragma unroll
+  for (int i = 0; i < S; ++i) x[i] = A.states[(size_t)s * S + i];
+  (void)Env<ENV>::observe(P, x, obs);                  // the start state's terminal code is ignored, as Environment::start has none
+
+  EpisodeSums e;
+  e.ret = 0; e.disc = 0; e.g = 1; e.steps = 0; e.code = 0; e.ties = 0;
+  long long member_ties = 0, agreement = 0;
+  unsigned round = 0;
+  bool active = true;
+  for (int step = 0; step < A.max_steps; ++step)
+  {
+    if (__ballot(active) == 0ull) break;               // block-uniform: every thread holds the same state
+    int votes[NA];
+    double sumq[NA];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) { votes[a] = 0; sumq[a] = 0.; }
+    for (int m0 = 0; m0 < G; m0 += kSlots, ++round)
+    {
+      double (*MQ)[8] = sh_m[round & 1u];
+      const bool member = m0 + slot < G;
+      const int r = r0 + (member ? m0 + slot : 0);
+      if (member) member_probe<ENV, NA>(P, table_of(P, 0, r), P.states[r], obs, j, lane, W);
+      wave_sync();
+      if (member && j < NA) MQ[slot][j] = member_q(P, W, g, j);
+      __syncthreads();
+      const int n = G - m0 < kSlots ? G - m0 : kSlots;
+      for (int m = 0; m < n; ++m)
+      {
+        double q[NA];
+#pragma unroll
+        for (int a = 0; a < NA; ++a) q[a] = MQ[m][a];
+        int mai, man;
+        findmax<NA>(q, mai, man);
+#pragma unroll
+        for (int a = 0; a < NA; ++a)
+        {
+          votes[a] += (mai == a) ? 1 : 0;
+          sumq[a] += q[a];
+        }
+        member_ties += man > 1 ? 1 : 0;
+      }
+    }
+    int mai, man;
+    if (A.rule == GRLX_ENSEMBLE_VOTE) findmax<NA>(votes, mai, man);
+    else findmax<NA>(sumq, mai, man);
+    int agree = votes[0];
+#pragma unroll
+    for (int a = 1; a < NA; ++a) agree = (mai == a) ? votes[a] : agree;
+    agreement += agree;
+    const double action = action_of<NA>(P, mai);
+    double reward = 0;
+    int terminal = 0;
+    uint32_t status = 0;
+    env_step<ENV, false, NoShare>(P, x, action, obs, reward, terminal, status);
+    active = episode_account(e, reward, gamma, terminal, status, man > 1);
+  }
+  if (threadIdx.x == 0)
+  {
+    const long long pair = blockIdx.x;                 // group * n_starts + start
+    A.ret[pair] = e.ret;
+    A.disc[pair] = e.disc;
+    A.steps[pair] = e.steps;
+    A.terminal[pair] = e.code;
+    A.ties[pair] = e.ties;
+    A.member_ties[pair] = member_ties;
+    A.agreement[pair] = agreement;
+#pragma unroll
+    for (int i = 0; i < S; ++i) A.final_state[(size_t)pair * S + i] = x[i];
+  }
 }
 
 // actor-critic: the noise-free actor, fmin(fmax(read(actor table, obs), action_min), action_max) (ActionPolicy::act(in, out) const)
@@ -247,6 +408,24 @@ hipError_t launch_evaluate(const DevParams &P, const EvaluateArgs &A, hipStream_
   else if (P.env == GRLX_ENV_ACROBOT) hipLaunchKernelGGL((evaluate_q_kernel<GRLX_ENV_ACROBOT, 3>), grid, block, 0, stream, P, A);
   else if (P.env == GRLX_ENV_CART_POLE) hipLaunchKernelGGL((evaluate_q_kernel<GRLX_ENV_CART_POLE, 3>), grid, block, 0, stream, P, A);
   else hipLaunchKernelGGL((evaluate_q_kernel<GRLX_ENV_COMPASS_WALKER, 3>), grid, block, 0, stream, P, A);
+  return hipGetLastError();
+}
+
+// one block per (group, start state)
+hipError_t launch_evaluate_ensemble(const DevParams &P, const EnsembleArgs &A, hipStream_t stream)
+{
+  if (A.group_size < 1 || A.n_replicas % A.group_size != 0) return hipErrorInvalidValue;
+  const long long blocks = (long long)(A.n_replicas / A.group_size) * A.n_starts;
+  if (blocks == 0) return hipSuccess;
+  if (P.agent == GRLX_AGENT_AC || !evaluate_built(P.agent, P.env, P.A) || A.max_steps < 1 || blocks > 0x7fffffffll ||
+      (A.rule != GRLX_ENSEMBLE_VOTE && A.rule != GRLX_ENSEMBLE_MEAN_Q))
+    return hipErrorInvalidValue;
+  const dim3 grid((unsigned)blocks), block(kQueryWaves * 64);
+  if (P.env == GRLX_ENV_PENDULUM && P.A == 3) hipLaunchKernelGGL((evaluate_ensemble_kernel<GRLX_ENV_PENDULUM, 3>), grid, block, 0, stream, P, A);
+  else if (P.env == GRLX_ENV_PENDULUM) hipLaunchKernelGGL((evaluate_ensemble_kernel<GRLX_ENV_PENDULUM, 5>), grid, block, 0, stream, P, A);
+  else if (P.env == GRLX_ENV_ACROBOT) hipLaunchKernelGGL((evaluate_ensemble_kernel<GRLX_ENV_ACROBOT, 3>), grid, block, 0, stream, P, A);
+  else if (P.env == GRLX_ENV_CART_POLE) hipLaunchKernelGGL((evaluate_ensemble_kernel<GRLX_ENV_CART_POLE, 3>), grid, block, 0, stream, P, A);
+  else hipLaunchKernelGGL((evaluate_ensemble_kernel<GRLX_ENV_COMPASS_WALKER, 3>), grid, block, 0, stream, P, A);
   return hipGetLastError();
 }
 

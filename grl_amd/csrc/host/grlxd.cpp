@@ -11,6 +11,8 @@
 // -E FILE: after the last trial of every run, one greedy episode per (clone, start state) from the model states of FILE (one per line) with
 // grlx_evaluate, and <output>-<run>-returns.txt: mean and standard deviation (n - 1) of the return, mean steps, the count of every terminal
 // code and the summed ties over the clones (objects.h),
+// -V vote|mean: with -E, also one episode per start state of the ensemble of all clones (with -p: of each point's repetitions) acting on
+// the members' vote or on their mean Q (grlx_evaluate_ensemble), written to <output>-<run>-ensemble.txt (objects.h),
 // -n: print the plan (one line per clone: i seed alpha gamma lambda epsilon) and exit before anything touches HIP, and
 // -g N: one process per GPU (rank r on the r-th visible device, started before anything touches HIP), every rank running -r replicas
 // (clones r * replicas ..., seeds and "@i" identities counted over the whole job), the learning curves reduced with one RCCL all-reduce
@@ -26,6 +28,7 @@
 #include <sstream>
 #include <vector>
 
+#include "../../../include/grlx.h"
 #include "configurable.h"
 #include "multi_gpu.h"
 #include "objects.h"
@@ -72,7 +75,9 @@ int main(int argc, char **argv)
   int gpus = 0;
   int c;
   std::vector<std::string> sweep_args;
-  while ((c = getopt(argc, argv, "vs:r:t:lqc:g:p:nk:K:Q:E:")) != -1)
+  std::string ensemble_arg;
+  bool ensemble = false;
+  while ((c = getopt(argc, argv, "vs:r:t:lqc:g:p:nk:K:Q:E:V:")) != -1)
   {
     switch (c)
     {
@@ -90,12 +95,13 @@ int main(int argc, char **argv)
       case 'K': opt.snapshot_load = optarg; break;
       case 'Q': opt.query_file = optarg; break;
       case 'E': opt.evaluate_file = optarg; break;
+      case 'V': ensemble_arg = optarg; ensemble = true; break;
       default: return 1;
     }
   }
   if (optind > argc - 1)
   {
-    log(0, std::string("Usage: \n  ") + argv[0] + " [-v] [-s seed] [-r replicas] [-g gpus] [-t trials] [-l] [-q] [-p path=v1,v2,...]... [-n] [-k snapshot] [-K snapshot] [-Q observations] [-E states] <yaml file> [yaml file...]");
+    log(0, std::string("Usage: \n  ") + argv[0] + " [-v] [-s seed] [-r replicas] [-g gpus] [-t trials] [-l] [-q] [-p path=v1,v2,...]... [-n] [-k snapshot] [-K snapshot] [-Q observations] [-E states] [-V vote|mean] <yaml file> [yaml file...]");
     return 1;
   }
   if (opt.seed == 0)
@@ -149,6 +155,13 @@ int main(int argc, char **argv)
       read_query_file(&opt);
     }
     catch (Exception &e) { log(0, e.what()); return 1; }
+  }
+  if (ensemble)
+  { // -V needs -E's states and one of the two rules: refused before any process is forked or any device looked for
+    if (ensemble_arg == "vote") opt.ensemble_rule = GRLX_ENSEMBLE_VOTE;
+    else if (ensemble_arg == "mean") opt.ensemble_rule = GRLX_ENSEMBLE_MEAN_Q;
+    else { log(0, "-V: unknown rule '" + ensemble_arg + "' (vote: the members' majority, mean: the argmax of their mean Q)"); return 1; }
+    if (opt.evaluate_file.empty()) { log(0, "-V " + ensemble_arg + ": an ensemble evaluation needs the start states of -E <states file>"); return 1; }
   }
   if (!opt.evaluate_file.empty())
   { // likewise: the state file is read, and -g and -r 1 refused, before any process is forked or any device looked for

@@ -1435,6 +1435,8 @@ struct OnlineLearningExperimentImpl : OnlineLearningExperiment, StepwiseExperime
         throw Exception("-E " + opt.evaluate_file + ": " + std::to_string(opt.evaluate_cols) + " columns, the model's state has " + std::to_string(state_dims) +
                         " (the time included)");
       if (output.empty()) throw Exception(path() + ": -E writes <output>-<run>-returns.txt: the experiment has no output");
+      if (opt.ensemble_rule >= 0 && c.agent == GRLX_AGENT_AC)
+        throw Exception(path() + ": -V: an ensemble evaluation is not built for the actor-critic agent (a vote over continuous actions is mapping/policy/multi's)");
     }
     if (sweep)
     {
@@ -1771,6 +1773,29 @@ struct OnlineLearningExperimentImpl : OnlineLearningExperiment, StepwiseExperime
                      codes[1], codes[2], codes[3], tie_sum);
             ofs << line << std::endl;
           }
+        if (opt.ensemble_rule >= 0)
+        { // the same start states on the vote or the mean Q of each group: one episode per (group, start state)
+          const size_t gp = (size_t)groups * (size_t)NS;
+          std::vector<double> vret(gp), vdisc(gp);
+          std::vector<int32_t> vsteps(gp), vterm(gp), vties(gp);
+          std::vector<int64_t> vmt(gp), vag(gp);
+          if (grlx_evaluate_ensemble(ctx, 0, opt.replicas, G, opt.ensemble_rule, opt.evaluate_states.data(), NS, 0, vret.data(), vdisc.data(), vsteps.data(),
+                                     vterm.data(), vties.data(), vmt.data(), vag.data(), nullptr) != GRLX_OK)
+          { std::string e = grlx_last_error(); grlx_destroy(ctx); throw Exception("-V: " + e); }
+          std::ostringstream vname;
+          vname << output << "-" << rr << "-ensemble.txt";
+          std::ofstream vofs(vname.str());
+          for (int g = 0; g < groups; ++g)
+            for (int s = 0; s < NS; ++s)
+            {
+              const size_t at = (size_t)g * (size_t)NS + (size_t)s;
+              char line[384];
+              int n0 = sweep ? snprintf(line, sizeof(line), "%d ", g) : 0;
+              snprintf(line + n0, sizeof(line) - (size_t)n0, "%.17g %.17g %d %d %d %lld %.17g", vret[at], vdisc[at], vsteps[at], vterm[at], vties[at],
+                       (long long)vmt[at], (double)vag[at] / ((double)vsteps[at] * (double)G));
+              vofs << line << std::endl;
+            }
+        }
       }
       if (opt.reducer && n > 0)
       { // the learning curve over the clones of ALL ranks: per row {sum, sum of squares, count} of this device's replicas (grlx_curve_stats,

@@ -50,6 +50,11 @@ struct RunOptions {
   std::string evaluate_file;
   std::vector<double> evaluate_states;    // [evaluate_rows][evaluate_cols]
   int evaluate_rows = 0, evaluate_cols = 0;
+  // `grlxd -E FILE -V vote|mean`: besides the unchanged returns file, one episode per (group, start state) with grlx_evaluate_ensemble, the
+  // group being all clones, with -p the repetitions of a point; rank 0 writes <output>-<run>-ensemble.txt: per start state one line
+  // "ret disc steps terminal ties member_ties agreement" (%.17g), agreement = grlx_evaluate_ensemble's divided by steps * group.  With -p:
+  // one line per (point, start state), the point's index first.  -1 = no -V; else GRLX_ENSEMBLE_VOTE / GRLX_ENSEMBLE_MEAN_Q.
+  int ensemble_rule = -1;
 };
 // ... the same for opt.evaluate_file -> opt.evaluate_states / _rows / _cols (messages begin with -E)
 void read_evaluate_file(RunOptions *opt);

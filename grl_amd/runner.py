@@ -579,8 +579,35 @@ class Runner:
                                           _ptr(final_state, C.c_double)))
         return Evaluation(ret, disc, steps, terminal, ties, final_state)
 
+    def evaluate_ensemble(self, states, group_size, rule="vote", replicas=None, max_steps=0):
+        """One greedy episode per (group of `group_size` consecutive replicas, start state) pair, on the device: at every step the
+        members' first maxima are counted and their Q-values summed in ascending replica order, and the episode takes the first maximum
+        of the votes (rule "vote") or of the summed Q (rule "mean").  EnsembleEvaluation(ret, disc, steps, terminal, ties, member_ties,
+        agreement, final_state), each [group][start]: ties = steps at which the combined score had more than one maximum, member_ties =
+        member-steps at which a member's own maximum was not unique, agreement = member-steps whose own first maximum was the action
+        taken.  disc uses the gamma of a group's first replica.  The context is not changed (include/grlx.h: grlx_evaluate_ensemble)."""
+        rules = {"vote": capi.ENSEMBLE_VOTE, "mean": capi.ENSEMBLE_MEAN_Q, "mean_q": capi.ENSEMBLE_MEAN_Q}
+        rule = rules[rule] if isinstance(rule, str) else int(rule)
+        states = np.ascontiguousarray(states, dtype=np.float64)
+        if states.ndim != 2 or states.shape[1] != self.state_dims:
+            raise ValueError(f"expected states of shape (n, {self.state_dims}), got {states.shape}")
+        first, count = self._replica_range(replicas)
+        group_size = int(group_size)
+        groups = count // group_size if group_size > 0 else 0
+        n = states.shape[0]
+        ret, disc = np.zeros((groups, n), np.float64), np.zeros((groups, n), np.float64)
+        steps, terminal, ties = np.zeros((groups, n), np.int32), np.zeros((groups, n), np.int32), np.zeros((groups, n), np.int32)
+        member_ties, agreement = np.zeros((groups, n), np.int64), np.zeros((groups, n), np.int64)
+        final_state = np.zeros((groups, n, self.state_dims), np.float64)
+        capi.check(self.lib.grlx_evaluate_ensemble(self._ctx, first, count, group_size, rule, _ptr(states, C.c_double), n, int(max_steps),
+                                                   _ptr(ret, C.c_double), _ptr(disc, C.c_double), _ptr(steps, C.c_int32), _ptr(terminal, C.c_int32),
+                                                   _ptr(ties, C.c_int32), _ptr(member_ties, C.c_int64), _ptr(agreement, C.c_int64),
+                                                   _ptr(final_state, C.c_double)))
+        return EnsembleEvaluation(ret, disc, steps, terminal, ties, member_ties, agreement, final_state)
+
 
 Evaluation = collections.namedtuple("Evaluation", "ret disc steps terminal ties final_state")
+EnsembleEvaluation = collections.namedtuple("EnsembleEvaluation", "ret disc steps terminal ties member_ties agreement final_state")
 
 
 class EnsembleResult:

@@ -462,9 +462,45 @@ int  grlx_query_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, int g
  * final state then being those of sines taken outside their domain), GRLX_ENV_EXTERNAL (no environment), projector/tile_coding:safe >= 1
  * ("not built"), an (environment, action count) pair without an instantiation (built: pendulum x {3, 5} actions, acrobot, cart-pole and
  * walker x 3; actor-critic: cart-pole and pendulum).  n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
- * NOT BUILT: per-step trajectories, the epsilon-greedy learning policy, acting on the target network, ensemble votes, the batch path. */
+ * NOT BUILT: per-step trajectories, the epsilon-greedy learning policy, acting on the target network, the batch path. */
 int  grlx_evaluate(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][state_dims]*/, int n_starts,
                    int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state);
+
+/* --- ensemble evaluation: greedy episodes on a group's vote or mean Q --------------------------------------------------------------
+ * Q agents.  The replicas [first_replica, first_replica + n_replicas) form n_replicas / group_size groups of group_size CONSECUTIVE
+ * replicas (the repetitions of one point of a sweep, as in grlx_query_ensemble and grlx_curve_stats_grouped).  For every (group, start
+ * state) pair one episode, on the device, in one launch: grlx_evaluate's loop -- the ignored terminal code of the start state, the
+ * terminal codes 0 / 1 / 2 / 3, max_steps (0 = GRLX_MAX_EPISODE_STEPS), the 2^17 bound on state components -- in which the members of
+ * the group share ONE environment state.  Reference: mapping/policy/discrete/multi (multi_discrete.cpp:120-235).
+ *   The action at observation o.  Over the members m in ASCENDING replica order: q_m[a], mai_m, man_m exactly as grlx_query_q defines
+ *               them (main parameters, peek only, initial_weight for a slot without an entry); votes[a] = the number of members with
+ *               mai_m == a; sumq[a] = one accumulator per action from 0.0 with += q_m[a] in that order (the bits of
+ *               grlx_query_ensemble's sum q column).  score = votes (GRLX_ENSEMBLE_VOTE) or sumq (GRLX_ENSEMBLE_MEAN_Q);
+ *               (mai, man) = findmax(score), the first maximum and the number of maxima; the action is actions[mai].  No random draw.
+ *   ties        += (man > 1) per step: the combined score had more than one maximum
+ *   member_ties += the number of members with man_m > 1, per step
+ *   agreement   += votes[mai] per step, under either rule: agreement / (steps * group_size) is the share of members that would have
+ *               taken the step the ensemble took
+ *   ret, disc, steps, terminal, final_state   as grlx_evaluate's.  disc uses the gamma of the group's FIRST replica: in a sweep context
+ *               a group is one point's repetitions, which share it.
+ * ret, disc, steps, terminal, ties, member_ties, agreement: [n_replicas / group_size][n_starts]; final_state has [state_dims] more.
+ * Host pointers; any output may be NULL.  group_size == 1 is grlx_evaluate (member_ties = its ties).
+ * Deviations from the reference.  Its member "best" is the first strictly greater entry of the member's distribution
+ * (multi_discrete.cpp), which under the greedy sampler is mai_m.  It then SAMPLES from softmax(votes); this entry point acts on the
+ * first maximum and reports ties, as grlx_evaluate does for a single policy.  GRLX_ENSEMBLE_MEAN_Q is not one of the reference's
+ * discrete strategies (its add_prob adds the members' greedy distributions): it is the argmax of grlx_query_ensemble's mean Q.
+ * An evaluation changes nothing in the context, waits for the stream of the last grlx_run, does not count as a launch and stages in
+ * chunks of start states under grlx_set_query_chunk_bytes' bound, like grlx_evaluate.
+ * Validated on the host before anything is launched (GRLX_ERR_INVALID, nothing written, the reason named): everything grlx_evaluate
+ * refuses, group_size < 1, n_replicas % group_size != 0, an unknown rule, an actor-critic context ("not built": a vote over
+ * continuous actions is mapping/policy/multi's).  n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
+ * NOT BUILT: the reference's other discrete strategies (multiply, rank voting, density based), sampling from the combined
+ * distribution, per-step trajectories, the batch path. */
+enum { GRLX_ENSEMBLE_VOTE = 0, GRLX_ENSEMBLE_MEAN_Q = 1 };
+int  grlx_evaluate_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule,
+                            const double *states /*[n_starts][state_dims]*/, int n_starts, int max_steps,
+                            double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                            int64_t *member_ties, int64_t *agreement, double *final_state);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * The per-step plug-in interfaces on the replicas of a context: one call of the reference's interface for EVERY replica per
