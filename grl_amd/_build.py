@@ -12,14 +12,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libgrlx.so")
-SOURCES = ["grlx_kernels.hip", "grlx_fqi.hip", "grlx_snapshot.hip", "grlx_query.hip", "grlx_evaluate.hip", "grlx_api.cpp", "grlx_plan.cpp", "grlx_snapshot_format.cpp"]
+# the C ABI (include/grlx.h), one unit per subject; they share grlx_host.h
+API_UNITS = ["grlx_api_config.cpp", "grlx_api_context.cpp", "grlx_api_run.cpp", "grlx_api_tables.cpp", "grlx_api_step.cpp", "grlx_api_read.cpp", "grlx_api_snapshot.cpp"]
+SOURCES = ["grlx_kernels.hip", "grlx_fqi.hip", "grlx_snapshot.hip", "grlx_query.hip", "grlx_evaluate.hip"] + API_UNITS + ["grlx_plan.cpp", "grlx_snapshot_format.cpp"]
+GRLX_H = os.path.join("..", "..", "include", "grlx.h")
+# what grlx_kernels.hip includes
 HEADERS = ["grlx_internal.h", "grlx_math.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_envs.h", "grlx_policy.h", "grlx_update.h", "grlx_frame.h",
            "grlx_rollout.h", "grlx_rollout_wide.h", "grlx_rollout_ac.h", "grlx_rollout_ac_wide.h", "grlx_rollout_qv.h", "grlx_rollout_acc.h", "grlx_rollout_tgt.h", "grlx_env_server.h", "grlx_env_server_wide.h", "grlx_step.h", "grlx_kernel_table.h",
-           os.path.join("..", "..", "include", "grlx.h")]
-FQI_HEADERS = ["grlx_math_batch.h"]          # included by grlx_fqi.hip only
-SNAPSHOT_HEADERS = ["grlx_snapshot.h", "grlx_snapshot_format.h"]      # grlx_snapshot.hip, grlx_snapshot_format.cpp and grlx_api.cpp only: no rollout kernel sees them
-QUERY_HEADERS = ["grlx_query.h"]            # grlx_query.hip and grlx_api.cpp only: the policy queries, no rollout kernel sees it
-EVALUATE_HEADERS = ["grlx_evaluate.h", "grlx_query_weights.h"]      # grlx_evaluate.hip (and grlx_api.cpp / grlx_query.hip): greedy evaluation episodes; the non-creating table read both units share
+           GRLX_H]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC"]
 TAG_DEFINE = "-DGRLX_BUILD_PIPELINE="
 # per-source device flags.  The batch path runs ONE wave per SIMD (92 KB of LDS per block): nothing but instruction-level parallelism
@@ -51,7 +51,8 @@ def _stale() -> bool:
     except OSError:
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS + FQI_HEADERS + SNAPSHOT_HEADERS + QUERY_HEADERS + EVALUATE_HEADERS] + [os.path.abspath(__file__), os.path.join(HERE, "_exec_prologue.py")]
+    units = set(SOURCES).union(*UNIT_DEPS.values())      # every source and everything a source includes: one list, UNIT_DEPS
+    deps = [os.path.join(CSRC, s) for s in sorted(units)] + [os.path.abspath(__file__), os.path.join(HERE, "_exec_prologue.py")]
     if not os.path.exists(LIB + ".asmfix"):
         return True
     return any(os.path.getmtime(d) > t for d in deps)
@@ -108,16 +109,18 @@ def _build_hip_object(hipcc, src, tmp, flags, verbose, report):
 
 
 # what each translation unit includes (besides itself): an object whose inputs did not change is taken from the object cache
-# (outside the tree: $GRLX_OBJCACHE or /tmp/grlx_objcache), so that editing grlx_api.cpp does not recompile the kernels
+# (outside the tree: $GRLX_OBJCACHE or /tmp/grlx_objcache), so that editing a unit of the C ABI does not recompile the kernels
+API_DEPS = ["grlx_host.h", "grlx_host_rules.h", "grlx_internal.h", "grlx_snapshot.h", "grlx_snapshot_format.h", "grlx_query.h", "grlx_evaluate.h", GRLX_H,
+            os.path.join("..", "..", "include", "grlx_diag.h")]
 UNIT_DEPS = {
-    "grlx_kernels.hip": [h for h in HEADERS],
-    "grlx_fqi.hip": ["grlx_internal.h", "grlx_math.h", "grlx_math_batch.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_envs.h", os.path.join("..", "..", "include", "grlx.h")],
-    "grlx_snapshot.hip": ["grlx_internal.h", "grlx_snapshot.h", "grlx_snapshot_format.h", os.path.join("..", "..", "include", "grlx.h")],
-    "grlx_query.hip": ["grlx_internal.h", "grlx_math.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_query.h", "grlx_query_weights.h", os.path.join("..", "..", "include", "grlx.h")],
-    "grlx_evaluate.hip": ["grlx_internal.h", "grlx_math.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_envs.h", "grlx_query_weights.h", "grlx_evaluate.h", os.path.join("..", "..", "include", "grlx.h")],
-    "grlx_api.cpp": ["grlx_internal.h", "grlx_snapshot.h", "grlx_snapshot_format.h", "grlx_query.h", "grlx_evaluate.h", os.path.join("..", "..", "include", "grlx.h"), os.path.join("..", "..", "include", "grlx_diag.h")],
-    "grlx_snapshot_format.cpp": ["grlx_snapshot_format.h", os.path.join("..", "..", "include", "grlx.h")],
-    "grlx_plan.cpp": ["grlx_internal.h", os.path.join("..", "..", "include", "grlx.h")],
+    "grlx_kernels.hip": HEADERS,
+    "grlx_fqi.hip": ["grlx_internal.h", "grlx_math.h", "grlx_math_batch.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_envs.h", GRLX_H],
+    "grlx_snapshot.hip": ["grlx_internal.h", "grlx_snapshot.h", "grlx_snapshot_format.h", GRLX_H],
+    "grlx_query.hip": ["grlx_internal.h", "grlx_math.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_query.h", "grlx_query_weights.h", GRLX_H],
+    "grlx_evaluate.hip": ["grlx_internal.h", "grlx_math.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_envs.h", "grlx_query_weights.h", "grlx_evaluate.h", GRLX_H],
+    **{unit: API_DEPS for unit in API_UNITS},
+    "grlx_snapshot_format.cpp": ["grlx_snapshot_format.h", GRLX_H],
+    "grlx_plan.cpp": ["grlx_internal.h", GRLX_H],
 }
 
 
@@ -163,7 +166,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
                 _run([hipcc] + flags + [TAG_DEFINE + '"' + PIPELINE + '"', "-c", src, "-o", obj], verbose)
             shutil.copy(obj, key + ".o")
             return key + ".o"
-        with ThreadPoolExecutor(max_workers=len(SOURCES)) as pool:
+        with ThreadPoolExecutor(max_workers=min(len(SOURCES), 16)) as pool:
             objs = list(pool.map(one, SOURCES))
         _run([hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", LIB] + objs, verbose)
     with open(FLAGS_FILE, "w") as f:

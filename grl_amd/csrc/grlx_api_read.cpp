@@ -1,0 +1,245 @@
+// grlx_api_read.cpp -- the C ABI declared in include/grlx.h: the read side -- policy queries and greedy evaluation episodes, chunked over the caller's observations / start states.
+#include "grlx_host.h"
+#include "grlx_query.h"
+#include "grlx_evaluate.h"
+
+// ------------------------------------------------------------------------------------------- policy queries ---
+namespace {
+
+constexpr uint64_t kQueryChunkDefault = 256ull << 20;
+uint64_t g_query_chunk_bytes = kQueryChunkDefault;
+
+bool q_agent(int agent) { return agent != GRLX_AGENT_AC; }      // every other agent acts through a policy/discrete/q on table 0
+
+// the replica range every read names: [first_replica, first_replica + n_replicas) inside the context
+int replica_range_ok(grlx_ctx *ctx, const char *who, int first_replica, int n_replicas)
+{
+  if (first_replica < 0 || n_replicas < 0 || (int64_t)first_replica + n_replicas > ctx->P.n_replicas)
+    return fail(GRLX_ERR_INVALID, "%s: replica range [%d, %lld) is outside the context's %d replicas", who, first_replica,
+                (long long)first_replica + n_replicas, ctx->P.n_replicas);
+  return GRLX_OK;
+}
+
+// what every query checks before it touches the device; tp: the projector of the table read, obs_dims: its share of the observation
+int query_admit(grlx_ctx *ctx, const char *who, int first_replica, int n_replicas, const double *obs, int n_obs, const TileParams &tp, int obs_dims)
+{
+  if (ctx->P.tile_safe >= 1)
+    return fail(GRLX_ERR_INVALID, "%s is not built for projector/tile_coding:safe >= 1 (a read would have to walk the claim table without claiming)", who);
+  if (n_obs < 0) return fail(GRLX_ERR_INVALID, "%s: n_obs = %d", who, n_obs);
+  if (int rc = replica_range_ok(ctx, who, first_replica, n_replicas)) return rc;
+  if (!obs) return fail(GRLX_ERR_INVALID, "%s: obs is null", who);
+  for (int o = 0; o < n_obs; ++o)
+    for (int i = 0; i < obs_dims; ++i)
+    { // tile_quant casts floor(x * scaling) to int (tile_coding.cpp:121-125)
+      const double x = obs[(size_t)o * obs_dims + i];
+      if (!std::isfinite(x)) return fail(GRLX_ERR_INVALID, "%s: observation row %d, dimension %d is not finite (%g)", who, o, i, x);
+      if (!(fabs(x * tp.scaling[i]) < 1073741824.))
+        return fail(GRLX_ERR_INVALID, "%s: observation row %d, dimension %d (%g) is out of range: |x * scaling| reaches 2^30", who, o, i, x);
+    }
+  return GRLX_OK;
+}
+
+// observations per chunk so that one chunk's device arrays stay within the bound; at least one
+int query_chunk(int n_obs, size_t bytes_per_obs)
+{
+  const uint64_t fit = g_query_chunk_bytes / (bytes_per_obs ? bytes_per_obs : 1);
+  return (int)(fit < 1 ? 1 : fit > (uint64_t)n_obs ? (uint64_t)n_obs : fit);
+}
+
+// rows [n_replicas] of `elem` bytes per observation: device [r][chunk] -> host [r][n_obs] at observation o0
+hipError_t query_copy_out(void *host, const void *dev, size_t elem, int n_replicas, int n_obs, int o0, int nc)
+{
+  return hipMemcpy2D((char *)host + (size_t)o0 * elem, (size_t)n_obs * elem, dev, (size_t)nc * elem, (size_t)nc * elem, (size_t)n_replicas,
+                     hipMemcpyDeviceToHost);
+}
+
+// One output of a chunked read: `rows` rows of `elem` bytes per column, copied to `host` when that is not null; `on_device`: the kernels
+// write it (or a reduction reads it) whether the caller asked for it or not.
+struct ReadOut { void *host; size_t elem; int rows; bool on_device; };
+constexpr int kMaxReadOuts = 8;
+
+// The skeleton of every read: the columns of `in` (observations or start states, `in_dims` doubles each) go through the device `chunk` at a
+// time.  Per chunk: the input in, launch(nc, input, outputs) -- device pointers, null for an output neither asked for nor needed -- and out
+// what the caller asked for.  `sync_each`: every output may be null, so the next chunk's copy-in must not overtake the launch.
+template <typename Launch>
+int chunked_read(grlx_ctx *ctx, const ReadOut *outs, int n_outs, int cols, const double *in, int in_dims, int chunk, bool sync_each, Launch launch)
+{
+  DevBuf din, dout[kMaxReadOuts];
+  HIP_TRY(din.alloc(sizeof(double) * (size_t)chunk * in_dims));
+  for (int k = 0; k < n_outs; ++k)
+    if (outs[k].host || outs[k].on_device) HIP_TRY(dout[k].alloc(outs[k].elem * (size_t)outs[k].rows * (size_t)chunk));
+  for (int c0 = 0; c0 < cols; c0 += chunk)
+  {
+    const int nc = cols - c0 < chunk ? cols - c0 : chunk;
+    HIP_TRY(hipMemcpy(din.get(), in + (size_t)c0 * in_dims, sizeof(double) * (size_t)nc * in_dims, hipMemcpyHostToDevice));
+    if (ctx->poison) HIP_TRY(launch_poison_registers(ctx->poison_pattern, nullptr));
+    if (int rc = launch(nc, din.as<double>(), dout)) return rc;
+    for (int k = 0; k < n_outs; ++k)
+      if (outs[k].host) HIP_TRY(query_copy_out(outs[k].host, dout[k].get(), outs[k].elem, outs[k].rows, cols, c0, nc));
+    if (sync_each) HIP_TRY(hipDeviceSynchronize());
+  }
+  return GRLX_OK;
+}
+
+int query_q_impl(grlx_ctx *ctx, const char *who, int first_replica, int n_replicas, int group_size, const double *obs, int n_obs,
+                 double *q, double *value, int32_t *greedy, int32_t *n_max, double *ensemble)
+{
+  if (!ctx) return fail(GRLX_ERR_INVALID, "bad argument");
+  if (!q_agent(ctx->cfg.agent)) return fail(GRLX_ERR_INVALID, "%s serves agents with a policy/discrete/q; the actor-critic's tables are read by grlx_query_state", who);
+  const int NA = ctx->P.A, D = ctx->P.tile.D - 1;
+  if (NA != 3 && NA != 5) return fail(GRLX_ERR_INVALID, "%s is not built for %d actions (3 or 5)", who, NA);
+  int rc = query_admit(ctx, who, first_replica, n_replicas, obs, n_obs, ctx->P.tile, D);
+  if (rc != GRLX_OK) return rc;
+  if (ensemble && (group_size < 1 || n_replicas % group_size != 0))
+    return fail(GRLX_ERR_INVALID, "%s: group_size %d does not divide the %d replicas", who, group_size, n_replicas);
+  if (n_obs == 0 || n_replicas == 0) return GRLX_OK;
+  DRAIN(ctx);
+  const int n_groups = ensemble ? n_replicas / group_size : 0, cols = 2 + 2 * NA;
+  const size_t per_pair = sizeof(double) * (size_t)NA + sizeof(double) + 2 * sizeof(int32_t);
+  const int chunk = query_chunk(n_obs, sizeof(double) * (size_t)D + per_pair * (size_t)n_replicas + sizeof(double) * (size_t)cols * (size_t)n_groups);
+  const bool e = ensemble != nullptr;              // the reduction reads q, value and greedy; the caller of grlx_query_ensemble gets only its result
+  const ReadOut outs[5] = {{q, sizeof(double) * NA, n_replicas, e}, {value, sizeof(double), n_replicas, e}, {greedy, sizeof(int32_t), n_replicas, e},
+                           {n_max, sizeof(int32_t), n_replicas, false}, {ensemble, sizeof(double) * cols, n_groups, false}};
+  return chunked_read(ctx, outs, 5, n_obs, obs, D, chunk, false, [&](int nc, const double *dobs, const DevBuf *d) -> int {
+    QueryArgs A;
+    A.first_replica = first_replica; A.n_replicas = n_replicas; A.n_obs = nc;
+    A.obs = dobs; A.q = d[0].as<double>(); A.value = d[1].as<double>(); A.greedy = d[2].as<int32_t>(); A.n_max = d[3].as<int32_t>();
+    HIP_TRY(launch_query_q(ctx->P, A, nullptr));
+    if (ensemble) HIP_TRY(launch_query_reduce(NA, n_groups, group_size, nc, A.q, A.value, A.greedy, d[4].as<double>(), nullptr));
+    return GRLX_OK;
+  });
+}
+
+} // namespace
+extern "C" {
+
+int grlx_set_query_chunk_bytes(uint64_t bytes)
+{
+  g_query_chunk_bytes = bytes ? bytes : kQueryChunkDefault;
+  set_fqi_query_chunk_bytes(bytes);
+  return GRLX_OK;
+}
+
+int grlx_query_q(grlx_ctx *ctx, int first_replica, int n_replicas, const double *obs, int n_obs, double *q, double *value, int32_t *greedy, int32_t *n_max)
+{
+  return query_q_impl(ctx, "grlx_query_q", first_replica, n_replicas, 0, obs, n_obs, q, value, greedy, n_max, nullptr);
+}
+
+int grlx_query_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, const double *obs, int n_obs, double *out)
+{
+  if (!out) return fail(GRLX_ERR_INVALID, "bad argument");
+  return query_q_impl(ctx, "grlx_query_ensemble", first_replica, n_replicas, group_size, obs, n_obs, nullptr, nullptr, nullptr, nullptr, out);
+}
+
+int grlx_query_state(grlx_ctx *ctx, int table, int first_replica, int n_replicas, const double *obs, int n_obs, double *out)
+{
+  if (!ctx || !out) return fail(GRLX_ERR_INVALID, "bad argument");
+  if (table < 0 || table >= ctx->n_tables) return fail(GRLX_ERR_INVALID, "grlx_query_state: table %d (the context has %d)", table, ctx->n_tables);
+  if (table == 0 && q_agent(ctx->cfg.agent))
+    return fail(GRLX_ERR_INVALID, "grlx_query_state: table 0 of a Q agent takes (observation, action): use grlx_query_q");
+  const TileParams &tp = table == 1 ? ctx->P.tile_actor : ctx->P.tile;
+  int rc = query_admit(ctx, "grlx_query_state", first_replica, n_replicas, obs, n_obs, tp, tp.D);
+  if (rc != GRLX_OK) return rc;
+  if (n_obs == 0 || n_replicas == 0) return GRLX_OK;
+  DRAIN(ctx);
+  const int D = tp.D;
+  const int chunk = query_chunk(n_obs, sizeof(double) * (size_t)D + sizeof(double) * (size_t)n_replicas);
+  const ReadOut outs[1] = {{out, sizeof(double), n_replicas, true}};
+  return chunked_read(ctx, outs, 1, n_obs, obs, D, chunk, false, [&](int nc, const double *dobs, const DevBuf *d) -> int {
+    QueryArgs A;
+    A.first_replica = first_replica; A.n_replicas = n_replicas; A.n_obs = nc;
+    A.obs = dobs; A.q = nullptr; A.value = d[0].as<double>(); A.greedy = nullptr; A.n_max = nullptr;
+    HIP_TRY(launch_query_state(ctx->P, table, A, nullptr));
+    return GRLX_OK;
+  });
+}
+
+// ---- policy evaluation: greedy episodes from start states of the caller's choice (grlx_evaluate.hip) -----------------------------------
+// what both evaluations check before they touch the device
+static int evaluate_admit(grlx_ctx *ctx, const char *who, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps)
+{
+  if (!ctx) return fail(GRLX_ERR_INVALID, "bad argument");
+  if (ctx->cfg.env == GRLX_ENV_EXTERNAL)
+    return fail(GRLX_ERR_INVALID, "%s: the context has no environment (GRLX_ENV_EXTERNAL): there is nothing to step", who);
+  if (ctx->P.tile_safe >= 1)
+    return fail(GRLX_ERR_INVALID, "%s is not built for projector/tile_coding:safe >= 1 (a read would have to walk the claim table without claiming)", who);
+  if (!evaluate_built(ctx->cfg.agent, ctx->cfg.env, ctx->P.A))
+    return fail(GRLX_ERR_INVALID, "%s is not built for environment %d with %d actions (Q agents: pendulum x {3, 5}, acrobot, cart-pole, walker x 3; actor-critic: cart-pole, pendulum)", who,
+                ctx->cfg.env, ctx->cfg.agent == GRLX_AGENT_AC ? 0 : ctx->P.A);
+  if (n_starts < 0) return fail(GRLX_ERR_INVALID, "%s: n_starts = %d", who, n_starts);
+  if (int rc = replica_range_ok(ctx, who, first_replica, n_replicas)) return rc;
+  if (!states) return fail(GRLX_ERR_INVALID, "%s: states is null", who);
+  if (max_steps < 0 || max_steps > GRLX_MAX_EPISODE_STEPS)
+    return fail(GRLX_ERR_INVALID, "%s: max_steps = %d is outside 1 ... GRLX_MAX_EPISODE_STEPS (%d; 0 = that cap)", who, max_steps, GRLX_MAX_EPISODE_STEPS);
+  const int S = ctx->S;
+  for (int s = 0; s < n_starts; ++s)
+    for (int i = 0; i < S; ++i)
+    { // below 2^17 the RK4 stages of one step stay inside the branch-free sine's domain (the cart-pole's case)
+      const double v = states[(size_t)s * S + i];
+      if (!std::isfinite(v)) return fail(GRLX_ERR_INVALID, "%s: state row %d, component %d is not finite (%g)", who, s, i, v);
+      if (!(fabs(v) < 0x1p17)) return fail(GRLX_ERR_INVALID, "%s: state row %d, component %d (%g) is out of range: its magnitude reaches 2^17", who, s, i, v);
+    }
+  return GRLX_OK;
+}
+
+int grlx_evaluate(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, double *ret, double *disc,
+                  int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state)
+{
+  int rc = evaluate_admit(ctx, "grlx_evaluate", first_replica, n_replicas, states, n_starts, max_steps);
+  if (rc != GRLX_OK) return rc;
+  if (max_steps == 0) max_steps = GRLX_MAX_EPISODE_STEPS;
+  const int S = ctx->S;
+  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
+  DRAIN(ctx);
+  const size_t per_pair = 2 * sizeof(double) + 3 * sizeof(int32_t) + sizeof(double) * (size_t)S;
+  const int chunk = query_chunk(n_starts, sizeof(double) * (size_t)S + per_pair * (size_t)n_replicas);
+  const ReadOut outs[6] = {{ret, sizeof(double), n_replicas, true}, {disc, sizeof(double), n_replicas, true}, {steps, sizeof(int32_t), n_replicas, true},
+                           {terminal, sizeof(int32_t), n_replicas, true}, {ties, sizeof(int32_t), n_replicas, true},
+                           {final_state, sizeof(double) * (size_t)S, n_replicas, true}};
+  return chunked_read(ctx, outs, 6, n_starts, states, S, chunk, true, [&](int nc, const double *dst, const DevBuf *d) -> int {
+    EvaluateArgs A;
+    A.first_replica = first_replica; A.n_replicas = n_replicas; A.n_starts = nc; A.max_steps = max_steps;
+    A.states = dst; A.sweep = ctx->sweep ? ctx->sweep_dev.get() : nullptr;
+    A.ret = d[0].as<double>(); A.disc = d[1].as<double>(); A.steps = d[2].as<int32_t>(); A.terminal = d[3].as<int32_t>(); A.ties = d[4].as<int32_t>();
+    A.final_state = d[5].as<double>();
+    HIP_TRY(launch_evaluate(ctx->P, A, nullptr));
+    return GRLX_OK;
+  });
+}
+
+// ---- ensemble evaluation: one episode per (group of consecutive replicas, start state) on the group's vote or mean Q ----------------------
+int grlx_evaluate_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule, const double *states, int n_starts,
+                           int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, int64_t *member_ties,
+                           int64_t *agreement, double *final_state)
+{
+  const char *who = "grlx_evaluate_ensemble";
+  int rc = evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps);
+  if (rc != GRLX_OK) return rc;
+  if (!q_agent(ctx->cfg.agent))
+    return fail(GRLX_ERR_INVALID, "%s is not built for the actor-critic agent (a vote over continuous actions is mapping/policy/multi's); it serves agents with a policy/discrete/q", who);
+  if (group_size < 1) return fail(GRLX_ERR_INVALID, "%s: group_size = %d is below 1", who, group_size);
+  if (n_replicas % group_size != 0) return fail(GRLX_ERR_INVALID, "%s: group_size %d does not divide the %d replicas", who, group_size, n_replicas);
+  if (rule != GRLX_ENSEMBLE_VOTE && rule != GRLX_ENSEMBLE_MEAN_Q)
+    return fail(GRLX_ERR_INVALID, "%s: unknown rule %d (GRLX_ENSEMBLE_VOTE = 0, GRLX_ENSEMBLE_MEAN_Q = 1)", who, rule);
+  if (max_steps == 0) max_steps = GRLX_MAX_EPISODE_STEPS;
+  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
+  DRAIN(ctx);
+  const int S = ctx->S, n_groups = n_replicas / group_size;
+  const size_t per_pair = 2 * sizeof(double) + 3 * sizeof(int32_t) + 2 * sizeof(int64_t) + sizeof(double) * (size_t)S;
+  int chunk = query_chunk(n_starts, sizeof(double) * (size_t)S + per_pair * (size_t)n_groups);
+  if ((int64_t)chunk * n_groups > 0x7fffffff) chunk = 0x7fffffff / n_groups;      // one block per pair: the grid's bound
+  const ReadOut outs[8] = {{ret, sizeof(double), n_groups, true}, {disc, sizeof(double), n_groups, true}, {steps, sizeof(int32_t), n_groups, true},
+                           {terminal, sizeof(int32_t), n_groups, true}, {ties, sizeof(int32_t), n_groups, true}, {member_ties, sizeof(int64_t), n_groups, true},
+                           {agreement, sizeof(int64_t), n_groups, true}, {final_state, sizeof(double) * (size_t)S, n_groups, true}};
+  return chunked_read(ctx, outs, 8, n_starts, states, S, chunk, true, [&](int nc, const double *dst, const DevBuf *d) -> int {
+    EnsembleArgs A;
+    A.first_replica = first_replica; A.n_replicas = n_replicas; A.group_size = group_size; A.rule = rule;
+    A.n_starts = nc; A.max_steps = max_steps; A.states = dst; A.sweep = ctx->sweep ? ctx->sweep_dev.get() : nullptr;
+    A.ret = d[0].as<double>(); A.disc = d[1].as<double>(); A.steps = d[2].as<int32_t>(); A.terminal = d[3].as<int32_t>(); A.ties = d[4].as<int32_t>();
+    A.member_ties = d[5].as<int64_t>(); A.agreement = d[6].as<int64_t>(); A.final_state = d[7].as<double>();
+    HIP_TRY(launch_evaluate_ensemble(ctx->P, A, nullptr));
+    return GRLX_OK;
+  });
+}
+
+} // extern "C"

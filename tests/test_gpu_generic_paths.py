@@ -502,6 +502,67 @@ def test_results_do_not_depend_on_stale_register_content(grlx, monkeypatch, patt
     _run_both(grlx, [51, 52, 53, 54], 12, {}, chunks=[5, 7])
 
 
+@pytest.mark.parametrize("graph,log2_capacity", [("pendulum_sarsa", 10), ("pendulum_sarsa", 12), ("cart_pole_ac", 16)])
+def test_every_lazily_created_group_survives_create_and_destroy_churn(grlx, graph, log2_capacity):
+    """What a context creates on first use -- the environment server's mailboxes, stream and events, the diagnostics buffer, the staging
+    buffers and the agent state of the per-step entries, the buffers of a query -- is owned by the context and goes with it.  Twenty
+    contexts in one process each create all of it, reset the run, run again and close; every call succeeds and the last context's rows,
+    streams and model state are the first one's bit for bit.  One trial in two is a test trial, so that two trials leave a row.
+
+    Two pendulum trials touch 2 235 to 3 790 slots per replica (measured, these seeds).  Tables of 2^10 entries cannot hold them, and a launch
+    cannot grow its tables: there grlx_sync reports GRLX_ERR_TABLE_FULL after either run, as it did before the context owned its memory,
+    and that refusal is what the case asserts beside the churn -- three contexts only: a launch that probes full tables takes a quarter
+    of a second.  2^12 is the smallest capacity at which every call succeeds."""
+    seeds = [71, 72, 73, 74]
+    n = len(seeds)
+    make = grlx.pendulum_sarsa_config if graph == "pendulum_sarsa" else grlx.cart_pole_ac_config
+    cfg = make(n, table_log2_capacity=log2_capacity, test_interval=1)
+    overflows = log2_capacity == 10
+
+    def run_two_trials(r):
+        r.run(2)
+        if not overflows:
+            r.sync()
+            return
+        with pytest.raises(grlx.capi.GrlxError) as ei:
+            r.sync()
+        assert ei.value.code == grlx.capi.ERR_TABLE_FULL
+
+    seen = []
+    for _ in range(3 if overflows else 20):
+        r = grlx.Runner(cfg, seeds)
+        run_two_trials(r)
+        first = [[np.array(c) for c in r.rows(k)] for k in range(n)]
+        r.set_diag(True)
+        assert r.read_diag().shape == (1, 8)
+        obs = r.env_start(0)
+        with pytest.raises(grlx.capi.GrlxError) as ei:          # refused by design while diagnostics are on
+            r.agent_start(0, obs)
+        assert ei.value.code == grlx.capi.ERR_INVALID and "diagnostics" in str(ei.value)
+        r.set_diag(False)
+        action = r.agent_start(0, obs)
+        assert action.shape == (n,) and np.isfinite(action).all()
+        if graph == "pendulum_sarsa":
+            q, value, greedy, n_max = r.query_q(obs)
+            assert q.shape == (n, n, 3) and np.isfinite(q).all()
+        else:
+            assert np.isfinite(r.query_state(obs, 0)).all()
+        r.reset_run()
+        run_two_trials(r)
+        second = [[np.array(c) for c in r.rows(k)] for k in range(n)]
+        seen.append((first, second, [list(r.rng(k)) for k in range(n)], [np.array(r.env_state(k)) for k in range(n)]))
+        r.close()
+    if overflows:
+        return
+    for k in range(n):
+        for run in (0, 1):
+            a, b = seen[0][run][k], seen[-1][run][k]
+            assert len(a[0]) == 1 and list(a[0]) == list(b[0]) and list(a[1]) == list(b[1])
+            assert_bit_equal(a[2], b[2], f"replica {k}, run {run}: returns of the first and the last context")
+        assert seen[0][2][k] == seen[-1][2][k], f"replica {k}: streams"
+        assert_bit_equal(seen[0][3][k], seen[-1][3][k], f"replica {k}: model state")
+
+
 # ------------------------------------------------ sparse tables that grow between launches ---
 def test_tables_grow_between_the_launches_of_one_call(grlx):
     """A deployer runs a whole run as ONE grlx_run, which the library chunks into launches of 32 trials: the tables must grow BETWEEN those
@@ -531,7 +592,7 @@ def test_tables_grow_between_the_launches_of_one_call(grlx):
 def test_tables_grow_between_launches(grlx, kind):
     """grlx_config.table_log2_capacity is the INITIAL size: started at 2^13 entries per replica, with a grlx_sync between
     launches the tables are re-hashed into larger ones whenever the fullest passes a quarter of its capacity
-    (grlx_api.cpp grow_tables, rehash_kernel).  Positions are internal -- to the tables, to the actor-critic's persisted
+    (grlx_api_context.cpp grow_tables, rehash_kernel).  Positions are internal -- to the tables, to the actor-critic's persisted
     critic trace and to the target network's values, which are translated -- so rows, RNG positions, environment state and
     weights must equal the oracle's as with large tables, for every kernel family that keeps positions."""
     from tests import configs

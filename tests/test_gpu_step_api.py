@@ -265,6 +265,44 @@ def test_both_sides_on_the_gpu_one_call_per_step_equal_the_fused_run(grlx, name,
     whole.close(); fresh.close(); fused.close(); stepped.close()
 
 
+# initial capacity (log2 entries per replica and table) of the stepped context.  A table found beyond a quarter full at one of the looks
+# (every 64 agent calls) grows until it is at most an eighth full.  After the trials of GRAPHS, with the seeds of the test:
+#   pendulum_sarsa: table_load 8 136 to 9 348 slots per replica, 2^13 = 8 192 entries have grown to 2^17
+#   cart_pole_ac:   table_load 9 754 to 13 188 slots per replica in either (twin) table, 2^13 has grown to 2^17
+GROWING_LOG2 = {"pendulum_sarsa": 13, "cart_pole_ac": 13}
+
+
+@pytest.mark.parametrize("name", ["pendulum_sarsa", "cart_pole_ac"])
+def test_tables_grow_between_per_step_calls_and_the_run_equals_the_fused_one(grlx, name):
+    """The per-step agent entries look at the tables' load every 64 calls and grow them like the fused path does between launches
+    (grow_if_loaded).  A context that starts with small tables and is driven one call per step must grow on the way -- the actor-critic's
+    two tables together, its persisted trace translated to the new positions -- and still equal the fused run bit for bit."""
+    seeds = [11, 12, 13, 14, 15, 16]
+    n, trials = len(seeds), GRAPHS[name][1]
+    cfg, spec = make(grlx, name, n)
+    fused = grlx.Runner(cfg, seeds)
+    fused.run(trials); fused.sync()
+    small, _ = make(grlx, name, n, table_log2_capacity=GROWING_LOG2[name])
+    stepped = grlx.Runner(small, seeds)
+    assert stepped.table_capacity() == GROWING_LOG2[name]
+    loop = HostLoop(n, small.test_interval, GpuEnv(stepped), GpuAgent(stepped))
+    loop.run(trials)
+    whole = ob.Experiment(spec, seed=seeds[1]); fresh = ob.Experiment(spec, seed=seeds[1])
+    whole.run(trials)
+    tables = (0, 1) if name == "cart_pole_ac" else (0,)
+    slots = {t: touched_slots(whole, fresh, t) for t in tables}
+    print(f"{name}: capacity 2^{GROWING_LOG2[name]} -> 2^{stepped.table_capacity()}, table_load {[[stepped.table_load(k, t) for t in tables] for k in range(n)]}")
+    for k in range(n):
+        assert_rows_equal(loop.rows[k], rows_of(fused, k), f"{name} replica {k}")
+        assert list(stepped.rng(k)) == list(fused.rng(k)), f"replica {k}: streams"
+        assert_bit_equal(stepped.env_state(k), fused.env_state(k), f"replica {k}: model state")
+        for t in tables:
+            assert_bit_equal(stepped.weights(k, slots[t], table=t), fused.weights(k, slots[t], table=t), f"replica {k}: table {t}")
+            assert stepped.table_load(k, t) == fused.table_load(k, t)
+    assert stepped.table_capacity() > GROWING_LOG2[name], "the tables did not grow: the case pins nothing"
+    whole.close(); fresh.close(); fused.close(); stepped.close()
+
+
 @pytest.mark.parametrize("name", ["pendulum_sarsa", "cart_pole_ac"])
 def test_fused_launches_and_per_step_calls_mix_on_one_context(grlx, name):
     """Per-step calls for some trials, grlx_run for the next ones, per-step calls again -- on ONE context: the state each side leaves
