@@ -177,9 +177,14 @@ def build(force: bool = False, verbose: bool = False) -> str:
     return LIB
 
 
-HOST_SOURCES = ["configurable.cpp", "objects.cpp", "multi_gpu.cpp", "grlxd.cpp"]       # multi_gpu.cpp: `grlxd -g N` (HIP runtime API + RCCL)
-OPS_SOURCES = ["configurable.cpp", "objects.cpp", "multi_gpu.cpp", "grlx_ops.cpp"]    # grlx_ops: Projector::project / Environment::step from the command line
-HOST_HEADERS = ["configurable.h", "objects.h", "multi_gpu.h"]
+# the host layer both binaries share, one unit per subject.  Every unit registers its classes from static
+# objects, so each is linked as an object of its own, never through an archive that could drop one.
+# multi_gpu.cpp: `grlxd -g N` (HIP runtime API + RCCL)
+HOST_UNITS = ["configurable.cpp", "objects_env.cpp", "objects_agent.cpp", "objects_csv.cpp", "objects_batch.cpp", "objects_online.cpp",
+              "objects_reports.cpp", "objects_multi.cpp", "multi_gpu.cpp"]
+HOST_SOURCES = HOST_UNITS + ["grlxd.cpp"]
+OPS_SOURCES = HOST_UNITS + ["grlx_ops.cpp"]    # grlx_ops: Projector::project / Environment::step from the command line
+HOST_HEADERS = ["configurable.h", "objects.h", "objects_impl.h", "report_rules.h", "multi_gpu.h"]
 BINDIR = os.path.join(HERE, "bin")
 GRLXD = os.path.join(BINDIR, "grlxd")
 GRLX_OPS = os.path.join(BINDIR, "grlx_ops")
@@ -193,16 +198,28 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
     if not force and os.path.exists(GRLXD) and os.path.exists(GRLX_OPS) and all(os.path.getmtime(d) <= min(os.path.getmtime(GRLXD), os.path.getmtime(GRLX_OPS)) for d in deps):
         return GRLXD
     os.makedirs(BINDIR, exist_ok=True)
-    for out, sources in ((GRLXD, HOST_SOURCES), (GRLX_OPS, OPS_SOURCES)):
-        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", "-o", out] + \
-              [os.path.join(hostdir, f) for f in sources] + \
-              ["-L" + LIBDIR, "-lgrlx", "-L/opt/rocm/lib", "-lrccl", "-lamdhip64", "-Wl,-rpath,$ORIGIN/../lib", "-Wl,-rpath,/opt/rocm/lib",
-               "-Wl,-rpath-link,/opt/rocm/lib"]
+    import tempfile
+    from concurrent.futures import ThreadPoolExecutor
+
+    def gxx(args):
+        cmd = ["g++", "-O2", "-std=c++17", "-Wall", "-Wextra", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"] + args
         if verbose:
             print(" ".join(cmd))
         res = subprocess.run(cmd, capture_output=True, text=True)
         if res.returncode != 0:
             raise RuntimeError("g++ failed:\n" + res.stdout + res.stderr)
+        if verbose and res.stderr:
+            print(res.stderr)            # warnings
+
+    with tempfile.TemporaryDirectory(prefix="grlx_host_") as tmp:
+        units = sorted(set(HOST_SOURCES + OPS_SOURCES))        # every unit is compiled once and linked into the binaries that list it
+        obj = {f: os.path.join(tmp, os.path.splitext(f)[0] + ".o") for f in units}
+        with ThreadPoolExecutor(max_workers=min(len(units), 16)) as pool:
+            list(pool.map(lambda f: gxx(["-c", os.path.join(hostdir, f), "-o", obj[f]]), units))
+        for out, sources in ((GRLXD, HOST_SOURCES), (GRLX_OPS, OPS_SOURCES)):
+            gxx(["-o", out] + [obj[f] for f in sources] +
+                ["-L" + LIBDIR, "-lgrlx", "-L/opt/rocm/lib", "-lrccl", "-lamdhip64", "-Wl,-rpath,$ORIGIN/../lib", "-Wl,-rpath,/opt/rocm/lib",
+                 "-Wl,-rpath-link,/opt/rocm/lib"])
     return GRLXD
 
 

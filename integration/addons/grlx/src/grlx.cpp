@@ -306,7 +306,7 @@ LargeVector GrlxOnlineLearningExperiment::run()
       // load_file: the .dat parameter files a (CPU or GPU) grl saved; names as ParameterizedRepresentation builds them
       // (representation.h:201-229: <file><config path with '/' -> '_'>.dat), `$run` replaced by the run number
       // ... one grlx_load_weights(ctx, table, 0, replicas_, data, count) per representation of the agent (table 0 =
-      // Q / critic, table 1 = actor / V) exactly as grl_amd/csrc/host/objects.cpp does; omitted when load_file is empty.
+      // Q / critic, table 1 = actor / V) exactly as grl_amd/csrc/host/objects_online.cpp does (names: rules::dat_name, report_rules.h); omitted when load_file is empty.
 
       // the trial loop with both of its bounds (online_learning.cpp:154); with a steps budget the clones stop at trials of their own
       if (steps_) check(grlx_run_steps(ctx, trials_ ? trials_ : (1 << 30), (uint64_t)steps_, NULL));

@@ -261,9 +261,69 @@ def test_deployer_multi_gpu_ranks_fail_cleanly_without_devices(tmp_path):
 
 def test_a_predictor_without_a_trace_block_is_accepted(grlxd, tmp_path):
     """`trace` is an optional parameter of the predictors (sarsa.cpp:45): without the block the host layer builds a configuration
-    with GRLX_TRACE_NONE (objects.cpp, `pred->trace ? ... : GRLX_TRACE_NONE`) instead of refusing the yaml.  `-n` stops after the
+    with GRLX_TRACE_NONE (objects_online.cpp, `pred->trace ? ... : GRLX_TRACE_NONE`) instead of refusing the yaml.  `-n` stops after the
     configuration is lowered, before anything touches a device; what such a context computes is tests/test_gpu_no_trace.py's."""
     block = "      trace:\n        type: trace/enumerated/replacing\n"
     res = run(grlxd, ["-s", "1", "-r", "2", "-n", _variant(tmp_path, block, "")], tmp_path)
     assert res.returncode == 0, res.stderr
     assert [ln.split()[:2] for ln in res.stdout.strip().split("\n")] == [["0", "1"], ["1", "2"]]
+
+
+# every type the host layer registers (the GRLX_TYPEINFO strings of its units)
+TYPES = ["dynamics/pendulum", "task/pendulum/swingup", "dynamics/acrobot", "task/acrobot/balancing", "dynamics/cart_pole", "task/cart_pole/swingup",
+         "model/compass_walker", "task/compass_walker/walk", "model/dynamical", "environment/modeled", "discretizer/uniform", "projector/tile_coding",
+         "representation/parameterized/linear", "sampler/greedy", "sampler/epsilon_greedy", "mapping/policy/action", "mapping/policy/discrete/value/q",
+         "mapping/policy/discrete/q", "trace/enumerated/replacing", "trace/enumerated/accumulating", "predictor/critic/sarsa", "predictor/critic/q",
+         "predictor/critic/advantage", "predictor/critic/expected_sarsa", "predictor/critic/qv", "predictor/sarsa", "predictor/q", "predictor/critic/td",
+         "predictor/ac/action", "agent/td", "agent/fixed", "exporter/csv", "projector/identity", "projector/pre/normalizing",
+         "representation/parameterized/ann", "representation/iterative", "predictor/fqi", "experiment/batch_learning", "experiment/online_learning",
+         "experiment/multi"]
+
+
+def test_every_registered_type_is_still_constructible(grlxd, tmp_path):
+    """The classes register themselves from static objects of several units, each linked into both binaries as an object of its own: a
+    unit left out of a binary would drop its types without a build error.  A top-level section of a known type is constructed (and then
+    stops at its first required parameter, or at the missing experiment); one of an unknown type is skipped with a warning."""
+    y = tmp_path / "one.yaml"
+    for t in TYPES + ["dynamics/flyer2d"]:
+        y.write_text("thing:\n  type: %s\n" % t)
+        res = run(grlxd, ["-s", "1", "-q", str(y)], tmp_path)
+        assert res.returncode == 1
+        unknown = "skipping top-level section" in res.stderr or "unknown object type" in res.stderr
+        assert unknown == (t == "dynamics/flyer2d"), t + "\n" + res.stderr
+    # ... and in the second binary, which links the same units: the committed yamls instantiate whole, so the command gets as far as
+    # finding that an experiment is no projector (before anything asks for a device)
+    ops = os.path.join(os.path.dirname(grlxd), "grlx_ops")
+    rows = tmp_path / "rows.txt"
+    rows.write_text("0 0 0\n")
+    for name in ("pendulum-sarsa-tc.yaml", "cart_pole-ac-tc.yaml", "compass_walker-q-tc.yaml", "pendulum-fqi-ann.yaml"):
+        res = subprocess.run([ops, "project", os.path.join(ROOT, "tests", "golden", name), "experiment", str(rows)], cwd=tmp_path, capture_output=True,
+                             text=True, timeout=60)
+        assert res.returncode == 1 and "experiment: not a projector" in res.stderr, name + "\n" + res.stderr
+
+
+def test_an_oversized_transition_log_is_refused_before_a_device_is_asked_for(grlxd, tmp_path):
+    """An exporter/csv taps every step of replica 0 on the device: 100,000 trials of 102 rows do not fit the tap buffer.  The refusal
+    belongs to the plan of the run, which needs no device: it comes on a machine without one, too, and before "no HIP device"."""
+    text = open(YAML).read()
+    assert "trials: 2000" in text and '  load_file: ""\n' in text
+    p = tmp_path / "variant.yaml"
+    p.write_text(text.replace("trials: 2000", "trials: 100000").replace('  load_file: ""\n', '  exporter:\n    type: exporter/csv\n    file: log\n  load_file: ""\n'))
+    res = run(grlxd, ["-s", "1", "-q", str(p)], tmp_path)
+    assert res.returncode != 0
+    assert "too large for the device-side tap buffer" in res.stderr, res.stderr
+    assert "no HIP device" not in res.stderr + res.stdout
+    assert not list(tmp_path.glob("*.csv")) and not list(tmp_path.glob("*.txt"))
+
+
+@pytest.mark.gpu
+def test_a_sweep_too_short_for_its_regret_is_refused_and_releases_the_device(grlxd, tmp_path):
+    """The simple regret of a sweep is the mean of the last rows / 20 rewards: ten trials with a test every eleventh write no row, and the run
+    is refused AFTER its context exists and its trials ran.  The context goes with the refusal: an ordinary run right after it succeeds."""
+    res = run(grlxd, ["-s", "5", "-r", "2", "-t", "10", "-q", "-p", "/experiment/agent/predictor/alpha=0.1,0.2", YAML], tmp_path)
+    assert res.returncode != 0
+    assert "at least 20 rows" in res.stderr, res.stderr
+    assert not list(tmp_path.glob("*-sweep.txt"))
+    res = run(grlxd, ["-s", "5", "-r", "2", "-t", "12", "-q", YAML], tmp_path)
+    assert res.returncode == 0, res.stderr
+    assert len((tmp_path / "pendulum-sarsa-tc-0@0.txt").read_text().strip().split("\n")) == 1
