@@ -26,6 +26,12 @@
 // The pass of the rollout wave exists twice (rollout_body, grlx_rollout.h): a full wave whose four replicas are all served and in mid-episode
 // takes its answers with ONE vote of the whole wave (mail_take_wave) in a loop of straight-line passes; a take that runs into its bound
 // there changes nothing and leaves that loop, and the general pass takes the same step again with mail_take, per replica, as described above.
+// The early take (SPEC::kEarlyTake, the specialised instantiations).  cand[n & 1][.] is stored the moment command n arrives -- a pass before
+// the sampler that chooses among its three states.  Inside that loop a pass therefore loads all fifteen units of cand[n & 1] during its
+// table phase (mail_prefetch_all), votes on their tags once its sampler has chosen (mail_vote_all, the same bound) and hands the chosen
+// candidate round (mail_hand_round): no trip through memory between the choice and the next state, and mail_take_wave is left with the
+// first pass of every visit to the loop.  A vote that runs into its bound changes nothing: the pass sends its command, issues the classic
+// mail_prefetch and leaves the loop, as above.  Such a pass loads 256 B per replica from the mailbox where the others load 80 B.
 #pragma once
 
 namespace grlx {
@@ -223,6 +229,55 @@ __device__ __forceinline__ bool mail_take_wave(const DevParams &N, const MailBox
   terminal = x[2] > N.timeout ? 1 : 0;                            // Env::observe
   if (!Env<ENV>::in_domain(x)) status |= ST_DOMAIN;             // env_step
   return true;
+}
+// The early take of the wave-uniform loop.  cand[n & 1][.] is stored the moment command n arrives, so while pass k + 1 (which follows
+// command n) works through its table phase the answers to ALL of its possible actions are already in the mailbox: lane j < 15 of a group
+// loads unit j of cand[n & 1] -- the three candidates are contiguous, unit 5 a + u at byte 16 (5 a + u) -- and lane 15 loads unit 0 again
+// (any valid unit: it only votes).  One 16-byte load per lane, as mail_prefetch; its trip through memory hides behind the trace
+// forwarding, the sums and the sampler.  Once the sampler has chosen a, mail_vote_all agrees on the tags (bounded polling, as
+// mail_take_wave; on running into the bound NOTHING has changed) and mail_hand_round gives every lane the five values of candidate a.
+// vmcnt(0) said in the source, for a place where nothing is in flight but the compiler cannot know it (its own wait would come later,
+// behind a store, and wait for that store)
+__device__ __forceinline__ void mail_nothing_in_flight() { __builtin_amdgcn_s_waitcnt(0x0F70); }
+__device__ __forceinline__ mail_u32x4 mail_prefetch_all(const MailBox &b, unsigned long long seq, int j)
+{
+  static_assert(sizeof(((EnvMail *)nullptr)->cand[0]) == 3 * kCandUnits * sizeof(MailUnit), "the three candidates of a command are contiguous");
+  // (b.at already holds unit j for j < 5 and unit 0 for the other lanes)
+  const unsigned unit = (j >= kCandUnits && j < 3 * kCandUnits) ? (unsigned)j : 0u;
+  const unsigned off = b.at + unit * (unsigned)sizeof(MailUnit) + ((unsigned)seq & 1u) * (unsigned)(3 * kCandUnits * sizeof(MailUnit));
+  return __builtin_amdgcn_raw_buffer_load_b128(b.rs, off, 0, 16);         // 16 = sc1: device scope
+}
+__device__ __forceinline__ bool mail_vote_all(const MailBox &b, mail_u32x4 &d, unsigned long long seq, int j, unsigned long long *polled = nullptr)
+{
+  unsigned polls = 0;
+  while (!__all((((unsigned long long)d.w << 32) | d.z) == seq))
+  {
+    if (++polls > kFetchPolls)
+    {
+      if (polled) *polled += polls;
+      return false;
+    }
+    d = mail_prefetch_all(b, seq, j);
+  }
+  if (polled) *polled += polls;
+  return true;
+}
+// (after a successful mail_vote_all; `a` is the group's: the same in its sixteen lanes, any of the three from group to group)
+template <int ENV>
+__device__ __forceinline__ void mail_hand_round(const DevParams &N, const mail_u32x4 &d, int a, int g, double *x, double *obs, double &reward,
+                                                int &terminal, uint32_t &status)
+{
+  static_assert(ENV == GRLX_ENV_PENDULUM, "the pendulum's mailbox");
+  const double v = __longlong_as_double((long long)(((unsigned long long)d.y << 32) | d.x));
+  const int base = g * 16 + kCandUnits * a;
+  x[0] = lane_fetch(v, base + 0);
+  x[1] = lane_fetch(v, base + 1);
+  x[2] = lane_fetch(v, base + 2);
+  obs[0] = lane_fetch(v, base + 3);
+  obs[1] = x[1];
+  reward = lane_fetch(v, base + 4);
+  terminal = x[2] > N.timeout ? 1 : 0;                            // Env::observe
+  if (!Env<ENV>::in_domain(x)) status |= ST_DOMAIN;             // env_step
 }
 
 // The server: block b serves the replicas 4b .. 4b+3 of rollout wave b.  It looks TWO steps ahead: lane 16 q + 3 a + a2 (a, a2 < NA) of

@@ -62,6 +62,9 @@ __device__ const DevParams d_spec_pendulum_tc = make_spec_pendulum_tc();
 // (a literal in a specialised build) -- what every policy but SpecSweep inherits.  `Rep` is what a lane keeps per replica: nothing here.
 struct SpecShared {
   static constexpr bool kPerReplica = false;
+  // rollout_served_kernel: does the wave-uniform loop take the next pass's environment step at the sampler (the rotated loop of
+  // rollout_body)?  It costs registers across the loop that only a specialised instantiation has
+  static constexpr bool kEarlyTake = false;
   struct Rep {};
   __device__ static __forceinline__ Rep replica(const SweepParams *, int) { return Rep{}; }
   __device__ static __forceinline__ double alpha(const DevParams &N, const Rep &) { return N.alpha; }
@@ -73,6 +76,7 @@ struct SpecShared {
 // AGENT: the predictor kind is a compile-time constant of the instantiation too (one per TD agent)
 template <int AGENT>
 struct SpecPendulumTcA : SpecShared {
+  static constexpr bool kEarlyTake = true;
   __device__ static __forceinline__ int agent(const DevParams &) { return AGENT; }
   // every numeric field the rollout kernel reads must equal the constant, bit for bit
   static bool matches(const DevParams &P)
@@ -397,20 +401,47 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials, c
         static_assert(!Env<ENV>::kAbsorbing, "has_next is taken as true");
         if (__all(live && running && !first && srv && !test && pd) && !(P.env_tune & 16u))
         {
-          do
-          {
-            DIAG_STAMP(0)
-            // [environment step] the candidate of the action taken; the vote is the whole wave's.  Not there within the bound: nothing has
-            // changed, the general pass takes this step (polls again, falls back per replica)
+          // [environment step] the candidate of the action taken, loaded ahead with mail_prefetch; the vote is the whole wave's.  Not there
+          // within the bound: nothing has changed, the general pass takes this step (polls again, falls back per replica)
+          auto take_classic = [&]() -> bool {
 #ifdef GRLX_ENV_SERVER_STATS
             const unsigned long long tf0 = mail_clock();
             const bool stepped = mail_take_wave<ENV>(N, mbox, mpre, mseq - 1, action_index, g, x, obs, reward, terminal, status, &st_polls);
             st_wait += mail_clock() - tf0;
             ++st_fetch;
+            return stepped;
 #else
-            const bool stepped = mail_take_wave<ENV>(N, mbox, mpre, mseq - 1, action_index, g, x, obs, reward, terminal, status);
+            return mail_take_wave<ENV>(N, mbox, mpre, mseq - 1, action_index, g, x, obs, reward, terminal, status);
 #endif
-            if (!stepped) break;
+          };
+          // EARLY (SPEC::kEarlyTake, profiles/served_early_take_ab.md): the loop is ROTATED.  A pass takes the NEXT pass's environment step at
+          // its own sampler -- the server stored the answers to all three actions a pass ago, so no trip through memory is left between the
+          // sampler's choice and the state it leads to -- and only the first pass of the loop takes its step here, as a prologue.  The
+          // next pass's hashing and bucket loads then follow the target and the bookkeeping at once:
+          //   [prologue: take]  count, hash, fence, issue -> update -> finish -> load the 15 candidate units -> forward, sums, sampler
+          //                     -> vote -> command -> target, bookkeeping -> held eviction -> hand the chosen candidate round -> next pass
+          // Order of table accesses: the only table store that lay between the old issue point and the new one is the held eviction, and
+          // it still precedes the fence and the loads; the deferred update of the next pass still follows those loads; the `risky`
+          // reload and the held-eviction patch keep their order.  A pass that is terminal in any lane, or whose vote runs into its bound,
+          // ends as the pass always did (per-lane command, the classic five-unit load ahead) and leaves the loop with nothing taken and
+          // nothing issued: the general pass takes that step with mail_take.
+          // !EARLY: every pass takes its own step at its top (the loop as it was: the generic instantiation has no register to spare).
+          constexpr bool EARLY = SPEC::kEarlyTake;
+          bool go = true;
+          if constexpr (EARLY)
+          {
+            DIAG_STAMP(0)
+            go = take_classic();
+            mail_nothing_in_flight();      // (as below, for the way into the loop: or the loop's head waits for the command's store)
+          }
+          if (go)
+          do
+          {
+            if constexpr (!EARLY)
+            {
+              DIAG_STAMP(0)
+              if (!take_classic()) break;
+            }
             ++n_uniform;
             total_reward += reward;                                          // :202
             time += 1;                                                       // tau = 1
@@ -487,6 +518,11 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials, c
               for (int a = 0; a < NA; ++a) w[a] = (held && pos[a] == ev.pos) ? ev.val : w[a];
               wp = (held && p_pos == ev.pos) ? ev.val : wp;
             }
+            // [EARLY: the next environment step, for every action] cand[mseq & 1][.] was stored when command mseq arrived, a pass ago.
+            // (Behind the reloads, not in front of them: the wait for a reload, which the compiler also places on the path that
+            // did not reload, would wait for this load too.)
+            mail_u32x4 mall = {0u, 0u, 0u, 0u};
+            if constexpr (EARLY) mall = mail_prefetch_all(mbox, mseq, j);
             // [trace_forward, the LDS rows]
 #pragma unroll
             for (int a = 0; a < NA; ++a)
@@ -526,60 +562,112 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials, c
             }
             else
               a_next = (man > 1) ? tie_break<NA>(q, best, man, G) : mai;
-            // [the command] (per lane: a side-effect guard, no state lives in it)
-            if (!terminal)
+            // [EARLY: the vote] every tag must be mseq; a bounded poll otherwise.  No lane may be terminal: a terminal pass has no
+            // successor in this episode
+            bool early = false;
+            if constexpr (EARLY)
             {
+              DIAG_STAMP(4)
+              if (!__any(terminal != 0))
+              {
+#ifdef GRLX_ENV_SERVER_STATS
+                const unsigned long long tf1 = mail_clock();
+                early = mail_vote_all(mbox, mall, mseq, j, &st_polls);
+                st_wait += mail_clock() - tf1;
+                ++st_fetch;
+#else
+                early = mail_vote_all(mbox, mall, mseq, j);
+#endif
+              }
+            }
+            // [predictor update: the target, queued for the next pass], [bookkeeping], [the eviction held back by the deferred update]
+            auto pass_tail = [&]() {
+              DIAG_STAMP(4)
+              // [predictor update: the target, queued for the next pass]
+              {
+                double target = reward;
+                if (SPEC::agent(P) == GRLX_AGENT_SARSA)
+                  target += SPEC::gamma(N, rep) * pick<double, NA>(q, a_next);
+                else if (SPEC::agent(P) == GRLX_AGENT_EXPECTED_SARSA)
+                { // QPolicy::value (q.cpp:60-73) = sum_a Q(s',a) * EpsilonGreedySampler::distribution (greedy.cpp:220-238)
+                  const double de = eps_decay * SPEC::epsilon(N, rep);
+                  double v = 0;
+#pragma unroll
+                  for (int kk = 0; kk < NA; ++kk)
+                  {
+                    double d = (q[kk] == best) ? 1. / man : 0.;
+                    if (d == 1) d = 1 - de;
+                    d += de / NA;
+                    v += q[kk] * d;
+                  }
+                  target += SPEC::gamma(N, rep) * v;
+                }
+                else
+                {
+                  double v = -__builtin_inf();
+#pragma unroll
+                  for (int kk = 0; kk < NA; ++kk) v = fmax(v, q[kk]);
+                  target += SPEC::gamma(N, rep) * v;
+                }
+                const double delta = target - qsa;
+                pd_dW = SPEC::alpha(N, rep) * (target - qsa);                    // LinearRepresentation::write (linear.cpp:186-196)
+                pd_dT = SPEC::alpha(N, rep) * delta;                             // VectorConstructor(alpha_*delta)
+                pd_pos = p_pos;
+                status |= (p_pos == kInvalidPos) ? ST_BAD_POS : 0u;
+                pd_sh = p_sh;
+                pd_wp = wp;
+              }
+              DIAG_STAMP(5)
+              // [bookkeeping]
+              ss++;                                                              // online_learning.cpp:218
+              action_index = a_next;                                             // (`action` itself: after the loop; p_slot: taps only)
+              p_pos = pick<uint32_t, NA>(pos, a_next);
+              p_sh = pick<bool, NA>(sh, a_next);
+              wp_seen = pick<double, NA>(w, a_next);
+              if (terminal) running = false;                                     // (per lane; ends this loop at its next test)
+              // [the eviction held back by the deferred update]
+              if (ev.pos != kInvalidPos) value_store(tab, ev.pos, ev.val);
+            };
+            // [the command] (per lane: a side-effect guard, no state lives in it), then the tail.  EARLY: a pass whose vote did not succeed
+            // leaves the loop from a tail of its own, with the classic load ahead of the one candidate (in EVERY lane: a terminal lane never
+            // looks at it) -- on one path with the pass that stays, `mpre` would live round the loop and its load be waited for there
+            if constexpr (EARLY)
+            {
+              if (!early)
+              {
+                if (!terminal)
+                {
+                  ++mseq;
+                  if (j == 0) mail_send(mail, mseq, (unsigned)a_next);
+                }
+                mpre = mail_prefetch(mbox, mseq - 1, a_next);
+                DIAG_STAMP(1)
+                pass_tail();
+                break;
+              }
+              // (the vote has waited for the only load in flight; in the compiler's picture of this path the poll loop's load and the
+              // load ahead of the leaving path may still be, and it would wait for them behind the command's store: for the store)
+              mail_nothing_in_flight();
               ++mseq;
               if (j == 0) mail_send(mail, mseq, (unsigned)a_next);
-              mpre = mail_prefetch(mbox, mseq - 1, a_next);
+              DIAG_STAMP(1)
+              pass_tail();
+              // [the environment step of the next pass] candidate a_next of the units voted on; the held eviction is stored, the fence
+              // and the loads follow at the top
+              DIAG_STAMP(0)
+              mail_hand_round<ENV>(N, mall, a_next, g, x, obs, reward, terminal, status);
             }
-
-            DIAG_STAMP(4)
-            // [predictor update: the target, queued for the next pass]
+            else
             {
-              double target = reward;
-              if (SPEC::agent(P) == GRLX_AGENT_SARSA)
-                target += SPEC::gamma(N, rep) * pick<double, NA>(q, a_next);
-              else if (SPEC::agent(P) == GRLX_AGENT_EXPECTED_SARSA)
-              { // QPolicy::value (q.cpp:60-73) = sum_a Q(s',a) * EpsilonGreedySampler::distribution (greedy.cpp:220-238)
-                const double de = eps_decay * SPEC::epsilon(N, rep);
-                double v = 0;
-#pragma unroll
-                for (int kk = 0; kk < NA; ++kk)
-                {
-                  double d = (q[kk] == best) ? 1. / man : 0.;
-                  if (d == 1) d = 1 - de;
-                  d += de / NA;
-                  v += q[kk] * d;
-                }
-                target += SPEC::gamma(N, rep) * v;
-              }
-              else
+              if (!terminal)
               {
-                double v = -__builtin_inf();
-#pragma unroll
-                for (int kk = 0; kk < NA; ++kk) v = fmax(v, q[kk]);
-                target += SPEC::gamma(N, rep) * v;
+                ++mseq;
+                if (j == 0) mail_send(mail, mseq, (unsigned)a_next);
+                mpre = mail_prefetch(mbox, mseq - 1, a_next);
               }
-              const double delta = target - qsa;
-              pd_dW = SPEC::alpha(N, rep) * (target - qsa);                    // LinearRepresentation::write (linear.cpp:186-196)
-              pd_dT = SPEC::alpha(N, rep) * delta;                             // VectorConstructor(alpha_*delta)
-              pd_pos = p_pos;
-              status |= (p_pos == kInvalidPos) ? ST_BAD_POS : 0u;
-              pd_sh = p_sh;
-              pd_wp = wp;
+              pass_tail();
             }
-            DIAG_STAMP(5)
-            // [bookkeeping]
-            ss++;                                                              // online_learning.cpp:218
-            action_index = a_next;                                             // (`action` itself: after the loop; p_slot: taps only)
-            p_pos = pick<uint32_t, NA>(pos, a_next);
-            p_sh = pick<bool, NA>(sh, a_next);
-            wp_seen = pick<double, NA>(w, a_next);
-            if (terminal) running = false;                                     // (per lane; ends this loop at its next test)
-            // [the eviction held back by the deferred update]
-            if (ev.pos != kInvalidPos) value_store(tab, ev.pos, ev.val);
-          } while (__all(running));
+          } while (EARLY || __all(running));
           // only the general pass reads the torque itself (its fall-back integrator): discretizer_->at(index), uniform.cpp:140-151
           action = pick<double, NA>(acts, action_index);
         }
