@@ -19,6 +19,10 @@
 //   server -> rollout wave: cand[seq & 1][a] = units {x0, x1, x2, obs0, reward} after command seq, stepped with action a (obs1 = x1;
 //                           terminal and the domain check are comparisons on x the rollout wave redoes).  Two buffers: the server writes
 //                           the candidates of command seq + 1 while the rollout wave may still be reading those of command seq.
+//                           In memory a buffer of the specialised pairs (SPEC::kCandByUnit) is laid out unit by unit, [seq & 1][unit][a]:
+//                           each of the server's five store instructions then writes its three units side by side, 48 contiguous bytes
+//                           of one 64-byte block.  Measured: the headline launch is a few per cent shorter that way.  The supposed reason,
+//                           which no counter has confirmed, is that the three become one write to memory.
 // The rollout wave never depends on the server: a fetch that does not arrive within kFetchPolls polls is computed locally (it has the state
 // and the action), the replica tells the server to stop and integrates by itself for the rest of the launch.  The server leaves when every
 // replica of its block has sent kExit (or has gone on without it), or after kServerStartPolls polls without a first command /
@@ -38,14 +42,18 @@ namespace grlx {
 
 struct __attribute__((aligned(16))) MailUnit { double v; unsigned long long seq; };
 constexpr int kCandUnits = 5;
+constexpr int kCandSlots = 4;                 // EnvMail::cand: four unit slots (64 B) per unit index, one per action, three of them used
 struct __attribute__((aligned(1024))) EnvMail {
   unsigned long long cmd[4];                    //   0
   MailUnit reset[3];                            //  32
   unsigned long long pad0[6];                   //  80
   unsigned long long stats[16];                 // 128  ([15]: served to the end 1 / fell back 2; [14]: passes of the replica's wave in the
                                                 //       wave-uniform loop; the rest: GRLX_ENV_SERVER_STATS builds)
-  MailUnit cand[2][3][kCandUnits];              // 256 .. 736
-  unsigned long long pad1[36];
+  union {                                       // 256 .. 896: ONE of the two layouts per launch, that of the kernel pair (SPEC::kCandByUnit)
+    MailUnit by_unit[2][kCandUnits][kCandSlots];  //   [seq & 1][unit][action slot]: unit by unit, the actions side by side
+    MailUnit by_cand[2][3][kCandUnits];           //   [seq & 1][action][unit], the first 480 B (the generic pair)
+  } cand;
+  unsigned long long pad1[16];                  // 896  ([0..7]: the rollout wave's stamps, GRLX_ENV_SERVER_STATS builds)
 };
 static_assert(sizeof(EnvMail) == kEnvMailBytes, "one mailbox = kEnvMailBytes");
 static_assert(offsetof(EnvMail, stats) + 15 * sizeof(unsigned long long) == kEnvMailFlagOffset, "the flag grlx_env_server_counts reads");
@@ -89,13 +97,13 @@ __device__ __forceinline__ void unit_store(MailUnit *p, double v, unsigned long 
   asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(d) : "memory");
 }
 // server side: unit I of a candidate, at a constant offset from the candidate's first unit (the address is computed once for the five)
-template <int I>
+template <int I, int STRIDE = 1>
 __device__ __forceinline__ void unit_store_at(MailUnit *p, double v, unsigned long long seq)
 {
   const unsigned long long b = (unsigned long long)__double_as_longlong(v);
   mail_u32x4 d;
   d.x = (unsigned)b; d.y = (unsigned)(b >> 32); d.z = (unsigned)seq; d.w = (unsigned)(seq >> 32);
-  asm volatile("global_store_dwordx4 %0, %1, off offset:%2 sc1\n\ts_nop 1" ::"v"(p), "v"(d), "n"(I * (int)sizeof(MailUnit)) : "memory");
+  asm volatile("global_store_dwordx4 %0, %1, off offset:%2 sc1\n\ts_nop 1" ::"v"(p), "v"(d), "n"(I * STRIDE * (int)sizeof(MailUnit)) : "memory");
 }
 // server side: the three units of a start state, all loads in flight together, then ONE wait; true when every unit carries `seq`
 // (inline assembly, waited for on the spot: nothing else is in flight in the server when it reads a start state)
@@ -151,24 +159,28 @@ __device__ __forceinline__ void mail_send_reset(const MailRef &m, unsigned long 
 // instead of 20), the group agrees on whether all five were the ones of `seq`, and the values are handed round.  The load is a buffer
 // load the compiler schedules and waits for itself, so that it can be issued early (mail_prefetch, right after the action is chosen: one
 // trip through memory, 2.3 k cycles, hidden behind the rest of the pass) and looked at late (mail_take, when the next pass starts).
+template <bool BY_UNIT>            // (a tag no member uses: the layout `at` was made for, so that a reader of the other layout does not compile)
 struct MailBox {
   __amdgpu_buffer_rsrc_t rs;      // all mailboxes of the launch
   unsigned at;                    // this lane's byte offset: its replica's mailbox + the unit it loads
 };
-__device__ __forceinline__ MailBox mailbox_of(const DevParams &P, int r, int j)
+template <bool BY_UNIT>
+__device__ __forceinline__ MailBox<BY_UNIT> mailbox_of(const DevParams &P, int r, int j)
 {
-  MailBox b;
+  MailBox<BY_UNIT> b;
   b.rs = __builtin_amdgcn_make_buffer_rsrc((void *)P.env_mail, 0, (int)((size_t)P.n_replicas * kEnvMailBytes), 0x00020000);
-  b.at = (unsigned)r * (unsigned)kEnvMailBytes + (unsigned)offsetof(EnvMail, cand) + (unsigned)(j < kCandUnits ? j : 0) * (unsigned)sizeof(MailUnit);
+  b.at = (unsigned)r * (unsigned)kEnvMailBytes + (unsigned)offsetof(EnvMail, cand) + (unsigned)(j < kCandUnits ? j : 0) * (unsigned)((BY_UNIT ? kCandSlots : 1) * sizeof(MailUnit));
   return b;
 }
-__device__ __forceinline__ mail_u32x4 mail_prefetch(const MailBox &b, unsigned long long seq, int a)
+template <bool BY_UNIT>
+__device__ __forceinline__ mail_u32x4 mail_prefetch(const MailBox<BY_UNIT> &b, unsigned long long seq, int a)
 {
-  const unsigned off = b.at + (((unsigned)seq & 1u) * 3u + (unsigned)a) * (unsigned)(kCandUnits * sizeof(MailUnit));
+  const unsigned off = BY_UNIT ? b.at + (((unsigned)seq & 1u) * (unsigned)(kCandUnits * kCandSlots) + (unsigned)a) * (unsigned)sizeof(MailUnit)
+                               : b.at + (((unsigned)seq & 1u) * 3u + (unsigned)a) * (unsigned)(kCandUnits * sizeof(MailUnit));
   return __builtin_amdgcn_raw_buffer_load_b128(b.rs, off, 0, 16);         // 16 = sc1: device scope
 }
-template <int ENV>
-__device__ __forceinline__ bool mail_take(const DevParams &N, const MailBox &b, mail_u32x4 d, unsigned long long seq, int a, int g,
+template <int ENV, bool BY_UNIT>
+__device__ __forceinline__ bool mail_take(const DevParams &N, const MailBox<BY_UNIT> &b, mail_u32x4 d, unsigned long long seq, int a, int g,
                                           unsigned long long gmask, double *x, double *obs, double &reward, int &terminal, uint32_t &status,
                                           unsigned long long *polled = nullptr)
 {
@@ -201,8 +213,8 @@ __device__ __forceinline__ bool mail_take(const DevParams &N, const MailBox &b, 
 // and nothing around it is per lane.  A unit that carries `seq` is final, so polling a group that already had its answer reads the same
 // values again: same bits as mail_take.  On running into kFetchPolls NOTHING is changed (x, obs, reward, terminal, status as they were):
 // the caller leaves its loop and the general pass takes this step with mail_take, falling back per replica there.
-template <int ENV>
-__device__ __forceinline__ bool mail_take_wave(const DevParams &N, const MailBox &b, mail_u32x4 d, unsigned long long seq, int a, int g,
+template <int ENV, bool BY_UNIT>
+__device__ __forceinline__ bool mail_take_wave(const DevParams &N, const MailBox<BY_UNIT> &b, mail_u32x4 d, unsigned long long seq, int a, int g,
                                                double *x, double *obs, double &reward, int &terminal, uint32_t &status,
                                                unsigned long long *polled = nullptr)
 {
@@ -232,22 +244,22 @@ __device__ __forceinline__ bool mail_take_wave(const DevParams &N, const MailBox
 }
 // The early take of the wave-uniform loop.  cand[n & 1][.] is stored the moment command n arrives, so while pass k + 1 (which follows
 // command n) works through its table phase the answers to ALL of its possible actions are already in the mailbox: lane j < 15 of a group
-// loads unit j of cand[n & 1] -- the three candidates are contiguous, unit 5 a + u at byte 16 (5 a + u) -- and lane 15 loads unit 0 again
+// loads one unit of cand[n & 1] -- lane 5 a + u unit u of candidate a, at byte 64 u + 16 a of the buffer -- and lane 15 loads unit 0 again
 // (any valid unit: it only votes).  One 16-byte load per lane, as mail_prefetch; its trip through memory hides behind the trace
 // forwarding, the sums and the sampler.  Once the sampler has chosen a, mail_vote_all agrees on the tags (bounded polling, as
 // mail_take_wave; on running into the bound NOTHING has changed) and mail_hand_round gives every lane the five values of candidate a.
 // vmcnt(0) said in the source, for a place where nothing is in flight but the compiler cannot know it (its own wait would come later,
 // behind a store, and wait for that store)
 __device__ __forceinline__ void mail_nothing_in_flight() { __builtin_amdgcn_s_waitcnt(0x0F70); }
-__device__ __forceinline__ mail_u32x4 mail_prefetch_all(const MailBox &b, unsigned long long seq, int j)
+__device__ __forceinline__ mail_u32x4 mail_prefetch_all(const MailBox<true> &b, unsigned long long seq, int j)
 {
-  static_assert(sizeof(((EnvMail *)nullptr)->cand[0]) == 3 * kCandUnits * sizeof(MailUnit), "the three candidates of a command are contiguous");
-  // (b.at already holds unit j for j < 5 and unit 0 for the other lanes)
-  const unsigned unit = (j >= kCandUnits && j < 3 * kCandUnits) ? (unsigned)j : 0u;
-  const unsigned off = b.at + unit * (unsigned)sizeof(MailUnit) + ((unsigned)seq & 1u) * (unsigned)(3 * kCandUnits * sizeof(MailUnit));
+  // lane j = 5 a + u loads unit u of candidate a.  (b.at already holds unit j of candidate 0 for j < 5 and unit 0 for the other lanes)
+  const unsigned jj = (j >= kCandUnits && j < 3 * kCandUnits) ? (unsigned)j : 0u;
+  const unsigned off = b.at + ((jj % (unsigned)kCandUnits) * (unsigned)kCandSlots + jj / (unsigned)kCandUnits) * (unsigned)sizeof(MailUnit) +
+                       ((unsigned)seq & 1u) * (unsigned)(kCandUnits * kCandSlots * sizeof(MailUnit));
   return __builtin_amdgcn_raw_buffer_load_b128(b.rs, off, 0, 16);         // 16 = sc1: device scope
 }
-__device__ __forceinline__ bool mail_vote_all(const MailBox &b, mail_u32x4 &d, unsigned long long seq, int j, unsigned long long *polled = nullptr)
+__device__ __forceinline__ bool mail_vote_all(const MailBox<true> &b, mail_u32x4 &d, unsigned long long seq, int j, unsigned long long *polled = nullptr)
 {
   unsigned polls = 0;
   while (!__all((((unsigned long long)d.w << 32) | d.z) == seq))
@@ -395,12 +407,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(48))) void env_s
     { // the answer: what the action taken leaves, for every next action
       if (worker && a == (int)op)
       {
-        MailUnit *u = &m->cand[expect & 1u][a2][0];
-        unit_store_at<0>(u, cx[0], expect);
-        unit_store_at<1>(u, cx[1], expect);
-        unit_store_at<2>(u, cx[2], expect);
-        unit_store_at<3>(u, cobs0, expect);
-        unit_store_at<4>(u, creward, expect);
+        // (unit by unit: the three lanes of a replica that store write 48 contiguous bytes of one 64-byte block with each instruction,
+        //  where candidate by candidate their units lie 80 bytes apart.  The launch is measurably shorter so; that the three become ONE
+        //  write to memory is the supposed reason, not a counted one: profiles/served_eager_answers_ab.md)
+        static_assert(NA <= kCandSlots, "slot a2 of every unit is this lane's");
+        constexpr bool BY_UNIT = SPEC::kCandByUnit;
+        constexpr int STRIDE = BY_UNIT ? kCandSlots : 1;
+        MailUnit *u;
+        if constexpr (BY_UNIT) u = &m->cand.by_unit[expect & 1u][0][a2];
+        else u = &m->cand.by_cand[expect & 1u][a2][0];
+        unit_store_at<0, STRIDE>(u, cx[0], expect);
+        unit_store_at<1, STRIDE>(u, cx[1], expect);
+        unit_store_at<2, STRIDE>(u, cx[2], expect);
+        unit_store_at<3, STRIDE>(u, cobs0, expect);
+        unit_store_at<4, STRIDE>(u, creward, expect);
       }
       // the level after it: lane (a, a2) continues from the state the lane (action taken, a) holds
       const int src = (lane & ~15) + (int)op * NA + (worker ? a : 0);

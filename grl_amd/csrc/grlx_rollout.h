@@ -65,6 +65,9 @@ struct SpecShared {
   // rollout_served_kernel: does the wave-uniform loop take the next pass's environment step at the sampler (the rotated loop of
   // rollout_body)?  It costs registers across the loop that only a specialised instantiation has
   static constexpr bool kEarlyTake = false;
+  // the layout of EnvMail::cand (grlx_env_server.h): unit by unit in the specialised pairs; the generic pair keeps candidate by candidate,
+  // and with it its instruction stream (at its register cap another offset expression was 16 B more scratch than it is allowed)
+  static constexpr bool kCandByUnit = false;
   struct Rep {};
   __device__ static __forceinline__ Rep replica(const SweepParams *, int) { return Rep{}; }
   __device__ static __forceinline__ double alpha(const DevParams &N, const Rep &) { return N.alpha; }
@@ -77,6 +80,7 @@ struct SpecShared {
 template <int AGENT>
 struct SpecPendulumTcA : SpecShared {
   static constexpr bool kEarlyTake = true;
+  static constexpr bool kCandByUnit = true;
   __device__ static __forceinline__ int agent(const DevParams &) { return AGENT; }
   // every numeric field the rollout kernel reads must equal the constant, bit for bit
   static bool matches(const DevParams &P)
@@ -207,6 +211,7 @@ struct SpecSweep {
   __device__ static __forceinline__ const DevParams &numeric(const DevParams &P) { return P; }
   __device__ static __forceinline__ int agent(const DevParams &P) { return P.agent; }
   static constexpr bool kPerReplica = true;
+  static constexpr bool kCandByUnit = false;      // (never served: the type of a mailbox it does not use)
   struct Rep { double alpha, gamma, gl, epsilon; };
   __device__ static __forceinline__ Rep replica(const SweepParams *sweep, int r)
   {
@@ -317,13 +322,13 @@ __device__ __forceinline__ void rollout_body(const DevParams &P, int n_trials, c
 #ifdef GRLX_ENV_SERVER_STATS
   unsigned long long st_wait = 0, st_polls = 0, st_fetch = 0, st_begin = mail_clock();
 #endif
-  MailBox mbox;
+  MailBox<SPEC::kCandByUnit> mbox;
   mail_u32x4 mpre = {0u, 0u, 0u, 0u};      // the unit this lane loaded ahead
   if constexpr (EXT)
   {
     srv = live && P.env_mail != nullptr;
     mail = MailRef{P.env_mail, (uint32_t)r};
-    mbox = mailbox_of(P, r, j);
+    mbox = mailbox_of<SPEC::kCandByUnit>(P, r, j);
     mail_setprio(P.env_tune & 3u);
   }
 

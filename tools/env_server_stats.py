@@ -32,7 +32,7 @@ print(f"rollout: kernel {st[:,4].mean():.0f} cycles, waiting for candidates {st[
       f"{st[:,6].mean():.0f} fetches, {st[:,5].sum()/max(st[:,6].sum(),1):.0f} cycles per fetch, {st[:,7].sum()/max(st[:,6].sum(),1):.2f} extra polls per fetch, "
       f"{int(st[:,8].sum())} of {n} replicas still served at the end")
 print(f"cycles per pass (rollout kernel / fetches): {st[:,4].sum()/max(st[:,6].sum(),1):.0f}   (s_memtime ticks = shader cycles)")
-ph = mail[:, 92:100].astype(np.float64)       # EnvMail::pad1[0..7]: the rollout wave's stamps (same slots as tools/diag_phases.py)
+ph = mail[:, 112:120].astype(np.float64)      # EnvMail::pad1[0..7], byte 896: the rollout wave's stamps
 # (the loop of the specialised kernels is rotated, SPEC::kEarlyTake: there "taking the server's answer" is the vote at the sampler, the
 #  command and, after the tail, the handing round; the load of the fifteen units is issued under "inserts + LDS writes"; the bucket loads
 #  are issued at the top of a pass, straight after the previous pass's tail, and waited for under "table lookup")
