@@ -139,6 +139,12 @@ _SIGS = {
                                 _P(C.c_int32), _P(C.c_double)]),
     "grlx_evaluate_ensemble": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_double), C.c_int, C.c_int, _P(C.c_double), _P(C.c_double),
                                          _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64), _P(C.c_double)]),
+    "grlx_trajectory_record_words": (C.c_int, [C.c_void_p, C.c_int]),
+    "grlx_evaluate_trajectory": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P(C.c_double), C.c_int, C.c_int, _P(C.c_double), _P(C.c_double), _P(C.c_int32),
+                                           _P(C.c_int32), _P(C.c_int32), _P(C.c_double), _P(C.c_double)]),
+    "grlx_evaluate_ensemble_trajectory": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_double), C.c_int, C.c_int, _P(C.c_double),
+                                                    _P(C.c_double), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64),
+                                                    _P(C.c_double), _P(C.c_double)]),
     "grlx_math": (C.c_int, [C.c_int, _P(C.c_double), _P(C.c_double), C.c_int, _P(C.c_double)]),
     "grlx_rand48_at": (C.c_int, [C.c_int64, _P(C.c_uint64), C.c_int, _P(C.c_double)]),
     "grlx_fqi_config_pendulum": (None, [_P(FqiConfig)]),
@@ -165,14 +171,19 @@ _DIAG_SIGS = {
     "grlx_snapshot_timing": (C.c_int, [C.c_void_p, _P(C.c_double), _P(C.c_double)]),
     "grlx_snapshot_naive_copy": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_double), _P(C.c_double)]),
     "grlx_set_query_chunk_bytes": (C.c_int, [C.c_uint64]),
+    "grlx_read_kernel_timing": (C.c_int, [C.c_int, _P(C.c_double), _P(C.c_int)]),
 }
 # entry points of include/grlx.h that a library named by GRLX_LIB may predate (A/B timing of an older build against this binding); the
 # library in the tree must export every one of them, as it must every other symbol of _SIGS
 _NEWER_SIGS = ("grlx_snapshot_size", "grlx_snapshot_save", "grlx_snapshot_load", "grlx_snapshot_info",
-               "grlx_query_q", "grlx_query_state", "grlx_query_ensemble", "grlx_fqi_query", "grlx_evaluate", "grlx_evaluate_ensemble")
+               "grlx_query_q", "grlx_query_state", "grlx_query_ensemble", "grlx_fqi_query", "grlx_evaluate", "grlx_evaluate_ensemble",
+               "grlx_trajectory_record_words", "grlx_evaluate_trajectory", "grlx_evaluate_ensemble_trajectory")
 # grlx_kernel_plan flags
 PLAN_STAMPS_IN_PLACE, PLAN_STAMPS_DEFERRED, PLAN_SWEEP, PLAN_SERVER_OFF, PLAN_WALKER_SERVER, PLAN_FITS_YES, PLAN_FITS_NO = 1, 2, 4, 8, 16, 32, 64
 ENSEMBLE_VOTE, ENSEMBLE_MEAN_Q = 0, 1       # grlx_evaluate_ensemble's rule
+# include/grlx.h: the words of a trajectory record (GRLX_TRAJ_*)
+TRAJ_ACTION, TRAJ_REWARD, TRAJ_VALUE, TRAJ_ACTION_INDEX, TRAJ_N_MAX, TRAJ_TERMINAL, TRAJ_OBS = 0, 1, 2, 3, 4, 5, 6
+TRAJ_ENS_AGREEMENT, TRAJ_ENS_MEMBER_TIES, TRAJ_ENS_OBS = 6, 7, 8
 ABI_VERSION = 2         # include/grlx.h: GRLX_ABI_VERSION
 
 

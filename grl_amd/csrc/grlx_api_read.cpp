@@ -53,10 +53,40 @@ hipError_t query_copy_out(void *host, const void *dev, size_t elem, int n_replic
                      hipMemcpyDeviceToHost);
 }
 
+// grlx_read_kernel_timing (include/grlx_diag.h): the device time of the chunks' launches, summed since timing was enabled
+bool g_read_timing = false;
+double g_read_ms = 0;
+int g_read_chunks = 0;
+
+struct ReadTimer {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~ReadTimer()
+  {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+  hipError_t start()
+  {
+    if (hipError_t err = hipEventCreate(&e0)) return err;
+    if (hipError_t err = hipEventCreate(&e1)) return err;
+    return hipEventRecord(e0, nullptr);
+  }
+  hipError_t stop()
+  {
+    if (hipError_t err = hipEventRecord(e1, nullptr)) return err;
+    if (hipError_t err = hipEventSynchronize(e1)) return err;
+    float ms = 0;
+    if (hipError_t err = hipEventElapsedTime(&ms, e0, e1)) return err;
+    g_read_ms += ms;
+    g_read_chunks++;
+    return hipSuccess;
+  }
+};
+
 // One output of a chunked read: `rows` rows of `elem` bytes per column, copied to `host` when that is not null; `on_device`: the kernels
 // write it (or a reduction reads it) whether the caller asked for it or not.
 struct ReadOut { void *host; size_t elem; int rows; bool on_device; };
-constexpr int kMaxReadOuts = 8;
+constexpr int kMaxReadOuts = 9;
 
 // The skeleton of every read: the columns of `in` (observations or start states, `in_dims` doubles each) go through the device `chunk` at a
 // time.  Per chunk: the input in, launch(nc, input, outputs) -- device pointers, null for an output neither asked for nor needed -- and out
@@ -73,7 +103,14 @@ int chunked_read(grlx_ctx *ctx, const ReadOut *outs, int n_outs, int cols, const
     const int nc = cols - c0 < chunk ? cols - c0 : chunk;
     HIP_TRY(hipMemcpy(din.get(), in + (size_t)c0 * in_dims, sizeof(double) * (size_t)nc * in_dims, hipMemcpyHostToDevice));
     if (ctx->poison) HIP_TRY(launch_poison_registers(ctx->poison_pattern, nullptr));
-    if (int rc = launch(nc, din.as<double>(), dout)) return rc;
+    if (g_read_timing)
+    { // grlx_read_kernel_timing: events around the chunk's launches, waited for here
+      ReadTimer timer;
+      HIP_TRY(timer.start());
+      if (int rc = launch(nc, din.as<double>(), dout)) return rc;
+      HIP_TRY(timer.stop());
+    }
+    else if (int rc = launch(nc, din.as<double>(), dout)) return rc;
     for (int k = 0; k < n_outs; ++k)
       if (outs[k].host) HIP_TRY(query_copy_out(outs[k].host, dout[k].get(), outs[k].elem, outs[k].rows, cols, c0, nc));
     if (sync_each) HIP_TRY(hipDeviceSynchronize());
@@ -117,6 +154,15 @@ int grlx_set_query_chunk_bytes(uint64_t bytes)
 {
   g_query_chunk_bytes = bytes ? bytes : kQueryChunkDefault;
   set_fqi_query_chunk_bytes(bytes);
+  return GRLX_OK;
+}
+
+int grlx_read_kernel_timing(int enable, double *ms, int *chunks)
+{
+  if (ms) *ms = g_read_ms;
+  if (chunks) *chunks = g_read_chunks;
+  g_read_timing = enable != 0;
+  if (enable) { g_read_ms = 0; g_read_chunks = 0; }
   return GRLX_OK;
 }
 
@@ -182,6 +228,18 @@ static int evaluate_admit(grlx_ctx *ctx, const char *who, int first_replica, int
   return GRLX_OK;
 }
 
+// what both ensemble evaluations check beyond evaluate_admit
+static int ensemble_admit(grlx_ctx *ctx, const char *who, int n_replicas, int group_size, int rule)
+{
+  if (!q_agent(ctx->cfg.agent))
+    return fail(GRLX_ERR_INVALID, "%s is not built for the actor-critic agent (a vote over continuous actions is mapping/policy/multi's); it serves agents with a policy/discrete/q", who);
+  if (group_size < 1) return fail(GRLX_ERR_INVALID, "%s: group_size = %d is below 1", who, group_size);
+  if (n_replicas % group_size != 0) return fail(GRLX_ERR_INVALID, "%s: group_size %d does not divide the %d replicas", who, group_size, n_replicas);
+  if (rule != GRLX_ENSEMBLE_VOTE && rule != GRLX_ENSEMBLE_MEAN_Q)
+    return fail(GRLX_ERR_INVALID, "%s: unknown rule %d (GRLX_ENSEMBLE_VOTE = 0, GRLX_ENSEMBLE_MEAN_Q = 1)", who, rule);
+  return GRLX_OK;
+}
+
 int grlx_evaluate(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, double *ret, double *disc,
                   int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state)
 {
@@ -215,12 +273,7 @@ int grlx_evaluate_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, int
   const char *who = "grlx_evaluate_ensemble";
   int rc = evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps);
   if (rc != GRLX_OK) return rc;
-  if (!q_agent(ctx->cfg.agent))
-    return fail(GRLX_ERR_INVALID, "%s is not built for the actor-critic agent (a vote over continuous actions is mapping/policy/multi's); it serves agents with a policy/discrete/q", who);
-  if (group_size < 1) return fail(GRLX_ERR_INVALID, "%s: group_size = %d is below 1", who, group_size);
-  if (n_replicas % group_size != 0) return fail(GRLX_ERR_INVALID, "%s: group_size %d does not divide the %d replicas", who, group_size, n_replicas);
-  if (rule != GRLX_ENSEMBLE_VOTE && rule != GRLX_ENSEMBLE_MEAN_Q)
-    return fail(GRLX_ERR_INVALID, "%s: unknown rule %d (GRLX_ENSEMBLE_VOTE = 0, GRLX_ENSEMBLE_MEAN_Q = 1)", who, rule);
+  if (int bad = ensemble_admit(ctx, who, n_replicas, group_size, rule)) return bad;
   if (max_steps == 0) max_steps = GRLX_MAX_EPISODE_STEPS;
   if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
   DRAIN(ctx);
@@ -238,6 +291,102 @@ int grlx_evaluate_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, int
     A.ret = d[0].as<double>(); A.disc = d[1].as<double>(); A.steps = d[2].as<int32_t>(); A.terminal = d[3].as<int32_t>(); A.ties = d[4].as<int32_t>();
     A.member_ties = d[5].as<int64_t>(); A.agreement = d[6].as<int64_t>(); A.final_state = d[7].as<double>();
     HIP_TRY(launch_evaluate_ensemble(ctx->P, A, nullptr));
+    return GRLX_OK;
+  });
+}
+
+// ---- per-step trajectories: the two evaluations with a record per step (grlx_evaluate.hip: trajectory_*_kernel) -----------------------------
+// What a trajectory call checks beyond its sibling, after the sibling's own checks; gives the start states per chunk.  `rows`: replicas or
+// groups; `in_and_sums`: a start state's other staged bytes (its state and its rows' sums).  Unlike the other reads a chunk never exceeds
+// the bound: the records are what the bound is for, so a column that does not fit is refused instead of staged as "at least one".
+static int trajectory_admit(const char *who, const char *sibling, const void *records, int max_steps, int rows, int n_starts,
+                            int R, size_t in_and_sums, int *chunk)
+{
+  if (!records) return fail(GRLX_ERR_INVALID, "%s: records is null (for the sums alone call %s)", who, sibling);
+  if (max_steps == 0)
+    return fail(GRLX_ERR_INVALID, "%s: max_steps = 0: the records are sized by max_steps, so there is no default here (1 ... GRLX_MAX_EPISODE_STEPS = %d)", who,
+                GRLX_MAX_EPISODE_STEPS);
+  const uint64_t column = (uint64_t)rows * (uint64_t)max_steps * (uint64_t)R * sizeof(double);
+  if (column + in_and_sums > g_query_chunk_bytes)
+    return fail(GRLX_ERR_INVALID, "%s: one start state's column of records is %llu bytes (%d rows x %d steps x %d words x 8; %llu with its sums) and exceeds "
+                "the staging bound of %llu bytes: ask for fewer replicas per call, a smaller max_steps, or raise the bound with grlx_set_query_chunk_bytes", who,
+                (unsigned long long)column, rows, max_steps, R, (unsigned long long)(column + in_and_sums), (unsigned long long)g_query_chunk_bytes);
+  *chunk = rows ? query_chunk(n_starts, (size_t)column + in_and_sums) : n_starts;
+  return GRLX_OK;
+}
+
+int grlx_trajectory_record_words(grlx_ctx *ctx, int ensemble)
+{
+  if (!ctx) return fail(GRLX_ERR_INVALID, "bad argument");
+  const char *who = "grlx_trajectory_record_words";
+  if (ctx->cfg.env == GRLX_ENV_EXTERNAL || !evaluate_built(ctx->cfg.agent, ctx->cfg.env, ctx->P.A))
+    return fail(GRLX_ERR_INVALID, "%s: no evaluation episodes are built for this context (environment %d)", who, ctx->cfg.env);
+  if (ensemble && !q_agent(ctx->cfg.agent)) return fail(GRLX_ERR_INVALID, "%s: the ensemble evaluation is not built for the actor-critic agent", who);
+  return trajectory_words(ctx->cfg.env, ensemble != 0);
+}
+
+int grlx_evaluate_trajectory(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, double *ret,
+                             double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state, double *records)
+{
+  const char *who = "grlx_evaluate_trajectory";
+  int rc = evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps);
+  if (rc != GRLX_OK) return rc;
+  const int S = ctx->S, R = trajectory_words(ctx->cfg.env, false);
+  const size_t per_pair = 2 * sizeof(double) + 3 * sizeof(int32_t) + sizeof(double) * (size_t)S;
+  int chunk = 0;
+  rc = trajectory_admit(who, "grlx_evaluate", records, max_steps, n_replicas, n_starts, R, sizeof(double) * (size_t)S + per_pair * (size_t)n_replicas, &chunk);
+  if (rc != GRLX_OK) return rc;
+  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
+  DRAIN(ctx);
+  const size_t rec_elem = sizeof(double) * (size_t)R * (size_t)max_steps;
+  const ReadOut outs[7] = {{ret, sizeof(double), n_replicas, true}, {disc, sizeof(double), n_replicas, true}, {steps, sizeof(int32_t), n_replicas, true},
+                           {terminal, sizeof(int32_t), n_replicas, true}, {ties, sizeof(int32_t), n_replicas, true},
+                           {final_state, sizeof(double) * (size_t)S, n_replicas, true}, {records, rec_elem, n_replicas, true}};
+  return chunked_read(ctx, outs, 7, n_starts, states, S, chunk, true, [&](int nc, const double *dst, const DevBuf *d) -> int {
+    TrajectoryArgs T;
+    EvaluateArgs &A = T.e;
+    A.first_replica = first_replica; A.n_replicas = n_replicas; A.n_starts = nc; A.max_steps = max_steps;
+    A.states = dst; A.sweep = ctx->sweep ? ctx->sweep_dev.get() : nullptr;
+    A.ret = d[0].as<double>(); A.disc = d[1].as<double>(); A.steps = d[2].as<int32_t>(); A.terminal = d[3].as<int32_t>(); A.ties = d[4].as<int32_t>();
+    A.final_state = d[5].as<double>();
+    T.records = d[6].as<double>();
+    HIP_TRY(hipMemsetAsync(T.records, 0, rec_elem * (size_t)n_replicas * (size_t)nc, nullptr));     // records behind an episode's end are +0.0
+    HIP_TRY(launch_trajectory(ctx->P, T, nullptr));
+    return GRLX_OK;
+  });
+}
+
+int grlx_evaluate_ensemble_trajectory(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule, const double *states, int n_starts,
+                                      int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, int64_t *member_ties,
+                                      int64_t *agreement, double *final_state, double *records)
+{
+  const char *who = "grlx_evaluate_ensemble_trajectory";
+  int rc = evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps);
+  if (rc != GRLX_OK) return rc;
+  if (int bad = ensemble_admit(ctx, who, n_replicas, group_size, rule)) return bad;
+  const int S = ctx->S, n_groups = n_replicas / group_size, R = trajectory_words(ctx->cfg.env, true);
+  const size_t per_pair = 2 * sizeof(double) + 3 * sizeof(int32_t) + 2 * sizeof(int64_t) + sizeof(double) * (size_t)S;
+  int chunk = 0;
+  rc = trajectory_admit(who, "grlx_evaluate_ensemble", records, max_steps, n_groups, n_starts, R, sizeof(double) * (size_t)S + per_pair * (size_t)n_groups, &chunk);
+  if (rc != GRLX_OK) return rc;
+  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
+  DRAIN(ctx);
+  if ((int64_t)chunk * n_groups > 0x7fffffff) chunk = 0x7fffffff / n_groups;      // one block per pair: the grid's bound
+  const size_t rec_elem = sizeof(double) * (size_t)R * (size_t)max_steps;
+  const ReadOut outs[9] = {{ret, sizeof(double), n_groups, true}, {disc, sizeof(double), n_groups, true}, {steps, sizeof(int32_t), n_groups, true},
+                           {terminal, sizeof(int32_t), n_groups, true}, {ties, sizeof(int32_t), n_groups, true}, {member_ties, sizeof(int64_t), n_groups, true},
+                           {agreement, sizeof(int64_t), n_groups, true}, {final_state, sizeof(double) * (size_t)S, n_groups, true},
+                           {records, rec_elem, n_groups, true}};
+  return chunked_read(ctx, outs, 9, n_starts, states, S, chunk, true, [&](int nc, const double *dst, const DevBuf *d) -> int {
+    EnsembleTrajectoryArgs T;
+    EnsembleArgs &A = T.e;
+    A.first_replica = first_replica; A.n_replicas = n_replicas; A.group_size = group_size; A.rule = rule;
+    A.n_starts = nc; A.max_steps = max_steps; A.states = dst; A.sweep = ctx->sweep ? ctx->sweep_dev.get() : nullptr;
+    A.ret = d[0].as<double>(); A.disc = d[1].as<double>(); A.steps = d[2].as<int32_t>(); A.terminal = d[3].as<int32_t>(); A.ties = d[4].as<int32_t>();
+    A.member_ties = d[5].as<int64_t>(); A.agreement = d[6].as<int64_t>(); A.final_state = d[7].as<double>();
+    T.records = d[8].as<double>();
+    HIP_TRY(hipMemsetAsync(T.records, 0, rec_elem * (size_t)n_groups * (size_t)nc, nullptr));
+    HIP_TRY(launch_trajectory_ensemble(ctx->P, T, nullptr));
     return GRLX_OK;
   });
 }

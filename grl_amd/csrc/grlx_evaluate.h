@@ -36,8 +36,24 @@ struct EnsembleArgs {
   double            *final_state;   // [pair][model state dimensions]
 };
 
+// grlx_evaluate_trajectory / grlx_evaluate_ensemble_trajectory: the same chunk with a place for every step.  records[pair][max_steps][R]
+// doubles, R = trajectory_words(); record t of a pair is its step t (include/grlx.h: GRLX_TRAJ_*).  The launchers expect the records
+// zero-filled: a kernel writes the records of the steps it takes and nothing behind an episode's end.  Structs of their own: the
+// parameter blocks of the evaluation kernels, and with them their machine code, stay what they were.
+struct TrajectoryArgs {
+  EvaluateArgs e;
+  double      *records;
+};
+struct EnsembleTrajectoryArgs {
+  EnsembleArgs e;
+  double      *records;
+};
+
 bool evaluate_built(int agent, int env, int actions);      // is there an instantiation for this context?
+int  trajectory_words(int env, bool ensemble);             // R of an environment's record; 0 for one without an instantiation
 hipError_t launch_evaluate(const DevParams &P, const EvaluateArgs &A, hipStream_t stream);
 hipError_t launch_evaluate_ensemble(const DevParams &P, const EnsembleArgs &A, hipStream_t stream);    // Q agents only
+hipError_t launch_trajectory(const DevParams &P, const TrajectoryArgs &A, hipStream_t stream);
+hipError_t launch_trajectory_ensemble(const DevParams &P, const EnsembleTrajectoryArgs &A, hipStream_t stream);    // Q agents only
 
 } // namespace grlx

@@ -23,6 +23,9 @@
 // evaluate_ensemble_kernel (grlx_evaluate_ensemble): the same episode for a GROUP of consecutive replicas that share one environment state
 // and act on their vote or their summed Q; its layout is described at the kernel.
 //
+// trajectory_q_kernel, trajectory_ac_kernel, trajectory_ensemble_kernel (grlx_evaluate_trajectory, grlx_evaluate_ensemble_trajectory): the
+// same episodes with one record per step taken, in kernels of their own below the three above, which they leave as they are.
+//
 // Compiled with -ffp-contract=off like every unit: g * reward is a plain product, the sums plain additions.
 #include "grlx_internal.h"
 #include "grlx_math.h"
@@ -383,6 +386,288 @@ __global__ __launch_bounds__(kQueryWaves * 64) void evaluate_ac_kernel(DevParams
   if (live && j == 0) episode_store<S>(A, pair, e, x);
 }
 
+// ---- per-step trajectories (grlx_evaluate_trajectory, grlx_evaluate_ensemble_trajectory) ------------------------------------------------
+// The episodes above with one record of R doubles per step taken (include/grlx.h: GRLX_TRAJ_*), in kernels of their own: the evaluation
+// kernels are not touched and share nothing new with these.  Same layouts.  The one new thing in the loop is the store.  Every lane of a
+// group (the ensemble: every thread of the block) holds the step's R values, bit for bit the same, so lane j stores word j -- and word
+// j + 16 where R > 16 --: one store instruction per wave and step (two for the walker), each group writing one contiguous run of 8 R
+// bytes, an episode's records one after the other.  The word is picked by selects unrolled at compile time; indexing the values by the
+// lane number would put them into scratch.  The store comes after episode_account, at index steps - 1, so that the terminal word is the
+// code after the step; finished and dead groups store nothing, and nothing is written behind an episode's end (the caller zero-fills).
+
+// Word w of a step's record, by selects over the values themselves: no array of the R words is formed (one that was went to scratch, 8 R
+// bytes of it, although only constants indexed it after unrolling).  ENS: the ensemble's record, whose two words more sit before the
+// observation.  Any w outside the record gives the action.
+template <bool ENS, int D, int S>
+__device__ __forceinline__ double record_word(int w, double action, double reward, double value, int mai, int man, int code, int agree, int member_ties,
+                                              const double (&obs)[D], const double (&x)[S])
+{
+  constexpr int OBS = ENS ? GRLX_TRAJ_ENS_OBS : GRLX_TRAJ_OBS;
+  double out = action;
+  out = (w == GRLX_TRAJ_REWARD) ? reward : out;
+  out = (w == GRLX_TRAJ_VALUE) ? value : out;
+  out = (w == GRLX_TRAJ_ACTION_INDEX) ? (double)mai : out;
+  out = (w == GRLX_TRAJ_N_MAX) ? (double)man : out;
+  out = (w == GRLX_TRAJ_TERMINAL) ? (double)code : out;
+  if constexpr (ENS)
+  {
+    out = (w == GRLX_TRAJ_ENS_AGREEMENT) ? (double)agree : out;
+    out = (w == GRLX_TRAJ_ENS_MEMBER_TIES) ? (double)member_ties : out;
+  }
+#pragma unroll
+  for (int i = 0; i < D; ++i) out = (w == OBS + i) ? obs[i] : out;
+#pragma unroll
+  for (int i = 0; i < S; ++i) out = (w == OBS + D + i) ? x[i] : out;
+  return out;
+}
+
+// lane j < 16 of a group writes its words of the single-policy record at rec: word j, and word j + 16 where the record has one
+template <int D, int S>
+__device__ __forceinline__ void record_store16(double *rec, int j, double action, double reward, double value, int mai, int man, int code,
+                                               const double (&obs)[D], const double (&x)[S])
+{
+  constexpr int R = GRLX_TRAJ_OBS + D + S;
+  if (j < R) rec[j] = record_word<false, D, S>(j, action, reward, value, mai, man, code, 0, 0, obs, x);
+  if constexpr (R > 16)
+    if (j + 16 < R) rec[j + 16] = record_word<false, D, S>(j + 16, action, reward, value, mai, man, code, 0, 0, obs, x);
+}
+
+// evaluate_q_kernel with records.  After the Q-values are in LDS every lane of the group reads them (broadcast) and runs findmax itself,
+// as the ensemble kernel's threads do: the same bits in every lane, and no word is handed back through LDS.
+template <int ENV, int NA>
+__global__ __launch_bounds__(kQueryWaves * 64) void trajectory_q_kernel(DevParams P, TrajectoryArgs T)
+{
+  constexpr int S = Env<ENV>::S, D = Env<ENV>::D, R = GRLX_TRAJ_OBS + D + S;
+  __shared__ double sh_w[kQueryWaves][NA * kRowStride];
+  __shared__ double sh_q[kQueryWaves][4 * 8];
+  const EvaluateArgs &A = T.e;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, j = lane & 15;
+  const long long n_pairs = (long long)A.n_replicas * A.n_starts;
+  const long long pair = ((long long)blockIdx.x * kQueryWaves + wave) * 4 + g;
+  const bool live = pair < n_pairs;                    // dead groups of the last wave neither load nor store
+  double *W = sh_w[wave], *Q = sh_q[wave];
+
+  const int rl = live ? (int)(pair / A.n_starts) : 0, s = live ? (int)(pair - (long long)rl * A.n_starts) : 0;
+  const int r = A.first_replica + rl;
+  const Table tab = table_of(P, 0, r);
+  const ReplicaState &rs = P.states[r];
+  const double gamma = A.sweep ? A.sweep[r].gamma : P.gamma;
+  double *rec = T.records + (live ? (size_t)pair * (size_t)A.max_steps * R : 0);     // 64-bit: pairs * max_steps * R * 8 bytes pass 2^32 at a million pairs of 100 steps
+  double x[S], obs[D];
+#pragma unroll
+  for (int i = 0; i < S; ++i) x[i] = live ? A.states[(size_t)s * S + i] : 0.;
+  (void)Env<ENV>::observe(P, x, obs);
+
+  EpisodeSums e;
+  e.ret = 0; e.disc = 0; e.g = 1; e.steps = 0; e.code = 0; e.ties = 0;
+  bool active = live;
+  for (int step = 0; step < A.max_steps; ++step)
+  {
+    if (__ballot(active) == 0ull) break;               // wave-uniform
+    if (active) member_probe<ENV, NA>(P, tab, rs, obs, j, lane, W);
+    wave_sync();
+    if (active && j < NA) Q[g * 8 + j] = member_q(P, W, g, j);
+    wave_sync();
+    if (active)
+    {
+      double q[NA];
+#pragma unroll
+      for (int a = 0; a < NA; ++a) q[a] = Q[g * 8 + a];
+      int mai, man;
+      findmax<NA>(q, mai, man);
+      const double action = action_of<NA>(P, mai);
+      double value = q[0];
+#pragma unroll
+      for (int a = 1; a < NA; ++a) value = (mai == a) ? q[a] : value;
+      double before[D];
+#pragma unroll
+      for (int i = 0; i < D; ++i) before[i] = obs[i];
+      double reward = 0;
+      int terminal = 0;
+      uint32_t status = 0;
+      env_step<ENV, false, NoShare>(P, x, action, obs, reward, terminal, status);
+      active = episode_account(e, reward, gamma, terminal, status, man > 1);
+      record_store16<D, S>(rec + (size_t)(e.steps - 1) * R, j, action, reward, value, mai, man, e.code, before, x);
+    }
+  }
+  if (live && j == 0) episode_store<S>(A, pair, e, x);
+}
+
+// evaluate_ac_kernel with records.  Every lane of the group sums the 16 weights itself (broadcast reads): the value word, the actor's
+// read before the action clip, is then in every lane, and nothing is handed back through LDS.
+template <int ENV>
+__global__ __launch_bounds__(kQueryWaves * 64) void trajectory_ac_kernel(DevParams P, TrajectoryArgs T)
+{
+  constexpr int S = Env<ENV>::S, D = Env<ENV>::D, R = GRLX_TRAJ_OBS + D + S;
+  __shared__ double sh_w[kQueryWaves][64];
+  const EvaluateArgs &A = T.e;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, j = lane & 15;
+  const long long n_pairs = (long long)A.n_replicas * A.n_starts;
+  const long long pair = ((long long)blockIdx.x * kQueryWaves + wave) * 4 + g;
+  const bool live = pair < n_pairs;
+  double *W = sh_w[wave];
+
+  const int rl = live ? (int)(pair / A.n_starts) : 0, s = live ? (int)(pair - (long long)rl * A.n_starts) : 0;
+  const int r = A.first_replica + rl;
+  const Table tab = table_of(P, 1, r);                 // twin tables: each holds its own keys
+  const ReplicaState &rs = P.states[r];
+  const double gamma = A.sweep ? A.sweep[r].gamma : P.gamma;
+  double *rec = T.records + (live ? (size_t)pair * (size_t)A.max_steps * R : 0);
+  double x[S], obs[D];
+#pragma unroll
+  for (int i = 0; i < S; ++i) x[i] = live ? A.states[(size_t)s * S + i] : 0.;
+  (void)Env<ENV>::observe(P, x, obs);
+
+  EpisodeSums e;
+  e.ret = 0; e.disc = 0; e.g = 1; e.steps = 0; e.code = 0; e.ties = 0;
+  bool active = live;
+  for (int step = 0; step < A.max_steps; ++step)
+  {
+    if (__ballot(active) == 0ull) break;
+    if (active)
+    { // project(obs) of the actor's projector, unrolled over the observation as in evaluate_ac_kernel
+      uint32_t h = 449u ^ (uint32_t)(D + 1);
+#pragma unroll
+      for (int i = 0; i < D; ++i)
+        h = murmur_mix(h, tile_coord<kLanesPerReplica>(P.tile_actor, i, tile_quant(P.tile_actor, i, obs[i]), j));
+      h = murmur_mix(h, j);
+      uint32_t slot[1] = {murmur_final(h) % (uint32_t)P.tile_actor.memory};
+      double w[1];
+      query_weights<1>(tab, rs, 1, P.lin_actor, slot, w);
+      W[lane] = w[0];
+    }
+    wave_sync();
+    if (active)
+    { // ActionPolicy::read (action.cpp:99-112) over LinearRepresentation::read, then the clip of act
+      double sum = 0;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) sum += W[g * 16 + k];
+      sum /= 16;
+      const double value = query_clamp(sum, P.lin_actor.out_min, P.lin_actor.out_max);
+      const double action = query_clamp(value, P.action_min, P.action_max);
+      double before[D];
+#pragma unroll
+      for (int i = 0; i < D; ++i) before[i] = obs[i];
+      double reward = 0;
+      int terminal = 0;
+      uint32_t status = 0;
+      env_step<ENV, false, NoShare>(P, x, action, obs, reward, terminal, status);
+      active = episode_account(e, reward, gamma, terminal, status, false);
+      record_store16<D, S>(rec + (size_t)(e.steps - 1) * R, j, action, reward, value, -1, 1, e.code, before, x);
+    }
+    wave_sync();                                       // the sums above are read before the next step's weights are written
+  }
+  if (live && j == 0) episode_store<S>(A, pair, e, x);
+}
+
+// evaluate_ensemble_kernel with records: two more words, the step's votes[mai] and its members with a tie; threads 0 .. R - 1 of the
+// block (all of wave 0: R <= 24) store one word each.
+template <int ENV, int NA>
+__global__ __launch_bounds__(kQueryWaves * 64) void trajectory_ensemble_kernel(DevParams P, EnsembleTrajectoryArgs T)
+{
+  constexpr int S = Env<ENV>::S, D = Env<ENV>::D, kSlots = kQueryWaves * 4, R = GRLX_TRAJ_ENS_OBS + D + S;
+  static_assert(R <= 64, "the record is stored by one wave");
+  __shared__ double sh_w[kQueryWaves][NA * kRowStride];
+  __shared__ double sh_m[2][kSlots][8];
+  const EnsembleArgs &A = T.e;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, j = lane & 15;
+  const int slot = wave * 4 + g;                       // the member of a round this lane group serves
+  const int G = A.group_size;
+  const int grp = (int)(blockIdx.x / (unsigned)A.n_starts), s = (int)(blockIdx.x - (unsigned)grp * (unsigned)A.n_starts);
+  const int r0 = A.first_replica + grp * G;
+  double *W = sh_w[wave];
+  double *rec = T.records + (size_t)blockIdx.x * (size_t)A.max_steps * R + threadIdx.x;      // the thread's word of the episode's first record
+
+  const double gamma = A.sweep ? A.sweep[r0].gamma : P.gamma;      // the group's first replica's
+  double x[S], obs[D];
+#pragma unroll
+  for (int i = 0; i < S; ++i) x[i] = A.states[(size_t)s * S + i];
+  (void)Env<ENV>::observe(P, x, obs);
+
+  EpisodeSums e;
+  e.ret = 0; e.disc = 0; e.g = 1; e.steps = 0; e.code = 0; e.ties = 0;
+  long long member_ties = 0, agreement = 0;
+  unsigned round = 0;
+  bool active = true;
+  for (int step = 0; step < A.max_steps; ++step)
+  {
+    if (__ballot(active) == 0ull) break;               // block-uniform: every thread holds the same state
+    int votes[NA];
+    const long long ties_before = member_ties;
+    double sumq[NA];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) { votes[a] = 0; sumq[a] = 0.; }
+    for (int m0 = 0; m0 < G; m0 += kSlots, ++round)
+    {
+      double (*MQ)[8] = sh_m[round & 1u];
+      const bool member = m0 + slot < G;
+      const int r = r0 + (member ? m0 + slot : 0);
+      if (member) member_probe<ENV, NA>(P, table_of(P, 0, r), P.states[r], obs, j, lane, W);
+      wave_sync();
+      if (member && j < NA) MQ[slot][j] = member_q(P, W, g, j);
+      __syncthreads();
+      const int n = G - m0 < kSlots ? G - m0 : kSlots;
+      for (int m = 0; m < n; ++m)
+      {
+        double q[NA];
+#pragma unroll
+        for (int a = 0; a < NA; ++a) q[a] = MQ[m][a];
+        int mai, man;
+        findmax<NA>(q, mai, man);
+#pragma unroll
+        for (int a = 0; a < NA; ++a)
+        {
+          votes[a] += (mai == a) ? 1 : 0;
+          sumq[a] += q[a];
+        }
+        member_ties += man > 1 ? 1 : 0;
+      }
+    }
+    int mai, man;
+    if (A.rule == GRLX_ENSEMBLE_VOTE) findmax<NA>(votes, mai, man);
+    else findmax<NA>(sumq, mai, man);
+    int agree = votes[0];
+    double score = sumq[0];
+#pragma unroll
+    for (int a = 1; a < NA; ++a)
+    {
+      agree = (mai == a) ? votes[a] : agree;
+      score = (mai == a) ? sumq[a] : score;
+    }
+    if (A.rule == GRLX_ENSEMBLE_VOTE) score = (double)agree;
+    agreement += agree;
+    const int step_ties = (int)(member_ties - ties_before);
+    const double action = action_of<NA>(P, mai);
+    double before[D];
+#pragma unroll
+    for (int i = 0; i < D; ++i) before[i] = obs[i];
+    double reward = 0;
+    int terminal = 0;
+    uint32_t status = 0;
+    env_step<ENV, false, NoShare>(P, x, action, obs, reward, terminal, status);
+    active = episode_account(e, reward, gamma, terminal, status, man > 1);
+    if (threadIdx.x < R)
+      rec[(size_t)(e.steps - 1) * R] =
+          record_word<true, D, S>((int)threadIdx.x, action, reward, score, mai, man, e.code, agree, step_ties, before, x);
+  }
+  if (threadIdx.x == 0)
+  {
+    const long long pair = blockIdx.x;                 // group * n_starts + start
+    A.ret[pair] = e.ret;
+    A.disc[pair] = e.disc;
+    A.steps[pair] = e.steps;
+    A.terminal[pair] = e.code;
+    A.ties[pair] = e.ties;
+    A.member_ties[pair] = member_ties;
+    A.agreement[pair] = agreement;
+#pragma unroll
+    for (int i = 0; i < S; ++i) A.final_state[(size_t)pair * S + i] = x[i];
+  }
+}
+
 // The instantiations: the (environment, action count) pairs grlx_create admits for the Q agents, and the actor-critic's two environments
 bool evaluate_built(int agent, int env, int actions)
 {
@@ -426,6 +711,58 @@ hipError_t launch_evaluate_ensemble(const DevParams &P, const EnsembleArgs &A, h
   else if (P.env == GRLX_ENV_ACROBOT) hipLaunchKernelGGL((evaluate_ensemble_kernel<GRLX_ENV_ACROBOT, 3>), grid, block, 0, stream, P, A);
   else if (P.env == GRLX_ENV_CART_POLE) hipLaunchKernelGGL((evaluate_ensemble_kernel<GRLX_ENV_CART_POLE, 3>), grid, block, 0, stream, P, A);
   else hipLaunchKernelGGL((evaluate_ensemble_kernel<GRLX_ENV_COMPASS_WALKER, 3>), grid, block, 0, stream, P, A);
+  return hipGetLastError();
+}
+
+int trajectory_words(int env, bool ensemble)
+{
+  const int head = ensemble ? GRLX_TRAJ_ENS_OBS : GRLX_TRAJ_OBS;
+  switch (env)
+  {
+    case GRLX_ENV_PENDULUM: return head + Env<GRLX_ENV_PENDULUM>::D + Env<GRLX_ENV_PENDULUM>::S;
+    case GRLX_ENV_ACROBOT: return head + Env<GRLX_ENV_ACROBOT>::D + Env<GRLX_ENV_ACROBOT>::S;
+    case GRLX_ENV_CART_POLE: return head + Env<GRLX_ENV_CART_POLE>::D + Env<GRLX_ENV_CART_POLE>::S;
+    case GRLX_ENV_COMPASS_WALKER: return head + Env<GRLX_ENV_COMPASS_WALKER>::D + Env<GRLX_ENV_COMPASS_WALKER>::S;
+    default: return 0;
+  }
+}
+
+// launch_evaluate's grid; A.records zero-filled by the caller
+hipError_t launch_trajectory(const DevParams &P, const TrajectoryArgs &A, hipStream_t stream)
+{
+  const long long pairs = (long long)A.e.n_replicas * A.e.n_starts;
+  const unsigned blocks = (unsigned)((pairs + 4 * kQueryWaves - 1) / (4 * kQueryWaves));
+  if (blocks == 0) return hipSuccess;
+  if (!evaluate_built(P.agent, P.env, P.A) || A.e.max_steps < 1 || !A.records) return hipErrorInvalidValue;
+  const dim3 grid(blocks), block(kQueryWaves * 64);
+  if (P.agent == GRLX_AGENT_AC)
+  {
+    if (P.env == GRLX_ENV_CART_POLE) hipLaunchKernelGGL(trajectory_ac_kernel<GRLX_ENV_CART_POLE>, grid, block, 0, stream, P, A);
+    else hipLaunchKernelGGL(trajectory_ac_kernel<GRLX_ENV_PENDULUM>, grid, block, 0, stream, P, A);
+  }
+  else if (P.env == GRLX_ENV_PENDULUM && P.A == 3) hipLaunchKernelGGL((trajectory_q_kernel<GRLX_ENV_PENDULUM, 3>), grid, block, 0, stream, P, A);
+  else if (P.env == GRLX_ENV_PENDULUM) hipLaunchKernelGGL((trajectory_q_kernel<GRLX_ENV_PENDULUM, 5>), grid, block, 0, stream, P, A);
+  else if (P.env == GRLX_ENV_ACROBOT) hipLaunchKernelGGL((trajectory_q_kernel<GRLX_ENV_ACROBOT, 3>), grid, block, 0, stream, P, A);
+  else if (P.env == GRLX_ENV_CART_POLE) hipLaunchKernelGGL((trajectory_q_kernel<GRLX_ENV_CART_POLE, 3>), grid, block, 0, stream, P, A);
+  else hipLaunchKernelGGL((trajectory_q_kernel<GRLX_ENV_COMPASS_WALKER, 3>), grid, block, 0, stream, P, A);
+  return hipGetLastError();
+}
+
+// one block per (group, start state); A.records zero-filled by the caller
+hipError_t launch_trajectory_ensemble(const DevParams &P, const EnsembleTrajectoryArgs &A, hipStream_t stream)
+{
+  if (A.e.group_size < 1 || A.e.n_replicas % A.e.group_size != 0) return hipErrorInvalidValue;
+  const long long blocks = (long long)(A.e.n_replicas / A.e.group_size) * A.e.n_starts;
+  if (blocks == 0) return hipSuccess;
+  if (P.agent == GRLX_AGENT_AC || !evaluate_built(P.agent, P.env, P.A) || A.e.max_steps < 1 || blocks > 0x7fffffffll || !A.records ||
+      (A.e.rule != GRLX_ENSEMBLE_VOTE && A.e.rule != GRLX_ENSEMBLE_MEAN_Q))
+    return hipErrorInvalidValue;
+  const dim3 grid((unsigned)blocks), block(kQueryWaves * 64);
+  if (P.env == GRLX_ENV_PENDULUM && P.A == 3) hipLaunchKernelGGL((trajectory_ensemble_kernel<GRLX_ENV_PENDULUM, 3>), grid, block, 0, stream, P, A);
+  else if (P.env == GRLX_ENV_PENDULUM) hipLaunchKernelGGL((trajectory_ensemble_kernel<GRLX_ENV_PENDULUM, 5>), grid, block, 0, stream, P, A);
+  else if (P.env == GRLX_ENV_ACROBOT) hipLaunchKernelGGL((trajectory_ensemble_kernel<GRLX_ENV_ACROBOT, 3>), grid, block, 0, stream, P, A);
+  else if (P.env == GRLX_ENV_CART_POLE) hipLaunchKernelGGL((trajectory_ensemble_kernel<GRLX_ENV_CART_POLE, 3>), grid, block, 0, stream, P, A);
+  else hipLaunchKernelGGL((trajectory_ensemble_kernel<GRLX_ENV_COMPASS_WALKER, 3>), grid, block, 0, stream, P, A);
   return hipGetLastError();
 }
 

@@ -13,6 +13,8 @@
 // code and the summed ties over the clones (objects.h),
 // -V vote|mean: with -E, also one episode per start state of the ensemble of all clones (with -p: of each point's repetitions) acting on
 // the members' vote or on their mean Q (grlx_evaluate_ensemble), written to <output>-<run>-ensemble.txt (objects.h),
+// -T STEPS: with -E, also the steps of those episodes, STEPS of each at the most (grlx_evaluate_trajectory), one line per step taken in
+// <output>-<run>-trajectories.txt, and with -V the ensemble's in <output>-<run>-ensemble-trajectories.txt (objects.h),
 // -n: print the plan (one line per clone: i seed alpha gamma lambda epsilon) and exit before anything touches HIP, and
 // -g N: one process per GPU (rank r on the r-th visible device, started before anything touches HIP), every rank running -r replicas
 // (clones r * replicas ..., seeds and "@i" identities counted over the whole job), the learning curves reduced with one RCCL all-reduce
@@ -76,8 +78,9 @@ int main(int argc, char **argv)
   int c;
   std::vector<std::string> sweep_args;
   std::string ensemble_arg;
-  bool ensemble = false;
-  while ((c = getopt(argc, argv, "vs:r:t:lqc:g:p:nk:K:Q:E:V:")) != -1)
+  bool ensemble = false, trajectory = false;
+  int trajectory_steps = 0;
+  while ((c = getopt(argc, argv, "vs:r:t:lqc:g:p:nk:K:Q:E:V:T:")) != -1)
   {
     switch (c)
     {
@@ -96,12 +99,13 @@ int main(int argc, char **argv)
       case 'Q': opt.query_file = optarg; break;
       case 'E': opt.evaluate_file = optarg; break;
       case 'V': ensemble_arg = optarg; ensemble = true; break;
+      case 'T': trajectory_steps = atoi(optarg); trajectory = true; break;
       default: return 1;
     }
   }
   if (optind > argc - 1)
   {
-    log(0, std::string("Usage: \n  ") + argv[0] + " [-v] [-s seed] [-r replicas] [-g gpus] [-t trials] [-l] [-q] [-p path=v1,v2,...]... [-n] [-k snapshot] [-K snapshot] [-Q observations] [-E states] [-V vote|mean] <yaml file> [yaml file...]");
+    log(0, std::string("Usage: \n  ") + argv[0] + " [-v] [-s seed] [-r replicas] [-g gpus] [-t trials] [-l] [-q] [-p path=v1,v2,...]... [-n] [-k snapshot] [-K snapshot] [-Q observations] [-E states] [-V vote|mean] [-T steps] <yaml file> [yaml file...]");
     return 1;
   }
   if (opt.seed == 0)
@@ -162,6 +166,16 @@ int main(int argc, char **argv)
     else if (ensemble_arg == "mean") opt.ensemble_rule = GRLX_ENSEMBLE_MEAN_Q;
     else { log(0, "-V: unknown rule '" + ensemble_arg + "' (vote: the members' majority, mean: the argmax of their mean Q)"); return 1; }
     if (opt.evaluate_file.empty()) { log(0, "-V " + ensemble_arg + ": an ensemble evaluation needs the start states of -E <states file>"); return 1; }
+  }
+  if (trajectory)
+  { // -T needs -E's states and a length the records can have; what -E refuses is refused here under -T's name
+    if (trajectory_steps < 1 || trajectory_steps > GRLX_MAX_EPISODE_STEPS)
+    { log(0, "-T " + std::to_string(trajectory_steps) + " is outside 1 ... GRLX_MAX_EPISODE_STEPS (" + std::to_string(GRLX_MAX_EPISODE_STEPS) + ")"); return 1; }
+    if (opt.evaluate_file.empty()) { log(0, "-T " + std::to_string(trajectory_steps) + ": per-step trajectories need the start states of -E <states file>"); return 1; }
+    if (gpus > 1) { log(0, "-T: trajectories of a policy evaluation run on one GPU (-g " + std::to_string(gpus) + " is not built)"); return 1; }
+    if ((sweep_args.empty() ? opt.replicas : opt.sweep_repetitions) < 2)
+    { log(0, "-T: -E needs -r >= 2: the standard deviation over the clones divides by n - 1"); return 1; }
+    opt.trajectory_steps = trajectory_steps;
   }
   if (!opt.evaluate_file.empty())
   { // likewise: the state file is read, and -g and -r 1 refused, before any process is forked or any device looked for

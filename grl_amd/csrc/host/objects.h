@@ -55,6 +55,12 @@ struct RunOptions {
   // "ret disc steps terminal ties member_ties agreement" (%.17g), agreement = grlx_evaluate_ensemble's divided by steps * group.  With -p:
   // one line per (point, start state), the point's index first.  -1 = no -V; else GRLX_ENSEMBLE_VOTE / GRLX_ENSEMBLE_MEAN_Q.
   int ensemble_rule = -1;
+  // `grlxd -E FILE -T STEPS`: besides the unchanged returns file, the steps of those episodes up to STEPS each (grlx_evaluate_trajectory,
+  // 1 ... GRLX_MAX_EPISODE_STEPS); rank 0 writes <output>-<run>-trajectories.txt: one line per (clone, start state, step taken), ascending,
+  // "clone start step" and the words of the record (include/grlx.h: GRLX_TRAJ_*) -- action index, number of maxima and terminal code as
+  // integers, the others %.17g.  With -V also <output>-<run>-ensemble-trajectories.txt (grlx_evaluate_ensemble_trajectory), its lines
+  // beginning "group start step".  The episodes of the returns and ensemble files are not cut at STEPS.  0 = no -T.
+  int trajectory_steps = 0;
 };
 // ... the same for opt.evaluate_file -> opt.evaluate_states / _rows / _cols (messages begin with -E)
 void read_evaluate_file(RunOptions *opt);

@@ -248,6 +248,14 @@ RunPlan OnlineImpl::plan(const RunOptions &opt) const
       throw Exception("-Q " + opt.query_file + ": " + std::to_string(opt.query_cols) + " columns, the agent's observation has " + std::to_string(c.projector.dims - 1));
     if (output.empty()) throw Exception(path() + ": -Q writes <output>-<run>-policy.txt: the experiment has no output");
   }
+  if (opt.trajectory_steps != 0)
+  { // -T rides on -E: refused here with its own name, before -E's checks say the same without it
+    if (opt.evaluate_file.empty()) throw Exception(path() + ": -T: per-step trajectories need the start states of -E <states file>");
+    if (opt.trajectory_steps < 1 || opt.trajectory_steps > GRLX_MAX_EPISODE_STEPS)
+      throw Exception(path() + ": -T " + std::to_string(opt.trajectory_steps) + " is outside 1 ... GRLX_MAX_EPISODE_STEPS (" + std::to_string(GRLX_MAX_EPISODE_STEPS) + ")");
+    if (opt.world > 1) throw Exception(path() + ": -T: trajectories of a policy evaluation run on one GPU (-g " + std::to_string(opt.world) + " is not built)");
+    if (p.group < 2) throw Exception(path() + ": -T: -E needs -r >= 2: the standard deviation over the clones divides by n - 1");
+  }
   p.evaluate = !opt.evaluate_file.empty();
   if (p.evaluate)
   { // (grlx_evaluate validates the states themselves, and what it is built for, before it launches)
@@ -455,6 +463,7 @@ std::vector<double> OnlineImpl::run(const RunOptions &opt)
     write_policy_file(p, ctx, rr);
     write_returns_file(p, ctx, rr);
     write_ensemble_file(p, ctx, rr);
+    write_trajectory_files(p, ctx, rr);
     write_mean_file(p, ctx, rr, rows);
     if (save_every == "run" && !output.empty()) save_policy(p, ctx, output + "-run" + std::to_string(rr));      // online_learning.cpp:294-302
 

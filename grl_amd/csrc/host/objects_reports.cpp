@@ -153,6 +153,62 @@ void OnlineImpl::write_ensemble_file(const RunPlan &p, grlx_ctx *ctx, int run) c
     }
 }
 
+// one line per step taken of records[rows][NS][max_steps][R]: "row start step" and the record, the three integer words as integers
+static void write_record_lines(std::ofstream &ofs, const std::vector<double> &records, const std::vector<int32_t> &steps, int rows, int NS, int max_steps, int R)
+{
+  std::string line;
+  char word[48];
+  for (int k = 0; k < rows; ++k)
+    for (int s = 0; s < NS; ++s)
+    {
+      const size_t pair = (size_t)k * (size_t)NS + (size_t)s;
+      for (int t = 0; t < steps[pair]; ++t)
+      {
+        const double *rec = records.data() + (pair * (size_t)max_steps + (size_t)t) * (size_t)R;
+        snprintf(word, sizeof(word), "%d %d %d", k, s, t);
+        line = word;
+        for (int w = 0; w < R; ++w)
+        {
+          if (w == GRLX_TRAJ_ACTION_INDEX || w == GRLX_TRAJ_N_MAX || w == GRLX_TRAJ_TERMINAL) snprintf(word, sizeof(word), " %lld", (long long)rec[w]);
+          else snprintf(word, sizeof(word), " %.17g", rec[w]);
+          line += word;
+        }
+        ofs << line << '\n';
+      }
+    }
+  ofs.flush();
+}
+
+// -E -T, <output>-<run>-trajectories.txt: the first -T steps of the returns file's episodes, step by step; with -V also
+// <output>-<run>-ensemble-trajectories.txt, the ensemble file's
+void OnlineImpl::write_trajectory_files(const RunPlan &p, grlx_ctx *ctx, int run) const
+{
+  const RunOptions &opt = *p.opt;
+  if (!p.evaluate || opt.rank != 0 || opt.trajectory_steps < 1) return;
+  const int G = p.group, groups = opt.replicas / G, NS = opt.evaluate_rows, T = opt.trajectory_steps;
+  {
+    const int R = grlx_trajectory_record_words(ctx, 0);
+    check(R < 0 ? R : GRLX_OK, "-T: ");
+    std::vector<double> records((size_t)opt.replicas * (size_t)NS * (size_t)T * (size_t)R);
+    std::vector<int32_t> tsteps((size_t)opt.replicas * (size_t)NS);
+    check(grlx_evaluate_trajectory(ctx, 0, opt.replicas, opt.evaluate_states.data(), NS, T, nullptr, nullptr, tsteps.data(), nullptr, nullptr, nullptr,
+                                   records.data()),
+          "-T " + std::to_string(T) + ": ");
+    std::ofstream ofs(rules::output_name(output, run, false, 0, "-trajectories"));
+    write_record_lines(ofs, records, tsteps, opt.replicas, NS, T, R);
+  }
+  if (opt.ensemble_rule < 0) return;
+  const int R = grlx_trajectory_record_words(ctx, 1);
+  check(R < 0 ? R : GRLX_OK, "-T -V: ");
+  std::vector<double> records((size_t)groups * (size_t)NS * (size_t)T * (size_t)R);
+  std::vector<int32_t> tsteps((size_t)groups * (size_t)NS);
+  check(grlx_evaluate_ensemble_trajectory(ctx, 0, opt.replicas, G, opt.ensemble_rule, opt.evaluate_states.data(), NS, T, nullptr, nullptr, tsteps.data(),
+                                          nullptr, nullptr, nullptr, nullptr, nullptr, records.data()),
+        "-T " + std::to_string(T) + " -V: ");
+  std::ofstream ofs(rules::output_name(output, run, false, 0, "-ensemble-trajectories"));
+  write_record_lines(ofs, records, tsteps, groups, NS, T, R);
+}
+
 // `grlxd -g N`, <output>-<run>-mean.txt: the learning curve over the clones of ALL ranks: per row {sum, sum of squares, count} of this
 // device's replicas (grlx_curve_stats, fixed reduction order), ONE all-reduce over the ranks, mean and standard deviation on rank 0.
 // (Trial-bounded runs write the same rows on every rank; a steps budget with more than one clone is refused by the plan.)

@@ -605,9 +605,102 @@ class Runner:
                                                    _ptr(final_state, C.c_double)))
         return EnsembleEvaluation(ret, disc, steps, terminal, ties, member_ties, agreement, final_state)
 
+    def trajectory_record_words(self, ensemble=False):
+        """R, the doubles of one trajectory record of this context (grlx_trajectory_record_words)"""
+        words = self.lib.grlx_trajectory_record_words(self._ctx, 1 if ensemble else 0)
+        if words < 0:
+            capi.check(words)
+        return words
+
+    def evaluate_trajectory(self, states, max_steps, replicas=None):
+        """Runner.evaluate with every step of every episode: Trajectory(ret, disc, steps, terminal, ties, final_state, records),
+        records[replica][start][max_steps][R] with one record per step taken and zeros behind an episode's end.  The views .action,
+        .reward, .value, .action_index, .n_max, .code, .obs and .state cut the records by name; .episode(k, s) gives the records of one
+        episode.  max_steps sizes the records, so it has no default (include/grlx.h: grlx_evaluate_trajectory)."""
+        states = np.ascontiguousarray(states, dtype=np.float64)
+        if states.ndim != 2 or states.shape[1] != self.state_dims:
+            raise ValueError(f"expected states of shape (n, {self.state_dims}), got {states.shape}")
+        first, count = self._replica_range(replicas)
+        n, max_steps = states.shape[0], int(max_steps)
+        words = self.trajectory_record_words(False)
+        ret, disc = np.zeros((count, n), np.float64), np.zeros((count, n), np.float64)
+        steps, terminal, ties = np.zeros((count, n), np.int32), np.zeros((count, n), np.int32), np.zeros((count, n), np.int32)
+        final_state = np.zeros((count, n, self.state_dims), np.float64)
+        records = np.zeros((count, n, max(max_steps, 0), words), np.float64)
+        capi.check(self.lib.grlx_evaluate_trajectory(self._ctx, first, count, _ptr(states, C.c_double), n, max_steps, _ptr(ret, C.c_double),
+                                                     _ptr(disc, C.c_double), _ptr(steps, C.c_int32), _ptr(terminal, C.c_int32),
+                                                     _ptr(ties, C.c_int32), _ptr(final_state, C.c_double), _ptr(records, C.c_double)))
+        return Trajectory(ret, disc, steps, terminal, ties, final_state, records)
+
+    def evaluate_ensemble_trajectory(self, states, group_size, max_steps, rule="vote", replicas=None):
+        """Runner.evaluate_ensemble with every step of every episode: EnsembleTrajectory(..., records), records[group][start][max_steps][R];
+        beside Trajectory's views .step_agreement (votes[mai] of the step) and .step_member_ties (members with a tie at the step), and
+        .value is the combined score of the action taken (include/grlx.h: grlx_evaluate_ensemble_trajectory)."""
+        rules = {"vote": capi.ENSEMBLE_VOTE, "mean": capi.ENSEMBLE_MEAN_Q, "mean_q": capi.ENSEMBLE_MEAN_Q}
+        rule = rules[rule] if isinstance(rule, str) else int(rule)
+        states = np.ascontiguousarray(states, dtype=np.float64)
+        if states.ndim != 2 or states.shape[1] != self.state_dims:
+            raise ValueError(f"expected states of shape (n, {self.state_dims}), got {states.shape}")
+        first, count = self._replica_range(replicas)
+        group_size, max_steps = int(group_size), int(max_steps)
+        groups = count // group_size if group_size > 0 else 0
+        n = states.shape[0]
+        words = self.trajectory_record_words(True)
+        ret, disc = np.zeros((groups, n), np.float64), np.zeros((groups, n), np.float64)
+        steps, terminal, ties = np.zeros((groups, n), np.int32), np.zeros((groups, n), np.int32), np.zeros((groups, n), np.int32)
+        member_ties, agreement = np.zeros((groups, n), np.int64), np.zeros((groups, n), np.int64)
+        final_state = np.zeros((groups, n, self.state_dims), np.float64)
+        records = np.zeros((groups, n, max(max_steps, 0), words), np.float64)
+        capi.check(self.lib.grlx_evaluate_ensemble_trajectory(self._ctx, first, count, group_size, rule, _ptr(states, C.c_double), n, max_steps,
+                                                              _ptr(ret, C.c_double), _ptr(disc, C.c_double), _ptr(steps, C.c_int32),
+                                                              _ptr(terminal, C.c_int32), _ptr(ties, C.c_int32), _ptr(member_ties, C.c_int64),
+                                                              _ptr(agreement, C.c_int64), _ptr(final_state, C.c_double), _ptr(records, C.c_double)))
+        return EnsembleTrajectory(ret, disc, steps, terminal, ties, member_ties, agreement, final_state, records)
+
 
 Evaluation = collections.namedtuple("Evaluation", "ret disc steps terminal ties final_state")
 EnsembleEvaluation = collections.namedtuple("EnsembleEvaluation", "ret disc steps terminal ties member_ties agreement final_state")
+
+
+class _RecordViews:
+    """Read-only views by name into records[..., max_steps, R] (include/grlx.h: GRLX_TRAJ_*).  `_OBS`: the word at which the observation
+    starts; the model state follows it and has final_state's width."""
+    __slots__ = ()
+    _OBS = capi.TRAJ_OBS
+
+    def _cut(self, lo, hi=None):
+        view = self.records[..., lo] if hi is None else self.records[..., lo:hi]
+        view.flags.writeable = False
+        return view
+
+    action = property(lambda self: self._cut(capi.TRAJ_ACTION))
+    reward = property(lambda self: self._cut(capi.TRAJ_REWARD))
+    value = property(lambda self: self._cut(capi.TRAJ_VALUE))
+    action_index = property(lambda self: self._cut(capi.TRAJ_ACTION_INDEX))
+    n_max = property(lambda self: self._cut(capi.TRAJ_N_MAX))
+    code = property(lambda self: self._cut(capi.TRAJ_TERMINAL))
+    obs = property(lambda self: self._cut(self._OBS, self.records.shape[-1] - self.final_state.shape[-1]))
+    state = property(lambda self: self._cut(self.records.shape[-1] - self.final_state.shape[-1], self.records.shape[-1]))
+
+    def episode(self, k, s):
+        """the records of the steps pair (k, s) took: [steps[k, s]][R]"""
+        view = self.records[k, s, :int(self.steps[k, s])]
+        view.flags.writeable = False
+        return view
+
+
+class Trajectory(_RecordViews, collections.namedtuple("Trajectory", "ret disc steps terminal ties final_state records")):
+    """What Runner.evaluate_trajectory returns: Evaluation's fields and records[replica][start][max_steps][R]."""
+    __slots__ = ()
+
+
+class EnsembleTrajectory(_RecordViews, collections.namedtuple("EnsembleTrajectory",
+                                                              "ret disc steps terminal ties member_ties agreement final_state records")):
+    """What Runner.evaluate_ensemble_trajectory returns: EnsembleEvaluation's fields and records[group][start][max_steps][R]."""
+    __slots__ = ()
+    _OBS = capi.TRAJ_ENS_OBS
+    step_agreement = property(lambda self: self._cut(capi.TRAJ_ENS_AGREEMENT))
+    step_member_ties = property(lambda self: self._cut(capi.TRAJ_ENS_MEMBER_TIES))
 
 
 class EnsembleResult:

@@ -462,7 +462,8 @@ int  grlx_query_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, int g
  * final state then being those of sines taken outside their domain), GRLX_ENV_EXTERNAL (no environment), projector/tile_coding:safe >= 1
  * ("not built"), an (environment, action count) pair without an instantiation (built: pendulum x {3, 5} actions, acrobot, cart-pole and
  * walker x 3; actor-critic: cart-pole and pendulum).  n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
- * NOT BUILT: per-step trajectories, the epsilon-greedy learning policy, acting on the target network, the batch path. */
+ * The steps of these episodes: grlx_evaluate_trajectory (below).
+ * NOT BUILT: the epsilon-greedy learning policy, acting on the target network, the batch path. */
 int  grlx_evaluate(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][state_dims]*/, int n_starts,
                    int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state);
 
@@ -494,13 +495,56 @@ int  grlx_evaluate(grlx_ctx *ctx, int first_replica, int n_replicas, const doubl
  * Validated on the host before anything is launched (GRLX_ERR_INVALID, nothing written, the reason named): everything grlx_evaluate
  * refuses, group_size < 1, n_replicas % group_size != 0, an unknown rule, an actor-critic context ("not built": a vote over
  * continuous actions is mapping/policy/multi's).  n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
+ * The steps of these episodes: grlx_evaluate_ensemble_trajectory (below).
  * NOT BUILT: the reference's other discrete strategies (multiply, rank voting, density based), sampling from the combined
- * distribution, per-step trajectories, the batch path. */
+ * distribution, the batch path. */
 enum { GRLX_ENSEMBLE_VOTE = 0, GRLX_ENSEMBLE_MEAN_Q = 1 };
 int  grlx_evaluate_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule,
                             const double *states /*[n_starts][state_dims]*/, int n_starts, int max_steps,
                             double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
                             int64_t *member_ties, int64_t *agreement, double *final_state);
+
+/* --- per-step trajectories of the evaluation episodes ----------------------------------------------------------------------------------
+ * grlx_evaluate and grlx_evaluate_ensemble with one more output: every step of every episode.  The episodes, the sums and every rule
+ * above are the sibling's, bit for bit; kernels of their own write, per step taken, one record of R doubles:
+ *   records[pair][max_steps][R], pair = (replica - first_replica) * n_starts + start (ensemble: group * n_starts + start), record t = the
+ *   pair's step t from 0.  R = grlx_trajectory_record_words(ctx, ensemble) = 6 + D + S (ensemble: 8 + D + S), D / S the environment's
+ *   observation / model state dimensions (grlx_env_dims): 11, 15, 15, 22 (13, 17, 17, 24) for pendulum, acrobot, cart-pole, walker.
+ * Small integers are stored as doubles, exactly.  The words of a record:
+ *   GRLX_TRAJ_ACTION        the value handed to the environment
+ *   GRLX_TRAJ_REWARD        the step's reward; added up in step order it is ret
+ *   GRLX_TRAJ_VALUE         Q agents: Q(obs, chosen action) after the representation's clamp, grlx_query_q's `value` at that observation.
+ *                           Actor-critic: the actor's read after the representation's clamp and BEFORE the action clip, what
+ *                           grlx_query_state(table 1) returns there.  Ensemble: the combined score of the action taken, votes[mai] as a
+ *                           double (GRLX_ENSEMBLE_VOTE) or sumq[mai], the sum and not the mean (GRLX_ENSEMBLE_MEAN_Q)
+ *   GRLX_TRAJ_ACTION_INDEX  mai (the ensemble: of the combined score); -1 for the actor-critic
+ *   GRLX_TRAJ_N_MAX         man, the number of maxima; 1 for the actor-critic
+ *   GRLX_TRAJ_TERMINAL      the episode's code AFTER this step: 0 while it goes on and in the last record of an episode cut at max_steps,
+ *                           else 1 / 2 / 3 as grlx_evaluate defines them
+ *   ensemble only:  GRLX_TRAJ_ENS_AGREEMENT  votes[mai] of this step, under either rule;  GRLX_TRAJ_ENS_MEMBER_TIES  the members with
+ *                   man_m > 1 at this step.  Summed over an episode's records they are agreement and member_ties.
+ *   GRLX_TRAJ_OBS (ensemble: GRLX_TRAJ_ENS_OBS) ... + D   the observation the policy ACTED ON, i.e. before the step
+ *   ... + D ... R           the MODEL state AFTER the step, time included: the last record's is final_state; the start state is the caller's
+ * Records at index >= the pair's steps are all-zero bits (+0.0).
+ * max_steps: 1 ... GRLX_MAX_EPISODE_STEPS.  It sizes the caller's buffer, so 0 is refused here.  records must not be NULL (without it, call
+ * the sibling); the other outputs may be.  Staged in chunks of start states under grlx_set_query_chunk_bytes' bound, records included:
+ * a chunk never exceeds the bound, so a single start state's column -- n_replicas (ensemble: groups) * max_steps * R * 8 bytes of records
+ * and its sums -- that does not fit is refused, with the remedies named (fewer replicas per call, a smaller max_steps, a larger bound).
+ * Validated on the host before anything is launched (GRLX_ERR_INVALID, nothing written, the reason named): everything the sibling
+ * refuses, and the three cases above.  Like the siblings they change nothing in the context, wait for the stream of the last grlx_run
+ * and do not count as a launch.
+ * NOT BUILT: trajectories of the batch path and of the epsilon-greedy learning policy, streaming records to a file descriptor. */
+enum { GRLX_TRAJ_ACTION = 0, GRLX_TRAJ_REWARD = 1, GRLX_TRAJ_VALUE = 2, GRLX_TRAJ_ACTION_INDEX = 3, GRLX_TRAJ_N_MAX = 4, GRLX_TRAJ_TERMINAL = 5,
+       GRLX_TRAJ_OBS = 6, GRLX_TRAJ_ENS_AGREEMENT = 6, GRLX_TRAJ_ENS_MEMBER_TIES = 7, GRLX_TRAJ_ENS_OBS = 8 };
+int  grlx_trajectory_record_words(grlx_ctx *ctx, int ensemble);      /* R; a negative status for a context without such episodes */
+int  grlx_evaluate_trajectory(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][state_dims]*/, int n_starts,
+                              int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state,
+                              double *records /*[n_replicas][n_starts][max_steps][R]*/);
+int  grlx_evaluate_ensemble_trajectory(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule,
+                                       const double *states /*[n_starts][state_dims]*/, int n_starts, int max_steps,
+                                       double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                                       int64_t *member_ties, int64_t *agreement, double *final_state,
+                                       double *records /*[n_replicas / group_size][n_starts][max_steps][R]*/);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * The per-step plug-in interfaces on the replicas of a context: one call of the reference's interface for EVERY replica per

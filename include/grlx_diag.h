@@ -60,6 +60,11 @@ int grlx_snapshot_naive_copy(grlx_ctx *ctx, uint64_t *bytes, double *out_ms, dou
 /* Policy queries (grlx_query_q / _state / _ensemble, grlx_fqi_query): the bound on the device scratch one call holds, process-wide; 0 = the default,
  * 256 MiB.  A chunk never has less than one observation.  For tests: a small value forces several chunks at a small shape. */
 int grlx_set_query_chunk_bytes(uint64_t bytes);
+/* The device time of the reads' kernels, for tools/trajectory_throughput.py.  enable != 0: from now on every chunk of every query,
+ * evaluation and trajectory call is timed by events around its launches (a trajectory chunk: the zero fill of its records and the kernel),
+ * each waited for before the chunk's outputs are copied; the sums start at zero.  enable == 0: timing off.  Either way *ms (may be NULL)
+ * receives the milliseconds and *chunks (may be NULL) the number of chunks timed since the last enabling call.  Process-wide, off by default. */
+int grlx_read_kernel_timing(int enable, double *ms, int *chunks);
 
 #ifdef __cplusplus
 }
