@@ -1125,3 +1125,239 @@ extern "C" int grlx_fqi_query(grlx_fqi_ctx *ctx, int first_replica, int n_replic
   if (err != hipSuccess) return ffail(GRLX_ERR_HIP, "grlx_fqi_query failed: %s", hipGetErrorString(err));
   return GRLX_OK;
 }
+
+// ----------------------------------------------------------------------------------- greedy evaluation episodes ---
+// grlx_fqi_evaluate, grlx_fqi_evaluate_trajectory: for every (replica, start state) pair one greedy episode of the batch path's policy
+// from a MODEL state of the caller's choice -- fqi_test_kernel's loop with the caller's state in place of Task::start and without the
+// tie-breaking draw (the first maximum acts; `ties` counts the steps with more than one).  Reads F.net, F.env and the projector's
+// constants only: no row, no batches_done, no stream, no status bit, no parameter changes.  Appended after the query: every kernel above
+// keeps its instruction stream.
+//
+// Layout.  The policy is A small dense forward passes per step, so ONE LANE is one pair; blockIdx.y is the replica, which makes the
+// network block-uniform: its P = 5 H + 1 parameters (the first of the replica's four P-blocks in F.net) are staged once into LDS, as
+// fqi_targets_kernel stages them, and handed to ann_forward<H> as they are (broadcast reads: every lane reads the same word).  blockIdx.x
+// covers the start states 64 at a time.  After the staging barrier no lane talks to another.  The episode loop is wave-uniform: it runs
+// while a ballot finds an active lane and the step counter is below max_steps; finished and dead lanes skip the step under a predicate.
+// Nothing is indexed at run time by a lane's value: the action of pass k and the chosen action are selects over the A actions (an
+// indexed read of F.actions, or of a local q[], would go to scratch), findmax runs on the Q-values as they are produced.
+// The two observation inputs of a step are the same in its A passes: fqi_normalise forms them from the same operands by the same
+// operations each time, so a compiler that forms them once changes no bit; ann_forward itself is not re-associated.
+// RECORD: one record of GRLX_TRAJ_OBS + 2 + 3 doubles per step taken, and -- behind the lane's own episode's end -- zeros up to
+// max_steps, written by the lane itself: the staging buffer is never filled twice.
+namespace grlx {
+
+constexpr int kFqiTrajWords = GRLX_TRAJ_OBS + kFqiD + kFqiS;
+constexpr int kFqiEvalDomain = 3;          // terminal code of a step that ended outside Env<PENDULUM>::in_domain (grlx_evaluate's)
+
+struct FqiEvalArgs {
+  int32_t first_replica, n_starts, max_steps;      // n_starts: of this chunk; max_steps: 1 ... GRLX_MAX_EPISODE_STEPS
+  const double *states;                            // [n_starts][3]
+  double  *ret, *disc;                             // [n_replicas][n_starts], as are steps, terminal and ties
+  int32_t *steps, *terminal, *ties;
+  double  *final_state;                            // [n_replicas][n_starts][3]
+  double  *records;                                // RECORD: [n_replicas][n_starts][max_steps][kFqiTrajWords]
+};
+
+template <int H, bool RECORD>
+__global__ __launch_bounds__(64) void fqi_evaluate_kernel(FqiParams F, FqiEvalArgs A)
+{
+  constexpr int R = kFqiTrajWords;
+  __shared__ double sh_net[(kFqiNIn + 1) * H + H + 1];
+  const int rl = blockIdx.y, r = A.first_replica + rl;
+  const double *net = F.net + (size_t)r * 4 * F.P;
+  for (int k = threadIdx.x; k < F.P; k += blockDim.x) sh_net[k] = net[k];
+  __syncthreads();
+  const int s = (int)blockIdx.x * 64 + (int)threadIdx.x;
+  const bool live = s < A.n_starts;                    // dead lanes of the last block neither load nor store
+  const size_t pair = (size_t)rl * (size_t)A.n_starts + (size_t)(live ? s : 0);
+  double *rec = RECORD ? A.records + pair * (size_t)A.max_steps * R : nullptr;      // 64-bit: pairs * max_steps * R * 8 bytes pass 2^32
+  double x[kFqiS], obs[kFqiD];
+#pragma unroll
+  for (int i = 0; i < kFqiS; ++i) x[i] = live ? A.states[(size_t)s * kFqiS + i] : 0.;
+  (void)Env<GRLX_ENV_PENDULUM>::observe(F.env, x, obs);                // the start state's terminal code is ignored
+
+  double ret = 0, disc = 0, g = 1;
+  int steps = 0, code = 0, ties = 0;
+  bool active = live;
+  for (int step = 0; step < A.max_steps; ++step)
+  {
+    if (__ballot(active) == 0ull) break;               // wave-uniform
+    if (active)
+    {
+      double best = 0, action = 0;
+      int mai = 0, man = 1;                            // GreedySampler::findmax (greedy.cpp:47-61), as fqi_test_kernel runs it
+      for (int k = 0; k < F.A; ++k)
+      {
+        double ak = F.actions[0];                      // k is uniform: scalar selects, no indexed read of the parameter block
+#pragma unroll
+        for (int a = 1; a < kMaxActions; ++a) ak = (k == a) ? F.actions[a] : ak;
+        double in[kFqiNIn];
+        fqi_normalise(F, obs, ak, in);
+        const double q = ann_forward<H>(sh_net, in, nullptr);
+        if (k == 0 || q > best) { best = q; action = ak; mai = k; man = 1; }
+        else if (q == best) man++;
+      }
+      double before[kFqiD];
+#pragma unroll
+      for (int i = 0; i < kFqiD; ++i) before[i] = obs[i];
+      double reward = 0;
+      int terminal = 0;
+      uint32_t status = 0;
+      env_step<GRLX_ENV_PENDULUM, false>(F.env, x, action, obs, reward, terminal, status);
+      ret += reward;
+      disc += g * reward;
+      g = g * F.gamma_tau;
+      ties += man > 1 ? 1 : 0;
+      code = (status & ST_DOMAIN) ? kFqiEvalDomain : terminal;
+      active = code == 0;
+      if constexpr (RECORD)
+      {
+        double *w = rec + (size_t)steps * R;
+        w[GRLX_TRAJ_ACTION] = action;
+        w[GRLX_TRAJ_REWARD] = reward;
+        w[GRLX_TRAJ_VALUE] = best;
+        w[GRLX_TRAJ_ACTION_INDEX] = (double)mai;
+        w[GRLX_TRAJ_N_MAX] = (double)man;
+        w[GRLX_TRAJ_TERMINAL] = (double)code;
+#pragma unroll
+        for (int i = 0; i < kFqiD; ++i) w[GRLX_TRAJ_OBS + i] = before[i];
+#pragma unroll
+        for (int i = 0; i < kFqiS; ++i) w[GRLX_TRAJ_OBS + kFqiD + i] = x[i];
+      }
+      steps++;
+    }
+  }
+  if (!live) return;
+  if constexpr (RECORD)
+    for (size_t k = (size_t)steps * R; k < (size_t)A.max_steps * R; ++k) rec[k] = 0.;       // behind the episode's end: all-zero bits
+  A.ret[pair] = ret;
+  A.disc[pair] = disc;
+  A.steps[pair] = steps;
+  A.terminal[pair] = code;
+  A.ties[pair] = ties;
+#pragma unroll
+  for (int i = 0; i < kFqiS; ++i) A.final_state[pair * kFqiS + i] = x[i];
+}
+
+} // namespace grlx
+
+namespace {
+
+// what both evaluations check before they touch the device
+int fqi_evaluate_admit(grlx_fqi_ctx *ctx, const char *who, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps)
+{
+  if (!ctx) return ffail(GRLX_ERR_INVALID, "%s: ctx is null", who);
+  if (n_starts < 0) return ffail(GRLX_ERR_INVALID, "%s: n_starts = %d", who, n_starts);
+  if (first_replica < 0 || n_replicas < 0 || (int64_t)first_replica + n_replicas > ctx->F.R)
+    return ffail(GRLX_ERR_INVALID, "%s: replica range [%d, %lld) is outside the context's %d replicas", who, first_replica,
+                 (long long)first_replica + n_replicas, ctx->F.R);
+  if (!states) return ffail(GRLX_ERR_INVALID, "%s: states is null", who);
+  if (max_steps < 0 || max_steps > GRLX_MAX_EPISODE_STEPS)
+    return ffail(GRLX_ERR_INVALID, "%s: max_steps = %d is outside 1 ... GRLX_MAX_EPISODE_STEPS (%d; 0 = that cap)", who, max_steps, GRLX_MAX_EPISODE_STEPS);
+  for (int s = 0; s < n_starts; ++s)
+    for (int i = 0; i < kFqiS; ++i)
+    { // below 2^17 the RK4 stages of one step stay inside the branch-free sine's domain (grlx_evaluate's bound)
+      const double v = states[(size_t)s * kFqiS + i];
+      if (!std::isfinite(v)) return ffail(GRLX_ERR_INVALID, "%s: state row %d, component %d is not finite (%g)", who, s, i, v);
+      if (!(std::fabs(v) < 0x1p17)) return ffail(GRLX_ERR_INVALID, "%s: state row %d, component %d (%g) is out of range: its magnitude reaches 2^17", who, s, i, v);
+    }
+  return GRLX_OK;
+}
+
+// the episodes of admitted arguments, in chunks of start states of at most per_start bytes of staging each; records == nullptr: the sums alone
+int fqi_evaluate_run(grlx_fqi_ctx *ctx, const char *who, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps,
+                     uint64_t per_start, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state, double *records)
+{
+  FQI_TRY(hipDeviceSynchronize());
+  const uint64_t fit = g_fqi_query_chunk_bytes / per_start;
+  const int chunk = (int)(fit < 1 ? 1 : fit > (uint64_t)n_starts ? (uint64_t)n_starts : fit);
+  const size_t rows = (size_t)n_replicas, pairs = rows * (size_t)chunk;
+  const size_t rec_elem = records ? sizeof(double) * (size_t)kFqiTrajWords * (size_t)max_steps : 0;
+  // one allocation, the doubles first: states, ret, disc, final_state, records, then the three int32 arrays
+  const size_t n_double = (size_t)chunk * kFqiS + 2 * pairs + pairs * kFqiS + pairs * (rec_elem / sizeof(double));
+  char *dev = nullptr;
+  if (hipMalloc((void **)&dev, n_double * sizeof(double) + 3 * pairs * sizeof(int32_t)) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return ffail(GRLX_ERR_OOM, "%s: out of device memory (%zu bytes of staging)", who, n_double * sizeof(double) + 3 * pairs * sizeof(int32_t));
+  }
+  double *dstates = (double *)dev, *dret = dstates + (size_t)chunk * kFqiS, *ddisc = dret + pairs, *dfinal = ddisc + pairs, *drec = dfinal + pairs * kFqiS;
+  int32_t *dsteps = (int32_t *)(drec + pairs * (rec_elem / sizeof(double))), *dterm = dsteps + pairs, *dties = dterm + pairs;
+  hipError_t err = hipSuccess;
+  for (int s0 = 0; s0 < n_starts && err == hipSuccess; s0 += chunk)
+  {
+    const int nc = n_starts - s0 < chunk ? n_starts - s0 : chunk;
+    err = hipMemcpy(dstates, states + (size_t)s0 * kFqiS, sizeof(double) * kFqiS * (size_t)nc, hipMemcpyHostToDevice);
+    if (err != hipSuccess) break;
+    FqiEvalArgs A;
+    A.first_replica = first_replica; A.n_starts = nc; A.max_steps = max_steps; A.states = dstates;
+    A.ret = dret; A.disc = ddisc; A.steps = dsteps; A.terminal = dterm; A.ties = dties; A.final_state = dfinal; A.records = records ? drec : nullptr;
+    const dim3 grid((unsigned)((nc + 63) / 64), (unsigned)n_replicas), block(64);
+    if (records) { FQI_FOR_H(ctx->F.H, hipLaunchKernelGGL((fqi_evaluate_kernel<HH, true>), grid, block, 0, nullptr, ctx->F, A)); }
+    else { FQI_FOR_H(ctx->F.H, hipLaunchKernelGGL((fqi_evaluate_kernel<HH, false>), grid, block, 0, nullptr, ctx->F, A)); }
+    err = hipGetLastError();
+    // device [replica][nc] -> host [replica][n_starts] at s0
+    const struct { void *host; const void *dev; size_t elem; } outs[7] = {
+        {ret, dret, sizeof(double)}, {disc, ddisc, sizeof(double)}, {steps, dsteps, sizeof(int32_t)}, {terminal, dterm, sizeof(int32_t)},
+        {ties, dties, sizeof(int32_t)}, {final_state, dfinal, sizeof(double) * kFqiS}, {records, drec, rec_elem}};
+    for (int o = 0; o < 7 && err == hipSuccess; ++o)
+      if (outs[o].host)
+        err = hipMemcpy2D((char *)outs[o].host + (size_t)s0 * outs[o].elem, (size_t)n_starts * outs[o].elem, outs[o].dev, (size_t)nc * outs[o].elem,
+                          (size_t)nc * outs[o].elem, rows, hipMemcpyDeviceToHost);
+  }
+  if (err == hipSuccess) err = hipDeviceSynchronize();
+  (void)hipFree(dev);
+  if (err != hipSuccess) return ffail(GRLX_ERR_HIP, "%s failed: %s", who, hipGetErrorString(err));
+  return GRLX_OK;
+}
+
+// a start state's staged bytes besides its records: the state and its rows' sums
+inline uint64_t fqi_evaluate_sums_bytes(int n_replicas)
+{
+  return sizeof(double) * kFqiS + (2 * sizeof(double) + 3 * sizeof(int32_t) + sizeof(double) * kFqiS) * (uint64_t)n_replicas;
+}
+
+} // namespace
+
+extern "C" {
+
+int grlx_fqi_evaluate(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, double *ret, double *disc,
+                      int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state)
+{
+  const char *who = "grlx_fqi_evaluate";
+  int rc = fqi_evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps);
+  if (rc != GRLX_OK) return rc;
+  if (max_steps == 0) max_steps = GRLX_MAX_EPISODE_STEPS;
+  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
+  return fqi_evaluate_run(ctx, who, first_replica, n_replicas, states, n_starts, max_steps, fqi_evaluate_sums_bytes(n_replicas), ret, disc, steps, terminal,
+                          ties, final_state, nullptr);
+}
+
+int grlx_fqi_trajectory_record_words(grlx_fqi_ctx *ctx)
+{
+  if (!ctx) return ffail(GRLX_ERR_INVALID, "grlx_fqi_trajectory_record_words: ctx is null");
+  return kFqiTrajWords;
+}
+
+int grlx_fqi_evaluate_trajectory(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, double *ret,
+                                 double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state, double *records)
+{
+  const char *who = "grlx_fqi_evaluate_trajectory";
+  int rc = fqi_evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps);
+  if (rc != GRLX_OK) return rc;
+  if (!records) return ffail(GRLX_ERR_INVALID, "%s: records is null (for the sums alone call grlx_fqi_evaluate)", who);
+  if (max_steps == 0)
+    return ffail(GRLX_ERR_INVALID, "%s: max_steps = 0: the records are sized by max_steps, so there is no default here (1 ... GRLX_MAX_EPISODE_STEPS = %d)", who,
+                 GRLX_MAX_EPISODE_STEPS);
+  // unlike the sums, a chunk with records never exceeds the bound: a column that does not fit is refused instead of staged as "at least one"
+  const uint64_t column = (uint64_t)n_replicas * (uint64_t)max_steps * (uint64_t)kFqiTrajWords * sizeof(double);
+  const uint64_t per_start = column + fqi_evaluate_sums_bytes(n_replicas);
+  if (per_start > g_fqi_query_chunk_bytes)
+    return ffail(GRLX_ERR_INVALID, "%s: one start state's column of records is %llu bytes (%d rows x %d steps x %d words x 8; %llu with its sums) and exceeds "
+                 "the staging bound of %llu bytes: ask for fewer replicas per call, a smaller max_steps, or raise the bound with grlx_set_query_chunk_bytes", who,
+                 (unsigned long long)column, n_replicas, max_steps, kFqiTrajWords, (unsigned long long)per_start, (unsigned long long)g_fqi_query_chunk_bytes);
+  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
+  return fqi_evaluate_run(ctx, who, first_replica, n_replicas, states, n_starts, max_steps, per_start, ret, disc, steps, terminal, ties, final_state, records);
+}
+
+} // extern "C"

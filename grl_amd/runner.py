@@ -799,15 +799,67 @@ class FqiRunner:
         obs = np.ascontiguousarray(obs, dtype=np.float64)
         if obs.ndim != 2 or obs.shape[1] != 2:
             raise ValueError(f"expected observations of shape (n, 2), got {obs.shape}")
-        if replicas is None:
-            first, count = 0, self.cfg.n_replicas
-        elif isinstance(replicas, range):
-            first, count = replicas.start, len(replicas)
-        else:
-            first, count = (int(x) for x in replicas)
+        first, count = self._replica_range(replicas)
         q = np.zeros((count, obs.shape[0], self.cfg.action_steps), np.float64)
         capi.check(self.lib.grlx_fqi_query(self._ctx, first, count, _ptr(obs, C.c_double), obs.shape[0], _ptr(q, C.c_double)))
         return q
+
+    def _replica_range(self, replicas):
+        if replicas is None:
+            return 0, self.cfg.n_replicas
+        if isinstance(replicas, range):
+            return replicas.start, len(replicas)
+        first, count = (int(x) for x in replicas)
+        return first, count
+
+    STATE_DIMS = 3          # the pendulum's model state: angle, velocity, time
+
+    def _state_rows(self, states):
+        states = np.ascontiguousarray(states, dtype=np.float64)
+        if states.ndim != 2 or states.shape[1] != self.STATE_DIMS:
+            raise ValueError(f"expected states of shape (n, {self.STATE_DIMS}), got {states.shape}")
+        return states
+
+    def evaluate(self, states, replicas=None, max_steps=0):
+        """One greedy episode of the fitted policy per (replica, start state) pair, on the device, from states[n][3] (the pendulum's
+        MODEL state: angle, velocity, time) to its end or to max_steps (0 = GRLX_MAX_EPISODE_STEPS): Evaluation(ret, disc, steps,
+        terminal, ties, final_state), each [replica][start].  The first maximum of Q(obs, .) acts; ties counts the steps at which it was
+        not unique (no random draw).  terminal: 1 timed out, 0 cut at max_steps, 3 left the portable math's domain.  disc discounts by
+        gamma ** control_step per step.  The context is not changed (include/grlx.h: grlx_fqi_evaluate)."""
+        states = self._state_rows(states)
+        first, count = self._replica_range(replicas)
+        n = states.shape[0]
+        ret, disc = np.zeros((count, n), np.float64), np.zeros((count, n), np.float64)
+        steps, terminal, ties = np.zeros((count, n), np.int32), np.zeros((count, n), np.int32), np.zeros((count, n), np.int32)
+        final_state = np.zeros((count, n, self.STATE_DIMS), np.float64)
+        capi.check(self.lib.grlx_fqi_evaluate(self._ctx, first, count, _ptr(states, C.c_double), n, int(max_steps), _ptr(ret, C.c_double),
+                                              _ptr(disc, C.c_double), _ptr(steps, C.c_int32), _ptr(terminal, C.c_int32), _ptr(ties, C.c_int32),
+                                              _ptr(final_state, C.c_double)))
+        return Evaluation(ret, disc, steps, terminal, ties, final_state)
+
+    def trajectory_record_words(self):
+        """R = 11, the doubles of one trajectory record (grlx_fqi_trajectory_record_words)"""
+        words = self.lib.grlx_fqi_trajectory_record_words(self._ctx)
+        if words < 0:
+            capi.check(words)
+        return words
+
+    def evaluate_trajectory(self, states, max_steps, replicas=None):
+        """FqiRunner.evaluate with every step of every episode: Trajectory(ret, disc, steps, terminal, ties, final_state, records),
+        records[replica][start][max_steps][11] with one record per step taken and zeros behind an episode's end; the views and
+        .episode(k, s) are Runner.evaluate_trajectory's (include/grlx.h: grlx_fqi_evaluate_trajectory)."""
+        states = self._state_rows(states)
+        first, count = self._replica_range(replicas)
+        n, max_steps = states.shape[0], int(max_steps)
+        words = self.trajectory_record_words()
+        ret, disc = np.zeros((count, n), np.float64), np.zeros((count, n), np.float64)
+        steps, terminal, ties = np.zeros((count, n), np.int32), np.zeros((count, n), np.int32), np.zeros((count, n), np.int32)
+        final_state = np.zeros((count, n, self.STATE_DIMS), np.float64)
+        records = np.zeros((count, n, max(max_steps, 0), words), np.float64)
+        capi.check(self.lib.grlx_fqi_evaluate_trajectory(self._ctx, first, count, _ptr(states, C.c_double), n, max_steps, _ptr(ret, C.c_double),
+                                                         _ptr(disc, C.c_double), _ptr(steps, C.c_int32), _ptr(terminal, C.c_int32),
+                                                         _ptr(ties, C.c_int32), _ptr(final_state, C.c_double), _ptr(records, C.c_double)))
+        return Trajectory(ret, disc, steps, terminal, ties, final_state, records)
 
     def info(self, replica: int):
         n = C.c_int64(); md = C.c_double(); it = C.c_int32(); err = C.c_double(); rng = (C.c_uint64 * 2)()

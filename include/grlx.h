@@ -462,8 +462,8 @@ int  grlx_query_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, int g
  * final state then being those of sines taken outside their domain), GRLX_ENV_EXTERNAL (no environment), projector/tile_coding:safe >= 1
  * ("not built"), an (environment, action count) pair without an instantiation (built: pendulum x {3, 5} actions, acrobot, cart-pole and
  * walker x 3; actor-critic: cart-pole and pendulum).  n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
- * The steps of these episodes: grlx_evaluate_trajectory (below).
- * NOT BUILT: the epsilon-greedy learning policy, acting on the target network, the batch path. */
+ * The steps of these episodes: grlx_evaluate_trajectory (below).  The batch path's episodes: grlx_fqi_evaluate (at the end of this file).
+ * NOT BUILT: the epsilon-greedy learning policy, acting on the target network. */
 int  grlx_evaluate(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][state_dims]*/, int n_starts,
                    int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state);
 
@@ -497,7 +497,7 @@ int  grlx_evaluate(grlx_ctx *ctx, int first_replica, int n_replicas, const doubl
  * continuous actions is mapping/policy/multi's).  n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
  * The steps of these episodes: grlx_evaluate_ensemble_trajectory (below).
  * NOT BUILT: the reference's other discrete strategies (multiply, rank voting, density based), sampling from the combined
- * distribution, the batch path. */
+ * distribution, an ensemble over the replicas of a grlx_fqi_ctx. */
 enum { GRLX_ENSEMBLE_VOTE = 0, GRLX_ENSEMBLE_MEAN_Q = 1 };
 int  grlx_evaluate_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule,
                             const double *states /*[n_starts][state_dims]*/, int n_starts, int max_steps,
@@ -532,8 +532,8 @@ int  grlx_evaluate_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, in
  * and its sums -- that does not fit is refused, with the remedies named (fewer replicas per call, a smaller max_steps, a larger bound).
  * Validated on the host before anything is launched (GRLX_ERR_INVALID, nothing written, the reason named): everything the sibling
  * refuses, and the three cases above.  Like the siblings they change nothing in the context, wait for the stream of the last grlx_run
- * and do not count as a launch.
- * NOT BUILT: trajectories of the batch path and of the epsilon-greedy learning policy, streaming records to a file descriptor. */
+ * and do not count as a launch.  The batch path's: grlx_fqi_evaluate_trajectory (at the end of this file), with the same words.
+ * NOT BUILT: trajectories of the epsilon-greedy learning policy, streaming records to a file descriptor. */
 enum { GRLX_TRAJ_ACTION = 0, GRLX_TRAJ_REWARD = 1, GRLX_TRAJ_VALUE = 2, GRLX_TRAJ_ACTION_INDEX = 3, GRLX_TRAJ_N_MAX = 4, GRLX_TRAJ_TERMINAL = 5,
        GRLX_TRAJ_OBS = 6, GRLX_TRAJ_ENS_AGREEMENT = 6, GRLX_TRAJ_ENS_MEMBER_TIES = 7, GRLX_TRAJ_ENS_OBS = 8 };
 int  grlx_trajectory_record_words(grlx_ctx *ctx, int ensemble);      /* R; a negative status for a context without such episodes */
@@ -643,6 +643,38 @@ int  grlx_fqi_info(grlx_fqi_ctx *ctx, int replica, int64_t *n_transitions, doubl
  * observation that is not finite (row and dimension named); n_obs == 0 or n_replicas == 0: GRLX_OK, nothing written.  Staged in
  * chunks of observations like the online queries. */
 int  grlx_fqi_query(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, const double *obs /*[n_obs][2]*/, int n_obs, double *q);
+/* The batch path's greedy evaluation episodes and their per-step trajectories: grlx_evaluate and grlx_evaluate_trajectory (above)
+ * restated for a grlx_fqi_ctx.  For every (replica, start state) pair one episode on the replica's CURRENT parameters, on the device, in
+ * one launch per chunk; pair = (replica - first_replica) * n_starts + start; states[n_starts][3] are MODEL states of the pendulum
+ * (angle, velocity, time).
+ *   The loop.   obs = observe(state); the start state's own terminal code is ignored, so an episode has at least one step.  Per step:
+ *               q[k] = Q(obs, a_k), k < action_steps, by the operations of grlx_fqi_query; (mai, man) = the first maximum and the number
+ *               of maxima (greedy.cpp:47-61: strict >, counting ==); actions[mai] acts; the model steps; ret += reward;
+ *               disc += g * reward; g = g * gamma^control_step (the factor the predictor applies to one step's successor value).
+ *               This is the test trial of grlx_fqi_run_batch from a state of the caller's choice WITHOUT its tie-breaking draw: `ties`
+ *               counts the steps with man > 1, and with ties == 0 an episode from the task's start (pi, 0, 0) returns, as ret, the
+ *               reward of the row the last batch wrote, bit for bit.
+ *   terminal    the task's code, 1 or 2; 3 when the step ended outside the portable math's domain (it outranks the task's code and sets
+ *               no sticky flag); 0 for an episode cut at max_steps.  max_steps: 1 ... GRLX_MAX_EPISODE_STEPS, 0 = that cap.
+ *   records     grlx_fqi_evaluate_trajectory: records[n_replicas][n_starts][max_steps][R], R = grlx_fqi_trajectory_record_words() =
+ *               6 + 2 + 3 = 11, the GRLX_TRAJ_* words unchanged: action, reward, value = q[mai], action index, number of maxima, the
+ *               code after the step, the observation acted on, the model state after the step.  Records at index >= the pair's steps
+ *               are all-zero bits.  max_steps sizes the buffer, so 0 is refused there, as is a null records.
+ * ret, disc, steps, terminal, ties: [n_replicas][n_starts]; final_state has [3] more.  Host pointers; any output but records may be NULL.
+ * AN EVALUATION CHANGES NOTHING in the context: no row, no batch counter, no stream, no status bit, no parameter.  It is allowed before
+ * the first grlx_fqi_run_batch and waits for the device as grlx_fqi_query does.  Staged in chunks of start states under
+ * grlx_set_query_chunk_bytes' bound, records included: a single start state's column of records that does not fit is refused, with
+ * the remedies named (fewer replicas per call, a smaller max_steps, a larger bound).
+ * Validated on the host before anything is launched (GRLX_ERR_INVALID, nothing written; row and component named): a null ctx, null
+ * states, n_starts < 0, the replica range, max_steps out of range, a state component that is not finite or reaches 2^17 in magnitude.
+ * n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
+ * NOT BUILT: an ensemble over the replicas, the reference's tie-breaking draw, tasks other than the pendulum's swing-up. */
+int  grlx_fqi_evaluate(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][3]*/, int n_starts, int max_steps,
+                       double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state);
+int  grlx_fqi_trajectory_record_words(grlx_fqi_ctx *ctx);      /* R = 11; a negative status for a null ctx */
+int  grlx_fqi_evaluate_trajectory(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][3]*/, int n_starts,
+                                  int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state,
+                                  double *records /*[n_replicas][n_starts][max_steps][R]*/);
 
 #ifdef __cplusplus
 }
