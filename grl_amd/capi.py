@@ -162,6 +162,13 @@ _SIGS = {
     "grlx_fqi_trajectory_record_words": (C.c_int, [C.c_void_p]),
     "grlx_fqi_evaluate_trajectory": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P(C.c_double), C.c_int, C.c_int, _P(C.c_double), _P(C.c_double),
                                                _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_double), _P(C.c_double)]),
+    "grlx_fqi_query_ensemble": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_double), C.c_int, _P(C.c_double)]),
+    "grlx_fqi_evaluate_ensemble": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_double), C.c_int, C.c_int, _P(C.c_double), _P(C.c_double),
+                                             _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64), _P(C.c_double)]),
+    "grlx_fqi_ensemble_trajectory_record_words": (C.c_int, [C.c_void_p]),
+    "grlx_fqi_evaluate_ensemble_trajectory": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_double), C.c_int, C.c_int, _P(C.c_double),
+                                                        _P(C.c_double), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64),
+                                                        _P(C.c_double), _P(C.c_double)]),
 }
 
 # include/grlx_diag.h: diagnostic exports (tools, tests, bench.py), not part of the boundary
@@ -183,7 +190,9 @@ _DIAG_SIGS = {
 _NEWER_SIGS = ("grlx_snapshot_size", "grlx_snapshot_save", "grlx_snapshot_load", "grlx_snapshot_info",
                "grlx_query_q", "grlx_query_state", "grlx_query_ensemble", "grlx_fqi_query", "grlx_evaluate", "grlx_evaluate_ensemble",
                "grlx_trajectory_record_words", "grlx_evaluate_trajectory", "grlx_evaluate_ensemble_trajectory",
-               "grlx_fqi_evaluate", "grlx_fqi_trajectory_record_words", "grlx_fqi_evaluate_trajectory")
+               "grlx_fqi_evaluate", "grlx_fqi_trajectory_record_words", "grlx_fqi_evaluate_trajectory",
+               "grlx_fqi_query_ensemble", "grlx_fqi_evaluate_ensemble", "grlx_fqi_ensemble_trajectory_record_words",
+               "grlx_fqi_evaluate_ensemble_trajectory")
 # grlx_kernel_plan flags
 PLAN_STAMPS_IN_PLACE, PLAN_STAMPS_DEFERRED, PLAN_SWEEP, PLAN_SERVER_OFF, PLAN_WALKER_SERVER, PLAN_FITS_YES, PLAN_FITS_NO = 1, 2, 4, 8, 16, 32, 64
 ENSEMBLE_VOTE, ENSEMBLE_MEAN_Q = 0, 1       # grlx_evaluate_ensemble's rule

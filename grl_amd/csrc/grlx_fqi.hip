@@ -1361,3 +1361,385 @@ int grlx_fqi_evaluate_trajectory(grlx_fqi_ctx *ctx, int first_replica, int n_rep
 }
 
 } // extern "C"
+
+// ---------------------------------------------------------------------------- the ensemble over groups of replicas ---
+// grlx_fqi_query_ensemble, grlx_fqi_evaluate_ensemble, grlx_fqi_evaluate_ensemble_trajectory: the replicas [first_replica, first_replica +
+// n_replicas) in groups of group_size consecutive ones (bagged FQI: every replica is a network of its own fitted to transitions of its
+// own).  Per observation the members are visited in ASCENDING replica order: q_m[k] by the operations of fqi_query_kernel, (mai_m, man_m)
+// by findmax, votes[mai_m] += 1, sumq[k] += q_m[k] into one accumulator per action from 0.0 -- that order is the specification.  The
+// episode is fqi_evaluate_kernel's with the first maximum of votes (GRLX_ENSEMBLE_VOTE) or sumq (GRLX_ENSEMBLE_MEAN_Q) acting.  Reads
+// F.net, F.env and the projector's constants only.  Appended after everything else of the unit: the kernels above keep their
+// instruction streams.
+//
+// Layout of the episodes.  One lane is one (group, start state) pair, blockIdx.y the group, the block one wave: the member loop is
+// block-uniform, and a lane walks its group's members one after the other.  A member's P = 5 H + 1 parameters (the first of the replica's
+// four P-blocks in F.net) are read where ann_forward<H> uses them, through the member's block-uniform global address: no LDS, no barrier,
+// no lane talks to another.  (Staging the members into LDS in rounds of 16 was measured against this and was never faster: DESIGN.md
+// section 4.2i.)  The step loop is wave-uniform: it runs while a ballot finds an active lane; finished and dead lanes skip the step.
+// Nothing is indexed at run time by a lane's value or by a loop counter that is not unrolled: the action of pass k, q[k] -> q[], the
+// member's vote, the chosen action and its score are selects over the kMaxActions actions.  ann_forward is called as it is.
+namespace grlx {
+
+constexpr int kFqiEnsTrajWords = GRLX_TRAJ_ENS_OBS + kFqiD + kFqiS;
+
+struct FqiEnsArgs {
+  int32_t first_replica, group_size, rule, n_starts, max_steps;      // n_starts: of this chunk; max_steps: 1 ... GRLX_MAX_EPISODE_STEPS
+  const double *states;                            // [n_starts][3]
+  double  *ret, *disc;                             // [groups][n_starts], as are steps, terminal, ties, member_ties and agreement
+  int32_t *steps, *terminal, *ties;
+  int64_t *member_ties, *agreement;
+  double  *final_state;                            // [groups][n_starts][3]
+  double  *records;                                // RECORD: [groups][n_starts][max_steps][kFqiEnsTrajWords]
+};
+
+// one member at obs: q[k] = Q(obs, a_k) for k < F.A (the others stay 0), sumq[k] += q[k], and findmax over them (greedy.cpp:47-61) as
+// they are produced.  A caller that does not read q[] pays nothing for it.
+template <int H>
+__device__ __forceinline__ void fqi_member_values(const FqiParams &F, const double *w, const double *obs, double (&q)[kMaxActions],
+                                                  double (&sumq)[kMaxActions], double &best, int &mai, int &man)
+{
+#pragma unroll
+  for (int a = 0; a < kMaxActions; ++a) q[a] = 0;
+  best = 0; mai = 0; man = 1;
+  for (int k = 0; k < F.A; ++k)
+  {
+    double ak = F.actions[0];                          // k is uniform: scalar selects, no indexed read of the parameter block
+#pragma unroll
+    for (int a = 1; a < kMaxActions; ++a) ak = (k == a) ? F.actions[a] : ak;
+    double in[kFqiNIn];
+    fqi_normalise(F, obs, ak, in);
+    const double qk = ann_forward<H>(w, in, nullptr);
+#pragma unroll
+    for (int a = 0; a < kMaxActions; ++a)
+    {
+      q[a] = (k == a) ? qk : q[a];
+      sumq[a] = (k == a) ? sumq[a] + qk : sumq[a];
+    }
+    if (k == 0 || qk > best) { best = qk; mai = k; man = 1; }
+    else if (qk == best) man++;
+  }
+}
+
+template <int H, bool RECORD>
+__global__ __launch_bounds__(64) void fqi_evaluate_ensemble_kernel(FqiParams F, FqiEnsArgs A)
+{
+  constexpr int R = kFqiEnsTrajWords;
+  const int gl = blockIdx.y, G = A.group_size;
+  const double *nets = F.net + (size_t)(A.first_replica + gl * G) * 4 * F.P;       // member m: nets + m * 4 * F.P, its first P-block
+  const int s = (int)blockIdx.x * 64 + (int)threadIdx.x;
+  const bool live = s < A.n_starts;                    // dead lanes of the last block neither load nor store
+  const size_t pair = (size_t)gl * (size_t)A.n_starts + (size_t)(live ? s : 0);
+  double *rec = RECORD ? A.records + pair * (size_t)A.max_steps * R : nullptr;      // 64-bit: pairs * max_steps * R * 8 bytes pass 2^32
+  double x[kFqiS], obs[kFqiD];
+#pragma unroll
+  for (int i = 0; i < kFqiS; ++i) x[i] = live ? A.states[(size_t)s * kFqiS + i] : 0.;
+  (void)Env<GRLX_ENV_PENDULUM>::observe(F.env, x, obs);                // the start state's terminal code is ignored
+
+  double ret = 0, disc = 0, g = 1;
+  int steps = 0, code = 0, ties = 0;
+  long long member_ties = 0, agreement = 0;
+  bool active = live;
+  for (int step = 0; step < A.max_steps; ++step)
+  {
+    if (__ballot(active) == 0ull) break;               // wave-uniform
+    int votes[kMaxActions], mties = 0;
+    double sumq[kMaxActions];
+#pragma unroll
+    for (int a = 0; a < kMaxActions; ++a) { votes[a] = 0; sumq[a] = 0.; }
+    if (active)
+      for (int m = 0; m < G; ++m)
+      {
+        double q[kMaxActions], best;
+        int mai, man;
+        fqi_member_values<H>(F, nets + (size_t)m * 4 * F.P, obs, q, sumq, best, mai, man);
+#pragma unroll
+        for (int a = 0; a < kMaxActions; ++a) votes[a] += (mai == a) ? 1 : 0;
+        mties += man > 1 ? 1 : 0;
+      }
+    if (active)
+    {
+      const bool vote = A.rule == GRLX_ENSEMBLE_VOTE;
+      double best = vote ? (double)votes[0] : sumq[0], action = F.actions[0];
+      int mai = 0, man = 1, agree = votes[0];          // findmax over the combined score; the first maximum acts, no draw
+#pragma unroll
+      for (int a = 1; a < kMaxActions; ++a)
+        if (a < F.A)
+        {
+          const double sc = vote ? (double)votes[a] : sumq[a];
+          if (sc > best) { best = sc; action = F.actions[a]; mai = a; man = 1; agree = votes[a]; }
+          else if (sc == best) man++;
+        }
+      double before[kFqiD];
+#pragma unroll
+      for (int i = 0; i < kFqiD; ++i) before[i] = obs[i];
+      double reward = 0;
+      int terminal = 0;
+      uint32_t status = 0;
+      env_step<GRLX_ENV_PENDULUM, false>(F.env, x, action, obs, reward, terminal, status);
+      ret += reward;
+      disc += g * reward;
+      g = g * F.gamma_tau;
+      ties += man > 1 ? 1 : 0;
+      member_ties += mties;
+      agreement += agree;
+      code = (status & ST_DOMAIN) ? kFqiEvalDomain : terminal;
+      active = code == 0;
+      if constexpr (RECORD)
+      {
+        double *w = rec + (size_t)steps * R;
+        w[GRLX_TRAJ_ACTION] = action;
+        w[GRLX_TRAJ_REWARD] = reward;
+        w[GRLX_TRAJ_VALUE] = best;
+        w[GRLX_TRAJ_ACTION_INDEX] = (double)mai;
+        w[GRLX_TRAJ_N_MAX] = (double)man;
+        w[GRLX_TRAJ_TERMINAL] = (double)code;
+        w[GRLX_TRAJ_ENS_AGREEMENT] = (double)agree;
+        w[GRLX_TRAJ_ENS_MEMBER_TIES] = (double)mties;
+#pragma unroll
+        for (int i = 0; i < kFqiD; ++i) w[GRLX_TRAJ_ENS_OBS + i] = before[i];
+#pragma unroll
+        for (int i = 0; i < kFqiS; ++i) w[GRLX_TRAJ_ENS_OBS + kFqiD + i] = x[i];
+      }
+      steps++;
+    }
+  }
+  if (!live) return;
+  if constexpr (RECORD)
+    for (size_t k = (size_t)steps * R; k < (size_t)A.max_steps * R; ++k) rec[k] = 0.;       // behind the episode's end: all-zero bits
+  A.ret[pair] = ret;
+  A.disc[pair] = disc;
+  A.steps[pair] = steps;
+  A.terminal[pair] = code;
+  A.ties[pair] = ties;
+  A.member_ties[pair] = member_ties;
+  A.agreement[pair] = agreement;
+#pragma unroll
+  for (int i = 0; i < kFqiS; ++i) A.final_state[pair * kFqiS + i] = x[i];
+}
+
+// one lane per (group, observation), blockIdx.y the group: grlx_query_ensemble's columns, every sum over the members in ascending order
+// into one accumulator.  out[group][n_obs][2 + 2 F.A].  The members are read as the evaluation reads them.
+template <int H>
+__global__ __launch_bounds__(64) void fqi_query_ensemble_kernel(FqiParams F, int first_replica, int group_size, const double *obs, int n_obs, double *out)
+{
+  const int o = (int)blockIdx.x * 64 + (int)threadIdx.x, gl = blockIdx.y;
+  if (o >= n_obs) return;
+  const double *nets = F.net + (size_t)(first_replica + gl * group_size) * 4 * F.P;
+  double ob[kFqiD];
+#pragma unroll
+  for (int d = 0; d < kFqiD; ++d) ob[d] = obs[(size_t)o * kFqiD + d];
+  double sv = 0, svv = 0, sumq[kMaxActions], votes[kMaxActions];
+#pragma unroll
+  for (int a = 0; a < kMaxActions; ++a) { sumq[a] = 0.; votes[a] = 0.; }
+  for (int m = 0; m < group_size; ++m)
+  {
+    double q[kMaxActions], best;
+    int mai, man;
+    fqi_member_values<H>(F, nets + (size_t)m * 4 * F.P, ob, q, sumq, best, mai, man);
+    double v = 0;                                       // q.cpp:56-68 over greedy.cpp:88-98, as grlx_query_q forms it
+#pragma unroll
+    for (int a = 0; a < kMaxActions; ++a)
+      if (a < F.A) v += q[a] * (q[a] == best ? 1. / man : 0.);
+    sv += v;
+    svv += v * v;
+#pragma unroll
+    for (int a = 0; a < kMaxActions; ++a) votes[a] += (mai == a) ? 1. : 0.;
+  }
+  double *row = out + ((size_t)gl * (size_t)n_obs + (size_t)o) * (size_t)(2 + 2 * F.A);
+  row[0] = sv;
+  row[1] = svv;
+#pragma unroll
+  for (int a = 0; a < kMaxActions; ++a)
+    if (a < F.A)
+    {
+      row[2 + a] = sumq[a];
+      row[2 + F.A + a] = votes[a];
+    }
+}
+
+} // namespace grlx
+
+namespace {
+
+// what the three grouped calls check after their single-policy sibling's rules
+int fqi_ensemble_admit(const char *who, int n_replicas, int group_size)
+{
+  if (group_size < 1) return ffail(GRLX_ERR_INVALID, "%s: group_size = %d (at least 1)", who, group_size);
+  if (n_replicas % group_size != 0)
+    return ffail(GRLX_ERR_INVALID, "%s: n_replicas = %d is not a multiple of group_size = %d", who, n_replicas, group_size);
+  return GRLX_OK;
+}
+
+int fqi_evaluate_ensemble_admit(grlx_fqi_ctx *ctx, const char *who, int first_replica, int n_replicas, int group_size, int rule, const double *states,
+                                int n_starts, int max_steps)
+{
+  int rc = fqi_evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps);
+  if (rc != GRLX_OK) return rc;
+  if ((rc = fqi_ensemble_admit(who, n_replicas, group_size)) != GRLX_OK) return rc;
+  if (rule != GRLX_ENSEMBLE_VOTE && rule != GRLX_ENSEMBLE_MEAN_Q)
+    return ffail(GRLX_ERR_INVALID, "%s: rule = %d is neither GRLX_ENSEMBLE_VOTE (0) nor GRLX_ENSEMBLE_MEAN_Q (1)", who, rule);
+  return GRLX_OK;
+}
+
+// a start state's staged bytes besides its records: the state and its groups' sums
+inline uint64_t fqi_ensemble_sums_bytes(int groups)
+{
+  return sizeof(double) * kFqiS + (2 * sizeof(double) + 3 * sizeof(int32_t) + 2 * sizeof(int64_t) + sizeof(double) * kFqiS) * (uint64_t)groups;
+}
+
+struct FqiEnsOut {
+  double *ret, *disc;
+  int32_t *steps, *terminal, *ties;
+  int64_t *member_ties, *agreement;
+  double *final_state, *records;
+};
+
+// the episodes of admitted arguments, in chunks of start states of at most per_start bytes of staging each; records == nullptr: the sums alone
+int fqi_ensemble_run(grlx_fqi_ctx *ctx, const char *who, int first_replica, int groups, int group_size, int rule, const double *states, int n_starts,
+                     int max_steps, uint64_t per_start, const FqiEnsOut &out)
+{
+  FQI_TRY(hipDeviceSynchronize());
+  const uint64_t fit = g_fqi_query_chunk_bytes / per_start;
+  const int chunk = (int)(fit < 1 ? 1 : fit > (uint64_t)n_starts ? (uint64_t)n_starts : fit);
+  const size_t rows = (size_t)groups, pairs = rows * (size_t)chunk;
+  const size_t rec_elem = out.records ? sizeof(double) * (size_t)kFqiEnsTrajWords * (size_t)max_steps : 0;
+  // one allocation, the 8-byte types first: states, ret, disc, final_state, records, member_ties, agreement, then the three int32 arrays
+  const size_t n_double = (size_t)chunk * kFqiS + 2 * pairs + pairs * kFqiS + pairs * (rec_elem / sizeof(double));
+  const size_t bytes = n_double * sizeof(double) + 2 * pairs * sizeof(int64_t) + 3 * pairs * sizeof(int32_t);
+  char *dev = nullptr;
+  if (hipMalloc((void **)&dev, bytes) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return ffail(GRLX_ERR_OOM, "%s: out of device memory (%zu bytes of staging)", who, bytes);
+  }
+  double *dstates = (double *)dev, *dret = dstates + (size_t)chunk * kFqiS, *ddisc = dret + pairs, *dfinal = ddisc + pairs, *drec = dfinal + pairs * kFqiS;
+  int64_t *dmties = (int64_t *)(drec + pairs * (rec_elem / sizeof(double))), *dagree = dmties + pairs;
+  int32_t *dsteps = (int32_t *)(dagree + pairs), *dterm = dsteps + pairs, *dties = dterm + pairs;
+  hipError_t err = hipSuccess;
+  for (int s0 = 0; s0 < n_starts && err == hipSuccess; s0 += chunk)
+  {
+    const int nc = n_starts - s0 < chunk ? n_starts - s0 : chunk;
+    err = hipMemcpy(dstates, states + (size_t)s0 * kFqiS, sizeof(double) * kFqiS * (size_t)nc, hipMemcpyHostToDevice);
+    if (err != hipSuccess) break;
+    FqiEnsArgs A;
+    A.first_replica = first_replica; A.group_size = group_size; A.rule = rule; A.n_starts = nc; A.max_steps = max_steps; A.states = dstates;
+    A.ret = dret; A.disc = ddisc; A.steps = dsteps; A.terminal = dterm; A.ties = dties; A.member_ties = dmties; A.agreement = dagree;
+    A.final_state = dfinal; A.records = out.records ? drec : nullptr;
+    const dim3 grid((unsigned)((nc + 63) / 64), (unsigned)groups), block(64);
+    if (out.records) { FQI_FOR_H(ctx->F.H, hipLaunchKernelGGL((fqi_evaluate_ensemble_kernel<HH, true>), grid, block, 0, nullptr, ctx->F, A)); }
+    else { FQI_FOR_H(ctx->F.H, hipLaunchKernelGGL((fqi_evaluate_ensemble_kernel<HH, false>), grid, block, 0, nullptr, ctx->F, A)); }
+    err = hipGetLastError();
+    // device [group][nc] -> host [group][n_starts] at s0
+    const struct { void *host; const void *dev; size_t elem; } outs[9] = {
+        {out.ret, dret, sizeof(double)}, {out.disc, ddisc, sizeof(double)}, {out.steps, dsteps, sizeof(int32_t)}, {out.terminal, dterm, sizeof(int32_t)},
+        {out.ties, dties, sizeof(int32_t)}, {out.member_ties, dmties, sizeof(int64_t)}, {out.agreement, dagree, sizeof(int64_t)},
+        {out.final_state, dfinal, sizeof(double) * kFqiS}, {out.records, drec, rec_elem}};
+    for (int o = 0; o < 9 && err == hipSuccess; ++o)
+      if (outs[o].host)
+        err = hipMemcpy2D((char *)outs[o].host + (size_t)s0 * outs[o].elem, (size_t)n_starts * outs[o].elem, outs[o].dev, (size_t)nc * outs[o].elem,
+                          (size_t)nc * outs[o].elem, rows, hipMemcpyDeviceToHost);
+  }
+  if (err == hipSuccess) err = hipDeviceSynchronize();
+  (void)hipFree(dev);
+  if (err != hipSuccess) return ffail(GRLX_ERR_HIP, "%s failed: %s", who, hipGetErrorString(err));
+  return GRLX_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int grlx_fqi_query_ensemble(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, int group_size, const double *obs, int n_obs, double *out)
+{
+  const char *who = "grlx_fqi_query_ensemble";
+  if (!ctx) return ffail(GRLX_ERR_INVALID, "%s: ctx is null", who);
+  if (!out) return ffail(GRLX_ERR_INVALID, "%s: out is null", who);
+  if (!obs) return ffail(GRLX_ERR_INVALID, "%s: obs is null", who);
+  if (n_obs < 0) return ffail(GRLX_ERR_INVALID, "%s: n_obs = %d", who, n_obs);
+  if (first_replica < 0 || n_replicas < 0 || (int64_t)first_replica + n_replicas > ctx->F.R)
+    return ffail(GRLX_ERR_INVALID, "%s: replica range [%d, %lld) is outside the context's %d replicas", who, first_replica,
+                 (long long)first_replica + n_replicas, ctx->F.R);
+  for (int o = 0; o < n_obs; ++o)
+    for (int d = 0; d < kFqiD; ++d)
+      if (!std::isfinite(obs[(size_t)o * kFqiD + d]))
+        return ffail(GRLX_ERR_INVALID, "%s: observation row %d, dimension %d is not finite", who, o, d);
+  int rc = fqi_ensemble_admit(who, n_replicas, group_size);
+  if (rc != GRLX_OK) return rc;
+  if (n_obs == 0 || n_replicas == 0) return GRLX_OK;
+  FQI_TRY(hipDeviceSynchronize());
+  const int groups = n_replicas / group_size;
+  const size_t cols = 2 + 2 * (size_t)ctx->F.A;
+  const uint64_t per_obs = sizeof(double) * kFqiD + sizeof(double) * cols * (uint64_t)groups;
+  const uint64_t fit = g_fqi_query_chunk_bytes / per_obs;
+  const int chunk = (int)(fit < 1 ? 1 : fit > (uint64_t)n_obs ? (uint64_t)n_obs : fit);
+  double *dobs = nullptr;
+  if (hipMalloc((void **)&dobs, sizeof(double) * (kFqiD + cols * (size_t)groups) * (size_t)chunk) != hipSuccess)
+  {
+    (void)hipGetLastError();
+    return ffail(GRLX_ERR_OOM, "%s: out of device memory", who);
+  }
+  double *dout = dobs + (size_t)kFqiD * (size_t)chunk;
+  hipError_t err = hipSuccess;
+  for (int o0 = 0; o0 < n_obs && err == hipSuccess; o0 += chunk)
+  {
+    const int nc = n_obs - o0 < chunk ? n_obs - o0 : chunk;
+    err = hipMemcpy(dobs, obs + (size_t)o0 * kFqiD, sizeof(double) * kFqiD * (size_t)nc, hipMemcpyHostToDevice);
+    if (err != hipSuccess) break;
+    const dim3 grid((unsigned)((nc + 63) / 64), (unsigned)groups), block(64);
+    FQI_FOR_H(ctx->F.H, hipLaunchKernelGGL(fqi_query_ensemble_kernel<HH>, grid, block, 0, nullptr, ctx->F, first_replica, group_size, dobs, nc, dout));
+    err = hipGetLastError();
+    if (err != hipSuccess) break;
+    const size_t elem = sizeof(double) * cols;                            // device [group][nc][cols] -> host [group][n_obs][cols] at o0
+    err = hipMemcpy2D((char *)out + (size_t)o0 * elem, (size_t)n_obs * elem, dout, (size_t)nc * elem, (size_t)nc * elem, (size_t)groups,
+                      hipMemcpyDeviceToHost);
+  }
+  (void)hipFree(dobs);
+  if (err != hipSuccess) return ffail(GRLX_ERR_HIP, "%s failed: %s", who, hipGetErrorString(err));
+  return GRLX_OK;
+}
+
+int grlx_fqi_evaluate_ensemble(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule, const double *states, int n_starts,
+                               int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, int64_t *member_ties,
+                               int64_t *agreement, double *final_state)
+{
+  const char *who = "grlx_fqi_evaluate_ensemble";
+  int rc = fqi_evaluate_ensemble_admit(ctx, who, first_replica, n_replicas, group_size, rule, states, n_starts, max_steps);
+  if (rc != GRLX_OK) return rc;
+  if (max_steps == 0) max_steps = GRLX_MAX_EPISODE_STEPS;
+  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
+  const int groups = n_replicas / group_size;
+  const FqiEnsOut out = {ret, disc, steps, terminal, ties, member_ties, agreement, final_state, nullptr};
+  return fqi_ensemble_run(ctx, who, first_replica, groups, group_size, rule, states, n_starts, max_steps, fqi_ensemble_sums_bytes(groups), out);
+}
+
+int grlx_fqi_ensemble_trajectory_record_words(grlx_fqi_ctx *ctx)
+{
+  if (!ctx) return ffail(GRLX_ERR_INVALID, "grlx_fqi_ensemble_trajectory_record_words: ctx is null");
+  return kFqiEnsTrajWords;
+}
+
+int grlx_fqi_evaluate_ensemble_trajectory(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule, const double *states, int n_starts,
+                                          int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                                          int64_t *member_ties, int64_t *agreement, double *final_state, double *records)
+{
+  const char *who = "grlx_fqi_evaluate_ensemble_trajectory";
+  int rc = fqi_evaluate_ensemble_admit(ctx, who, first_replica, n_replicas, group_size, rule, states, n_starts, max_steps);
+  if (rc != GRLX_OK) return rc;
+  if (!records) return ffail(GRLX_ERR_INVALID, "%s: records is null (for the sums alone call grlx_fqi_evaluate_ensemble)", who);
+  if (max_steps == 0)
+    return ffail(GRLX_ERR_INVALID, "%s: max_steps = 0: the records are sized by max_steps, so there is no default here (1 ... GRLX_MAX_EPISODE_STEPS = %d)", who,
+                 GRLX_MAX_EPISODE_STEPS);
+  // a chunk with records never exceeds the bound: a column that does not fit is refused instead of staged as "at least one"
+  const int groups = n_replicas / group_size;
+  const uint64_t column = (uint64_t)groups * (uint64_t)max_steps * (uint64_t)kFqiEnsTrajWords * sizeof(double);
+  const uint64_t per_start = column + fqi_ensemble_sums_bytes(groups);
+  if (per_start > g_fqi_query_chunk_bytes)
+    return ffail(GRLX_ERR_INVALID, "%s: one start state's column of records is %llu bytes (%d groups x %d steps x %d words x 8; %llu with its sums) and exceeds "
+                 "the staging bound of %llu bytes: ask for fewer replicas per call, a smaller max_steps, or raise the bound with grlx_set_query_chunk_bytes", who,
+                 (unsigned long long)column, groups, max_steps, kFqiEnsTrajWords, (unsigned long long)per_start, (unsigned long long)g_fqi_query_chunk_bytes);
+  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
+  const FqiEnsOut out = {ret, disc, steps, terminal, ties, member_ties, agreement, final_state, records};
+  return fqi_ensemble_run(ctx, who, first_replica, groups, group_size, rule, states, n_starts, max_steps, per_start, out);
+}
+
+} // extern "C"

@@ -861,6 +861,77 @@ class FqiRunner:
                                                          _ptr(ties, C.c_int32), _ptr(final_state, C.c_double), _ptr(records, C.c_double)))
         return Trajectory(ret, disc, steps, terminal, ties, final_state, records)
 
+    # ---- the ensemble over groups of `group_size` consecutive replicas (bagged FQI): Runner's calls of the same names restated
+    def _groups(self, replicas, group_size):
+        first, count = self._replica_range(replicas)
+        group_size = max(count, 1) if group_size is None else int(group_size)      # an empty range is GRLX_OK with nothing written
+        return first, count, group_size, (count // group_size if group_size > 0 else 0)
+
+    def query_ensemble_raw(self, obs, group_size=None, replicas=None):
+        """grlx_fqi_query_ensemble as it is: out[group][obs][2 + 2A] = {sum value, sum value^2, sum q[0..A), votes[0..A)}, every sum over
+        the group's replicas in ascending order (Runner.query_ensemble_raw's columns)."""
+        obs = np.ascontiguousarray(obs, dtype=np.float64)
+        if obs.ndim != 2 or obs.shape[1] != 2:
+            raise ValueError(f"expected observations of shape (n, 2), got {obs.shape}")
+        first, count, group_size, groups = self._groups(replicas, group_size)
+        out = np.zeros((groups, obs.shape[0], 2 + 2 * int(self.cfg.action_steps)), np.float64)
+        capi.check(self.lib.grlx_fqi_query_ensemble(self._ctx, first, count, group_size, _ptr(obs, C.c_double), obs.shape[0], _ptr(out, C.c_double)))
+        return out
+
+    def query_ensemble(self, obs, group_size=None, replicas=None):
+        """Ensemble statistics per group of `group_size` consecutive replicas (default: one group of all) and observation."""
+        group_size = self._groups(replicas, group_size)[2]
+        return EnsembleResult(self.query_ensemble_raw(obs, group_size, replicas), group_size, int(self.cfg.action_steps))
+
+    _RULES = {"vote": capi.ENSEMBLE_VOTE, "mean": capi.ENSEMBLE_MEAN_Q, "mean_q": capi.ENSEMBLE_MEAN_Q}
+
+    def evaluate_ensemble(self, states, group_size, rule="vote", replicas=None, max_steps=0):
+        """One greedy episode per (group of `group_size` consecutive replicas, start state) pair, on the device: at every step the
+        members' first maxima are counted and their Q-values summed in ascending replica order, and the episode takes the first maximum
+        of the votes (rule "vote") or of the summed Q (rule "mean").  EnsembleEvaluation(ret, disc, steps, terminal, ties, member_ties,
+        agreement, final_state), each [group][start], as Runner.evaluate_ensemble defines them; the episode is FqiRunner.evaluate's.
+        The context is not changed (include/grlx.h: grlx_fqi_evaluate_ensemble)."""
+        rule = self._RULES[rule] if isinstance(rule, str) else int(rule)
+        states = self._state_rows(states)
+        first, count, group_size, groups = self._groups(replicas, group_size)
+        n = states.shape[0]
+        ret, disc = np.zeros((groups, n), np.float64), np.zeros((groups, n), np.float64)
+        steps, terminal, ties = np.zeros((groups, n), np.int32), np.zeros((groups, n), np.int32), np.zeros((groups, n), np.int32)
+        member_ties, agreement = np.zeros((groups, n), np.int64), np.zeros((groups, n), np.int64)
+        final_state = np.zeros((groups, n, self.STATE_DIMS), np.float64)
+        capi.check(self.lib.grlx_fqi_evaluate_ensemble(self._ctx, first, count, group_size, rule, _ptr(states, C.c_double), n, int(max_steps),
+                                                       _ptr(ret, C.c_double), _ptr(disc, C.c_double), _ptr(steps, C.c_int32),
+                                                       _ptr(terminal, C.c_int32), _ptr(ties, C.c_int32), _ptr(member_ties, C.c_int64),
+                                                       _ptr(agreement, C.c_int64), _ptr(final_state, C.c_double)))
+        return EnsembleEvaluation(ret, disc, steps, terminal, ties, member_ties, agreement, final_state)
+
+    def ensemble_trajectory_record_words(self):
+        """R = 13, the doubles of one record of the ensemble's trajectory (grlx_fqi_ensemble_trajectory_record_words)"""
+        words = self.lib.grlx_fqi_ensemble_trajectory_record_words(self._ctx)
+        if words < 0:
+            capi.check(words)
+        return words
+
+    def evaluate_ensemble_trajectory(self, states, group_size, max_steps, rule="vote", replicas=None):
+        """FqiRunner.evaluate_ensemble with every step of every episode: EnsembleTrajectory(..., records), records[group][start][max_steps]
+        [13]; the views, .step_agreement, .step_member_ties and .episode(k, s) are Runner.evaluate_ensemble_trajectory's
+        (include/grlx.h: grlx_fqi_evaluate_ensemble_trajectory)."""
+        rule = self._RULES[rule] if isinstance(rule, str) else int(rule)
+        states = self._state_rows(states)
+        first, count, group_size, groups = self._groups(replicas, group_size)
+        n, max_steps = states.shape[0], int(max_steps)
+        words = self.ensemble_trajectory_record_words()
+        ret, disc = np.zeros((groups, n), np.float64), np.zeros((groups, n), np.float64)
+        steps, terminal, ties = np.zeros((groups, n), np.int32), np.zeros((groups, n), np.int32), np.zeros((groups, n), np.int32)
+        member_ties, agreement = np.zeros((groups, n), np.int64), np.zeros((groups, n), np.int64)
+        final_state = np.zeros((groups, n, self.STATE_DIMS), np.float64)
+        records = np.zeros((groups, n, max(max_steps, 0), words), np.float64)
+        capi.check(self.lib.grlx_fqi_evaluate_ensemble_trajectory(self._ctx, first, count, group_size, rule, _ptr(states, C.c_double), n, max_steps,
+                                                                  _ptr(ret, C.c_double), _ptr(disc, C.c_double), _ptr(steps, C.c_int32),
+                                                                  _ptr(terminal, C.c_int32), _ptr(ties, C.c_int32), _ptr(member_ties, C.c_int64),
+                                                                  _ptr(agreement, C.c_int64), _ptr(final_state, C.c_double), _ptr(records, C.c_double)))
+        return EnsembleTrajectory(ret, disc, steps, terminal, ties, member_ties, agreement, final_state, records)
+
     def info(self, replica: int):
         n = C.c_int64(); md = C.c_double(); it = C.c_int32(); err = C.c_double(); rng = (C.c_uint64 * 2)()
         capi.check(self.lib.grlx_fqi_info(self._ctx, replica, C.byref(n), C.byref(md), C.byref(it), C.byref(err), rng))

@@ -496,8 +496,9 @@ int  grlx_evaluate(grlx_ctx *ctx, int first_replica, int n_replicas, const doubl
  * refuses, group_size < 1, n_replicas % group_size != 0, an unknown rule, an actor-critic context ("not built": a vote over
  * continuous actions is mapping/policy/multi's).  n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
  * The steps of these episodes: grlx_evaluate_ensemble_trajectory (below).
+ * The batch path's: grlx_fqi_evaluate_ensemble (at the end of this file).
  * NOT BUILT: the reference's other discrete strategies (multiply, rank voting, density based), sampling from the combined
- * distribution, an ensemble over the replicas of a grlx_fqi_ctx. */
+ * distribution. */
 enum { GRLX_ENSEMBLE_VOTE = 0, GRLX_ENSEMBLE_MEAN_Q = 1 };
 int  grlx_evaluate_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule,
                             const double *states /*[n_starts][state_dims]*/, int n_starts, int max_steps,
@@ -668,13 +669,58 @@ int  grlx_fqi_query(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, const 
  * Validated on the host before anything is launched (GRLX_ERR_INVALID, nothing written; row and component named): a null ctx, null
  * states, n_starts < 0, the replica range, max_steps out of range, a state component that is not finite or reaches 2^17 in magnitude.
  * n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
- * NOT BUILT: an ensemble over the replicas, the reference's tie-breaking draw, tasks other than the pendulum's swing-up. */
+ * The same episodes on a group's vote or mean Q: grlx_fqi_evaluate_ensemble (below).
+ * NOT BUILT: the reference's tie-breaking draw, tasks other than the pendulum's swing-up. */
 int  grlx_fqi_evaluate(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][3]*/, int n_starts, int max_steps,
                        double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state);
 int  grlx_fqi_trajectory_record_words(grlx_fqi_ctx *ctx);      /* R = 11; a negative status for a null ctx */
 int  grlx_fqi_evaluate_trajectory(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][3]*/, int n_starts,
                                   int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state,
                                   double *records /*[n_replicas][n_starts][max_steps][R]*/);
+/* The batch path's ensemble: grlx_query_ensemble, grlx_evaluate_ensemble and grlx_evaluate_ensemble_trajectory (above) restated for a
+ * grlx_fqi_ctx, whose replicas are independently seeded networks fitted to independently drawn transition sets (bagged FQI).  The
+ * replicas [first_replica, first_replica + n_replicas) form n_replicas / group_size groups of group_size CONSECUTIVE replicas; grouping,
+ * outputs and refusals follow the online siblings.
+ *   Member values.  For each member m in ASCENDING replica order: q_m[k] = Q(obs, a_k) by the operations of grlx_fqi_query on the
+ *               replica's CURRENT parameters; (mai_m, man_m) = the first maximum and the number of maxima (strict >, counting ==);
+ *               votes[mai_m] += 1; sumq[k] += q_m[k], one accumulator per action from 0.0 (no tree: that order is the specification);
+ *               member_ties += (man_m > 1).
+ *   Acting.     score = votes (GRLX_ENSEMBLE_VOTE) or sumq (GRLX_ENSEMBLE_MEAN_Q); (mai, man) = findmax(score); actions[mai] acts, no
+ *               draw; ties += (man > 1); agreement += votes[mai] under either rule.
+ *   The episode.  grlx_fqi_evaluate's, the members sharing ONE model state: the start state's terminal code is ignored; terminal 0 cut at
+ *               max_steps, 1 timed out, 3 left the portable math's domain; max_steps 0 = GRLX_MAX_EPISODE_STEPS; disc uses the context's
+ *               gamma^control_step.  group_size == 1 is grlx_fqi_evaluate bit for bit (member_ties = its ties; under GRLX_ENSEMBLE_VOTE one
+ *               vote never ties).
+ *   records     grlx_fqi_evaluate_ensemble_trajectory: records[groups][n_starts][max_steps][R], R =
+ *               grlx_fqi_ensemble_trajectory_record_words() = 8 + 2 + 3 = 13, the online ensemble's words (GRLX_TRAJ_*, GRLX_TRAJ_ENS_*):
+ *               GRLX_TRAJ_VALUE is (double)votes[mai] or sumq[mai] (the sum, not the mean), GRLX_TRAJ_ENS_AGREEMENT votes[mai],
+ *               GRLX_TRAJ_ENS_MEMBER_TIES the members with man_m > 1 at the step, the observation acted on at GRLX_TRAJ_ENS_OBS, the model
+ *               state after the step behind it.  Records at index >= the pair's steps are all-zero bits.  max_steps == 0 and a null
+ *               records are refused; so is a start state's column of records (groups * max_steps * R * 8 bytes, with its sums) that
+ *               exceeds grlx_set_query_chunk_bytes' bound, with the remedies named.
+ *   grlx_fqi_query_ensemble   out[groups][n_obs][2 + 2 * action_steps] = { sum value, sum value * value, sum q[0 .. A), votes[0 .. A) },
+ *               grlx_query_ensemble's columns: a member's value is grlx_query_q's (v = 0; for a in order: v += q[a] * dist[a], dist =
+ *               1. / man at the maxima and 0 elsewhere); every sum runs in ascending replica order into one accumulator, on the device.
+ * ret, disc, steps, terminal, ties, member_ties, agreement: [groups][n_starts]; final_state has [3] more.  Host pointers; any output but
+ * records may be NULL.  All four calls wait for the device as grlx_fqi_query does, stage in chunks of start states or observations under
+ * grlx_set_query_chunk_bytes' bound and CHANGE NOTHING in the context: no row, no batch counter, no stream, no status bit, no parameter.
+ * Validated on the host before anything is launched (GRLX_ERR_INVALID, nothing written, the entry point and the reason named):
+ * everything grlx_fqi_evaluate / grlx_fqi_query refuse, group_size < 1, n_replicas % group_size != 0, an unknown rule.  n_starts == 0,
+ * n_obs == 0 or n_replicas == 0: GRLX_OK, nothing written.
+ * NOT BUILT: sampling from the combined distribution, the reference's other discrete strategies (multiply, rank voting, density based),
+ * the reference's tie-breaking draw. */
+int  grlx_fqi_query_ensemble(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, int group_size, const double *obs /*[n_obs][2]*/, int n_obs,
+                             double *out);
+int  grlx_fqi_evaluate_ensemble(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule,
+                                const double *states /*[n_starts][3]*/, int n_starts, int max_steps,
+                                double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                                int64_t *member_ties, int64_t *agreement, double *final_state);
+int  grlx_fqi_ensemble_trajectory_record_words(grlx_fqi_ctx *ctx);      /* R = 13; a negative status for a null ctx */
+int  grlx_fqi_evaluate_ensemble_trajectory(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule,
+                                           const double *states /*[n_starts][3]*/, int n_starts, int max_steps,
+                                           double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                                           int64_t *member_ties, int64_t *agreement, double *final_state,
+                                           double *records /*[n_replicas / group_size][n_starts][max_steps][R]*/);
 
 #ifdef __cplusplus
 }
