@@ -3,17 +3,20 @@
  * ModeledEnvironment + DynamicalModel (RK4): base/src/environments/modeled.cpp:132-276
  * Pendulum dynamics + swing-up task:          base/src/environments/pendulum.cpp:40-145
  * Acrobot dynamics + balancing task:         base/src/environments/acrobot.cpp:48-151
- *   (no reference test pins the acrobot: parity unpinned by reference tests)
+ *   (pinned by the reference's own acrobot.cpp in oracle/_ref/ref_envs, bit for bit: tests/test_oracle_ref_envs.py)
  * Cart-pole dynamics + swing-up task:        base/src/environments/cart_pole.cpp:58-237
  *   (the swing-up TASK is unpinned; the DYNAMICS -- end_stop = 1, incl. the :65 quirk -- and DynamicalModel::step
  *   are pinned by tests/template/cart_pole_balancing-pid-0.txt through the balancing task below)
  * Cart-pole balancing task:                  base/src/environments/cart_pole.cpp:239-320
  * Compass walker model + walk task:          base/src/environments/compass_walker/SWModel.cpp:15-258,
  *   base/include/grl/environments/compass_walker/SWModel.h:40-59, compass_walker.cpp:41-95, 198-344
- *   (parity unpinned by reference tests)
+ *   (pinned by the reference's own SWModel.cpp and compass_walker.cpp in oracle/_ref/ref_envs, bit for bit, likewise)
  *
  * All arithmetic is IEEE double in the reference's expression order with no
- * fused multiply-add (compile with -ffp-contract=off).
+ * fused multiply-add (compile with -ffp-contract=off).  "Bit for bit" is the reference's SOURCE evaluated call by call
+ * (oracle/Makefile builds it -fno-builtin): a reference binary whose compiler fuses sin(x) and cos(x) into one sincos call
+ * (g++ at plain -O2) differs by 1 ulp in rare steps -- 7 of 12,206 walker steps, none of the committed cases, with g++ 11.4.0
+ * and glibc 2.35 (tools/record_ref_envs.py).
  */
 #include <math.h>
 #include <stdint.h>
@@ -264,12 +267,18 @@ static double sw_hip_y(const orc_spec *s, const sw_state *m) { return orc_m_cos(
 static double sw_swing_x(const orc_spec *s, const sw_state *m) { return sw_hip_x(s, m) + orc_m_sin(s, m->sla - m->ha); }   /* :42 */
 static double sw_swing_y(const orc_spec *s, const sw_state *m) { return sw_hip_y(s, m) - orc_m_cos(s, m->sla - m->ha); }   /* :43 */
 
+/* What the sub-steps of one model step did, for the case generators of the tests (orc_walker_step_diag): counted only
+ * while sw_diag points somewhere, and nothing below reads it back. */
+enum { WD_CROSSINGS = 0, WD_STRIKES, WD_REFUSED_HIP_SIGN, WD_REFUSED_STANCE_RATE, WD_REFUSED_HIP_ANGLE, WD_WRAPS, WD_SEARCH_ITERATIONS, WD_SIZE };
+static int *sw_diag;
+#define SW_DIAG(what) do { if (sw_diag) what; } while (0)
+
 static void sw_wrap(sw_state *m)
 { /* SWModel.h:48-59 */
-  if (m->sla >= M_PI) m->sla -= 2*M_PI;
-  if (m->sla < -M_PI) m->sla += 2*M_PI;
-  if (m->ha >= M_PI) m->ha -= 2*M_PI;
-  if (m->ha < -M_PI) m->ha += 2*M_PI;
+  if (m->sla >= M_PI) { m->sla -= 2*M_PI; SW_DIAG(sw_diag[WD_WRAPS] |= 1); }
+  if (m->sla < -M_PI) { m->sla += 2*M_PI; SW_DIAG(sw_diag[WD_WRAPS] |= 2); }
+  if (m->ha >= M_PI) { m->ha -= 2*M_PI; SW_DIAG(sw_diag[WD_WRAPS] |= 4); }
+  if (m->ha < -M_PI) { m->ha += 2*M_PI; SW_DIAG(sw_diag[WD_WRAPS] |= 8); }
 }
 
 static void sw_accel(const orc_spec *s, const sw_state *m, double torque, sw_accels *a)
@@ -349,15 +358,20 @@ static double sw_heelstrike_moment(const orc_spec *s, const sw_state *t0, const 
     else
       timeLeft = dt - s1time;
   }
+  SW_DIAG(sw_diag[WD_SEARCH_ITERATIONS] = iIter >= maxIterations ? maxIterations + 1 : iIter + 1);   /* 11: left without reaching the precision */
   return timeLeft;
 }
 
 static double sw_detect_events(const orc_spec *s, const sw_state *t0, sw_state *hs, sw_state *t1, double torque, double dt)
 { /* SWModel.cpp:30-45 and processStanceLegChange :106-124 */
   if ((sw_swing_y(s, t0) >= 0) && (sw_swing_y(s, t1) < 0))
+  {
+    SW_DIAG(sw_diag[WD_CROSSINGS]++);
     if (((t0->ha < 0) && (t1->ha < 0)) || ((t0->ha > 0) && (t1->ha > 0)))
+    {
       if ((t1->slar < 0) && (t1->ha < 0))
       {
+        SW_DIAG(sw_diag[WD_STRIKES]++);
         double timeleft = sw_heelstrike_moment(s, t0, t1, hs, torque, 1.0E-11, dt);
         t1->har  = hs->slar*(orc_m_cos(s, 2.0*hs->sla)*(1.0 - orc_m_cos(s, 2.0*hs->sla)));
         t1->slar = hs->slar*(orc_m_cos(s, 2.0*hs->sla));
@@ -367,6 +381,11 @@ static double sw_detect_events(const orc_spec *s, const sw_state *t0, sw_state *
         t1->changed = 1;
         return timeleft;
       }
+      SW_DIAG(sw_diag[!(t1->ha < 0) ? WD_REFUSED_HIP_ANGLE : WD_REFUSED_STANCE_RATE]++);
+    }
+    else
+      SW_DIAG(sw_diag[WD_REFUSED_HIP_SIGN]++);
+  }
   t1->changed = 0;
   return 0;
 }
@@ -411,6 +430,18 @@ static void walker_model_step(const orc_spec *s, const double *x, double torque,
   next[W_TIMEOUT] = x[W_TIMEOUT];
   /* siStepDistance is never written by CompassWalkerModel::step (uninitialised in the reference); it is
    * not observable with the walk task's default mask and is kept at its start value 0 here */
+}
+
+/* One model step as orc_env_step takes it, and what its sub-steps did: out[0] floor crossings of the swing foot, [1] heel strikes,
+ * crossings that detectEvents refused because [2] the hip angle changed sign, [3] the stance rate was >= 0 (hip angle < 0),
+ * [4] the hip angle was >= 0; [5] angle wraps (bits: sla >= pi, sla < -pi, ha >= pi, ha < -pi); [6] iterations of the last
+ * secant search (11: all 10 without reaching the height precision).  Not reentrant. */
+void orc_walker_step_diag(const orc_spec *s, const double *x, double torque, double *next, int *out)
+{
+  memset(out, 0, sizeof(int) * WD_SIZE);
+  sw_diag = out;
+  walker_model_step(s, x, torque, next);
+  sw_diag = NULL;
 }
 
 static void walker_start(const orc_spec *s, orc_exp *e, int test, double *x)
@@ -517,15 +548,14 @@ int orc_env_observe(const orc_spec *s, const double *x, double *obs)
 }
 
 /* DynamicalModel::step, modeled.cpp:254-276: `steps` classical RK4 sub-steps of
- * h = tau/steps; next += (k1 + 2*k2 + 2*k3 + k4)/6 with a true division. */
-static void rk4_step(const orc_spec *s, const double *x, double u, double *next)
+ * h; next += (k1 + 2*k2 + 2*k3 + k4)/6 with a true division. */
+void orc_env_integrate(const orc_spec *s, const double *x, double u, double h, int steps, double *next)
 {
   int S = orc_env_state_dims(s->env);
-  double h = s->control_step / s->integration_steps;
   double xd[ORC_MAX_STATE], k1[ORC_MAX_STATE], k2[ORC_MAX_STATE], k3[ORC_MAX_STATE], k4[ORC_MAX_STATE], t[ORC_MAX_STATE];
 
   memcpy(next, x, sizeof(double) * S);
-  for (int ii = 0; ii < s->integration_steps; ++ii)
+  for (int ii = 0; ii < steps; ++ii)
   {
     env_eom(s, next, u, xd);
     for (int i = 0; i < S; ++i) { k1[i] = h * xd[i]; t[i] = next[i] + k1[i] / 2; }
@@ -542,6 +572,44 @@ static void rk4_step(const orc_spec *s, const double *x, double u, double *next)
   }
 }
 
+static void rk4_step(const orc_spec *s, const double *x, double u, double *next)
+{ /* h = tau/steps */
+  orc_env_integrate(s, x, u, s->control_step / s->integration_steps, s->integration_steps, next);
+}
+
+/* Dynamics::eom of the environments that have one (not the compass walker, whose model integrates itself) */
+void orc_env_eom(const orc_spec *s, const double *x, double u, double *xd)
+{
+  env_eom(s, x, u, xd);
+}
+
+/* Task::evaluate: the reward of the transition (state, action) -> next */
+double orc_env_evaluate(const orc_spec *s, const double *state, double action, const double *next)
+{
+  switch (s->env)
+  {
+    case ORC_ENV_PENDULUM: return pendulum_evaluate(s, state, action, next);
+    case ORC_ENV_ACROBOT: return !acrobot_failed(next);                  /* acrobot.cpp:127-133 */
+    case ORC_ENV_CART_POLE: return cart_pole_evaluate(s, state, action, next);
+    case ORC_ENV_CART_POLE_BALANCING: return balancing_evaluate(state, next);
+    case ORC_ENV_COMPASS_WALKER: return walker_evaluate(s, next);
+  }
+  return 0;
+}
+
+/* Task::start from explicit stream positions (48-bit states of the global and the thread-local generator), which are advanced
+ * past the draws the start consumed */
+void orc_env_start_at(const orc_spec *s, uint64_t *global, uint64_t *thread_local_, int test, double *x)
+{
+  orc_exp e;
+  memset(&e, 0, sizeof(e));
+  e.G.x = *global;
+  e.TL.x = *thread_local_;
+  orc_env_start(s, &e, test, x);
+  *global = e.G.x;
+  *thread_local_ = e.TL.x;
+}
+
 /* ModeledEnvironment::step, modeled.cpp:160-213 (window 1, no delta, no
  * exporter, discrete_time 1 => returns 1). */
 double orc_env_step(const orc_spec *s, double *state, double action,
@@ -556,15 +624,7 @@ double orc_env_step(const orc_spec *s, double *state, double action,
   else
     rk4_step(s, state, actuation, next);
   *terminal = orc_env_observe(s, next, obs);
-  switch (s->env)
-  {
-    case ORC_ENV_PENDULUM: *reward = pendulum_evaluate(s, state, action, next); break;
-    case ORC_ENV_ACROBOT: *reward = !acrobot_failed(next); break;        /* acrobot.cpp:127-133 */
-    case ORC_ENV_CART_POLE: *reward = cart_pole_evaluate(s, state, action, next); break;
-    case ORC_ENV_CART_POLE_BALANCING: *reward = balancing_evaluate(state, next); break;
-    case ORC_ENV_COMPASS_WALKER: *reward = walker_evaluate(s, next); break;
-    default: *reward = 0;
-  }
+  *reward = orc_env_evaluate(s, state, action, next);
   memcpy(state, next, sizeof(double) * S);
   return 1;
 }

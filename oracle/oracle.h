@@ -25,9 +25,10 @@
  * configuration with seed 1 reproduces the reference's own golden file
  * tests/template/pendulum-sarsa-tc-0.txt byte for byte (tests/test_oracle_golden.py;
  * fixture committed as tests/golden/pendulum-sarsa-tc-0.txt).  Everything the
- * reference's tests do not pin (Q-learning, actor-critic, cart-pole, acrobot,
- * compass walker) is marked "parity unpinned by reference tests" where it is
- * implemented.
+ * reference's tests do not pin (Q-learning, actor-critic, the cart-pole swing-up
+ * task) is marked "parity unpinned by reference tests" where it is implemented.
+ * The acrobot and the compass walker are pinned by the reference's own sources,
+ * compiled unmodified into oracle/_ref/ref_envs (oracle/ref, tests/test_oracle_ref_envs.py).
  *
  * MATH MODES.  ORC_MATH_LIBM calls the host libm (sin/cos/fmod/pow/log) exactly
  * where the reference does.  ORC_MATH_PORTABLE replaces the transcendental calls by
@@ -164,6 +165,19 @@ double orc_env_step(const orc_spec *s, double *state, double action,
                     double *obs, double *reward, int *terminal);
 int    orc_env_state_dims(int env);
 int    orc_env_obs_dims(int env);
+/* The pieces orc_env_step is made of, one per interface of the reference (Dynamics::eom, DynamicalModel::step's `steps` RK4
+ * sub-steps of h, Task::observe -> terminal code, Task::evaluate -> reward, Task::start), so that each can be held against the
+ * reference's own code (oracle/ref, tests/test_oracle_ref_envs.py).  orc_env_start_at takes the 48-bit states of the global
+ * (drand48) and the thread-local (RandGen) generator and leaves them advanced past the draws the start consumed. */
+void   orc_env_eom(const orc_spec *s, const double *x, double u, double *xd);
+void   orc_env_integrate(const orc_spec *s, const double *x, double u, double h, int steps, double *next);
+int    orc_env_observe(const orc_spec *s, const double *x, double *obs);
+double orc_env_evaluate(const orc_spec *s, const double *state, double action, const double *next);
+void   orc_env_start_at(const orc_spec *s, uint64_t *global, uint64_t *thread_local_, int test, double *x);
+/* One compass-walker model step (next[11]) and what its sub-steps did, for the tests' case generators: out[7] = floor crossings
+ * of the swing foot, heel strikes, crossings refused for the hip angle changing sign / the stance rate >= 0 / the hip angle >= 0,
+ * wrap bits (sla >= pi, sla < -pi, ha >= pi, ha < -pi), iterations of the last secant search (11: all 10 spent).  Not reentrant. */
+void   orc_walker_step_diag(const orc_spec *s, const double *x, double torque, double *next, int *out);
 
 /* --------------------------------------------------------- experiment -- */
 typedef struct orc_exp orc_exp;

@@ -62,6 +62,5 @@ double orc_m_sqr(const orc_spec *s, double x);
 double orc_m_powtau(const orc_spec *s, double base, double tau);
 
 void orc_env_start(const orc_spec *s, orc_exp *e, int test, double *x);
-int  orc_env_observe(const orc_spec *s, const double *x, double *obs);
 
 #endif

@@ -99,6 +99,12 @@ def load():
     L.orc_env_step.argtypes = [P(Spec), P(C.c_double), C.c_double, P(C.c_double), P(C.c_double), P(C.c_int)]
     L.orc_env_step.restype = C.c_double
     L.orc_env_state_dims.argtypes = [C.c_int]; L.orc_env_obs_dims.argtypes = [C.c_int]
+    L.orc_env_eom.argtypes = [P(Spec), P(C.c_double), C.c_double, P(C.c_double)]; L.orc_env_eom.restype = None
+    L.orc_env_integrate.argtypes = [P(Spec), P(C.c_double), C.c_double, C.c_double, C.c_int, P(C.c_double)]; L.orc_env_integrate.restype = None
+    L.orc_env_observe.argtypes = [P(Spec), P(C.c_double), P(C.c_double)]; L.orc_env_observe.restype = C.c_int
+    L.orc_env_evaluate.argtypes = [P(Spec), P(C.c_double), C.c_double, P(C.c_double)]; L.orc_env_evaluate.restype = C.c_double
+    L.orc_env_start_at.argtypes = [P(Spec), P(C.c_uint64), P(C.c_uint64), C.c_int, P(C.c_double)]; L.orc_env_start_at.restype = None
+    L.orc_walker_step_diag.argtypes = [P(Spec), P(C.c_double), C.c_double, P(C.c_double), P(C.c_int)]; L.orc_walker_step_diag.restype = None
     L.orc_create.argtypes = [P(Spec), C.c_long]; L.orc_create.restype = C.c_void_p
     L.orc_destroy.argtypes = [C.c_void_p]
     L.orc_run.argtypes = [C.c_void_p, C.c_int, P(Row), C.c_int, P(Tap), C.c_int, P(C.c_int)]; L.orc_run.restype = C.c_int
