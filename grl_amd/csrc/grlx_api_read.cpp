@@ -1,7 +1,8 @@
-// grlx_api_read.cpp -- the C ABI declared in include/grlx.h: the read side -- policy queries and greedy evaluation episodes, chunked over the caller's observations / start states.
+// grlx_api_read.cpp -- the C ABI declared in include/grlx.h: the read side -- policy queries, greedy and sampled evaluation episodes, chunked over the caller's observations / start states.
 #include "grlx_host.h"
 #include "grlx_query.h"
 #include "grlx_evaluate.h"
+#include "grlx_evaluate_sampled.h"
 
 // ------------------------------------------------------------------------------------------- policy queries ---
 namespace {
@@ -87,21 +88,30 @@ struct ReadTimer {
 // write it (or a reduction reads it) whether the caller asked for it or not.
 struct ReadOut { void *host; size_t elem; int rows; bool on_device; };
 constexpr int kMaxReadOuts = 9;
+// A second per-column input of a chunked read, laid out like an output: host [rows][cols] of `elem` bytes -> `dev` [rows][chunk], so that
+// a chunk's rows begin at its first column for EVERY row (a strided copy, not a contiguous one).  host null: nothing is staged.
+struct ReadIn { const void *host; size_t elem; int rows; DevBuf *dev; };
 
 // The skeleton of every read: the columns of `in` (observations or start states, `in_dims` doubles each) go through the device `chunk` at a
 // time.  Per chunk: the input in, launch(nc, input, outputs) -- device pointers, null for an output neither asked for nor needed -- and out
 // what the caller asked for.  `sync_each`: every output may be null, so the next chunk's copy-in must not overtake the launch.
+// `extra`: a second input staged beside the first (ReadIn), or null.
 template <typename Launch>
-int chunked_read(grlx_ctx *ctx, const ReadOut *outs, int n_outs, int cols, const double *in, int in_dims, int chunk, bool sync_each, Launch launch)
+int chunked_read(grlx_ctx *ctx, const ReadOut *outs, int n_outs, int cols, const double *in, int in_dims, int chunk, bool sync_each, Launch launch,
+                 const ReadIn *extra = nullptr)
 {
   DevBuf din, dout[kMaxReadOuts];
   HIP_TRY(din.alloc(sizeof(double) * (size_t)chunk * in_dims));
+  if (extra && extra->host) HIP_TRY(extra->dev->alloc(extra->elem * (size_t)extra->rows * (size_t)chunk));
   for (int k = 0; k < n_outs; ++k)
     if (outs[k].host || outs[k].on_device) HIP_TRY(dout[k].alloc(outs[k].elem * (size_t)outs[k].rows * (size_t)chunk));
   for (int c0 = 0; c0 < cols; c0 += chunk)
   {
     const int nc = cols - c0 < chunk ? cols - c0 : chunk;
     HIP_TRY(hipMemcpy(din.get(), in + (size_t)c0 * in_dims, sizeof(double) * (size_t)nc * in_dims, hipMemcpyHostToDevice));
+    if (extra && extra->host)
+      HIP_TRY(hipMemcpy2D(extra->dev->get(), (size_t)nc * extra->elem, (const char *)extra->host + (size_t)c0 * extra->elem, (size_t)cols * extra->elem,
+                          (size_t)nc * extra->elem, (size_t)extra->rows, hipMemcpyHostToDevice));
     if (ctx->poison) HIP_TRY(launch_poison_registers(ctx->poison_pattern, nullptr));
     if (g_read_timing)
     { // grlx_read_kernel_timing: events around the chunk's launches, waited for here
@@ -389,6 +399,122 @@ int grlx_evaluate_ensemble_trajectory(grlx_ctx *ctx, int first_replica, int n_re
     HIP_TRY(launch_trajectory_ensemble(ctx->P, T, nullptr));
     return GRLX_OK;
   });
+}
+
+// ---- sampled evaluation: the episodes of grlx_evaluate acted by the reference's samplers on streams the episodes carry (grlx_evaluate_sampled.hip)
+// what both sampled evaluations check beyond evaluate_admit
+static int sampled_admit(grlx_ctx *ctx, const char *who, int n_replicas, int n_starts, int sampler, double epsilon, const uint64_t *streams)
+{
+  if (!q_agent(ctx->cfg.agent))
+    return fail(GRLX_ERR_INVALID, "%s is not built for the actor-critic agent (its Gaussian / Ornstein-Uhlenbeck exploration needs the policy's noise state); "
+                "it serves agents with a policy/discrete/q", who);
+  if (sampler != GRLX_SAMPLER_GREEDY && sampler != GRLX_SAMPLER_EPSILON_GREEDY)
+    return fail(GRLX_ERR_INVALID, "%s: unknown sampler %d (GRLX_SAMPLER_GREEDY = 0, GRLX_SAMPLER_EPSILON_GREEDY = 1)", who, sampler);
+  if (!std::isfinite(epsilon)) return fail(GRLX_ERR_INVALID, "%s: epsilon is not finite (%g)", who, epsilon);
+  if (epsilon != GRLX_EPSILON_OWN && !(epsilon >= 0. && epsilon <= 1.))
+    return fail(GRLX_ERR_INVALID, "%s: epsilon = %g is outside [0, 1] and is not GRLX_EPSILON_OWN (-1)", who, epsilon);
+  if (streams)
+    for (int64_t row = 0; row < (int64_t)n_replicas * n_starts; ++row)
+      for (int w = 0; w < 2; ++w)
+        if (streams[row * 2 + w] >> 48)
+          return fail(GRLX_ERR_INVALID, "%s: stream row %lld (replica %lld, start state %lld), word %d is 0x%llx: a rand48 state is below 2^48", who,
+                      (long long)row, (long long)(row / n_starts), (long long)(row % n_starts), w, (unsigned long long)streams[row * 2 + w]);
+  return GRLX_OK;
+}
+
+static int evaluate_sampled_impl(grlx_ctx *ctx, const char *who, bool trajectory, int first_replica, int n_replicas, const double *states, int n_starts,
+                                 int max_steps, int sampler, double epsilon, const uint64_t *streams, double *ret, double *disc, int32_t *steps,
+                                 int32_t *terminal, int32_t *ties, int32_t *explored, double *final_state, uint64_t *streams_out, double *records)
+{
+  int rc = evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps);
+  if (rc != GRLX_OK) return rc;
+  if (int bad = sampled_admit(ctx, who, n_replicas, n_starts, sampler, epsilon, streams)) return bad;
+  const int S = ctx->S, R = trajectory ? sampled_trajectory_words(ctx->cfg.env) : 0;
+  const size_t per_pair = 2 * sizeof(double) + 4 * sizeof(int32_t) + sizeof(double) * (size_t)S + 4 * sizeof(uint64_t);     // the sums, both streams in and out
+  int chunk = 0;
+  if (trajectory)
+  {
+    rc = trajectory_admit(who, "grlx_evaluate_sampled", records, max_steps, n_replicas, n_starts, R, sizeof(double) * (size_t)S + per_pair * (size_t)n_replicas, &chunk);
+    if (rc != GRLX_OK) return rc;
+  }
+  else chunk = query_chunk(n_starts, sizeof(double) * (size_t)S + per_pair * (size_t)n_replicas);
+  if (max_steps == 0) max_steps = GRLX_MAX_EPISODE_STEPS;
+  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
+  DRAIN(ctx);
+  const size_t rec_elem = sizeof(double) * (size_t)R * (size_t)max_steps;
+  const ReadOut outs[9] = {{ret, sizeof(double), n_replicas, true}, {disc, sizeof(double), n_replicas, true}, {steps, sizeof(int32_t), n_replicas, true},
+                           {terminal, sizeof(int32_t), n_replicas, true}, {ties, sizeof(int32_t), n_replicas, true},
+                           {final_state, sizeof(double) * (size_t)S, n_replicas, true}, {explored, sizeof(int32_t), n_replicas, true},
+                           {streams_out, 2 * sizeof(uint64_t), n_replicas, true}, {records, rec_elem, n_replicas, true}};
+  DevBuf dstreams;
+  const ReadIn in_streams = {streams, 2 * sizeof(uint64_t), n_replicas, &dstreams};     // [replica][start][2]: a chunk is strided, not contiguous
+  return chunked_read(ctx, outs, trajectory ? 9 : 8, n_starts, states, S, chunk, true, [&](int nc, const double *dst, const DevBuf *d) -> int {
+    SampledArgs T;
+    EvaluateArgs &A = T.e;
+    A.first_replica = first_replica; A.n_replicas = n_replicas; A.n_starts = nc; A.max_steps = max_steps;
+    A.states = dst; A.sweep = ctx->sweep ? ctx->sweep_dev.get() : nullptr;
+    A.ret = d[0].as<double>(); A.disc = d[1].as<double>(); A.steps = d[2].as<int32_t>(); A.terminal = d[3].as<int32_t>(); A.ties = d[4].as<int32_t>();
+    A.final_state = d[5].as<double>();
+    T.sampler = sampler; T.epsilon = epsilon;
+    T.streams = streams ? dstreams.as<uint64_t>() : nullptr;
+    T.explored = d[6].as<int32_t>(); T.streams_out = d[7].as<uint64_t>();
+    T.records = trajectory ? d[8].as<double>() : nullptr;
+    if (trajectory)
+    {
+      HIP_TRY(hipMemsetAsync(T.records, 0, rec_elem * (size_t)n_replicas * (size_t)nc, nullptr));     // records behind an episode's end are +0.0
+      HIP_TRY(launch_trajectory_sampled(ctx->P, T, nullptr));
+    }
+    else HIP_TRY(launch_evaluate_sampled(ctx->P, T, nullptr));
+    return GRLX_OK;
+  }, &in_streams);
+}
+
+int grlx_evaluate_sampled(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, int sampler, double epsilon,
+                          const uint64_t *streams, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, int32_t *explored,
+                          double *final_state, uint64_t *streams_out)
+{
+  return evaluate_sampled_impl(ctx, "grlx_evaluate_sampled", false, first_replica, n_replicas, states, n_starts, max_steps, sampler, epsilon, streams, ret,
+                               disc, steps, terminal, ties, explored, final_state, streams_out, nullptr);
+}
+
+int grlx_sampled_trajectory_record_words(grlx_ctx *ctx)
+{
+  if (!ctx) return fail(GRLX_ERR_INVALID, "bad argument");
+  const char *who = "grlx_sampled_trajectory_record_words";
+  if (ctx->cfg.env == GRLX_ENV_EXTERNAL || !evaluate_built(ctx->cfg.agent, ctx->cfg.env, ctx->P.A))
+    return fail(GRLX_ERR_INVALID, "%s: no evaluation episodes are built for this context (environment %d)", who, ctx->cfg.env);
+  if (!q_agent(ctx->cfg.agent)) return fail(GRLX_ERR_INVALID, "%s: the sampled evaluation is not built for the actor-critic agent", who);
+  return sampled_trajectory_words(ctx->cfg.env);
+}
+
+int grlx_evaluate_sampled_trajectory(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, int sampler,
+                                     double epsilon, const uint64_t *streams, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                                     int32_t *explored, double *final_state, uint64_t *streams_out, double *records)
+{
+  return evaluate_sampled_impl(ctx, "grlx_evaluate_sampled_trajectory", true, first_replica, n_replicas, states, n_starts, max_steps, sampler, epsilon,
+                               streams, ret, disc, steps, terminal, ties, explored, final_state, streams_out, records);
+}
+
+// host only: stream k = srand48(seed) advanced by k * 2^20 draws, k = 2 * pair + which
+void grlx_episode_streams(long seed, int64_t first_pair, int64_t n_pairs, uint64_t *out)
+{
+  if (!out || n_pairs <= 0 || first_pair < 0) return;
+  constexpr uint64_t kA = 0x5DEECE66DULL, kC = 0xBULL, kMask = (1ULL << 48) - 1;
+  uint64_t ja = kA, jc = kC;                            // the affine map of 2^20 draws, by 20 squarings
+  for (int i = 0; i < 20; ++i) { jc = ((ja + 1) * jc) & kMask; ja = (ja * ja) & kMask; }
+  // ... and of first_pair * 2 such jumps: x -> A^n x + C_n by repeated squaring over the bits of n
+  uint64_t x = h_seed(seed), a = ja, c = jc;
+  for (uint64_t n = (uint64_t)first_pair * 2; n; n >>= 1)
+  {
+    if (n & 1) x = (a * x + c) & kMask;
+    c = ((a + 1) * c) & kMask;
+    a = (a * a) & kMask;
+  }
+  for (int64_t k = 0; k < 2 * n_pairs; ++k)
+  {
+    out[k] = x;
+    x = (ja * x + jc) & kMask;
+  }
 }
 
 } // extern "C"

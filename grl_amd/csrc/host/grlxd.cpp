@@ -15,6 +15,9 @@
 // the members' vote or on their mean Q (grlx_evaluate_ensemble), written to <output>-<run>-ensemble.txt (objects.h),
 // -T STEPS: with -E, also the steps of those episodes, STEPS of each at the most (grlx_evaluate_trajectory), one line per step taken in
 // <output>-<run>-trajectories.txt, and with -V the ensemble's in <output>-<run>-ensemble-trajectories.txt (objects.h),
+// -e EPSILON|own|greedy: with -E, also one SAMPLED episode per (clone, start state) with grlx_evaluate_sampled -- the epsilon-greedy sampler on
+// EPSILON in [0, 1] or on every clone's own decayed epsilon, or the greedy sampler with its drawn tie break -- on the streams of
+// grlx_episode_streams(-s seed), written to <output>-<run>-sampled.txt, and with -T the steps in <output>-<run>-sampled-trajectories.txt (objects.h),
 // -n: print the plan (one line per clone: i seed alpha gamma lambda epsilon) and exit before anything touches HIP, and
 // -g N: one process per GPU (rank r on the r-th visible device, started before anything touches HIP), every rank running -r replicas
 // (clones r * replicas ..., seeds and "@i" identities counted over the whole job), the learning curves reduced with one RCCL all-reduce
@@ -78,9 +81,9 @@ int main(int argc, char **argv)
   int c;
   std::vector<std::string> sweep_args;
   std::string ensemble_arg;
-  bool ensemble = false, trajectory = false;
+  bool ensemble = false, trajectory = false, sampled = false;
   int trajectory_steps = 0;
-  while ((c = getopt(argc, argv, "vs:r:t:lqc:g:p:nk:K:Q:E:V:T:")) != -1)
+  while ((c = getopt(argc, argv, "vs:r:t:lqc:g:p:nk:K:Q:E:V:T:e:")) != -1)
   {
     switch (c)
     {
@@ -100,12 +103,13 @@ int main(int argc, char **argv)
       case 'E': opt.evaluate_file = optarg; break;
       case 'V': ensemble_arg = optarg; ensemble = true; break;
       case 'T': trajectory_steps = atoi(optarg); trajectory = true; break;
+      case 'e': opt.sampled_arg = optarg; sampled = true; break;
       default: return 1;
     }
   }
   if (optind > argc - 1)
   {
-    log(0, std::string("Usage: \n  ") + argv[0] + " [-v] [-s seed] [-r replicas] [-g gpus] [-t trials] [-l] [-q] [-p path=v1,v2,...]... [-n] [-k snapshot] [-K snapshot] [-Q observations] [-E states] [-V vote|mean] [-T steps] <yaml file> [yaml file...]");
+    log(0, std::string("Usage: \n  ") + argv[0] + " [-v] [-s seed] [-r replicas] [-g gpus] [-t trials] [-l] [-q] [-p path=v1,v2,...]... [-n] [-k snapshot] [-K snapshot] [-Q observations] [-E states] [-V vote|mean] [-T steps] [-e epsilon|own|greedy] <yaml file> [yaml file...]");
     return 1;
   }
   if (opt.seed == 0)
@@ -176,6 +180,20 @@ int main(int argc, char **argv)
     if ((sweep_args.empty() ? opt.replicas : opt.sweep_repetitions) < 2)
     { log(0, "-T: -E needs -r >= 2: the standard deviation over the clones divides by n - 1"); return 1; }
     opt.trajectory_steps = trajectory_steps;
+  }
+  if (sampled)
+  { // -e needs -E's states and a sampler; what -E refuses is refused here under -e's name, before any process is forked or any device looked for
+    const std::string &arg = opt.sampled_arg;
+    char *stop = nullptr;
+    const double eps = strtod(arg.c_str(), &stop);
+    if (arg == "greedy") { opt.sampled_sampler = GRLX_SAMPLER_GREEDY; opt.sampled_epsilon = 0; }
+    else if (arg == "own") { opt.sampled_sampler = GRLX_SAMPLER_EPSILON_GREEDY; opt.sampled_epsilon = GRLX_EPSILON_OWN; }
+    else if (!arg.empty() && *stop == 0 && eps >= 0. && eps <= 1.) { opt.sampled_sampler = GRLX_SAMPLER_EPSILON_GREEDY; opt.sampled_epsilon = eps; }
+    else { log(0, "-e: '" + arg + "' is neither a number in [0, 1] nor 'own' (every clone's decayed epsilon) nor 'greedy' (the greedy sampler with its drawn tie break)"); return 1; }
+    if (opt.evaluate_file.empty()) { log(0, "-e " + arg + ": a sampled evaluation needs the start states of -E <states file>"); return 1; }
+    if (gpus > 1) { log(0, "-e: a sampled policy evaluation runs on one GPU (-g " + std::to_string(gpus) + " is not built)"); return 1; }
+    if ((sweep_args.empty() ? opt.replicas : opt.sweep_repetitions) < 2)
+    { log(0, "-e: -E needs -r >= 2: the standard deviation over the clones divides by n - 1"); return 1; }
   }
   if (!opt.evaluate_file.empty())
   { // likewise: the state file is read, and -g and -r 1 refused, before any process is forked or any device looked for

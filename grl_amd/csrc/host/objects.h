@@ -61,6 +61,16 @@ struct RunOptions {
   // integers, the others %.17g.  With -V also <output>-<run>-ensemble-trajectories.txt (grlx_evaluate_ensemble_trajectory), its lines
   // beginning "group start step".  The episodes of the returns and ensemble files are not cut at STEPS.  0 = no -T.
   int trajectory_steps = 0;
+  // `grlxd -E FILE -e <epsilon | own | greedy>`: besides the unchanged returns file, one SAMPLED episode per (clone, start state) with
+  // grlx_evaluate_sampled -- the epsilon-greedy sampler on a number in [0, 1] or on every clone's own decayed epsilon, or the greedy sampler
+  // with its drawn tie break -- on the streams of grlx_episode_streams(-s seed, pair 0 ...); rank 0 writes <output>-<run>-sampled.txt: per
+  // start state one line "mean sd mean_steps n0 n1 n2 n3 ties explored", the returns file's columns and the summed explored steps.  With -p:
+  // one line per (point, start state), the point's index first.  With -T also <output>-<run>-sampled-trajectories.txt
+  // (grlx_evaluate_sampled_trajectory), the trajectories file's lines with one word more, the record's last: 1 where the step explored.
+  // sampled_sampler: -1 = no -e; else GRLX_SAMPLER_*.  sampled_epsilon: the number, or GRLX_EPSILON_OWN.
+  int sampled_sampler = -1;
+  double sampled_epsilon = 0;
+  std::string sampled_arg;
 };
 // ... the same for opt.evaluate_file -> opt.evaluate_states / _rows / _cols (messages begin with -E)
 void read_evaluate_file(RunOptions *opt);

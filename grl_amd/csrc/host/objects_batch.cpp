@@ -236,6 +236,8 @@ struct BatchLearningExperimentImpl : Experiment {
       throw Exception(path() + ": a policy query (-Q) is built for experiment/online_learning, not for experiment/batch_learning");
     if (opt.trajectory_steps != 0)
       throw Exception(path() + ": per-step trajectories (-T) are built for experiment/online_learning, not for experiment/batch_learning");
+    if (opt.sampled_sampler >= 0)
+      throw Exception(path() + ": a sampled policy evaluation (-e) is built for experiment/online_learning, not for experiment/batch_learning");
     if (!opt.evaluate_file.empty())
       throw Exception(path() + ": a policy evaluation (-E) is built for experiment/online_learning, not for experiment/batch_learning");
     grlx_fqi_config c;

@@ -256,6 +256,14 @@ RunPlan OnlineImpl::plan(const RunOptions &opt) const
     if (opt.world > 1) throw Exception(path() + ": -T: trajectories of a policy evaluation run on one GPU (-g " + std::to_string(opt.world) + " is not built)");
     if (p.group < 2) throw Exception(path() + ": -T: -E needs -r >= 2: the standard deviation over the clones divides by n - 1");
   }
+  if (opt.sampled_sampler >= 0)
+  { // -e rides on -E: refused here with its own name, before -E's checks say the same without it
+    if (opt.evaluate_file.empty()) throw Exception(path() + ": -e: a sampled evaluation needs the start states of -E <states file>");
+    if (opt.world > 1) throw Exception(path() + ": -e: a sampled policy evaluation runs on one GPU (-g " + std::to_string(opt.world) + " is not built)");
+    if (p.group < 2) throw Exception(path() + ": -e: -E needs -r >= 2: the standard deviation over the clones divides by n - 1");
+    if (c.agent == GRLX_AGENT_AC)
+      throw Exception(path() + ": -e: a sampled evaluation is not built for the actor-critic agent (its Gaussian / Ornstein-Uhlenbeck exploration needs the policy's noise state)");
+  }
   p.evaluate = !opt.evaluate_file.empty();
   if (p.evaluate)
   { // (grlx_evaluate validates the states themselves, and what it is built for, before it launches)
@@ -464,6 +472,7 @@ std::vector<double> OnlineImpl::run(const RunOptions &opt)
     write_returns_file(p, ctx, rr);
     write_ensemble_file(p, ctx, rr);
     write_trajectory_files(p, ctx, rr);
+    write_sampled_files(p, ctx, rr);
     write_mean_file(p, ctx, rr, rows);
     if (save_every == "run" && !output.empty()) save_policy(p, ctx, output + "-run" + std::to_string(rr));      // online_learning.cpp:294-302
 

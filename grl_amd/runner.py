@@ -657,6 +657,70 @@ class Runner:
                                                               _ptr(agreement, C.c_int64), _ptr(final_state, C.c_double), _ptr(records, C.c_double)))
         return EnsembleTrajectory(ret, disc, steps, terminal, ties, member_ties, agreement, final_state, records)
 
+    # ---- sampled evaluation: the same episodes acted by the reference's samplers on streams the episodes carry (grlx_evaluate_sampled)
+    def _sampled_args(self, states, sampler, epsilon, streams, replicas):
+        samplers = {"greedy": capi.SAMPLER_GREEDY, "epsilon": capi.SAMPLER_EPSILON_GREEDY, "epsilon_greedy": capi.SAMPLER_EPSILON_GREEDY}
+        sampler = samplers[sampler] if isinstance(sampler, str) else int(sampler)
+        if isinstance(epsilon, str):
+            if epsilon != "own":
+                raise ValueError('epsilon: a number in [0, 1] or "own"')
+            epsilon = capi.EPSILON_OWN
+        states = np.ascontiguousarray(states, dtype=np.float64)
+        if states.ndim != 2 or states.shape[1] != self.state_dims:
+            raise ValueError(f"expected states of shape (n, {self.state_dims}), got {states.shape}")
+        first, count = self._replica_range(replicas)
+        n = states.shape[0]
+        if streams is not None:
+            streams = np.ascontiguousarray(streams, dtype=np.uint64)
+            if streams.shape != (count, n, 2):
+                raise ValueError(f"expected streams of shape ({count}, {n}, 2), got {streams.shape}")
+        return states, sampler, float(epsilon), streams, first, count, n
+
+    def evaluate_sampled(self, states, sampler="epsilon", epsilon="own", streams=None, replicas=None, max_steps=0):
+        """Runner.evaluate's episodes acted by a sampler of the reference: "greedy" (the first maximum, a tie broken by a draw) or
+        "epsilon" (epsilon-greedy; epsilon a number in [0, 1] for every replica, or "own": the replica's decayed epsilon as it stands).
+        streams[replica][start][2]: the rand48 states every episode starts from -- [..][0] the sampler's stream (the epsilon draw),
+        [..][1] the global stream (the random action, the tie break); None = copies of the replica's own two streams (see episode_streams).
+        SampledEvaluation(ret, disc, steps, terminal, ties, explored, final_state, streams): ties = tie breaks drawn, explored = random
+        actions taken, streams = both states after the last step.  The context is not changed (include/grlx.h: grlx_evaluate_sampled)."""
+        states, sampler, epsilon, streams, first, count, n = self._sampled_args(states, sampler, epsilon, streams, replicas)
+        ret, disc = np.zeros((count, n), np.float64), np.zeros((count, n), np.float64)
+        steps, terminal, ties, explored = (np.zeros((count, n), np.int32) for _ in range(4))
+        final_state = np.zeros((count, n, self.state_dims), np.float64)
+        out = np.zeros((count, n, 2), np.uint64)
+        capi.check(self.lib.grlx_evaluate_sampled(self._ctx, first, count, _ptr(states, C.c_double), n, int(max_steps), sampler, epsilon,
+                                                  None if streams is None else _ptr(streams, C.c_uint64), _ptr(ret, C.c_double),
+                                                  _ptr(disc, C.c_double), _ptr(steps, C.c_int32), _ptr(terminal, C.c_int32), _ptr(ties, C.c_int32),
+                                                  _ptr(explored, C.c_int32), _ptr(final_state, C.c_double), _ptr(out, C.c_uint64)))
+        return SampledEvaluation(ret, disc, steps, terminal, ties, explored, final_state, out)
+
+    def sampled_trajectory_record_words(self):
+        """R of evaluate_sampled_trajectory's records: trajectory_record_words() + 1 (grlx_sampled_trajectory_record_words)"""
+        words = self.lib.grlx_sampled_trajectory_record_words(self._ctx)
+        if words < 0:
+            capi.check(words)
+        return words
+
+    def evaluate_sampled_trajectory(self, states, max_steps, sampler="epsilon", epsilon="own", streams=None, replicas=None):
+        """Runner.evaluate_sampled with every step of every episode: SampledTrajectory(..., records), records[replica][start][max_steps][R]
+        with Trajectory's views -- .action_index the index that acted, .n_max the number of maxima, .value Q of the action taken -- and
+        .explored, 1.0 where the action was the random draw; the per-episode count is the field n_explored (include/grlx.h:
+        grlx_evaluate_sampled_trajectory)."""
+        states, sampler, epsilon, streams, first, count, n = self._sampled_args(states, sampler, epsilon, streams, replicas)
+        max_steps = int(max_steps)
+        words = self.sampled_trajectory_record_words()
+        ret, disc = np.zeros((count, n), np.float64), np.zeros((count, n), np.float64)
+        steps, terminal, ties, explored = (np.zeros((count, n), np.int32) for _ in range(4))
+        final_state = np.zeros((count, n, self.state_dims), np.float64)
+        out = np.zeros((count, n, 2), np.uint64)
+        records = np.zeros((count, n, max(max_steps, 0), words), np.float64)
+        capi.check(self.lib.grlx_evaluate_sampled_trajectory(self._ctx, first, count, _ptr(states, C.c_double), n, max_steps, sampler, epsilon,
+                                                             None if streams is None else _ptr(streams, C.c_uint64), _ptr(ret, C.c_double),
+                                                             _ptr(disc, C.c_double), _ptr(steps, C.c_int32), _ptr(terminal, C.c_int32),
+                                                             _ptr(ties, C.c_int32), _ptr(explored, C.c_int32), _ptr(final_state, C.c_double),
+                                                             _ptr(out, C.c_uint64), _ptr(records, C.c_double)))
+        return SampledTrajectory(ret, disc, steps, terminal, ties, explored, final_state, out, records)
+
 
 Evaluation = collections.namedtuple("Evaluation", "ret disc steps terminal ties final_state")
 EnsembleEvaluation = collections.namedtuple("EnsembleEvaluation", "ret disc steps terminal ties member_ties agreement final_state")
@@ -701,6 +765,28 @@ class EnsembleTrajectory(_RecordViews, collections.namedtuple("EnsembleTrajector
     _OBS = capi.TRAJ_ENS_OBS
     step_agreement = property(lambda self: self._cut(capi.TRAJ_ENS_AGREEMENT))
     step_member_ties = property(lambda self: self._cut(capi.TRAJ_ENS_MEMBER_TIES))
+
+
+SampledEvaluation = collections.namedtuple("SampledEvaluation", "ret disc steps terminal ties explored final_state streams")
+
+
+class SampledTrajectory(_RecordViews, collections.namedtuple("SampledTrajectory",
+                                                             "ret disc steps terminal ties n_explored final_state streams records")):
+    """What Runner.evaluate_sampled_trajectory returns: SampledEvaluation's fields and records[replica][start][max_steps][R], whose last word
+    (after the model state) says whether the step's action was the random draw: the view .explored, per step.  The per-episode count that
+    SampledEvaluation calls explored is the field n_explored here."""
+    __slots__ = ()
+    obs = property(lambda self: self._cut(self._OBS, self.records.shape[-1] - 1 - self.final_state.shape[-1]))
+    state = property(lambda self: self._cut(self.records.shape[-1] - 1 - self.final_state.shape[-1], self.records.shape[-1] - 1))
+    explored = property(lambda self: self._cut(self.records.shape[-1] - 1))
+
+
+def episode_streams(seed: int, n_replicas: int, n_starts: int, first_pair: int = 0):
+    """streams[n_replicas][n_starts][2] for Runner.evaluate_sampled from one seed (grlx_episode_streams; host only): stream k =
+    2 * (first_pair + replica * n_starts + start) + which is srand48(seed) advanced by k * 2^20 draws, so no two episodes share a draw."""
+    out = np.zeros((int(n_replicas), int(n_starts), 2), np.uint64)
+    capi.load().grlx_episode_streams(int(seed), int(first_pair), out.shape[0] * out.shape[1], _ptr(out, C.c_uint64))
+    return out
 
 
 class EnsembleResult:

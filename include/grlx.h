@@ -463,7 +463,8 @@ int  grlx_query_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, int g
  * ("not built"), an (environment, action count) pair without an instantiation (built: pendulum x {3, 5} actions, acrobot, cart-pole and
  * walker x 3; actor-critic: cart-pole and pendulum).  n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
  * The steps of these episodes: grlx_evaluate_trajectory (below).  The batch path's episodes: grlx_fqi_evaluate (at the end of this file).
- * NOT BUILT: the epsilon-greedy learning policy, acting on the target network. */
+ * The samplers -- the drawn tie break, the epsilon-greedy learning policy --: grlx_evaluate_sampled (below).
+ * NOT BUILT: acting on the target network. */
 int  grlx_evaluate(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][state_dims]*/, int n_starts,
                    int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state);
 
@@ -534,7 +535,8 @@ int  grlx_evaluate_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, in
  * Validated on the host before anything is launched (GRLX_ERR_INVALID, nothing written, the reason named): everything the sibling
  * refuses, and the three cases above.  Like the siblings they change nothing in the context, wait for the stream of the last grlx_run
  * and do not count as a launch.  The batch path's: grlx_fqi_evaluate_trajectory (at the end of this file), with the same words.
- * NOT BUILT: trajectories of the epsilon-greedy learning policy, streaming records to a file descriptor. */
+ * Trajectories of the samplers' episodes: grlx_evaluate_sampled_trajectory (below).
+ * NOT BUILT: streaming records to a file descriptor. */
 enum { GRLX_TRAJ_ACTION = 0, GRLX_TRAJ_REWARD = 1, GRLX_TRAJ_VALUE = 2, GRLX_TRAJ_ACTION_INDEX = 3, GRLX_TRAJ_N_MAX = 4, GRLX_TRAJ_TERMINAL = 5,
        GRLX_TRAJ_OBS = 6, GRLX_TRAJ_ENS_AGREEMENT = 6, GRLX_TRAJ_ENS_MEMBER_TIES = 7, GRLX_TRAJ_ENS_OBS = 8 };
 int  grlx_trajectory_record_words(grlx_ctx *ctx, int ensemble);      /* R; a negative status for a context without such episodes */
@@ -546,6 +548,66 @@ int  grlx_evaluate_ensemble_trajectory(grlx_ctx *ctx, int first_replica, int n_r
                                        double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
                                        int64_t *member_ties, int64_t *agreement, double *final_state,
                                        double *records /*[n_replicas / group_size][n_starts][max_steps][R]*/);
+
+/* --- sampled evaluation: the episodes of grlx_evaluate acted by the reference's samplers ------------------------------------------------
+ * Q agents.  For every (replica, start state) pair one episode, on the device, in one launch: grlx_evaluate's loop, unchanged -- the
+ * ignored terminal code of the start state, the terminal codes 0 / 1 / 2 / 3, max_steps (0 = GRLX_MAX_EPISODE_STEPS; the trajectory call
+ * refuses 0), the 2^17 bound on state components, ret, disc (the replica's own gamma in a sweep context) and final_state as there, on
+ * grlx_query_q's Q-values (main parameters, peek only, initial_weight for a slot without an entry) -- in which the action index comes
+ * from a SAMPLER (greedy.cpp:63-86, 144-218) instead of the first maximum.  Nothing in the context changes; the call waits for the stream
+ * of the last grlx_run, does not count as a launch and stages in chunks of start states under grlx_set_query_chunk_bytes' bound.
+ *   Streams.    Every episode carries two 48-bit rand48 states, streams[n_replicas][n_starts][2]:
+ *               [..][0] the sampler's private stream (the role of the learning policy's sampler stream: the epsilon draw),
+ *               [..][1] the global stream (the random action index and the tie break).
+ *               streams == NULL: every episode of replica r starts from COPIES of that replica's sampler stream and global stream
+ *               as they stand (grlx_get_rng's words 2 and 0); the context's own streams do not move.
+ *               streams_out[n_replicas][n_starts][2] receives both states after the episode's last step; it may be NULL.
+ *               grlx_episode_streams (below) makes disjoint streams from one seed.
+ *   A step.     (mai, man) = GreedySampler::findmax(Q(obs, .)); then, in exactly the order of draws of the rollout kernels' sampler:
+ *               GRLX_SAMPLER_GREEDY          man > 1: the global stream advances, jj = lrand48 % man, the (jj + 1)-th maximal entry acts
+ *                                            and ties++; else mai acts and no draw is made.  epsilon is ignored but must be valid.
+ *               GRLX_SAMPLER_EPSILON_GREEDY  the sampler's stream advances, rnd = drand48; rnd < e: the global stream advances,
+ *                                            lrand48 % action_steps acts and explored++; else as the greedy sampler.
+ *               e is `epsilon` for every replica, or with GRLX_EPSILON_OWN the product eps_decay * epsilon as the rollout kernels form
+ *               it: the replica's current decay (EpsilonGreedySampler::decay_) times the configuration's epsilon, in a sweep context
+ *               that replica's own.  THE ONE DEVIATION: the decay is never advanced -- the reference decays once more at episode time 0
+ *               -- which is the price of changing nothing in the context.
+ *   ties        steps at which a tie break was DRAWN (man > 1 on a step that did not explore)
+ *   explored    steps at which the action was the random draw
+ * ret, disc, steps, terminal, ties, explored: [n_replicas][n_starts]; final_state has [state_dims] more.  Host pointers; any output may be NULL.
+ * Consequences.  With GRLX_SAMPLER_GREEDY and the replica's own streams (streams == NULL) an episode from the task's test start state is
+ * the reference's next test episode, bit for bit, WITH OR WITHOUT TIES.  With ties == 0 under GRLX_SAMPLER_GREEDY every output equals
+ * grlx_evaluate's and streams_out == streams.
+ *   Records.    grlx_evaluate_sampled_trajectory: records[pair][max_steps][R], R = grlx_sampled_trajectory_record_words(ctx) =
+ *               grlx_trajectory_record_words(ctx, 0) + 1.  Every word of grlx_evaluate_trajectory keeps its index:
+ *               GRLX_TRAJ_ACTION_INDEX is the index that ACTED, GRLX_TRAJ_N_MAX is man, GRLX_TRAJ_VALUE is Q of the action taken; the new
+ *               last word GRLX_TRAJ_SAMPLED_EXPLORED = R - 1 is 1.0 where the action was the random draw, else 0.0.  Records behind an
+ *               episode's end are zeros.  The staging rule and its refusal (a start state's column that exceeds the bound) are the sibling's.
+ * Agents: everything grlx_evaluate accepts as a Q agent -- SARSA, Q, Expected SARSA, advantage learning, QV's table 0, an accumulating
+ * trace, a context with a target network (the main parameters are read), the five (environment, actions) pairs that are built.
+ * Validated on the host before anything is launched (GRLX_ERR_INVALID, nothing written, the reason and the function named): everything
+ * grlx_evaluate refuses; an unknown sampler; epsilon that is not finite; epsilon outside [0, 1] that is not exactly GRLX_EPSILON_OWN;
+ * a stream word >= 2^48 (row and word named); the actor-critic ("not built": its Gaussian / Ornstein-Uhlenbeck exploration needs the
+ * policy's noise state and is a follow-up).  n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
+ * NOT BUILT: the actor-critic's exploration, a sampled ensemble (softmax(votes)), the tie-breaking draw of grlx_fqi_evaluate, the
+ * decay at episode time 0. */
+enum { GRLX_SAMPLER_GREEDY = 0, GRLX_SAMPLER_EPSILON_GREEDY = 1 };
+#define GRLX_EPSILON_OWN (-1.0)
+int  grlx_evaluate_sampled(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][state_dims]*/, int n_starts,
+                           int max_steps, int sampler, double epsilon, const uint64_t *streams /*[n_replicas][n_starts][2] or NULL*/,
+                           double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, int32_t *explored,
+                           double *final_state, uint64_t *streams_out /*[n_replicas][n_starts][2]*/);
+int  grlx_sampled_trajectory_record_words(grlx_ctx *ctx);      /* R = grlx_trajectory_record_words(ctx, 0) + 1; a negative status otherwise */
+int  grlx_evaluate_sampled_trajectory(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][state_dims]*/,
+                                      int n_starts, int max_steps, int sampler, double epsilon,
+                                      const uint64_t *streams /*[n_replicas][n_starts][2] or NULL*/, double *ret, double *disc,
+                                      int32_t *steps, int32_t *terminal, int32_t *ties, int32_t *explored, double *final_state,
+                                      uint64_t *streams_out /*[n_replicas][n_starts][2]*/,
+                                      double *records /*[n_replicas][n_starts][max_steps][R]*/);
+/* Host only, no context: out[n_pairs][2], the streams of the pairs first_pair ... first_pair + n_pairs - 1.  Stream k = 2 * pair + which
+ * is srand48(seed) advanced by k * 2^20 draws.  An episode draws at most one value per stream and step and 2^20 exceeds
+ * GRLX_MAX_EPISODE_STEPS, so the streams of different episodes are disjoint.  first_pair < 0 or out == NULL: nothing is written. */
+void grlx_episode_streams(long seed, int64_t first_pair, int64_t n_pairs, uint64_t *out /*[n_pairs][2]*/);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * The per-step plug-in interfaces on the replicas of a context: one call of the reference's interface for EVERY replica per
