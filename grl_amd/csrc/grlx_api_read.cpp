@@ -1,8 +1,9 @@
-// grlx_api_read.cpp -- the C ABI declared in include/grlx.h: the read side -- policy queries, greedy and sampled evaluation episodes, chunked over the caller's observations / start states.
+// grlx_api_read.cpp -- the C ABI declared in include/grlx.h: the read side -- policy queries, greedy, sampled and noisy evaluation episodes, chunked over the caller's observations / start states.
 #include "grlx_host.h"
 #include "grlx_query.h"
 #include "grlx_evaluate.h"
 #include "grlx_evaluate_sampled.h"
+#include "grlx_evaluate_noisy.h"
 
 // ------------------------------------------------------------------------------------------- policy queries ---
 namespace {
@@ -406,8 +407,8 @@ int grlx_evaluate_ensemble_trajectory(grlx_ctx *ctx, int first_replica, int n_re
 static int sampled_admit(grlx_ctx *ctx, const char *who, int n_replicas, int n_starts, int sampler, double epsilon, const uint64_t *streams)
 {
   if (!q_agent(ctx->cfg.agent))
-    return fail(GRLX_ERR_INVALID, "%s is not built for the actor-critic agent (its Gaussian / Ornstein-Uhlenbeck exploration needs the policy's noise state); "
-                "it serves agents with a policy/discrete/q", who);
+    return fail(GRLX_ERR_INVALID, "%s is not built for the actor-critic agent (its Gaussian / Ornstein-Uhlenbeck exploration needs the policy's noise state: "
+                "grlx_evaluate_noisy carries it); it serves agents with a policy/discrete/q", who);
   if (sampler != GRLX_SAMPLER_GREEDY && sampler != GRLX_SAMPLER_EPSILON_GREEDY)
     return fail(GRLX_ERR_INVALID, "%s: unknown sampler %d (GRLX_SAMPLER_GREEDY = 0, GRLX_SAMPLER_EPSILON_GREEDY = 1)", who, sampler);
   if (!std::isfinite(epsilon)) return fail(GRLX_ERR_INVALID, "%s: epsilon is not finite (%g)", who, epsilon);
@@ -515,6 +516,129 @@ void grlx_episode_streams(long seed, int64_t first_pair, int64_t n_pairs, uint64
     out[k] = x;
     x = (ja * x + jc) & kMask;
   }
+}
+
+// ---- noisy evaluation: the actor-critic's episodes under its exploration, on a stream and a noise state the episodes carry (grlx_evaluate_noisy.hip)
+// what both noisy evaluations check beyond evaluate_admit
+static int noisy_admit(grlx_ctx *ctx, const char *who, int n_replicas, int n_starts, double sigma, double theta, const uint64_t *streams, const double *noise)
+{
+  if (q_agent(ctx->cfg.agent))
+    return fail(GRLX_ERR_INVALID, "%s serves the actor-critic only (Gaussian / Ornstein-Uhlenbeck noise on a continuous action); the samplers of an agent with a "
+                "policy/discrete/q are grlx_evaluate_sampled's", who);
+  if (!std::isfinite(sigma)) return fail(GRLX_ERR_INVALID, "%s: sigma is not finite (%g)", who, sigma);
+  if (sigma != GRLX_SIGMA_OWN && !(sigma >= 0.)) return fail(GRLX_ERR_INVALID, "%s: sigma = %g is negative and is not GRLX_SIGMA_OWN (-1)", who, sigma);
+  if (!std::isfinite(theta)) return fail(GRLX_ERR_INVALID, "%s: theta is not finite (%g)", who, theta);
+  if (theta != GRLX_THETA_OWN && !(theta >= 0. && theta <= 1.))
+    return fail(GRLX_ERR_INVALID, "%s: theta = %g is outside [0, 1] and is not GRLX_THETA_OWN (-1)", who, theta);
+  for (int64_t row = 0; row < (int64_t)n_replicas * n_starts; ++row)
+  {
+    if (streams && streams[row] >> 48)
+      return fail(GRLX_ERR_INVALID, "%s: stream row %lld (replica %lld, start state %lld) is 0x%llx: a rand48 state is below 2^48", who, (long long)row,
+                  (long long)(row / n_starts), (long long)(row % n_starts), (unsigned long long)streams[row]);
+    if (noise && !std::isfinite(noise[row]))
+      return fail(GRLX_ERR_INVALID, "%s: noise row %lld (replica %lld, start state %lld) is not finite (%g)", who, (long long)row, (long long)(row / n_starts),
+                  (long long)(row % n_starts), noise[row]);
+  }
+  return GRLX_OK;
+}
+
+static int evaluate_noisy_impl(grlx_ctx *ctx, const char *who, bool trajectory, int first_replica, int n_replicas, const double *states, int n_starts,
+                               int max_steps, double sigma, double theta, const uint64_t *streams, const double *noise, double *ret, double *disc,
+                               int32_t *steps, int32_t *terminal, int32_t *clipped, double *final_state, uint64_t *streams_out, double *noise_out,
+                               double *records)
+{
+  int rc = evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps);
+  if (rc != GRLX_OK) return rc;
+  if (int bad = noisy_admit(ctx, who, n_replicas, n_starts, sigma, theta, streams, noise)) return bad;
+  const int S = ctx->S, R = trajectory ? noisy_trajectory_words(ctx->cfg.env) : 0;
+  const size_t per_pair = 2 * sizeof(double) + 3 * sizeof(int32_t) + sizeof(double) * (size_t)S + 4 * sizeof(uint64_t);     // the sums, stream and noise in and out
+  int chunk = 0;
+  if (trajectory)
+  {
+    rc = trajectory_admit(who, "grlx_evaluate_noisy", records, max_steps, n_replicas, n_starts, R, sizeof(double) * (size_t)S + per_pair * (size_t)n_replicas, &chunk);
+    if (rc != GRLX_OK) return rc;
+  }
+  else chunk = query_chunk(n_starts, sizeof(double) * (size_t)S + per_pair * (size_t)n_replicas);
+  if (max_steps == 0) max_steps = GRLX_MAX_EPISODE_STEPS;
+  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
+  if (theta == GRLX_THETA_OWN) theta = ctx->P.theta;
+  // the two 8-byte inputs of a pair travel as one 16-byte column of the staging skeleton: [replica][start]{stream, bits of the noise};
+  // an absent array is filled with what the kernel takes as its default (kNoisyOwnStream: the replica's own stream; +0.0)
+  std::vector<uint64_t> packed;
+  if (streams || noise)
+  {
+    const size_t rows = (size_t)n_replicas * (size_t)n_starts;
+    packed.resize(rows * 2);
+    for (size_t row = 0; row < rows; ++row)
+    {
+      packed[row * 2] = streams ? streams[row] : kNoisyOwnStream;
+      uint64_t bits = 0;
+      if (noise) memcpy(&bits, &noise[row], sizeof bits);
+      packed[row * 2 + 1] = bits;
+    }
+  }
+  DRAIN(ctx);
+  const size_t rec_elem = sizeof(double) * (size_t)R * (size_t)max_steps;
+  const ReadOut outs[9] = {{ret, sizeof(double), n_replicas, true}, {disc, sizeof(double), n_replicas, true}, {steps, sizeof(int32_t), n_replicas, true},
+                           {terminal, sizeof(int32_t), n_replicas, true}, {clipped, sizeof(int32_t), n_replicas, true},
+                           {final_state, sizeof(double) * (size_t)S, n_replicas, true}, {streams_out, sizeof(uint64_t), n_replicas, true},
+                           {noise_out, sizeof(double), n_replicas, true}, {records, rec_elem, n_replicas, true}};
+  DevBuf dinputs;
+  const ReadIn in_pairs = {packed.empty() ? nullptr : packed.data(), 2 * sizeof(uint64_t), n_replicas, &dinputs};
+  return chunked_read(ctx, outs, trajectory ? 9 : 8, n_starts, states, S, chunk, true, [&](int nc, const double *dst, const DevBuf *d) -> int {
+    NoisyArgs T;
+    EvaluateArgs &A = T.e;
+    A.first_replica = first_replica; A.n_replicas = n_replicas; A.n_starts = nc; A.max_steps = max_steps;
+    A.states = dst; A.sweep = ctx->sweep ? ctx->sweep_dev.get() : nullptr;
+    A.ret = d[0].as<double>(); A.disc = d[1].as<double>(); A.steps = d[2].as<int32_t>(); A.terminal = d[3].as<int32_t>(); A.ties = d[4].as<int32_t>();
+    A.final_state = d[5].as<double>();
+    T.sigma = sigma; T.theta = theta;
+    T.inputs = packed.empty() ? nullptr : dinputs.as<uint64_t>();
+    T.streams_out = d[6].as<uint64_t>(); T.noise_out = d[7].as<double>();
+    T.records = trajectory ? d[8].as<double>() : nullptr;
+    if (trajectory)
+    {
+      HIP_TRY(hipMemsetAsync(T.records, 0, rec_elem * (size_t)n_replicas * (size_t)nc, nullptr));     // records behind an episode's end are +0.0
+      HIP_TRY(launch_trajectory_noisy(ctx->P, T, nullptr));
+    }
+    else HIP_TRY(launch_evaluate_noisy(ctx->P, T, nullptr));
+    return GRLX_OK;
+  }, &in_pairs);
+}
+
+int grlx_evaluate_noisy(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, double sigma, double theta,
+                        const uint64_t *streams, const double *noise, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *clipped,
+                        double *final_state, uint64_t *streams_out, double *noise_out)
+{
+  return evaluate_noisy_impl(ctx, "grlx_evaluate_noisy", false, first_replica, n_replicas, states, n_starts, max_steps, sigma, theta, streams, noise, ret,
+                             disc, steps, terminal, clipped, final_state, streams_out, noise_out, nullptr);
+}
+
+int grlx_noisy_trajectory_record_words(grlx_ctx *ctx)
+{
+  if (!ctx) return fail(GRLX_ERR_INVALID, "bad argument");
+  const char *who = "grlx_noisy_trajectory_record_words";
+  if (ctx->cfg.env == GRLX_ENV_EXTERNAL || !evaluate_built(ctx->cfg.agent, ctx->cfg.env, ctx->P.A))
+    return fail(GRLX_ERR_INVALID, "%s: no evaluation episodes are built for this context (environment %d)", who, ctx->cfg.env);
+  if (q_agent(ctx->cfg.agent)) return fail(GRLX_ERR_INVALID, "%s: the noisy evaluation serves the actor-critic only", who);
+  return noisy_trajectory_words(ctx->cfg.env);
+}
+
+int grlx_evaluate_noisy_trajectory(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, double sigma,
+                                   double theta, const uint64_t *streams, const double *noise, double *ret, double *disc, int32_t *steps,
+                                   int32_t *terminal, int32_t *clipped, double *final_state, uint64_t *streams_out, double *noise_out, double *records)
+{
+  return evaluate_noisy_impl(ctx, "grlx_evaluate_noisy_trajectory", true, first_replica, n_replicas, states, n_starts, max_steps, sigma, theta, streams,
+                             noise, ret, disc, steps, terminal, clipped, final_state, streams_out, noise_out, records);
+}
+
+// host only: the even streams of grlx_episode_streams, one per pair
+void grlx_episode_stream_words(long seed, int64_t first_pair, int64_t n_pairs, uint64_t *out)
+{
+  if (!out || n_pairs <= 0 || first_pair < 0) return;
+  std::vector<uint64_t> both((size_t)n_pairs * 2);
+  grlx_episode_streams(seed, first_pair, n_pairs, both.data());
+  for (int64_t k = 0; k < n_pairs; ++k) out[k] = both[(size_t)k * 2];
 }
 
 } // extern "C"

@@ -18,6 +18,9 @@
 // -e EPSILON|own|greedy: with -E, also one SAMPLED episode per (clone, start state) with grlx_evaluate_sampled -- the epsilon-greedy sampler on
 // EPSILON in [0, 1] or on every clone's own decayed epsilon, or the greedy sampler with its drawn tie break -- on the streams of
 // grlx_episode_streams(-s seed), written to <output>-<run>-sampled.txt, and with -T the steps in <output>-<run>-sampled-trajectories.txt (objects.h),
+// -N SIGMA|own: with -E on an actor-critic, also one NOISY episode per (clone, start state) with grlx_evaluate_noisy -- the exploring policy on a
+// standard deviation SIGMA >= 0 or on every clone's own decayed sigma, on the configuration's theta -- on the streams of
+// grlx_episode_stream_words(-s seed), written to <output>-<run>-noisy.txt, and with -T the steps in <output>-<run>-noisy-trajectories.txt (objects.h),
 // -n: print the plan (one line per clone: i seed alpha gamma lambda epsilon) and exit before anything touches HIP, and
 // -g N: one process per GPU (rank r on the r-th visible device, started before anything touches HIP), every rank running -r replicas
 // (clones r * replicas ..., seeds and "@i" identities counted over the whole job), the learning curves reduced with one RCCL all-reduce
@@ -26,6 +29,7 @@
 #include <sys/wait.h>
 #include <unistd.h>
 
+#include <cmath>
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
@@ -81,9 +85,9 @@ int main(int argc, char **argv)
   int c;
   std::vector<std::string> sweep_args;
   std::string ensemble_arg;
-  bool ensemble = false, trajectory = false, sampled = false;
+  bool ensemble = false, trajectory = false, sampled = false, noisy = false;
   int trajectory_steps = 0;
-  while ((c = getopt(argc, argv, "vs:r:t:lqc:g:p:nk:K:Q:E:V:T:e:")) != -1)
+  while ((c = getopt(argc, argv, "vs:r:t:lqc:g:p:nk:K:Q:E:V:T:e:N:")) != -1)
   {
     switch (c)
     {
@@ -104,12 +108,13 @@ int main(int argc, char **argv)
       case 'V': ensemble_arg = optarg; ensemble = true; break;
       case 'T': trajectory_steps = atoi(optarg); trajectory = true; break;
       case 'e': opt.sampled_arg = optarg; sampled = true; break;
+      case 'N': opt.noisy_arg = optarg; noisy = true; break;
       default: return 1;
     }
   }
   if (optind > argc - 1)
   {
-    log(0, std::string("Usage: \n  ") + argv[0] + " [-v] [-s seed] [-r replicas] [-g gpus] [-t trials] [-l] [-q] [-p path=v1,v2,...]... [-n] [-k snapshot] [-K snapshot] [-Q observations] [-E states] [-V vote|mean] [-T steps] [-e epsilon|own|greedy] <yaml file> [yaml file...]");
+    log(0, std::string("Usage: \n  ") + argv[0] + " [-v] [-s seed] [-r replicas] [-g gpus] [-t trials] [-l] [-q] [-p path=v1,v2,...]... [-n] [-k snapshot] [-K snapshot] [-Q observations] [-E states] [-V vote|mean] [-T steps] [-e epsilon|own|greedy] [-N sigma|own] <yaml file> [yaml file...]");
     return 1;
   }
   if (opt.seed == 0)
@@ -194,6 +199,20 @@ int main(int argc, char **argv)
     if (gpus > 1) { log(0, "-e: a sampled policy evaluation runs on one GPU (-g " + std::to_string(gpus) + " is not built)"); return 1; }
     if ((sweep_args.empty() ? opt.replicas : opt.sweep_repetitions) < 2)
     { log(0, "-e: -E needs -r >= 2: the standard deviation over the clones divides by n - 1"); return 1; }
+  }
+  if (noisy)
+  { // -N needs -E's states and a standard deviation; what -E refuses is refused here under -N's name, before any process is forked or any device looked for
+    const std::string &arg = opt.noisy_arg;
+    char *stop = nullptr;
+    const double sigma = strtod(arg.c_str(), &stop);
+    if (arg == "own") opt.noisy_sigma = GRLX_SIGMA_OWN;
+    else if (!arg.empty() && *stop == 0 && std::isfinite(sigma) && sigma >= 0.) opt.noisy_sigma = sigma;
+    else { log(0, "-N: '" + arg + "' is neither a finite number >= 0 nor 'own' (every clone's decayed sigma)"); return 1; }
+    opt.noisy = true;
+    if (opt.evaluate_file.empty()) { log(0, "-N " + arg + ": a noisy evaluation needs the start states of -E <states file>"); return 1; }
+    if (gpus > 1) { log(0, "-N: a noisy policy evaluation runs on one GPU (-g " + std::to_string(gpus) + " is not built)"); return 1; }
+    if (!sweep_args.empty()) { log(0, "-N: a noisy evaluation is the actor-critic's, for which per-replica parameters (-p) are not built"); return 1; }
+    if (opt.replicas < 2) { log(0, "-N: -E needs -r >= 2: the standard deviation over the clones divides by n - 1"); return 1; }
   }
   if (!opt.evaluate_file.empty())
   { // likewise: the state file is read, and -g and -r 1 refused, before any process is forked or any device looked for

@@ -71,6 +71,16 @@ struct RunOptions {
   int sampled_sampler = -1;
   double sampled_epsilon = 0;
   std::string sampled_arg;
+  // `grlxd -E FILE -N <sigma | own>`: besides the unchanged returns file, one NOISY episode per (clone, start state) of an actor-critic with
+  // grlx_evaluate_noisy -- the exploring policy on a standard deviation >= 0 or on every clone's own decayed sigma, on the configuration's
+  // theta -- on the streams of grlx_episode_stream_words(-s seed, pair 0 ...), from a noise state of 0; rank 0 writes
+  // <output>-<run>-noisy.txt: per start state one line "mean sd mean_steps n0 n1 n2 n3 ties clipped", the returns file's columns (ties is
+  // 0: a continuous action has none) and the summed clipped steps.  With -T also <output>-<run>-noisy-trajectories.txt
+  // (grlx_evaluate_noisy_trajectory), the trajectories file's lines with two words more, the record's last: the noise state after the
+  // step, 1 where the step clipped.  noisy_sigma: the number, or GRLX_SIGMA_OWN.
+  bool noisy = false;
+  double noisy_sigma = 0;
+  std::string noisy_arg;
 };
 // ... the same for opt.evaluate_file -> opt.evaluate_states / _rows / _cols (messages begin with -E)
 void read_evaluate_file(RunOptions *opt);

@@ -262,7 +262,16 @@ RunPlan OnlineImpl::plan(const RunOptions &opt) const
     if (opt.world > 1) throw Exception(path() + ": -e: a sampled policy evaluation runs on one GPU (-g " + std::to_string(opt.world) + " is not built)");
     if (p.group < 2) throw Exception(path() + ": -e: -E needs -r >= 2: the standard deviation over the clones divides by n - 1");
     if (c.agent == GRLX_AGENT_AC)
-      throw Exception(path() + ": -e: a sampled evaluation is not built for the actor-critic agent (its Gaussian / Ornstein-Uhlenbeck exploration needs the policy's noise state)");
+      throw Exception(path() + ": -e: a sampled evaluation is not built for the actor-critic agent (its Gaussian / Ornstein-Uhlenbeck exploration needs the policy's noise state: -N <sigma | own> carries it)");
+  }
+  if (opt.noisy)
+  { // -N rides on -E: refused here with its own name, before -E's checks say the same without it
+    if (opt.evaluate_file.empty()) throw Exception(path() + ": -N: a noisy evaluation needs the start states of -E <states file>");
+    if (opt.world > 1) throw Exception(path() + ": -N: a noisy policy evaluation runs on one GPU (-g " + std::to_string(opt.world) + " is not built)");
+    if (p.sweep) throw Exception(path() + ": -N: a noisy evaluation is the actor-critic's, for which per-replica parameters (-p) are not built");
+    if (p.group < 2) throw Exception(path() + ": -N: -E needs -r >= 2: the standard deviation over the clones divides by n - 1");
+    if (c.agent != GRLX_AGENT_AC)
+      throw Exception(path() + ": -N: a noisy evaluation serves the actor-critic agent only; the samplers of an agent with a policy/discrete/q are -e <epsilon | own | greedy>'s");
   }
   p.evaluate = !opt.evaluate_file.empty();
   if (p.evaluate)
@@ -473,6 +482,7 @@ std::vector<double> OnlineImpl::run(const RunOptions &opt)
     write_ensemble_file(p, ctx, rr);
     write_trajectory_files(p, ctx, rr);
     write_sampled_files(p, ctx, rr);
+    write_noisy_files(p, ctx, rr);
     write_mean_file(p, ctx, rr, rows);
     if (save_every == "run" && !output.empty()) save_policy(p, ctx, output + "-run" + std::to_string(rr));      // online_learning.cpp:294-302
 

@@ -262,6 +262,58 @@ void OnlineImpl::write_sampled_files(const RunPlan &p, grlx_ctx *ctx, int run) c
   write_record_lines(ofs, records, tsteps, opt.replicas, NS, T, R);
 }
 
+// -E -N, <output>-<run>-noisy.txt: the returns file's start states of an actor-critic under its exploring policy (grlx_evaluate_noisy) on the
+// configuration's theta, the streams of grlx_episode_stream_words(-s seed) and a noise state of 0: the returns file's columns (ties: 0) and
+// the summed clipped steps; the statistics on the host, ascending clones.  With -T also <output>-<run>-noisy-trajectories.txt, the first
+// -T steps of noisy episodes on the same streams, step by step.
+void OnlineImpl::write_noisy_files(const RunPlan &p, grlx_ctx *ctx, int run) const
+{
+  const RunOptions &opt = *p.opt;
+  if (!p.evaluate || opt.rank != 0 || !opt.noisy) return;
+  const int G = p.group, groups = opt.replicas / G, NS = opt.evaluate_rows;
+  const size_t pairs = (size_t)opt.replicas * (size_t)NS;
+  std::vector<uint64_t> streams(pairs);
+  grlx_episode_stream_words(opt.seed, 0, (int64_t)pairs, streams.data());
+  std::vector<double> ret(pairs);
+  std::vector<int32_t> esteps(pairs), eterm(pairs), eclip(pairs);
+  check(grlx_evaluate_noisy(ctx, 0, opt.replicas, opt.evaluate_states.data(), NS, 0, opt.noisy_sigma, GRLX_THETA_OWN, streams.data(), nullptr, ret.data(),
+                            nullptr, esteps.data(), eterm.data(), eclip.data(), nullptr, nullptr, nullptr),
+        "-N " + opt.noisy_arg + ": ");
+  {
+    std::ofstream ofs(rules::output_name(output, run, false, 0, "-noisy"));
+    for (int g = 0; g < groups; ++g)
+      for (int s = 0; s < NS; ++s)
+      {
+        const size_t first = (size_t)g * (size_t)G * (size_t)NS + (size_t)s;      // clone k of the group: first + k * NS
+        double step_sum = 0;
+        long long codes[4] = {0, 0, 0, 0}, clipped_sum = 0;
+        for (int k = 0; k < G; ++k)
+        {
+          const size_t at = first + (size_t)k * (size_t)NS;
+          step_sum += (double)esteps[at];
+          codes[eterm[at] & 3]++;
+          clipped_sum += eclip[at];
+        }
+        double mean = 0, sd = 0;
+        rules::mean_sd_two_pass(ret.data() + first, G, (size_t)NS, &mean, &sd);
+        char line[416];
+        snprintf(line, sizeof(line), "%.17g %.17g %.17g %lld %lld %lld %lld %lld %lld", mean, sd, step_sum / G, codes[0], codes[1], codes[2], codes[3], 0ll,
+                 clipped_sum);
+        ofs << line << std::endl;
+      }
+  }
+  if (opt.trajectory_steps < 1) return;
+  const int T = opt.trajectory_steps, R = grlx_noisy_trajectory_record_words(ctx);
+  check(R < 0 ? R : GRLX_OK, "-N -T: ");
+  std::vector<double> records(pairs * (size_t)T * (size_t)R);
+  std::vector<int32_t> tsteps(pairs);
+  check(grlx_evaluate_noisy_trajectory(ctx, 0, opt.replicas, opt.evaluate_states.data(), NS, T, opt.noisy_sigma, GRLX_THETA_OWN, streams.data(), nullptr,
+                                       nullptr, nullptr, tsteps.data(), nullptr, nullptr, nullptr, nullptr, nullptr, records.data()),
+        "-N " + opt.noisy_arg + " -T " + std::to_string(T) + ": ");
+  std::ofstream ofs(rules::output_name(output, run, false, 0, "-noisy-trajectories"));
+  write_record_lines(ofs, records, tsteps, opt.replicas, NS, T, R);
+}
+
 // `grlxd -g N`, <output>-<run>-mean.txt: the learning curve over the clones of ALL ranks: per row {sum, sum of squares, count} of this
 // device's replicas (grlx_curve_stats, fixed reduction order), ONE all-reduce over the ranks, mean and standard deviation on rank 0.
 // (Trial-bounded runs write the same rows on every rank; a steps budget with more than one clone is refused by the plan.)

@@ -721,6 +721,80 @@ class Runner:
                                                              _ptr(out, C.c_uint64), _ptr(records, C.c_double)))
         return SampledTrajectory(ret, disc, steps, terminal, ties, explored, final_state, out, records)
 
+    # ---- noisy evaluation: the actor-critic's episodes under its exploration, on a stream and a noise state the episodes carry (grlx_evaluate_noisy)
+    def _noisy_args(self, states, sigma, theta, streams, noise, replicas):
+        if isinstance(sigma, str):
+            if sigma != "own":
+                raise ValueError('sigma: a number >= 0 or "own"')
+            sigma = capi.SIGMA_OWN
+        if isinstance(theta, str):
+            if theta != "own":
+                raise ValueError('theta: a number in [0, 1] or "own"')
+            theta = capi.THETA_OWN
+        states = np.ascontiguousarray(states, dtype=np.float64)
+        if states.ndim != 2 or states.shape[1] != self.state_dims:
+            raise ValueError(f"expected states of shape (n, {self.state_dims}), got {states.shape}")
+        first, count = self._replica_range(replicas)
+        n = states.shape[0]
+        if streams is not None:
+            streams = np.ascontiguousarray(streams, dtype=np.uint64)
+            if streams.shape != (count, n):
+                raise ValueError(f"expected streams of shape ({count}, {n}), got {streams.shape}")
+        if noise is not None:
+            noise = np.ascontiguousarray(noise, dtype=np.float64)
+            if noise.shape != (count, n):
+                raise ValueError(f"expected noise of shape ({count}, {n}), got {noise.shape}")
+        return states, float(sigma), float(theta), streams, noise, first, count, n
+
+    def evaluate_noisy(self, states, sigma="own", theta="own", streams=None, noise=None, replicas=None, max_steps=0):
+        """Runner.evaluate's episodes of the actor-critic acted by the policy that collects its data: the actor's read plus Gaussian /
+        Ornstein-Uhlenbeck noise, clipped to the action range.  sigma: a number >= 0 for every replica, or "own": the replica's decayed
+        sigma as it stands; theta: a number in [0, 1] (1 = independent Gaussian noise), or "own": the configuration's.
+        streams[replica][start]: the rand48 state every episode draws from, None = a copy of the replica's thread-local stream (see
+        episode_stream_words); noise[replica][start]: the noise state every episode starts on, None = 0.
+        NoisyEvaluation(ret, disc, steps, terminal, clipped, final_state, streams, noise): clipped = steps whose noisy action lay outside
+        the action range, streams / noise = both states after the last step.  The context is not changed (include/grlx.h:
+        grlx_evaluate_noisy)."""
+        states, sigma, theta, streams, noise, first, count, n = self._noisy_args(states, sigma, theta, streams, noise, replicas)
+        ret, disc = np.zeros((count, n), np.float64), np.zeros((count, n), np.float64)
+        steps, terminal, clipped = (np.zeros((count, n), np.int32) for _ in range(3))
+        final_state = np.zeros((count, n, self.state_dims), np.float64)
+        out, noise_out = np.zeros((count, n), np.uint64), np.zeros((count, n), np.float64)
+        capi.check(self.lib.grlx_evaluate_noisy(self._ctx, first, count, _ptr(states, C.c_double), n, int(max_steps), sigma, theta,
+                                                None if streams is None else _ptr(streams, C.c_uint64),
+                                                None if noise is None else _ptr(noise, C.c_double), _ptr(ret, C.c_double), _ptr(disc, C.c_double),
+                                                _ptr(steps, C.c_int32), _ptr(terminal, C.c_int32), _ptr(clipped, C.c_int32),
+                                                _ptr(final_state, C.c_double), _ptr(out, C.c_uint64), _ptr(noise_out, C.c_double)))
+        return NoisyEvaluation(ret, disc, steps, terminal, clipped, final_state, out, noise_out)
+
+    def noisy_trajectory_record_words(self):
+        """R of evaluate_noisy_trajectory's records: trajectory_record_words() + 2 (grlx_noisy_trajectory_record_words)"""
+        words = self.lib.grlx_noisy_trajectory_record_words(self._ctx)
+        if words < 0:
+            capi.check(words)
+        return words
+
+    def evaluate_noisy_trajectory(self, states, max_steps, sigma="own", theta="own", streams=None, noise=None, replicas=None):
+        """Runner.evaluate_noisy with every step of every episode: NoisyTrajectory(..., records), records[replica][start][max_steps][R]
+        with Trajectory's views -- .action the action that acted (noisy, clipped), .value the actor's read before noise and clip -- and
+        .noise (the noise state after the step) and .clipped (1.0 where the step clipped); the per-episode count is the field n_clipped
+        (include/grlx.h: grlx_evaluate_noisy_trajectory)."""
+        states, sigma, theta, streams, noise, first, count, n = self._noisy_args(states, sigma, theta, streams, noise, replicas)
+        max_steps = int(max_steps)
+        words = self.noisy_trajectory_record_words()
+        ret, disc = np.zeros((count, n), np.float64), np.zeros((count, n), np.float64)
+        steps, terminal, clipped = (np.zeros((count, n), np.int32) for _ in range(3))
+        final_state = np.zeros((count, n, self.state_dims), np.float64)
+        out, noise_out = np.zeros((count, n), np.uint64), np.zeros((count, n), np.float64)
+        records = np.zeros((count, n, max(max_steps, 0), words), np.float64)
+        capi.check(self.lib.grlx_evaluate_noisy_trajectory(self._ctx, first, count, _ptr(states, C.c_double), n, max_steps, sigma, theta,
+                                                           None if streams is None else _ptr(streams, C.c_uint64),
+                                                           None if noise is None else _ptr(noise, C.c_double), _ptr(ret, C.c_double),
+                                                           _ptr(disc, C.c_double), _ptr(steps, C.c_int32), _ptr(terminal, C.c_int32),
+                                                           _ptr(clipped, C.c_int32), _ptr(final_state, C.c_double), _ptr(out, C.c_uint64),
+                                                           _ptr(noise_out, C.c_double), _ptr(records, C.c_double)))
+        return NoisyTrajectory(ret, disc, steps, terminal, clipped, final_state, out, noise_out, records)
+
 
 Evaluation = collections.namedtuple("Evaluation", "ret disc steps terminal ties final_state")
 EnsembleEvaluation = collections.namedtuple("EnsembleEvaluation", "ret disc steps terminal ties member_ties agreement final_state")
@@ -786,6 +860,29 @@ def episode_streams(seed: int, n_replicas: int, n_starts: int, first_pair: int =
     2 * (first_pair + replica * n_starts + start) + which is srand48(seed) advanced by k * 2^20 draws, so no two episodes share a draw."""
     out = np.zeros((int(n_replicas), int(n_starts), 2), np.uint64)
     capi.load().grlx_episode_streams(int(seed), int(first_pair), out.shape[0] * out.shape[1], _ptr(out, C.c_uint64))
+    return out
+
+
+NoisyEvaluation = collections.namedtuple("NoisyEvaluation", "ret disc steps terminal clipped final_state streams noise")
+
+
+class NoisyTrajectory(_RecordViews, collections.namedtuple("NoisyTrajectory",
+                                                           "ret disc steps terminal n_clipped final_state streams final_noise records")):
+    """What Runner.evaluate_noisy_trajectory returns: NoisyEvaluation's fields and records[replica][start][max_steps][R], whose two last
+    words (after the model state) are the noise state after the step and whether the step clipped: the views .noise and .clipped, per step.
+    The per-episode count that NoisyEvaluation calls clipped is the field n_clipped here, its noise the field final_noise."""
+    __slots__ = ()
+    obs = property(lambda self: self._cut(self._OBS, self.records.shape[-1] - 2 - self.final_state.shape[-1]))
+    state = property(lambda self: self._cut(self.records.shape[-1] - 2 - self.final_state.shape[-1], self.records.shape[-1] - 2))
+    noise = property(lambda self: self._cut(self.records.shape[-1] - 2))
+    clipped = property(lambda self: self._cut(self.records.shape[-1] - 1))
+
+
+def episode_stream_words(seed: int, n_replicas: int, n_starts: int, first_pair: int = 0):
+    """streams[n_replicas][n_starts] for Runner.evaluate_noisy from one seed (grlx_episode_stream_words; host only): the even streams
+    of episode_streams, episode_streams(...)[..., 0] -- stream of pair p = srand48(seed) advanced by p * 2^21 draws."""
+    out = np.zeros((int(n_replicas), int(n_starts)), np.uint64)
+    capi.load().grlx_episode_stream_words(int(seed), int(first_pair), out.shape[0] * out.shape[1], _ptr(out, C.c_uint64))
     return out
 
 

@@ -588,8 +588,8 @@ int  grlx_evaluate_ensemble_trajectory(grlx_ctx *ctx, int first_replica, int n_r
  * Validated on the host before anything is launched (GRLX_ERR_INVALID, nothing written, the reason and the function named): everything
  * grlx_evaluate refuses; an unknown sampler; epsilon that is not finite; epsilon outside [0, 1] that is not exactly GRLX_EPSILON_OWN;
  * a stream word >= 2^48 (row and word named); the actor-critic ("not built": its Gaussian / Ornstein-Uhlenbeck exploration needs the
- * policy's noise state and is a follow-up).  n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
- * NOT BUILT: the actor-critic's exploration, a sampled ensemble (softmax(votes)), the tie-breaking draw of grlx_fqi_evaluate, the
+ * policy's noise state, which grlx_evaluate_noisy below carries).  n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
+ * NOT BUILT: a sampled ensemble (softmax(votes)), the tie-breaking draw of grlx_fqi_evaluate, the
  * decay at episode time 0. */
 enum { GRLX_SAMPLER_GREEDY = 0, GRLX_SAMPLER_EPSILON_GREEDY = 1 };
 #define GRLX_EPSILON_OWN (-1.0)
@@ -608,6 +608,62 @@ int  grlx_evaluate_sampled_trajectory(grlx_ctx *ctx, int first_replica, int n_re
  * is srand48(seed) advanced by k * 2^20 draws.  An episode draws at most one value per stream and step and 2^20 exceeds
  * GRLX_MAX_EPISODE_STEPS, so the streams of different episodes are disjoint.  first_pair < 0 or out == NULL: nothing is written. */
 void grlx_episode_streams(long seed, int64_t first_pair, int64_t n_pairs, uint64_t *out /*[n_pairs][2]*/);
+
+/* Noisy evaluation episodes: grlx_evaluate's episodes of the ACTOR-CRITIC acted by the policy that collects its data instead of the
+ * noise-free actor -- ActionPolicy::act(time, in, out) (action.cpp:127-158): the actor's read plus Gaussian or Ornstein-Uhlenbeck noise
+ * drawn by Box-Muller (Rand::getNormal, utils.h:120-125), clipped to the action range.  For every (replica, start state) pair one episode,
+ * on the device, in one launch per chunk; the loop, terminal, max_steps, the replica range, the staging and "changes nothing" are
+ * grlx_evaluate's.  What it answers: the return the learning policy gives up to its exploration at a sigma, how robust a learned actor is
+ * to action noise, a sweep over sigma from fixed start states without retraining.
+ *   State.      Every episode carries ONE rand48 state (the role of the thread-local stream) and ONE double (the noise state,
+ *               ActionPolicy::n_) in and out.  streams[n_replicas][n_starts] / noise[n_replicas][n_starts].
+ *               streams == NULL: every episode of replica r starts from a COPY of that replica's thread-local stream as it stands
+ *               (grlx_get_rng's word 1); the context's own stream does not move.  noise == NULL: 0.0 for every episode.
+ *               streams_out / noise_out [n_replicas][n_starts] receive both after the episode's last step; either may be NULL.
+ *               grlx_episode_stream_words (below) makes disjoint streams from one seed: an episode draws two values per step and
+ *               2^20 exceeds 2 * GRLX_MAX_EPISODE_STEPS.
+ *   A step.     u = the actor's read at the observation, clamped to the actor representation's output range (grlx_evaluate's).  If the
+ *               model time of the state acted on is 0, noise = 0.  If sg != 0: U1 = drand48, U2 = drand48 of the episode's stream,
+ *               nrm = sqrt(-2 * log(U1)) * cos(2 * pi * U2) * sg + 0, noise = (1 - theta) * noise + nrm, out = u + noise -- the
+ *               operations and their order are the rollout kernels', on the portable log and cos; otherwise out = u, nothing is drawn
+ *               and the noise state stays.  action = fmin(fmax(out, action_min), action_max); clipped++ where out lay outside.
+ *   sg          `sigma` (>= 0) for every replica, or with GRLX_SIGMA_OWN the product ac_decay * sigma as the rollout kernels form it:
+ *               the replica's current decay (ActionPolicy::decay_) times the configuration's sigma.  THE ONE DEVIATION, as under
+ *               GRLX_EPSILON_OWN: the decay is never advanced -- the reference decays once more at episode time 0.
+ *   theta       the caller's, in [0, 1] (1: independent Gaussian noise, 0: a running sum), or with GRLX_THETA_OWN the configuration's.
+ *   clipped     steps whose noisy action lay outside [action_min, action_max]
+ * ret, disc, steps, terminal, clipped: [n_replicas][n_starts]; final_state has [state_dims] more.  Host pointers; any output may be NULL.
+ * Consequences.  With sigma == 0 every output equals grlx_evaluate's, streams_out == streams and noise_out == noise wherever the start
+ * state's time is not 0.
+ *   Records.    grlx_evaluate_noisy_trajectory: records[pair][max_steps][R], R = grlx_noisy_trajectory_record_words(ctx) =
+ *               grlx_trajectory_record_words(ctx, 0) + 2.  Every word of grlx_evaluate_trajectory's actor-critic record keeps its index:
+ *               GRLX_TRAJ_ACTION is the action that ACTED (noisy, clipped), GRLX_TRAJ_VALUE the actor's read before noise and clip; the
+ *               two new last words are the noise state after the step (R - 2) and 1.0 where the step clipped (R - 1).  Records behind an
+ *               episode's end are zeros.  The staging rule and its refusal are the sibling's.
+ * Validated on the host before anything is launched (GRLX_ERR_INVALID, nothing written, the reason and the function named): everything
+ * grlx_evaluate refuses; a Q agent ("actor-critic only": grlx_evaluate_sampled serves those); sigma that is not finite, or negative and
+ * not exactly GRLX_SIGMA_OWN; theta that is not finite, or outside [0, 1] and not exactly GRLX_THETA_OWN; a stream word >= 2^48 (row
+ * named); a noise entry that is not finite (row named); for the trajectory call max_steps == 0 and a column beyond the staging bound.
+ * n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
+ * NOT BUILT: noise for the Q agents, a noisy actor-critic ensemble, the decay at episode time 0, per-dimension sigma / theta (actions
+ * here are one-dimensional). */
+#define GRLX_SIGMA_OWN (-1.0)
+#define GRLX_THETA_OWN (-1.0)
+int  grlx_evaluate_noisy(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][state_dims]*/, int n_starts,
+                         int max_steps, double sigma, double theta, const uint64_t *streams /*[n_replicas][n_starts] or NULL*/,
+                         const double *noise /*[n_replicas][n_starts] or NULL*/, double *ret, double *disc, int32_t *steps, int32_t *terminal,
+                         int32_t *clipped, double *final_state, uint64_t *streams_out /*[n_replicas][n_starts]*/,
+                         double *noise_out /*[n_replicas][n_starts]*/);
+int  grlx_noisy_trajectory_record_words(grlx_ctx *ctx);        /* R = grlx_trajectory_record_words(ctx, 0) + 2; a negative status otherwise */
+int  grlx_evaluate_noisy_trajectory(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][state_dims]*/,
+                                    int n_starts, int max_steps, double sigma, double theta,
+                                    const uint64_t *streams /*[n_replicas][n_starts] or NULL*/,
+                                    const double *noise /*[n_replicas][n_starts] or NULL*/, double *ret, double *disc, int32_t *steps,
+                                    int32_t *terminal, int32_t *clipped, double *final_state, uint64_t *streams_out, double *noise_out,
+                                    double *records /*[n_replicas][n_starts][max_steps][R]*/);
+/* Host only, no context: out[n_pairs], the EVEN streams of grlx_episode_streams -- stream 2 * pair of the seed, srand48(seed) advanced
+ * by pair * 2^21 draws -- one per pair, for calls whose episodes carry one stream.  first_pair < 0 or out == NULL: nothing is written. */
+void grlx_episode_stream_words(long seed, int64_t first_pair, int64_t n_pairs, uint64_t *out /*[n_pairs]*/);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * The per-step plug-in interfaces on the replicas of a context: one call of the reference's interface for EVERY replica per
