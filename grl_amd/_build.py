@@ -112,16 +112,17 @@ def _build_hip_object(hipcc, src, tmp, flags, verbose, report):
 # (outside the tree: $GRLX_OBJCACHE or /tmp/grlx_objcache), so that editing a unit of the C ABI does not recompile the kernels
 API_DEPS = ["grlx_host.h", "grlx_host_rules.h", "grlx_internal.h", "grlx_snapshot.h", "grlx_snapshot_format.h", "grlx_query.h", "grlx_evaluate.h", "grlx_evaluate_sampled.h", "grlx_evaluate_noisy.h", GRLX_H,
             os.path.join("..", "..", "include", "grlx_diag.h")]
+# what the three units of the evaluation episodes share; grlx_episode.h: their common device helpers and dispatch
+EVALUATE_DEPS = ["grlx_internal.h", "grlx_math.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_envs.h", "grlx_query_weights.h", "grlx_evaluate.h",
+                 "grlx_episode.h", GRLX_H]
 UNIT_DEPS = {
     "grlx_kernels.hip": HEADERS,
     "grlx_fqi.hip": ["grlx_internal.h", "grlx_math.h", "grlx_math_batch.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_envs.h", GRLX_H],
     "grlx_snapshot.hip": ["grlx_internal.h", "grlx_snapshot.h", "grlx_snapshot_format.h", GRLX_H],
     "grlx_query.hip": ["grlx_internal.h", "grlx_math.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_query.h", "grlx_query_weights.h", GRLX_H],
-    "grlx_evaluate.hip": ["grlx_internal.h", "grlx_math.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_envs.h", "grlx_query_weights.h", "grlx_evaluate.h", GRLX_H],
-    "grlx_evaluate_sampled.hip": ["grlx_internal.h", "grlx_math.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_envs.h", "grlx_query_weights.h", "grlx_evaluate.h",
-                                  "grlx_evaluate_sampled.h", GRLX_H],
-    "grlx_evaluate_noisy.hip": ["grlx_internal.h", "grlx_math.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_envs.h", "grlx_query_weights.h", "grlx_evaluate.h",
-                                "grlx_evaluate_noisy.h", GRLX_H],
+    "grlx_evaluate.hip": EVALUATE_DEPS,
+    "grlx_evaluate_sampled.hip": EVALUATE_DEPS + ["grlx_evaluate_sampled.h"],
+    "grlx_evaluate_noisy.hip": EVALUATE_DEPS + ["grlx_evaluate_noisy.h"],
     **{unit: API_DEPS for unit in API_UNITS},
     "grlx_snapshot_format.cpp": ["grlx_snapshot_format.h", GRLX_H],
     "grlx_plan.cpp": ["grlx_internal.h", GRLX_H],

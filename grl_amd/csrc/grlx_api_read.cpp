@@ -158,6 +158,206 @@ int query_q_impl(grlx_ctx *ctx, const char *who, int first_replica, int n_replic
   });
 }
 
+// ---- policy evaluation: greedy episodes from start states of the caller's choice (grlx_evaluate.hip) -----------------------------------
+// what both evaluations check before they touch the device
+int evaluate_admit(grlx_ctx *ctx, const char *who, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps)
+{
+  if (!ctx) return fail(GRLX_ERR_INVALID, "bad argument");
+  if (ctx->cfg.env == GRLX_ENV_EXTERNAL)
+    return fail(GRLX_ERR_INVALID, "%s: the context has no environment (GRLX_ENV_EXTERNAL): there is nothing to step", who);
+  if (ctx->P.tile_safe >= 1)
+    return fail(GRLX_ERR_INVALID, "%s is not built for projector/tile_coding:safe >= 1 (a read would have to walk the claim table without claiming)", who);
+  if (!evaluate_built(ctx->cfg.agent, ctx->cfg.env, ctx->P.A))
+    return fail(GRLX_ERR_INVALID, "%s is not built for environment %d with %d actions (Q agents: pendulum x {3, 5}, acrobot, cart-pole, walker x 3; actor-critic: cart-pole, pendulum)", who,
+                ctx->cfg.env, ctx->cfg.agent == GRLX_AGENT_AC ? 0 : ctx->P.A);
+  if (n_starts < 0) return fail(GRLX_ERR_INVALID, "%s: n_starts = %d", who, n_starts);
+  if (int rc = replica_range_ok(ctx, who, first_replica, n_replicas)) return rc;
+  if (!states) return fail(GRLX_ERR_INVALID, "%s: states is null", who);
+  if (max_steps < 0 || max_steps > GRLX_MAX_EPISODE_STEPS)
+    return fail(GRLX_ERR_INVALID, "%s: max_steps = %d is outside 1 ... GRLX_MAX_EPISODE_STEPS (%d; 0 = that cap)", who, max_steps, GRLX_MAX_EPISODE_STEPS);
+  const int S = ctx->S;
+  for (int s = 0; s < n_starts; ++s)
+    for (int i = 0; i < S; ++i)
+    { // below 2^17 the RK4 stages of one step stay inside the branch-free sine's domain (DESIGN.md section 8: the cart-pole's case)
+      const double v = states[(size_t)s * S + i];
+      if (!std::isfinite(v)) return fail(GRLX_ERR_INVALID, "%s: state row %d, component %d is not finite (%g)", who, s, i, v);
+      if (!(fabs(v) < 0x1p17)) return fail(GRLX_ERR_INVALID, "%s: state row %d, component %d (%g) is out of range: its magnitude reaches 2^17", who, s, i, v);
+    }
+  return GRLX_OK;
+}
+
+// what both ensemble evaluations check beyond evaluate_admit
+int ensemble_admit(grlx_ctx *ctx, const char *who, int n_replicas, int group_size, int rule)
+{
+  if (!q_agent(ctx->cfg.agent))
+    return fail(GRLX_ERR_INVALID, "%s is not built for the actor-critic agent (a vote over continuous actions is mapping/policy/multi's); it serves agents with a policy/discrete/q", who);
+  if (group_size < 1) return fail(GRLX_ERR_INVALID, "%s: group_size = %d is below 1", who, group_size);
+  if (n_replicas % group_size != 0) return fail(GRLX_ERR_INVALID, "%s: group_size %d does not divide the %d replicas", who, group_size, n_replicas);
+  if (rule != GRLX_ENSEMBLE_VOTE && rule != GRLX_ENSEMBLE_MEAN_Q)
+    return fail(GRLX_ERR_INVALID, "%s: unknown rule %d (GRLX_ENSEMBLE_VOTE = 0, GRLX_ENSEMBLE_MEAN_Q = 1)", who, rule);
+  return GRLX_OK;
+}
+
+// ---- per-step trajectories: the two evaluations with a record per step (grlx_evaluate.hip: trajectory_*_kernel) -----------------------------
+// What a trajectory call checks beyond its sibling, after the sibling's own checks; gives the start states per chunk.  `rows`: replicas or
+// groups; `in_and_sums`: a start state's other staged bytes (its state and its rows' sums).  Unlike the other reads a chunk never exceeds
+// the bound: the records are what the bound is for, so a column that does not fit is refused instead of staged as "at least one".
+int trajectory_admit(const char *who, const char *sibling, const void *records, int max_steps, int rows, int n_starts,
+                            int R, size_t in_and_sums, int *chunk)
+{
+  if (!records) return fail(GRLX_ERR_INVALID, "%s: records is null (for the sums alone call %s)", who, sibling);
+  if (max_steps == 0)
+    return fail(GRLX_ERR_INVALID, "%s: max_steps = 0: the records are sized by max_steps, so there is no default here (1 ... GRLX_MAX_EPISODE_STEPS = %d)", who,
+                GRLX_MAX_EPISODE_STEPS);
+  const uint64_t column = (uint64_t)rows * (uint64_t)max_steps * (uint64_t)R * sizeof(double);
+  if (column + in_and_sums > g_query_chunk_bytes)
+    return fail(GRLX_ERR_INVALID, "%s: one start state's column of records is %llu bytes (%d rows x %d steps x %d words x 8; %llu with its sums) and exceeds "
+                "the staging bound of %llu bytes: ask for fewer replicas per call, a smaller max_steps, or raise the bound with grlx_set_query_chunk_bytes", who,
+                (unsigned long long)column, rows, max_steps, R, (unsigned long long)(column + in_and_sums), (unsigned long long)g_query_chunk_bytes);
+  *chunk = rows ? query_chunk(n_starts, (size_t)column + in_and_sums) : n_starts;
+  return GRLX_OK;
+}
+
+// ---- sampled evaluation: the episodes of grlx_evaluate acted by the reference's samplers on streams the episodes carry (grlx_evaluate_sampled.hip)
+// what both sampled evaluations check beyond evaluate_admit
+int sampled_admit(grlx_ctx *ctx, const char *who, int n_replicas, int n_starts, int sampler, double epsilon, const uint64_t *streams)
+{
+  if (!q_agent(ctx->cfg.agent))
+    return fail(GRLX_ERR_INVALID, "%s is not built for the actor-critic agent (its Gaussian / Ornstein-Uhlenbeck exploration needs the policy's noise state: "
+                "grlx_evaluate_noisy carries it); it serves agents with a policy/discrete/q", who);
+  if (sampler != GRLX_SAMPLER_GREEDY && sampler != GRLX_SAMPLER_EPSILON_GREEDY)
+    return fail(GRLX_ERR_INVALID, "%s: unknown sampler %d (GRLX_SAMPLER_GREEDY = 0, GRLX_SAMPLER_EPSILON_GREEDY = 1)", who, sampler);
+  if (!std::isfinite(epsilon)) return fail(GRLX_ERR_INVALID, "%s: epsilon is not finite (%g)", who, epsilon);
+  if (epsilon != GRLX_EPSILON_OWN && !(epsilon >= 0. && epsilon <= 1.))
+    return fail(GRLX_ERR_INVALID, "%s: epsilon = %g is outside [0, 1] and is not GRLX_EPSILON_OWN (-1)", who, epsilon);
+  if (streams)
+    for (int64_t row = 0; row < (int64_t)n_replicas * n_starts; ++row)
+      for (int w = 0; w < 2; ++w)
+        if (streams[row * 2 + w] >> 48)
+          return fail(GRLX_ERR_INVALID, "%s: stream row %lld (replica %lld, start state %lld), word %d is 0x%llx: a rand48 state is below 2^48", who,
+                      (long long)row, (long long)(row / n_starts), (long long)(row % n_starts), w, (unsigned long long)streams[row * 2 + w]);
+  return GRLX_OK;
+}
+
+// ---- noisy evaluation: the actor-critic's episodes under its exploration, on a stream and a noise state the episodes carry (grlx_evaluate_noisy.hip)
+// what both noisy evaluations check beyond evaluate_admit
+int noisy_admit(grlx_ctx *ctx, const char *who, int n_replicas, int n_starts, double sigma, double theta, const uint64_t *streams, const double *noise)
+{
+  if (q_agent(ctx->cfg.agent))
+    return fail(GRLX_ERR_INVALID, "%s serves the actor-critic only (Gaussian / Ornstein-Uhlenbeck noise on a continuous action); the samplers of an agent with a "
+                "policy/discrete/q are grlx_evaluate_sampled's", who);
+  if (!std::isfinite(sigma)) return fail(GRLX_ERR_INVALID, "%s: sigma is not finite (%g)", who, sigma);
+  if (sigma != GRLX_SIGMA_OWN && !(sigma >= 0.)) return fail(GRLX_ERR_INVALID, "%s: sigma = %g is negative and is not GRLX_SIGMA_OWN (-1)", who, sigma);
+  if (!std::isfinite(theta)) return fail(GRLX_ERR_INVALID, "%s: theta is not finite (%g)", who, theta);
+  if (theta != GRLX_THETA_OWN && !(theta >= 0. && theta <= 1.))
+    return fail(GRLX_ERR_INVALID, "%s: theta = %g is outside [0, 1] and is not GRLX_THETA_OWN (-1)", who, theta);
+  for (int64_t row = 0; row < (int64_t)n_replicas * n_starts; ++row)
+  {
+    if (streams && streams[row] >> 48)
+      return fail(GRLX_ERR_INVALID, "%s: stream row %lld (replica %lld, start state %lld) is 0x%llx: a rand48 state is below 2^48", who, (long long)row,
+                  (long long)(row / n_starts), (long long)(row % n_starts), (unsigned long long)streams[row]);
+    if (noise && !std::isfinite(noise[row]))
+      return fail(GRLX_ERR_INVALID, "%s: noise row %lld (replica %lld, start state %lld) is not finite (%g)", who, (long long)row, (long long)(row / n_starts),
+                  (long long)(row % n_starts), noise[row]);
+  }
+  return GRLX_OK;
+}
+
+// ---- one description of an episode call: what the evaluation entry points share around their launch -----------------------------------------
+// Every variant has the six base outputs -- ret, disc, steps, terminal, ties (the noisy variant: clipped) and final_state -- for `rows`
+// replicas or groups, up to two outputs of its own, and, as a trajectory, the records.  An entry point fills this in and keeps its admit
+// and its launch.
+struct EpisodeCall {
+  const char   *who;
+  int           first_replica, n_replicas;
+  int           group_size;                 // 0: an episode per replica; else per group of this many (one block per pair: the grid's bound)
+  const double *states;
+  int           n_starts, max_steps;
+  double       *ret, *disc;
+  int32_t      *steps, *terminal, *ties;
+  double       *final_state;
+  ReadOut       extra[2];                   // the variant's own outputs: host and elem; the rows are filled in here
+  int           n_extra;
+  size_t        extra_bytes;                // per pair, what the variant stages beyond the six outputs: part of what cuts the chunks
+  const ReadIn *in;                         // the variant's second input, or null
+  // trajectory calls only: the call that gives the sums alone (named in a refusal), the caller's records, R of an environment's record
+  const char   *sibling;
+  double       *records;
+  int         (*record_words)(int env);
+};
+constexpr int kBaseOuts = 6;
+
+// the ReadOut rows of a call: the six, the variant's own, the records (rec_elem bytes per pair; 0: none)
+int episode_outs(const EpisodeCall &c, int rows, int S, size_t rec_elem, ReadOut *outs)
+{
+  const ReadOut base[kBaseOuts] = {{c.ret, sizeof(double), rows, true}, {c.disc, sizeof(double), rows, true}, {c.steps, sizeof(int32_t), rows, true},
+                                   {c.terminal, sizeof(int32_t), rows, true}, {c.ties, sizeof(int32_t), rows, true},
+                                   {c.final_state, sizeof(double) * (size_t)S, rows, true}};
+  int n = 0;
+  for (const ReadOut &o : base) outs[n++] = o;
+  for (int k = 0; k < c.n_extra; ++k) outs[n++] = {c.extra[k].host, c.extra[k].elem, rows, true};
+  if (rec_elem) outs[n++] = {c.records, rec_elem, rows, true};
+  return n;
+}
+
+// the base fields of a chunk's argument block (EvaluateArgs, EnsembleArgs: the same member names) for nc start states at dst
+template <class Args>
+void episode_args(Args &A, grlx_ctx *ctx, const EpisodeCall &c, int max_steps, int nc, const double *dst, const DevBuf *d)
+{
+  A.first_replica = c.first_replica; A.n_replicas = c.n_replicas; A.n_starts = nc; A.max_steps = max_steps;
+  A.states = dst; A.sweep = ctx->sweep ? ctx->sweep_dev.get() : nullptr;
+  A.ret = d[0].as<double>(); A.disc = d[1].as<double>(); A.steps = d[2].as<int32_t>(); A.terminal = d[3].as<int32_t>(); A.ties = d[4].as<int32_t>();
+  A.final_state = d[5].as<double>();
+}
+
+// The path of every evaluation call.  admit(): the variant's checks, after evaluate_admit's.  launch(A, extra, records): the variant's
+// kernels on a chunk -- A with its base fields filled, the device arrays of c.extra, the chunk's zero-filled records (null: no trajectory).
+template <class Args, class Admit, class Launch>
+int episode_read(grlx_ctx *ctx, const EpisodeCall &c, Admit admit, Launch launch)
+{
+  int max_steps = c.max_steps;
+  if (int rc = evaluate_admit(ctx, c.who, c.first_replica, c.n_replicas, c.states, c.n_starts, max_steps)) return rc;
+  if (int rc = admit()) return rc;
+  const int S = ctx->S, rows = c.group_size ? c.n_replicas / c.group_size : c.n_replicas, R = c.sibling ? c.record_words(ctx->cfg.env) : 0;
+  const size_t per_pair = 2 * sizeof(double) + 3 * sizeof(int32_t) + sizeof(double) * (size_t)S + c.extra_bytes;
+  const size_t in_and_sums = sizeof(double) * (size_t)S + per_pair * (size_t)rows;
+  int chunk = 0;
+  if (c.sibling)
+  {
+    if (int rc = trajectory_admit(c.who, c.sibling, c.records, max_steps, rows, c.n_starts, R, in_and_sums, &chunk)) return rc;
+  }
+  else chunk = query_chunk(c.n_starts, in_and_sums);
+  if (max_steps == 0) max_steps = GRLX_MAX_EPISODE_STEPS;
+  if (c.n_starts == 0 || c.n_replicas == 0) return GRLX_OK;
+  DRAIN(ctx);
+  if (c.group_size && (int64_t)chunk * rows > 0x7fffffff) chunk = 0x7fffffff / rows;
+  const size_t rec_elem = sizeof(double) * (size_t)R * (size_t)max_steps;
+  ReadOut outs[kMaxReadOuts];
+  const int n_outs = episode_outs(c, rows, S, rec_elem, outs);
+  return chunked_read(ctx, outs, n_outs, c.n_starts, c.states, S, chunk, true, [&](int nc, const double *dst, const DevBuf *d) -> int {
+    Args A{};
+    episode_args(A, ctx, c, max_steps, nc, dst, d);
+    double *records = rec_elem ? d[n_outs - 1].as<double>() : nullptr;
+    if (records) HIP_TRY(hipMemsetAsync(records, 0, rec_elem * (size_t)rows * (size_t)nc, nullptr));     // records behind an episode's end are +0.0
+    HIP_TRY(launch(A, d + kBaseOuts, records));
+    return GRLX_OK;
+  }, c.in);
+}
+
+// what the *_record_words calls check; wrong_agent(ctx): the variant does not serve the context's agent, `why` says so
+int record_words_admit(grlx_ctx *ctx, const char *who, bool (*wrong_agent)(grlx_ctx *), const char *why)
+{
+  if (!ctx) return fail(GRLX_ERR_INVALID, "bad argument");
+  if (ctx->cfg.env == GRLX_ENV_EXTERNAL || !evaluate_built(ctx->cfg.agent, ctx->cfg.env, ctx->P.A))
+    return fail(GRLX_ERR_INVALID, "%s: no evaluation episodes are built for this context (environment %d)", who, ctx->cfg.env);
+  if (wrong_agent && wrong_agent(ctx)) return fail(GRLX_ERR_INVALID, "%s: %s", who, why);
+  return GRLX_OK;
+}
+bool is_ac(grlx_ctx *ctx) { return !q_agent(ctx->cfg.agent); }
+bool is_q(grlx_ctx *ctx) { return q_agent(ctx->cfg.agent); }
+int greedy_words(int env) { return trajectory_words(env, false); }
+int ensemble_words(int env) { return trajectory_words(env, true); }
+
 } // namespace
 extern "C" {
 
@@ -211,280 +411,105 @@ int grlx_query_state(grlx_ctx *ctx, int table, int first_replica, int n_replicas
   });
 }
 
-// ---- policy evaluation: greedy episodes from start states of the caller's choice (grlx_evaluate.hip) -----------------------------------
-// what both evaluations check before they touch the device
-static int evaluate_admit(grlx_ctx *ctx, const char *who, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps)
+// ---- policy evaluation: greedy episodes, per replica or per group of replicas on their vote or mean Q, with or without a record per step ---
+// (grlx_evaluate.hip); records null: the sums alone
+static int evaluate_impl(grlx_ctx *ctx, const char *who, const char *sibling, int first_replica, int n_replicas, const double *states, int n_starts,
+                         int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state, double *records)
 {
-  if (!ctx) return fail(GRLX_ERR_INVALID, "bad argument");
-  if (ctx->cfg.env == GRLX_ENV_EXTERNAL)
-    return fail(GRLX_ERR_INVALID, "%s: the context has no environment (GRLX_ENV_EXTERNAL): there is nothing to step", who);
-  if (ctx->P.tile_safe >= 1)
-    return fail(GRLX_ERR_INVALID, "%s is not built for projector/tile_coding:safe >= 1 (a read would have to walk the claim table without claiming)", who);
-  if (!evaluate_built(ctx->cfg.agent, ctx->cfg.env, ctx->P.A))
-    return fail(GRLX_ERR_INVALID, "%s is not built for environment %d with %d actions (Q agents: pendulum x {3, 5}, acrobot, cart-pole, walker x 3; actor-critic: cart-pole, pendulum)", who,
-                ctx->cfg.env, ctx->cfg.agent == GRLX_AGENT_AC ? 0 : ctx->P.A);
-  if (n_starts < 0) return fail(GRLX_ERR_INVALID, "%s: n_starts = %d", who, n_starts);
-  if (int rc = replica_range_ok(ctx, who, first_replica, n_replicas)) return rc;
-  if (!states) return fail(GRLX_ERR_INVALID, "%s: states is null", who);
-  if (max_steps < 0 || max_steps > GRLX_MAX_EPISODE_STEPS)
-    return fail(GRLX_ERR_INVALID, "%s: max_steps = %d is outside 1 ... GRLX_MAX_EPISODE_STEPS (%d; 0 = that cap)", who, max_steps, GRLX_MAX_EPISODE_STEPS);
-  const int S = ctx->S;
-  for (int s = 0; s < n_starts; ++s)
-    for (int i = 0; i < S; ++i)
-    { // below 2^17 the RK4 stages of one step stay inside the branch-free sine's domain (DESIGN.md section 8: the cart-pole's case)
-      const double v = states[(size_t)s * S + i];
-      if (!std::isfinite(v)) return fail(GRLX_ERR_INVALID, "%s: state row %d, component %d is not finite (%g)", who, s, i, v);
-      if (!(fabs(v) < 0x1p17)) return fail(GRLX_ERR_INVALID, "%s: state row %d, component %d (%g) is out of range: its magnitude reaches 2^17", who, s, i, v);
-    }
-  return GRLX_OK;
+  EpisodeCall c{who, first_replica, n_replicas, 0, states, n_starts, max_steps, ret, disc, steps, terminal, ties, final_state};
+  c.sibling = sibling; c.records = records; c.record_words = greedy_words;
+  return episode_read<EvaluateArgs>(ctx, c, [] { return GRLX_OK; }, [&](EvaluateArgs &A, const DevBuf *, double *rec) {
+    return rec ? launch_trajectory(ctx->P, TrajectoryArgs{A, rec}, nullptr) : launch_evaluate(ctx->P, A, nullptr);
+  });
 }
 
-// what both ensemble evaluations check beyond evaluate_admit
-static int ensemble_admit(grlx_ctx *ctx, const char *who, int n_replicas, int group_size, int rule)
+static int evaluate_ensemble_impl(grlx_ctx *ctx, const char *who, const char *sibling, int first_replica, int n_replicas, int group_size, int rule,
+                                  const double *states, int n_starts, int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal,
+                                  int32_t *ties, int64_t *member_ties, int64_t *agreement, double *final_state, double *records)
 {
-  if (!q_agent(ctx->cfg.agent))
-    return fail(GRLX_ERR_INVALID, "%s is not built for the actor-critic agent (a vote over continuous actions is mapping/policy/multi's); it serves agents with a policy/discrete/q", who);
-  if (group_size < 1) return fail(GRLX_ERR_INVALID, "%s: group_size = %d is below 1", who, group_size);
-  if (n_replicas % group_size != 0) return fail(GRLX_ERR_INVALID, "%s: group_size %d does not divide the %d replicas", who, group_size, n_replicas);
-  if (rule != GRLX_ENSEMBLE_VOTE && rule != GRLX_ENSEMBLE_MEAN_Q)
-    return fail(GRLX_ERR_INVALID, "%s: unknown rule %d (GRLX_ENSEMBLE_VOTE = 0, GRLX_ENSEMBLE_MEAN_Q = 1)", who, rule);
-  return GRLX_OK;
+  EpisodeCall c{who, first_replica, n_replicas, group_size, states, n_starts, max_steps, ret, disc, steps, terminal, ties, final_state};
+  c.extra[0] = {member_ties, sizeof(int64_t)}; c.extra[1] = {agreement, sizeof(int64_t)}; c.n_extra = 2;
+  c.extra_bytes = 2 * sizeof(int64_t);
+  c.sibling = sibling; c.records = records; c.record_words = ensemble_words;
+  return episode_read<EnsembleArgs>(ctx, c, [&] { return ensemble_admit(ctx, who, n_replicas, group_size, rule); },
+                                    [&](EnsembleArgs &A, const DevBuf *extra, double *rec) {
+    A.group_size = group_size; A.rule = rule;
+    A.member_ties = extra[0].as<int64_t>(); A.agreement = extra[1].as<int64_t>();
+    return rec ? launch_trajectory_ensemble(ctx->P, EnsembleTrajectoryArgs{A, rec}, nullptr) : launch_evaluate_ensemble(ctx->P, A, nullptr);
+  });
 }
 
 int grlx_evaluate(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, double *ret, double *disc,
                   int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state)
 {
-  int rc = evaluate_admit(ctx, "grlx_evaluate", first_replica, n_replicas, states, n_starts, max_steps);
-  if (rc != GRLX_OK) return rc;
-  if (max_steps == 0) max_steps = GRLX_MAX_EPISODE_STEPS;
-  const int S = ctx->S;
-  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
-  DRAIN(ctx);
-  const size_t per_pair = 2 * sizeof(double) + 3 * sizeof(int32_t) + sizeof(double) * (size_t)S;
-  const int chunk = query_chunk(n_starts, sizeof(double) * (size_t)S + per_pair * (size_t)n_replicas);
-  const ReadOut outs[6] = {{ret, sizeof(double), n_replicas, true}, {disc, sizeof(double), n_replicas, true}, {steps, sizeof(int32_t), n_replicas, true},
-                           {terminal, sizeof(int32_t), n_replicas, true}, {ties, sizeof(int32_t), n_replicas, true},
-                           {final_state, sizeof(double) * (size_t)S, n_replicas, true}};
-  return chunked_read(ctx, outs, 6, n_starts, states, S, chunk, true, [&](int nc, const double *dst, const DevBuf *d) -> int {
-    EvaluateArgs A;
-    A.first_replica = first_replica; A.n_replicas = n_replicas; A.n_starts = nc; A.max_steps = max_steps;
-    A.states = dst; A.sweep = ctx->sweep ? ctx->sweep_dev.get() : nullptr;
-    A.ret = d[0].as<double>(); A.disc = d[1].as<double>(); A.steps = d[2].as<int32_t>(); A.terminal = d[3].as<int32_t>(); A.ties = d[4].as<int32_t>();
-    A.final_state = d[5].as<double>();
-    HIP_TRY(launch_evaluate(ctx->P, A, nullptr));
-    return GRLX_OK;
-  });
+  return evaluate_impl(ctx, "grlx_evaluate", nullptr, first_replica, n_replicas, states, n_starts, max_steps, ret, disc, steps, terminal, ties, final_state,
+                       nullptr);
 }
 
-// ---- ensemble evaluation: one episode per (group of consecutive replicas, start state) on the group's vote or mean Q ----------------------
 int grlx_evaluate_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule, const double *states, int n_starts,
                            int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, int64_t *member_ties,
                            int64_t *agreement, double *final_state)
 {
-  const char *who = "grlx_evaluate_ensemble";
-  int rc = evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps);
-  if (rc != GRLX_OK) return rc;
-  if (int bad = ensemble_admit(ctx, who, n_replicas, group_size, rule)) return bad;
-  if (max_steps == 0) max_steps = GRLX_MAX_EPISODE_STEPS;
-  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
-  DRAIN(ctx);
-  const int S = ctx->S, n_groups = n_replicas / group_size;
-  const size_t per_pair = 2 * sizeof(double) + 3 * sizeof(int32_t) + 2 * sizeof(int64_t) + sizeof(double) * (size_t)S;
-  int chunk = query_chunk(n_starts, sizeof(double) * (size_t)S + per_pair * (size_t)n_groups);
-  if ((int64_t)chunk * n_groups > 0x7fffffff) chunk = 0x7fffffff / n_groups;      // one block per pair: the grid's bound
-  const ReadOut outs[8] = {{ret, sizeof(double), n_groups, true}, {disc, sizeof(double), n_groups, true}, {steps, sizeof(int32_t), n_groups, true},
-                           {terminal, sizeof(int32_t), n_groups, true}, {ties, sizeof(int32_t), n_groups, true}, {member_ties, sizeof(int64_t), n_groups, true},
-                           {agreement, sizeof(int64_t), n_groups, true}, {final_state, sizeof(double) * (size_t)S, n_groups, true}};
-  return chunked_read(ctx, outs, 8, n_starts, states, S, chunk, true, [&](int nc, const double *dst, const DevBuf *d) -> int {
-    EnsembleArgs A;
-    A.first_replica = first_replica; A.n_replicas = n_replicas; A.group_size = group_size; A.rule = rule;
-    A.n_starts = nc; A.max_steps = max_steps; A.states = dst; A.sweep = ctx->sweep ? ctx->sweep_dev.get() : nullptr;
-    A.ret = d[0].as<double>(); A.disc = d[1].as<double>(); A.steps = d[2].as<int32_t>(); A.terminal = d[3].as<int32_t>(); A.ties = d[4].as<int32_t>();
-    A.member_ties = d[5].as<int64_t>(); A.agreement = d[6].as<int64_t>(); A.final_state = d[7].as<double>();
-    HIP_TRY(launch_evaluate_ensemble(ctx->P, A, nullptr));
-    return GRLX_OK;
-  });
-}
-
-// ---- per-step trajectories: the two evaluations with a record per step (grlx_evaluate.hip: trajectory_*_kernel) -----------------------------
-// What a trajectory call checks beyond its sibling, after the sibling's own checks; gives the start states per chunk.  `rows`: replicas or
-// groups; `in_and_sums`: a start state's other staged bytes (its state and its rows' sums).  Unlike the other reads a chunk never exceeds
-// the bound: the records are what the bound is for, so a column that does not fit is refused instead of staged as "at least one".
-static int trajectory_admit(const char *who, const char *sibling, const void *records, int max_steps, int rows, int n_starts,
-                            int R, size_t in_and_sums, int *chunk)
-{
-  if (!records) return fail(GRLX_ERR_INVALID, "%s: records is null (for the sums alone call %s)", who, sibling);
-  if (max_steps == 0)
-    return fail(GRLX_ERR_INVALID, "%s: max_steps = 0: the records are sized by max_steps, so there is no default here (1 ... GRLX_MAX_EPISODE_STEPS = %d)", who,
-                GRLX_MAX_EPISODE_STEPS);
-  const uint64_t column = (uint64_t)rows * (uint64_t)max_steps * (uint64_t)R * sizeof(double);
-  if (column + in_and_sums > g_query_chunk_bytes)
-    return fail(GRLX_ERR_INVALID, "%s: one start state's column of records is %llu bytes (%d rows x %d steps x %d words x 8; %llu with its sums) and exceeds "
-                "the staging bound of %llu bytes: ask for fewer replicas per call, a smaller max_steps, or raise the bound with grlx_set_query_chunk_bytes", who,
-                (unsigned long long)column, rows, max_steps, R, (unsigned long long)(column + in_and_sums), (unsigned long long)g_query_chunk_bytes);
-  *chunk = rows ? query_chunk(n_starts, (size_t)column + in_and_sums) : n_starts;
-  return GRLX_OK;
+  return evaluate_ensemble_impl(ctx, "grlx_evaluate_ensemble", nullptr, first_replica, n_replicas, group_size, rule, states, n_starts, max_steps, ret, disc,
+                                steps, terminal, ties, member_ties, agreement, final_state, nullptr);
 }
 
 int grlx_trajectory_record_words(grlx_ctx *ctx, int ensemble)
 {
-  if (!ctx) return fail(GRLX_ERR_INVALID, "bad argument");
-  const char *who = "grlx_trajectory_record_words";
-  if (ctx->cfg.env == GRLX_ENV_EXTERNAL || !evaluate_built(ctx->cfg.agent, ctx->cfg.env, ctx->P.A))
-    return fail(GRLX_ERR_INVALID, "%s: no evaluation episodes are built for this context (environment %d)", who, ctx->cfg.env);
-  if (ensemble && !q_agent(ctx->cfg.agent)) return fail(GRLX_ERR_INVALID, "%s: the ensemble evaluation is not built for the actor-critic agent", who);
+  if (int rc = record_words_admit(ctx, "grlx_trajectory_record_words", ensemble ? is_ac : nullptr, "the ensemble evaluation is not built for the actor-critic agent"))
+    return rc;
   return trajectory_words(ctx->cfg.env, ensemble != 0);
 }
 
 int grlx_evaluate_trajectory(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, double *ret,
                              double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state, double *records)
 {
-  const char *who = "grlx_evaluate_trajectory";
-  int rc = evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps);
-  if (rc != GRLX_OK) return rc;
-  const int S = ctx->S, R = trajectory_words(ctx->cfg.env, false);
-  const size_t per_pair = 2 * sizeof(double) + 3 * sizeof(int32_t) + sizeof(double) * (size_t)S;
-  int chunk = 0;
-  rc = trajectory_admit(who, "grlx_evaluate", records, max_steps, n_replicas, n_starts, R, sizeof(double) * (size_t)S + per_pair * (size_t)n_replicas, &chunk);
-  if (rc != GRLX_OK) return rc;
-  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
-  DRAIN(ctx);
-  const size_t rec_elem = sizeof(double) * (size_t)R * (size_t)max_steps;
-  const ReadOut outs[7] = {{ret, sizeof(double), n_replicas, true}, {disc, sizeof(double), n_replicas, true}, {steps, sizeof(int32_t), n_replicas, true},
-                           {terminal, sizeof(int32_t), n_replicas, true}, {ties, sizeof(int32_t), n_replicas, true},
-                           {final_state, sizeof(double) * (size_t)S, n_replicas, true}, {records, rec_elem, n_replicas, true}};
-  return chunked_read(ctx, outs, 7, n_starts, states, S, chunk, true, [&](int nc, const double *dst, const DevBuf *d) -> int {
-    TrajectoryArgs T;
-    EvaluateArgs &A = T.e;
-    A.first_replica = first_replica; A.n_replicas = n_replicas; A.n_starts = nc; A.max_steps = max_steps;
-    A.states = dst; A.sweep = ctx->sweep ? ctx->sweep_dev.get() : nullptr;
-    A.ret = d[0].as<double>(); A.disc = d[1].as<double>(); A.steps = d[2].as<int32_t>(); A.terminal = d[3].as<int32_t>(); A.ties = d[4].as<int32_t>();
-    A.final_state = d[5].as<double>();
-    T.records = d[6].as<double>();
-    HIP_TRY(hipMemsetAsync(T.records, 0, rec_elem * (size_t)n_replicas * (size_t)nc, nullptr));     // records behind an episode's end are +0.0
-    HIP_TRY(launch_trajectory(ctx->P, T, nullptr));
-    return GRLX_OK;
-  });
+  return evaluate_impl(ctx, "grlx_evaluate_trajectory", "grlx_evaluate", first_replica, n_replicas, states, n_starts, max_steps, ret, disc, steps, terminal,
+                       ties, final_state, records);
 }
 
 int grlx_evaluate_ensemble_trajectory(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule, const double *states, int n_starts,
                                       int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, int64_t *member_ties,
                                       int64_t *agreement, double *final_state, double *records)
 {
-  const char *who = "grlx_evaluate_ensemble_trajectory";
-  int rc = evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps);
-  if (rc != GRLX_OK) return rc;
-  if (int bad = ensemble_admit(ctx, who, n_replicas, group_size, rule)) return bad;
-  const int S = ctx->S, n_groups = n_replicas / group_size, R = trajectory_words(ctx->cfg.env, true);
-  const size_t per_pair = 2 * sizeof(double) + 3 * sizeof(int32_t) + 2 * sizeof(int64_t) + sizeof(double) * (size_t)S;
-  int chunk = 0;
-  rc = trajectory_admit(who, "grlx_evaluate_ensemble", records, max_steps, n_groups, n_starts, R, sizeof(double) * (size_t)S + per_pair * (size_t)n_groups, &chunk);
-  if (rc != GRLX_OK) return rc;
-  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
-  DRAIN(ctx);
-  if ((int64_t)chunk * n_groups > 0x7fffffff) chunk = 0x7fffffff / n_groups;      // one block per pair: the grid's bound
-  const size_t rec_elem = sizeof(double) * (size_t)R * (size_t)max_steps;
-  const ReadOut outs[9] = {{ret, sizeof(double), n_groups, true}, {disc, sizeof(double), n_groups, true}, {steps, sizeof(int32_t), n_groups, true},
-                           {terminal, sizeof(int32_t), n_groups, true}, {ties, sizeof(int32_t), n_groups, true}, {member_ties, sizeof(int64_t), n_groups, true},
-                           {agreement, sizeof(int64_t), n_groups, true}, {final_state, sizeof(double) * (size_t)S, n_groups, true},
-                           {records, rec_elem, n_groups, true}};
-  return chunked_read(ctx, outs, 9, n_starts, states, S, chunk, true, [&](int nc, const double *dst, const DevBuf *d) -> int {
-    EnsembleTrajectoryArgs T;
-    EnsembleArgs &A = T.e;
-    A.first_replica = first_replica; A.n_replicas = n_replicas; A.group_size = group_size; A.rule = rule;
-    A.n_starts = nc; A.max_steps = max_steps; A.states = dst; A.sweep = ctx->sweep ? ctx->sweep_dev.get() : nullptr;
-    A.ret = d[0].as<double>(); A.disc = d[1].as<double>(); A.steps = d[2].as<int32_t>(); A.terminal = d[3].as<int32_t>(); A.ties = d[4].as<int32_t>();
-    A.member_ties = d[5].as<int64_t>(); A.agreement = d[6].as<int64_t>(); A.final_state = d[7].as<double>();
-    T.records = d[8].as<double>();
-    HIP_TRY(hipMemsetAsync(T.records, 0, rec_elem * (size_t)n_groups * (size_t)nc, nullptr));
-    HIP_TRY(launch_trajectory_ensemble(ctx->P, T, nullptr));
-    return GRLX_OK;
-  });
+  return evaluate_ensemble_impl(ctx, "grlx_evaluate_ensemble_trajectory", "grlx_evaluate_ensemble", first_replica, n_replicas, group_size, rule, states,
+                                n_starts, max_steps, ret, disc, steps, terminal, ties, member_ties, agreement, final_state, records);
 }
 
-// ---- sampled evaluation: the episodes of grlx_evaluate acted by the reference's samplers on streams the episodes carry (grlx_evaluate_sampled.hip)
-// what both sampled evaluations check beyond evaluate_admit
-static int sampled_admit(grlx_ctx *ctx, const char *who, int n_replicas, int n_starts, int sampler, double epsilon, const uint64_t *streams)
-{
-  if (!q_agent(ctx->cfg.agent))
-    return fail(GRLX_ERR_INVALID, "%s is not built for the actor-critic agent (its Gaussian / Ornstein-Uhlenbeck exploration needs the policy's noise state: "
-                "grlx_evaluate_noisy carries it); it serves agents with a policy/discrete/q", who);
-  if (sampler != GRLX_SAMPLER_GREEDY && sampler != GRLX_SAMPLER_EPSILON_GREEDY)
-    return fail(GRLX_ERR_INVALID, "%s: unknown sampler %d (GRLX_SAMPLER_GREEDY = 0, GRLX_SAMPLER_EPSILON_GREEDY = 1)", who, sampler);
-  if (!std::isfinite(epsilon)) return fail(GRLX_ERR_INVALID, "%s: epsilon is not finite (%g)", who, epsilon);
-  if (epsilon != GRLX_EPSILON_OWN && !(epsilon >= 0. && epsilon <= 1.))
-    return fail(GRLX_ERR_INVALID, "%s: epsilon = %g is outside [0, 1] and is not GRLX_EPSILON_OWN (-1)", who, epsilon);
-  if (streams)
-    for (int64_t row = 0; row < (int64_t)n_replicas * n_starts; ++row)
-      for (int w = 0; w < 2; ++w)
-        if (streams[row * 2 + w] >> 48)
-          return fail(GRLX_ERR_INVALID, "%s: stream row %lld (replica %lld, start state %lld), word %d is 0x%llx: a rand48 state is below 2^48", who,
-                      (long long)row, (long long)(row / n_starts), (long long)(row % n_starts), w, (unsigned long long)streams[row * 2 + w]);
-  return GRLX_OK;
-}
-
-static int evaluate_sampled_impl(grlx_ctx *ctx, const char *who, bool trajectory, int first_replica, int n_replicas, const double *states, int n_starts,
+// ---- sampled evaluation (grlx_evaluate_sampled.hip); sibling null: the sums alone
+static int evaluate_sampled_impl(grlx_ctx *ctx, const char *who, const char *sibling, int first_replica, int n_replicas, const double *states, int n_starts,
                                  int max_steps, int sampler, double epsilon, const uint64_t *streams, double *ret, double *disc, int32_t *steps,
                                  int32_t *terminal, int32_t *ties, int32_t *explored, double *final_state, uint64_t *streams_out, double *records)
 {
-  int rc = evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps);
-  if (rc != GRLX_OK) return rc;
-  if (int bad = sampled_admit(ctx, who, n_replicas, n_starts, sampler, epsilon, streams)) return bad;
-  const int S = ctx->S, R = trajectory ? sampled_trajectory_words(ctx->cfg.env) : 0;
-  const size_t per_pair = 2 * sizeof(double) + 4 * sizeof(int32_t) + sizeof(double) * (size_t)S + 4 * sizeof(uint64_t);     // the sums, both streams in and out
-  int chunk = 0;
-  if (trajectory)
-  {
-    rc = trajectory_admit(who, "grlx_evaluate_sampled", records, max_steps, n_replicas, n_starts, R, sizeof(double) * (size_t)S + per_pair * (size_t)n_replicas, &chunk);
-    if (rc != GRLX_OK) return rc;
-  }
-  else chunk = query_chunk(n_starts, sizeof(double) * (size_t)S + per_pair * (size_t)n_replicas);
-  if (max_steps == 0) max_steps = GRLX_MAX_EPISODE_STEPS;
-  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
-  DRAIN(ctx);
-  const size_t rec_elem = sizeof(double) * (size_t)R * (size_t)max_steps;
-  const ReadOut outs[9] = {{ret, sizeof(double), n_replicas, true}, {disc, sizeof(double), n_replicas, true}, {steps, sizeof(int32_t), n_replicas, true},
-                           {terminal, sizeof(int32_t), n_replicas, true}, {ties, sizeof(int32_t), n_replicas, true},
-                           {final_state, sizeof(double) * (size_t)S, n_replicas, true}, {explored, sizeof(int32_t), n_replicas, true},
-                           {streams_out, 2 * sizeof(uint64_t), n_replicas, true}, {records, rec_elem, n_replicas, true}};
   DevBuf dstreams;
   const ReadIn in_streams = {streams, 2 * sizeof(uint64_t), n_replicas, &dstreams};     // [replica][start][2]: a chunk is strided, not contiguous
-  return chunked_read(ctx, outs, trajectory ? 9 : 8, n_starts, states, S, chunk, true, [&](int nc, const double *dst, const DevBuf *d) -> int {
+  EpisodeCall c{who, first_replica, n_replicas, 0, states, n_starts, max_steps, ret, disc, steps, terminal, ties, final_state};
+  c.extra[0] = {explored, sizeof(int32_t)}; c.extra[1] = {streams_out, 2 * sizeof(uint64_t)}; c.n_extra = 2;
+  c.extra_bytes = sizeof(int32_t) + 4 * sizeof(uint64_t);     // explored, both streams in and out
+  c.in = &in_streams;
+  c.sibling = sibling; c.records = records; c.record_words = sampled_trajectory_words;
+  return episode_read<EvaluateArgs>(ctx, c, [&] { return sampled_admit(ctx, who, n_replicas, n_starts, sampler, epsilon, streams); },
+                                    [&](EvaluateArgs &A, const DevBuf *extra, double *rec) {
     SampledArgs T;
-    EvaluateArgs &A = T.e;
-    A.first_replica = first_replica; A.n_replicas = n_replicas; A.n_starts = nc; A.max_steps = max_steps;
-    A.states = dst; A.sweep = ctx->sweep ? ctx->sweep_dev.get() : nullptr;
-    A.ret = d[0].as<double>(); A.disc = d[1].as<double>(); A.steps = d[2].as<int32_t>(); A.terminal = d[3].as<int32_t>(); A.ties = d[4].as<int32_t>();
-    A.final_state = d[5].as<double>();
-    T.sampler = sampler; T.epsilon = epsilon;
+    T.e = A; T.sampler = sampler; T.epsilon = epsilon;
     T.streams = streams ? dstreams.as<uint64_t>() : nullptr;
-    T.explored = d[6].as<int32_t>(); T.streams_out = d[7].as<uint64_t>();
-    T.records = trajectory ? d[8].as<double>() : nullptr;
-    if (trajectory)
-    {
-      HIP_TRY(hipMemsetAsync(T.records, 0, rec_elem * (size_t)n_replicas * (size_t)nc, nullptr));     // records behind an episode's end are +0.0
-      HIP_TRY(launch_trajectory_sampled(ctx->P, T, nullptr));
-    }
-    else HIP_TRY(launch_evaluate_sampled(ctx->P, T, nullptr));
-    return GRLX_OK;
-  }, &in_streams);
+    T.explored = extra[0].as<int32_t>(); T.streams_out = extra[1].as<uint64_t>();
+    T.records = rec;
+    return rec ? launch_trajectory_sampled(ctx->P, T, nullptr) : launch_evaluate_sampled(ctx->P, T, nullptr);
+  });
 }
 
 int grlx_evaluate_sampled(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, int sampler, double epsilon,
                           const uint64_t *streams, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, int32_t *explored,
                           double *final_state, uint64_t *streams_out)
 {
-  return evaluate_sampled_impl(ctx, "grlx_evaluate_sampled", false, first_replica, n_replicas, states, n_starts, max_steps, sampler, epsilon, streams, ret,
+  return evaluate_sampled_impl(ctx, "grlx_evaluate_sampled", nullptr, first_replica, n_replicas, states, n_starts, max_steps, sampler, epsilon, streams, ret,
                                disc, steps, terminal, ties, explored, final_state, streams_out, nullptr);
 }
 
 int grlx_sampled_trajectory_record_words(grlx_ctx *ctx)
 {
-  if (!ctx) return fail(GRLX_ERR_INVALID, "bad argument");
-  const char *who = "grlx_sampled_trajectory_record_words";
-  if (ctx->cfg.env == GRLX_ENV_EXTERNAL || !evaluate_built(ctx->cfg.agent, ctx->cfg.env, ctx->P.A))
-    return fail(GRLX_ERR_INVALID, "%s: no evaluation episodes are built for this context (environment %d)", who, ctx->cfg.env);
-  if (!q_agent(ctx->cfg.agent)) return fail(GRLX_ERR_INVALID, "%s: the sampled evaluation is not built for the actor-critic agent", who);
+  if (int rc = record_words_admit(ctx, "grlx_sampled_trajectory_record_words", is_ac, "the sampled evaluation is not built for the actor-critic agent")) return rc;
   return sampled_trajectory_words(ctx->cfg.env);
 }
 
@@ -492,8 +517,73 @@ int grlx_evaluate_sampled_trajectory(grlx_ctx *ctx, int first_replica, int n_rep
                                      double epsilon, const uint64_t *streams, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
                                      int32_t *explored, double *final_state, uint64_t *streams_out, double *records)
 {
-  return evaluate_sampled_impl(ctx, "grlx_evaluate_sampled_trajectory", true, first_replica, n_replicas, states, n_starts, max_steps, sampler, epsilon,
-                               streams, ret, disc, steps, terminal, ties, explored, final_state, streams_out, records);
+  return evaluate_sampled_impl(ctx, "grlx_evaluate_sampled_trajectory", "grlx_evaluate_sampled", first_replica, n_replicas, states, n_starts, max_steps,
+                               sampler, epsilon, streams, ret, disc, steps, terminal, ties, explored, final_state, streams_out, records);
+}
+
+// ---- noisy evaluation (grlx_evaluate_noisy.hip); sibling null: the sums alone
+static int evaluate_noisy_impl(grlx_ctx *ctx, const char *who, const char *sibling, int first_replica, int n_replicas, const double *states, int n_starts,
+                               int max_steps, double sigma, double theta, const uint64_t *streams, const double *noise, double *ret, double *disc,
+                               int32_t *steps, int32_t *terminal, int32_t *clipped, double *final_state, uint64_t *streams_out, double *noise_out,
+                               double *records)
+{
+  // the two 8-byte inputs of a pair travel as one 16-byte column of the staging skeleton: [replica][start]{stream, bits of the noise};
+  // an absent array is filled with what the kernel takes as its default (kNoisyOwnStream: the replica's own stream; +0.0)
+  std::vector<uint64_t> packed;
+  DevBuf dinputs;
+  ReadIn in_pairs = {nullptr, 2 * sizeof(uint64_t), n_replicas, &dinputs};
+  EpisodeCall c{who, first_replica, n_replicas, 0, states, n_starts, max_steps, ret, disc, steps, terminal, clipped, final_state};
+  c.extra[0] = {streams_out, sizeof(uint64_t)}; c.extra[1] = {noise_out, sizeof(double)}; c.n_extra = 2;
+  c.extra_bytes = 4 * sizeof(uint64_t);     // stream and noise in and out
+  c.in = &in_pairs;
+  c.sibling = sibling; c.records = records; c.record_words = noisy_trajectory_words;
+  return episode_read<EvaluateArgs>(ctx, c, [&]() -> int {
+    if (int rc = noisy_admit(ctx, who, n_replicas, n_starts, sigma, theta, streams, noise)) return rc;
+    if (theta == GRLX_THETA_OWN) theta = ctx->P.theta;
+    if (streams || noise)
+    {
+      const size_t rows = (size_t)n_replicas * (size_t)n_starts;
+      packed.resize(rows * 2);
+      for (size_t row = 0; row < rows; ++row)
+      {
+        packed[row * 2] = streams ? streams[row] : kNoisyOwnStream;
+        uint64_t bits = 0;
+        if (noise) memcpy(&bits, &noise[row], sizeof bits);
+        packed[row * 2 + 1] = bits;
+      }
+    }
+    in_pairs.host = packed.empty() ? nullptr : packed.data();
+    return GRLX_OK;
+  }, [&](EvaluateArgs &A, const DevBuf *extra, double *rec) {
+    NoisyArgs T;
+    T.e = A; T.sigma = sigma; T.theta = theta;
+    T.inputs = packed.empty() ? nullptr : dinputs.as<uint64_t>();
+    T.streams_out = extra[0].as<uint64_t>(); T.noise_out = extra[1].as<double>();
+    T.records = rec;
+    return rec ? launch_trajectory_noisy(ctx->P, T, nullptr) : launch_evaluate_noisy(ctx->P, T, nullptr);
+  });
+}
+
+int grlx_evaluate_noisy(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, double sigma, double theta,
+                        const uint64_t *streams, const double *noise, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *clipped,
+                        double *final_state, uint64_t *streams_out, double *noise_out)
+{
+  return evaluate_noisy_impl(ctx, "grlx_evaluate_noisy", nullptr, first_replica, n_replicas, states, n_starts, max_steps, sigma, theta, streams, noise, ret,
+                             disc, steps, terminal, clipped, final_state, streams_out, noise_out, nullptr);
+}
+
+int grlx_noisy_trajectory_record_words(grlx_ctx *ctx)
+{
+  if (int rc = record_words_admit(ctx, "grlx_noisy_trajectory_record_words", is_q, "the noisy evaluation serves the actor-critic only")) return rc;
+  return noisy_trajectory_words(ctx->cfg.env);
+}
+
+int grlx_evaluate_noisy_trajectory(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, double sigma,
+                                   double theta, const uint64_t *streams, const double *noise, double *ret, double *disc, int32_t *steps,
+                                   int32_t *terminal, int32_t *clipped, double *final_state, uint64_t *streams_out, double *noise_out, double *records)
+{
+  return evaluate_noisy_impl(ctx, "grlx_evaluate_noisy_trajectory", "grlx_evaluate_noisy", first_replica, n_replicas, states, n_starts, max_steps, sigma,
+                             theta, streams, noise, ret, disc, steps, terminal, clipped, final_state, streams_out, noise_out, records);
 }
 
 // host only: stream k = srand48(seed) advanced by k * 2^20 draws, k = 2 * pair + which
@@ -516,120 +606,6 @@ void grlx_episode_streams(long seed, int64_t first_pair, int64_t n_pairs, uint64
     out[k] = x;
     x = (ja * x + jc) & kMask;
   }
-}
-
-// ---- noisy evaluation: the actor-critic's episodes under its exploration, on a stream and a noise state the episodes carry (grlx_evaluate_noisy.hip)
-// what both noisy evaluations check beyond evaluate_admit
-static int noisy_admit(grlx_ctx *ctx, const char *who, int n_replicas, int n_starts, double sigma, double theta, const uint64_t *streams, const double *noise)
-{
-  if (q_agent(ctx->cfg.agent))
-    return fail(GRLX_ERR_INVALID, "%s serves the actor-critic only (Gaussian / Ornstein-Uhlenbeck noise on a continuous action); the samplers of an agent with a "
-                "policy/discrete/q are grlx_evaluate_sampled's", who);
-  if (!std::isfinite(sigma)) return fail(GRLX_ERR_INVALID, "%s: sigma is not finite (%g)", who, sigma);
-  if (sigma != GRLX_SIGMA_OWN && !(sigma >= 0.)) return fail(GRLX_ERR_INVALID, "%s: sigma = %g is negative and is not GRLX_SIGMA_OWN (-1)", who, sigma);
-  if (!std::isfinite(theta)) return fail(GRLX_ERR_INVALID, "%s: theta is not finite (%g)", who, theta);
-  if (theta != GRLX_THETA_OWN && !(theta >= 0. && theta <= 1.))
-    return fail(GRLX_ERR_INVALID, "%s: theta = %g is outside [0, 1] and is not GRLX_THETA_OWN (-1)", who, theta);
-  for (int64_t row = 0; row < (int64_t)n_replicas * n_starts; ++row)
-  {
-    if (streams && streams[row] >> 48)
-      return fail(GRLX_ERR_INVALID, "%s: stream row %lld (replica %lld, start state %lld) is 0x%llx: a rand48 state is below 2^48", who, (long long)row,
-                  (long long)(row / n_starts), (long long)(row % n_starts), (unsigned long long)streams[row]);
-    if (noise && !std::isfinite(noise[row]))
-      return fail(GRLX_ERR_INVALID, "%s: noise row %lld (replica %lld, start state %lld) is not finite (%g)", who, (long long)row, (long long)(row / n_starts),
-                  (long long)(row % n_starts), noise[row]);
-  }
-  return GRLX_OK;
-}
-
-static int evaluate_noisy_impl(grlx_ctx *ctx, const char *who, bool trajectory, int first_replica, int n_replicas, const double *states, int n_starts,
-                               int max_steps, double sigma, double theta, const uint64_t *streams, const double *noise, double *ret, double *disc,
-                               int32_t *steps, int32_t *terminal, int32_t *clipped, double *final_state, uint64_t *streams_out, double *noise_out,
-                               double *records)
-{
-  int rc = evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps);
-  if (rc != GRLX_OK) return rc;
-  if (int bad = noisy_admit(ctx, who, n_replicas, n_starts, sigma, theta, streams, noise)) return bad;
-  const int S = ctx->S, R = trajectory ? noisy_trajectory_words(ctx->cfg.env) : 0;
-  const size_t per_pair = 2 * sizeof(double) + 3 * sizeof(int32_t) + sizeof(double) * (size_t)S + 4 * sizeof(uint64_t);     // the sums, stream and noise in and out
-  int chunk = 0;
-  if (trajectory)
-  {
-    rc = trajectory_admit(who, "grlx_evaluate_noisy", records, max_steps, n_replicas, n_starts, R, sizeof(double) * (size_t)S + per_pair * (size_t)n_replicas, &chunk);
-    if (rc != GRLX_OK) return rc;
-  }
-  else chunk = query_chunk(n_starts, sizeof(double) * (size_t)S + per_pair * (size_t)n_replicas);
-  if (max_steps == 0) max_steps = GRLX_MAX_EPISODE_STEPS;
-  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
-  if (theta == GRLX_THETA_OWN) theta = ctx->P.theta;
-  // the two 8-byte inputs of a pair travel as one 16-byte column of the staging skeleton: [replica][start]{stream, bits of the noise};
-  // an absent array is filled with what the kernel takes as its default (kNoisyOwnStream: the replica's own stream; +0.0)
-  std::vector<uint64_t> packed;
-  if (streams || noise)
-  {
-    const size_t rows = (size_t)n_replicas * (size_t)n_starts;
-    packed.resize(rows * 2);
-    for (size_t row = 0; row < rows; ++row)
-    {
-      packed[row * 2] = streams ? streams[row] : kNoisyOwnStream;
-      uint64_t bits = 0;
-      if (noise) memcpy(&bits, &noise[row], sizeof bits);
-      packed[row * 2 + 1] = bits;
-    }
-  }
-  DRAIN(ctx);
-  const size_t rec_elem = sizeof(double) * (size_t)R * (size_t)max_steps;
-  const ReadOut outs[9] = {{ret, sizeof(double), n_replicas, true}, {disc, sizeof(double), n_replicas, true}, {steps, sizeof(int32_t), n_replicas, true},
-                           {terminal, sizeof(int32_t), n_replicas, true}, {clipped, sizeof(int32_t), n_replicas, true},
-                           {final_state, sizeof(double) * (size_t)S, n_replicas, true}, {streams_out, sizeof(uint64_t), n_replicas, true},
-                           {noise_out, sizeof(double), n_replicas, true}, {records, rec_elem, n_replicas, true}};
-  DevBuf dinputs;
-  const ReadIn in_pairs = {packed.empty() ? nullptr : packed.data(), 2 * sizeof(uint64_t), n_replicas, &dinputs};
-  return chunked_read(ctx, outs, trajectory ? 9 : 8, n_starts, states, S, chunk, true, [&](int nc, const double *dst, const DevBuf *d) -> int {
-    NoisyArgs T;
-    EvaluateArgs &A = T.e;
-    A.first_replica = first_replica; A.n_replicas = n_replicas; A.n_starts = nc; A.max_steps = max_steps;
-    A.states = dst; A.sweep = ctx->sweep ? ctx->sweep_dev.get() : nullptr;
-    A.ret = d[0].as<double>(); A.disc = d[1].as<double>(); A.steps = d[2].as<int32_t>(); A.terminal = d[3].as<int32_t>(); A.ties = d[4].as<int32_t>();
-    A.final_state = d[5].as<double>();
-    T.sigma = sigma; T.theta = theta;
-    T.inputs = packed.empty() ? nullptr : dinputs.as<uint64_t>();
-    T.streams_out = d[6].as<uint64_t>(); T.noise_out = d[7].as<double>();
-    T.records = trajectory ? d[8].as<double>() : nullptr;
-    if (trajectory)
-    {
-      HIP_TRY(hipMemsetAsync(T.records, 0, rec_elem * (size_t)n_replicas * (size_t)nc, nullptr));     // records behind an episode's end are +0.0
-      HIP_TRY(launch_trajectory_noisy(ctx->P, T, nullptr));
-    }
-    else HIP_TRY(launch_evaluate_noisy(ctx->P, T, nullptr));
-    return GRLX_OK;
-  }, &in_pairs);
-}
-
-int grlx_evaluate_noisy(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, double sigma, double theta,
-                        const uint64_t *streams, const double *noise, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *clipped,
-                        double *final_state, uint64_t *streams_out, double *noise_out)
-{
-  return evaluate_noisy_impl(ctx, "grlx_evaluate_noisy", false, first_replica, n_replicas, states, n_starts, max_steps, sigma, theta, streams, noise, ret,
-                             disc, steps, terminal, clipped, final_state, streams_out, noise_out, nullptr);
-}
-
-int grlx_noisy_trajectory_record_words(grlx_ctx *ctx)
-{
-  if (!ctx) return fail(GRLX_ERR_INVALID, "bad argument");
-  const char *who = "grlx_noisy_trajectory_record_words";
-  if (ctx->cfg.env == GRLX_ENV_EXTERNAL || !evaluate_built(ctx->cfg.agent, ctx->cfg.env, ctx->P.A))
-    return fail(GRLX_ERR_INVALID, "%s: no evaluation episodes are built for this context (environment %d)", who, ctx->cfg.env);
-  if (q_agent(ctx->cfg.agent)) return fail(GRLX_ERR_INVALID, "%s: the noisy evaluation serves the actor-critic only", who);
-  return noisy_trajectory_words(ctx->cfg.env);
-}
-
-int grlx_evaluate_noisy_trajectory(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, double sigma,
-                                   double theta, const uint64_t *streams, const double *noise, double *ret, double *disc, int32_t *steps,
-                                   int32_t *terminal, int32_t *clipped, double *final_state, uint64_t *streams_out, double *noise_out, double *records)
-{
-  return evaluate_noisy_impl(ctx, "grlx_evaluate_noisy_trajectory", true, first_replica, n_replicas, states, n_starts, max_steps, sigma, theta, streams,
-                             noise, ret, disc, steps, terminal, clipped, final_state, streams_out, noise_out, records);
 }
 
 // host only: the even streams of grlx_episode_streams, one per pair

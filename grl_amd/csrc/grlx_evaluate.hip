@@ -26,6 +26,10 @@
 // trajectory_q_kernel, trajectory_ac_kernel, trajectory_ensemble_kernel (grlx_evaluate_trajectory, grlx_evaluate_ensemble_trajectory): the
 // same episodes with one record per step taken, in kernels of their own below the three above, which they leave as they are.
 //
+// The step's helpers (the probes, the reads, findmax, the bookkeeping, the head of a record) and the dispatch over the instantiations
+// live in grlx_episode.h, which the units of the evaluation variants share.  evaluate_q_kernel, evaluate_ac_kernel and
+// trajectory_ac_kernel mirror some of them inline, each under a comment that says which and why.
+//
 // Compiled with -ffp-contract=off like every unit: g * reward is a plain product, the sums plain additions.
 #include "grlx_internal.h"
 #include "grlx_math.h"
@@ -35,103 +39,13 @@
 #include "grlx_envs.h"
 #include "grlx_query_weights.h"
 #include "grlx_evaluate.h"
+#include "grlx_episode.h"
 
 namespace grlx {
 
-// what a group carries through the loop besides the model state
-struct EpisodeSums {
-  double ret, disc, g;
-  int steps, code, ties;
-};
-
-// one step's bookkeeping (online_learning.cpp:202; disc += g * reward; g = g * gamma); returns whether the episode goes on
-__device__ __forceinline__ bool episode_account(EpisodeSums &e, double reward, double gamma, int terminal, uint32_t status, bool tie)
-{
-  e.ret += reward;
-  e.disc += e.g * reward;
-  e.g = e.g * gamma;
-  e.steps++;
-  e.ties += tie ? 1 : 0;
-  e.code = (status & ST_DOMAIN) ? kEvaluateDomain : terminal;
-  return e.code == 0;
-}
-
-template <int S>
-__device__ __forceinline__ void episode_store(const EvaluateArgs &A, long long pair, const EpisodeSums &e, const double (&x)[S])
-{
-  A.ret[pair] = e.ret;
-  A.disc[pair] = e.disc;
-  A.steps[pair] = e.steps;
-  A.terminal[pair] = e.code;
-  A.ties[pair] = e.ties;
-#pragma unroll
-  for (int i = 0; i < S; ++i) A.final_state[(size_t)pair * S + i] = x[i];
-}
-
-// The probe of one member by its 16-lane group, evaluate_q_kernel's written as a function for evaluate_ensemble_kernel: project(obs, a_k),
-// k < NA -- the hash of the observation once, then the action's coordinate and the tiling (tile_coding.cpp:103-149) --, query_weights,
-// the lane's NA weights into its column of the wave's tile.  evaluate_q_kernel keeps its own copy of these lines, and of findmax and
-// action_of below: calling any of the three from it changed its machine code (instruction counts, on the walker the registers), and
-// the existing kernels stay the code they were.  member_q is shared: it leaves evaluate_q_kernel instruction for instruction the same.
-template <int ENV, int NA>
-__device__ __forceinline__ void member_probe(const DevParams &P, const Table &tab, const ReplicaState &rs,
-                                             const double (&obs)[Env<ENV>::D], int j, int lane, double *W)
-{
-  constexpr int T = kLanesPerReplica, D = Env<ENV>::D;
-  uint32_t hpre = 449u ^ (uint32_t)(D + 2);
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-    hpre = murmur_mix(hpre, tile_coord<T>(P.tile, i, tile_quant(P.tile, i, obs[i]), j));
-  uint32_t slot[NA];
-#pragma unroll
-  for (int a = 0; a < NA; ++a)
-  {
-    uint32_t h = murmur_mix(hpre, tile_coord<T>(P.tile, D, tile_quant(P.tile, D, P.actions[a]), j));
-    h = murmur_mix(h, j);
-    slot[a] = murmur_final(h) % (uint32_t)P.tile.memory;
-  }
-  double w[NA];
-  query_weights<NA>(tab, rs, 0, P.lin, slot, w);
-#pragma unroll
-  for (int a = 0; a < NA; ++a) W[a * kRowStride + lane] = w[a];
-}
-
-// LinearRepresentation::read (linear.cpp:136-184) by lane j < NA of group g: serial sum over the 16 tilings, mean, clamp
-__device__ __forceinline__ double member_q(const DevParams &P, const double *W, int g, int j)
-{
-  double sum = 0;
-#pragma unroll
-  for (int k = 0; k < 16; ++k) sum += W[j * kRowStride + g * 16 + k];
-  sum /= 16;
-  return query_clamp(sum, P.lin.out_min, P.lin.out_max);
-}
-
-// GreedySampler::findmax (greedy.cpp:47-61): the first maximum and the number of maxima
-template <int NA, class V>
-__device__ __forceinline__ void findmax(const V *v, int &mai, int &man)
-{
-  mai = 0; man = 1;
-  V best = v[0];
-#pragma unroll
-  for (int a = 1; a < NA; ++a)
-  {
-    const V q = v[a];
-    if (q > best) { best = q; mai = a; man = 1; }
-    else if (q == best) man++;
-  }
-}
-
-// actions[mai] by selects, not an indexed read of the parameter block: no scratch copy of it
-template <int NA>
-__device__ __forceinline__ double action_of(const DevParams &P, int mai)
-{
-  double action = P.actions[0];
-#pragma unroll
-  for (int a = 1; a < NA; ++a) action = (mai == a) ? P.actions[a] : action;
-  return action;
-}
-
-// Q agents: actions[first maximum of Q(obs, .)] at every step
+// Q agents: actions[first maximum of Q(obs, .)] at every step.  The probe, the maximum and the action select below mirror member_probe,
+// findmax and action_of (grlx_episode.h) inline: calling any of the three from this kernel changed its machine code (instruction counts,
+// on the walker the registers).  member_q is called: it leaves the kernel instruction for instruction the same.
 template <int ENV, int NA>
 __global__ __launch_bounds__(kQueryWaves * 64) void evaluate_q_kernel(DevParams P, EvaluateArgs A)
 {
@@ -231,6 +145,22 @@ __global__ __launch_bounds__(kQueryWaves * 64) void evaluate_q_kernel(DevParams 
 // has passed the block barrier of round k + 1, which every thread reaches only after its reads of round k (buffer p) are done.  The
 // wave's tile W is written again only after that block barrier too, which orders it after the wave's own reads of the round before.
 // Dead member slots (member >= G) skip loads and stores; nobody reads their slots.
+// thread 0 of the block writes the pair's outputs once, after the loop
+template <int S>
+__device__ __forceinline__ void ensemble_store(const EnsembleArgs &A, const EpisodeSums &e, long long member_ties, long long agreement, const double (&x)[S])
+{
+  const long long pair = blockIdx.x;                   // group * n_starts + start
+  A.ret[pair] = e.ret;
+  A.disc[pair] = e.disc;
+  A.steps[pair] = e.steps;
+  A.terminal[pair] = e.code;
+  A.ties[pair] = e.ties;
+  A.member_ties[pair] = member_ties;
+  A.agreement[pair] = agreement;
+#pragma unroll
+  for (int i = 0; i < S; ++i) A.final_state[(size_t)pair * S + i] = x[i];
+}
+
 template <int ENV, int NA>
 __global__ __launch_bounds__(kQueryWaves * 64) void evaluate_ensemble_kernel(DevParams P, EnsembleArgs A)
 {
@@ -303,22 +233,11 @@ __global__ __launch_bounds__(kQueryWaves * 64) void evaluate_ensemble_kernel(Dev
     env_step<ENV, false, NoShare>(P, x, action, obs, reward, terminal, status);
     active = episode_account(e, reward, gamma, terminal, status, man > 1);
   }
-  if (threadIdx.x == 0)
-  {
-    const long long pair = blockIdx.x;                 // group * n_starts + start
-    A.ret[pair] = e.ret;
-    A.disc[pair] = e.disc;
-    A.steps[pair] = e.steps;
-    A.terminal[pair] = e.code;
-    A.ties[pair] = e.ties;
-    A.member_ties[pair] = member_ties;
-    A.agreement[pair] = agreement;
-#pragma unroll
-    for (int i = 0; i < S; ++i) A.final_state[(size_t)pair * S + i] = x[i];
-  }
+  if (threadIdx.x == 0) ensemble_store<S>(A, e, member_ties, agreement, x);
 }
 
-// actor-critic: the noise-free actor, fmin(fmax(read(actor table, obs), action_min), action_max) (ActionPolicy::act(in, out) const)
+// actor-critic: the noise-free actor, fmin(fmax(read(actor table, obs), action_min), action_max) (ActionPolicy::act(in, out) const).
+// The projection and the read mirror actor_probe and read_actor (grlx_episode.h) inline: calling them changes this kernel's machine code.
 template <int ENV>
 __global__ __launch_bounds__(kQueryWaves * 64) void evaluate_ac_kernel(DevParams P, EvaluateArgs A)
 {
@@ -395,29 +314,24 @@ __global__ __launch_bounds__(kQueryWaves * 64) void evaluate_ac_kernel(DevParams
 // lane number would put them into scratch.  The store comes after episode_account, at index steps - 1, so that the terminal word is the
 // code after the step; finished and dead groups store nothing, and nothing is written behind an episode's end (the caller zero-fills).
 
-// Word w of a step's record, by selects over the values themselves: no array of the R words is formed (one that was went to scratch, 8 R
-// bytes of it, although only constants indexed it after unrolling).  ENS: the ensemble's record, whose two words more sit before the
-// observation.  Any w outside the record gives the action.
-template <bool ENS, int D, int S>
-__device__ __forceinline__ double record_word(int w, double action, double reward, double value, int mai, int man, int code, int agree, int member_ties,
-                                              const double (&obs)[D], const double (&x)[S])
+// Word w of a step's record of the ensemble, whose two words more sit before the observation: record_head's selects (grlx_episode.h) in
+// the record's own order.  Any w outside the record gives the action.
+template <int D, int S>
+__device__ __forceinline__ double ensemble_record_word(int w, double action, double reward, double value, int mai, int man, int code, int agree,
+                                                       int member_ties, const double (&obs)[D], const double (&x)[S])
 {
-  constexpr int OBS = ENS ? GRLX_TRAJ_ENS_OBS : GRLX_TRAJ_OBS;
   double out = action;
   out = (w == GRLX_TRAJ_REWARD) ? reward : out;
   out = (w == GRLX_TRAJ_VALUE) ? value : out;
   out = (w == GRLX_TRAJ_ACTION_INDEX) ? (double)mai : out;
   out = (w == GRLX_TRAJ_N_MAX) ? (double)man : out;
   out = (w == GRLX_TRAJ_TERMINAL) ? (double)code : out;
-  if constexpr (ENS)
-  {
-    out = (w == GRLX_TRAJ_ENS_AGREEMENT) ? (double)agree : out;
-    out = (w == GRLX_TRAJ_ENS_MEMBER_TIES) ? (double)member_ties : out;
-  }
+  out = (w == GRLX_TRAJ_ENS_AGREEMENT) ? (double)agree : out;
+  out = (w == GRLX_TRAJ_ENS_MEMBER_TIES) ? (double)member_ties : out;
 #pragma unroll
-  for (int i = 0; i < D; ++i) out = (w == OBS + i) ? obs[i] : out;
+  for (int i = 0; i < D; ++i) out = (w == GRLX_TRAJ_ENS_OBS + i) ? obs[i] : out;
 #pragma unroll
-  for (int i = 0; i < S; ++i) out = (w == OBS + D + i) ? x[i] : out;
+  for (int i = 0; i < S; ++i) out = (w == GRLX_TRAJ_ENS_OBS + D + i) ? x[i] : out;
   return out;
 }
 
@@ -427,9 +341,9 @@ __device__ __forceinline__ void record_store16(double *rec, int j, double action
                                                const double (&obs)[D], const double (&x)[S])
 {
   constexpr int R = GRLX_TRAJ_OBS + D + S;
-  if (j < R) rec[j] = record_word<false, D, S>(j, action, reward, value, mai, man, code, 0, 0, obs, x);
+  if (j < R) rec[j] = record_head<D, S>(j, action, reward, value, mai, man, code, obs, x);
   if constexpr (R > 16)
-    if (j + 16 < R) rec[j + 16] = record_word<false, D, S>(j + 16, action, reward, value, mai, man, code, 0, 0, obs, x);
+    if (j + 16 < R) rec[j + 16] = record_head<D, S>(j + 16, action, reward, value, mai, man, code, obs, x);
 }
 
 // evaluate_q_kernel with records.  After the Q-values are in LDS every lane of the group reads them (broadcast) and runs findmax itself,
@@ -495,7 +409,8 @@ __global__ __launch_bounds__(kQueryWaves * 64) void trajectory_q_kernel(DevParam
 }
 
 // evaluate_ac_kernel with records.  Every lane of the group sums the 16 weights itself (broadcast reads): the value word, the actor's
-// read before the action clip, is then in every lane, and nothing is handed back through LDS.
+// read before the action clip, is then in every lane, and nothing is handed back through LDS.  The projection and the read mirror
+// actor_probe and read_actor (grlx_episode.h) inline, as evaluate_ac_kernel's do and for its reason.
 template <int ENV>
 __global__ __launch_bounds__(kQueryWaves * 64) void trajectory_ac_kernel(DevParams P, TrajectoryArgs T)
 {
@@ -651,21 +566,9 @@ __global__ __launch_bounds__(kQueryWaves * 64) void trajectory_ensemble_kernel(D
     active = episode_account(e, reward, gamma, terminal, status, man > 1);
     if (threadIdx.x < R)
       rec[(size_t)(e.steps - 1) * R] =
-          record_word<true, D, S>((int)threadIdx.x, action, reward, score, mai, man, e.code, agree, step_ties, before, x);
+          ensemble_record_word<D, S>((int)threadIdx.x, action, reward, score, mai, man, e.code, agree, step_ties, before, x);
   }
-  if (threadIdx.x == 0)
-  {
-    const long long pair = blockIdx.x;                 // group * n_starts + start
-    A.ret[pair] = e.ret;
-    A.disc[pair] = e.disc;
-    A.steps[pair] = e.steps;
-    A.terminal[pair] = e.code;
-    A.ties[pair] = e.ties;
-    A.member_ties[pair] = member_ties;
-    A.agreement[pair] = agreement;
-#pragma unroll
-    for (int i = 0; i < S; ++i) A.final_state[(size_t)pair * S + i] = x[i];
-  }
+  if (threadIdx.x == 0) ensemble_store<S>(A, e, member_ties, agreement, x);
 }
 
 // The instantiations: the (environment, action count) pairs grlx_create admits for the Q agents, and the actor-critic's two environments
@@ -678,21 +581,16 @@ bool evaluate_built(int agent, int env, int actions)
 
 hipError_t launch_evaluate(const DevParams &P, const EvaluateArgs &A, hipStream_t stream)
 {
-  const long long pairs = (long long)A.n_replicas * A.n_starts;
-  const unsigned blocks = (unsigned)((pairs + 4 * kQueryWaves - 1) / (4 * kQueryWaves));
+  const unsigned blocks = pair_blocks(A);
   if (blocks == 0) return hipSuccess;
   if (!evaluate_built(P.agent, P.env, P.A) || A.max_steps < 1) return hipErrorInvalidValue;
   const dim3 grid(blocks), block(kQueryWaves * 64);
   if (P.agent == GRLX_AGENT_AC)
-  {
-    if (P.env == GRLX_ENV_CART_POLE) hipLaunchKernelGGL(evaluate_ac_kernel<GRLX_ENV_CART_POLE>, grid, block, 0, stream, P, A);
-    else hipLaunchKernelGGL(evaluate_ac_kernel<GRLX_ENV_PENDULUM>, grid, block, 0, stream, P, A);
-  }
-  else if (P.env == GRLX_ENV_PENDULUM && P.A == 3) hipLaunchKernelGGL((evaluate_q_kernel<GRLX_ENV_PENDULUM, 3>), grid, block, 0, stream, P, A);
-  else if (P.env == GRLX_ENV_PENDULUM) hipLaunchKernelGGL((evaluate_q_kernel<GRLX_ENV_PENDULUM, 5>), grid, block, 0, stream, P, A);
-  else if (P.env == GRLX_ENV_ACROBOT) hipLaunchKernelGGL((evaluate_q_kernel<GRLX_ENV_ACROBOT, 3>), grid, block, 0, stream, P, A);
-  else if (P.env == GRLX_ENV_CART_POLE) hipLaunchKernelGGL((evaluate_q_kernel<GRLX_ENV_CART_POLE, 3>), grid, block, 0, stream, P, A);
-  else hipLaunchKernelGGL((evaluate_q_kernel<GRLX_ENV_COMPASS_WALKER, 3>), grid, block, 0, stream, P, A);
+    with_ac_instance(P, [&](auto env) { hipLaunchKernelGGL(evaluate_ac_kernel<decltype(env)::value>, grid, block, 0, stream, P, A); });
+  else
+    with_q_instance(P, [&](auto env, auto na) {
+      hipLaunchKernelGGL((evaluate_q_kernel<decltype(env)::value, decltype(na)::value>), grid, block, 0, stream, P, A);
+    });
   return hipGetLastError();
 }
 
@@ -706,11 +604,9 @@ hipError_t launch_evaluate_ensemble(const DevParams &P, const EnsembleArgs &A, h
       (A.rule != GRLX_ENSEMBLE_VOTE && A.rule != GRLX_ENSEMBLE_MEAN_Q))
     return hipErrorInvalidValue;
   const dim3 grid((unsigned)blocks), block(kQueryWaves * 64);
-  if (P.env == GRLX_ENV_PENDULUM && P.A == 3) hipLaunchKernelGGL((evaluate_ensemble_kernel<GRLX_ENV_PENDULUM, 3>), grid, block, 0, stream, P, A);
-  else if (P.env == GRLX_ENV_PENDULUM) hipLaunchKernelGGL((evaluate_ensemble_kernel<GRLX_ENV_PENDULUM, 5>), grid, block, 0, stream, P, A);
-  else if (P.env == GRLX_ENV_ACROBOT) hipLaunchKernelGGL((evaluate_ensemble_kernel<GRLX_ENV_ACROBOT, 3>), grid, block, 0, stream, P, A);
-  else if (P.env == GRLX_ENV_CART_POLE) hipLaunchKernelGGL((evaluate_ensemble_kernel<GRLX_ENV_CART_POLE, 3>), grid, block, 0, stream, P, A);
-  else hipLaunchKernelGGL((evaluate_ensemble_kernel<GRLX_ENV_COMPASS_WALKER, 3>), grid, block, 0, stream, P, A);
+  with_q_instance(P, [&](auto env, auto na) {
+    hipLaunchKernelGGL((evaluate_ensemble_kernel<decltype(env)::value, decltype(na)::value>), grid, block, 0, stream, P, A);
+  });
   return hipGetLastError();
 }
 
@@ -730,21 +626,16 @@ int trajectory_words(int env, bool ensemble)
 // launch_evaluate's grid; A.records zero-filled by the caller
 hipError_t launch_trajectory(const DevParams &P, const TrajectoryArgs &A, hipStream_t stream)
 {
-  const long long pairs = (long long)A.e.n_replicas * A.e.n_starts;
-  const unsigned blocks = (unsigned)((pairs + 4 * kQueryWaves - 1) / (4 * kQueryWaves));
+  const unsigned blocks = pair_blocks(A.e);
   if (blocks == 0) return hipSuccess;
   if (!evaluate_built(P.agent, P.env, P.A) || A.e.max_steps < 1 || !A.records) return hipErrorInvalidValue;
   const dim3 grid(blocks), block(kQueryWaves * 64);
   if (P.agent == GRLX_AGENT_AC)
-  {
-    if (P.env == GRLX_ENV_CART_POLE) hipLaunchKernelGGL(trajectory_ac_kernel<GRLX_ENV_CART_POLE>, grid, block, 0, stream, P, A);
-    else hipLaunchKernelGGL(trajectory_ac_kernel<GRLX_ENV_PENDULUM>, grid, block, 0, stream, P, A);
-  }
-  else if (P.env == GRLX_ENV_PENDULUM && P.A == 3) hipLaunchKernelGGL((trajectory_q_kernel<GRLX_ENV_PENDULUM, 3>), grid, block, 0, stream, P, A);
-  else if (P.env == GRLX_ENV_PENDULUM) hipLaunchKernelGGL((trajectory_q_kernel<GRLX_ENV_PENDULUM, 5>), grid, block, 0, stream, P, A);
-  else if (P.env == GRLX_ENV_ACROBOT) hipLaunchKernelGGL((trajectory_q_kernel<GRLX_ENV_ACROBOT, 3>), grid, block, 0, stream, P, A);
-  else if (P.env == GRLX_ENV_CART_POLE) hipLaunchKernelGGL((trajectory_q_kernel<GRLX_ENV_CART_POLE, 3>), grid, block, 0, stream, P, A);
-  else hipLaunchKernelGGL((trajectory_q_kernel<GRLX_ENV_COMPASS_WALKER, 3>), grid, block, 0, stream, P, A);
+    with_ac_instance(P, [&](auto env) { hipLaunchKernelGGL(trajectory_ac_kernel<decltype(env)::value>, grid, block, 0, stream, P, A); });
+  else
+    with_q_instance(P, [&](auto env, auto na) {
+      hipLaunchKernelGGL((trajectory_q_kernel<decltype(env)::value, decltype(na)::value>), grid, block, 0, stream, P, A);
+    });
   return hipGetLastError();
 }
 
@@ -758,11 +649,9 @@ hipError_t launch_trajectory_ensemble(const DevParams &P, const EnsembleTrajecto
       (A.e.rule != GRLX_ENSEMBLE_VOTE && A.e.rule != GRLX_ENSEMBLE_MEAN_Q))
     return hipErrorInvalidValue;
   const dim3 grid((unsigned)blocks), block(kQueryWaves * 64);
-  if (P.env == GRLX_ENV_PENDULUM && P.A == 3) hipLaunchKernelGGL((trajectory_ensemble_kernel<GRLX_ENV_PENDULUM, 3>), grid, block, 0, stream, P, A);
-  else if (P.env == GRLX_ENV_PENDULUM) hipLaunchKernelGGL((trajectory_ensemble_kernel<GRLX_ENV_PENDULUM, 5>), grid, block, 0, stream, P, A);
-  else if (P.env == GRLX_ENV_ACROBOT) hipLaunchKernelGGL((trajectory_ensemble_kernel<GRLX_ENV_ACROBOT, 3>), grid, block, 0, stream, P, A);
-  else if (P.env == GRLX_ENV_CART_POLE) hipLaunchKernelGGL((trajectory_ensemble_kernel<GRLX_ENV_CART_POLE, 3>), grid, block, 0, stream, P, A);
-  else hipLaunchKernelGGL((trajectory_ensemble_kernel<GRLX_ENV_COMPASS_WALKER, 3>), grid, block, 0, stream, P, A);
+  with_q_instance(P, [&](auto env, auto na) {
+    hipLaunchKernelGGL((trajectory_ensemble_kernel<decltype(env)::value, decltype(na)::value>), grid, block, 0, stream, P, A);
+  });
   return hipGetLastError();
 }
 

@@ -4,8 +4,9 @@
 // (Rand::getNormal, utils.h:120-125), clipped to the action range -- instead of the noise-free actor.  Every episode carries one rand48
 // state (the role of the thread-local stream) and one double (the noise state, ActionPolicy::n_) in and out.
 //
-// A unit of its own: grlx_evaluate.hip's and the rollout kernels' machine code stays what it was.  The draw, the read and the record
-// word below are this unit's own copies, in a namespace of their own; the draw is the expression of grlx_rollout_ac.h / grlx_step.h.
+// A unit of its own beside grlx_evaluate.hip.  The actor's probe and read, the bookkeeping and the head of a record are
+// grlx_episode.h's, which every evaluation unit shares; what is below is this unit's alone: the policy's state, its draw (the
+// expression of grlx_rollout_ac.h / grlx_step.h), the store and the record's two last words.
 //
 // Layout: evaluate_ac_kernel's.  A 16-lane group serves one pair, lane = tiling, four pairs per wave, kQueryWaves waves per block, no wave
 // waits for another.  The episode loop is wave-uniform on __ballot(active), bounded by max_steps; finished and dead groups skip loads, LDS
@@ -28,6 +29,7 @@
 #include "grlx_envs.h"
 #include "grlx_query_weights.h"
 #include "grlx_evaluate_noisy.h"
+#include "grlx_episode.h"
 
 namespace grlx {
 namespace noisy {
@@ -39,33 +41,6 @@ struct Policy {
   double   sg, theta;           // the standard deviation of a draw, the Ornstein-Uhlenbeck pull
   int      clipped;
 };
-
-// the lane's weight of the actor's read at obs into the wave's tile: project(obs) of the actor's projector (tile_coding.cpp:103-149),
-// unrolled over the observation (a run-time index would put obs into scratch), and the peek-only probe of grlx_query_weights.h
-template <int ENV>
-__device__ __forceinline__ void probe(const DevParams &P, const Table &tab, const ReplicaState &rs, const double (&obs)[Env<ENV>::D], int j, int lane, double *W)
-{
-  constexpr int D = Env<ENV>::D;
-  uint32_t h = 449u ^ (uint32_t)(D + 1);
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-    h = murmur_mix(h, tile_coord<kLanesPerReplica>(P.tile_actor, i, tile_quant(P.tile_actor, i, obs[i]), j));
-  h = murmur_mix(h, j);
-  uint32_t slot[1] = {murmur_final(h) % (uint32_t)P.tile_actor.memory};
-  double w[1];
-  query_weights<1>(tab, rs, 1, P.lin_actor, slot, w);
-  W[lane] = w[0];
-}
-
-// ActionPolicy::read (action.cpp:99-112) over LinearRepresentation::read (linear.cpp:136-184) of group g: serial sum, mean, clamp
-__device__ __forceinline__ double read_actor(const DevParams &P, const double *W, int g)
-{
-  double sum = 0;
-#pragma unroll
-  for (int k = 0; k < 16; ++k) sum += W[g * 16 + k];
-  sum /= 16;
-  return query_clamp(sum, P.lin_actor.out_min, P.lin_actor.out_max);
-}
 
 // ActionPolicy::act(time, in, out) (action.cpp:127-158) on the actor's read u at model time `time`, in the rollout kernels' order: the
 // noise state is reset at time 0; sg != 0: two draws (Rand::getNormal, utils.h:120-125), the noise state moves, out = u + noise; the
@@ -89,23 +64,6 @@ __device__ __forceinline__ double act(const DevParams &P, Policy &p, double u, d
   return fmin(fmax(out, P.action_min), P.action_max);
 }
 
-// what a group carries through the loop besides the model state
-struct Sums {
-  double ret, disc, g;
-  int steps, code;
-};
-
-// one step's bookkeeping (online_learning.cpp:202; disc += g * reward; g = g * gamma); returns whether the episode goes on
-__device__ __forceinline__ bool account(Sums &e, double reward, double gamma, int terminal, uint32_t status)
-{
-  e.ret += reward;
-  e.disc += e.g * reward;
-  e.g = e.g * gamma;
-  e.steps++;
-  e.code = (status & ST_DOMAIN) ? kEvaluateDomain : terminal;
-  return e.code == 0;
-}
-
 // the pair's policy state at its episode's start
 __device__ __forceinline__ void policy_init(const DevParams &P, const NoisyArgs &T, const ReplicaState &rs, long long pair, bool holds, Policy &p)
 {
@@ -122,7 +80,7 @@ __device__ __forceinline__ void policy_init(const DevParams &P, const NoisyArgs 
 }
 
 template <int S>
-__device__ __forceinline__ void store(const NoisyArgs &T, long long pair, const Sums &e, const Policy &p, const double (&x)[S])
+__device__ __forceinline__ void store(const NoisyArgs &T, long long pair, const EpisodeSums &e, const Policy &p, const double (&x)[S])
 {
   const EvaluateArgs &A = T.e;
   A.ret[pair] = e.ret;
@@ -136,22 +94,13 @@ __device__ __forceinline__ void store(const NoisyArgs &T, long long pair, const 
   for (int i = 0; i < S; ++i) A.final_state[(size_t)pair * S + i] = x[i];
 }
 
-// Word w of a step's record by selects over the values themselves (grlx_evaluate.hip: record_word); the actor-critic's record -- action
-// index -1, one maximum -- with the noise state after the step and the clip flag behind the model state
+// Word w of a step's record: record_head's words for the actor-critic -- action index -1, one maximum --, then the noise state after the
+// step and the clip flag
 template <int D, int S>
 __device__ __forceinline__ double record_word(int w, double action, double reward, double value, int code, double noise, bool clip,
                                               const double (&obs)[D], const double (&x)[S])
 {
-  double out = action;
-  out = (w == GRLX_TRAJ_REWARD) ? reward : out;
-  out = (w == GRLX_TRAJ_VALUE) ? value : out;
-  out = (w == GRLX_TRAJ_ACTION_INDEX) ? -1.0 : out;
-  out = (w == GRLX_TRAJ_N_MAX) ? 1.0 : out;
-  out = (w == GRLX_TRAJ_TERMINAL) ? (double)code : out;
-#pragma unroll
-  for (int i = 0; i < D; ++i) out = (w == GRLX_TRAJ_OBS + i) ? obs[i] : out;
-#pragma unroll
-  for (int i = 0; i < S; ++i) out = (w == GRLX_TRAJ_OBS + D + i) ? x[i] : out;
+  double out = record_head<D, S>(w, action, reward, value, -1, 1, code, obs, x);
   out = (w == GRLX_TRAJ_OBS + D + S) ? noise : out;
   out = (w == GRLX_TRAJ_OBS + D + S + 1) ? (clip ? 1.0 : 0.0) : out;
   return out;
@@ -185,20 +134,20 @@ __global__ __launch_bounds__(kQueryWaves * 64) void evaluate_noisy_kernel(DevPar
   for (int i = 0; i < S; ++i) x[i] = live ? A.states[(size_t)s * S + i] : 0.;
   (void)Env<ENV>::observe(P, x, obs);                  // the start state's terminal code is ignored, as Environment::start has none
 
-  noisy::Sums e;
-  e.ret = 0; e.disc = 0; e.g = 1; e.steps = 0; e.code = 0;
+  EpisodeSums e;                                       // ties stays 0: the steps that clipped are the policy's count
+  e.ret = 0; e.disc = 0; e.g = 1; e.steps = 0; e.code = 0; e.ties = 0;
   noisy::Policy p;
   noisy::policy_init(P, T, rs, pair, live && j == 0, p);
   bool active = live;
   for (int step = 0; step < A.max_steps; ++step)
   {
     if (__ballot(active) == 0ull) break;               // wave-uniform
-    if (active) noisy::probe<ENV>(P, tab, rs, obs, j, lane, W);
+    if (active) actor_probe<ENV>(P, tab, rs, obs, j, lane, W);
     wave_sync();
     if (active && j == 0)
     { // the draws sit under the step's predicate: a finished group's stream and noise stand where its last step left them
       bool clip;
-      ACT[g] = noisy::act(P, p, noisy::read_actor(P, W, g), x[S - 1], clip);
+      ACT[g] = noisy::act(P, p, read_actor(P, W, g), x[S - 1], clip);
     }
     wave_sync();
     if (active)
@@ -208,7 +157,7 @@ __global__ __launch_bounds__(kQueryWaves * 64) void evaluate_noisy_kernel(DevPar
       int terminal = 0;
       uint32_t status = 0;
       env_step<ENV, false, NoShare>(P, x, action, obs, reward, terminal, status);
-      active = noisy::account(e, reward, gamma, terminal, status);
+      active = episode_account(e, reward, gamma, terminal, status, false);
     }
   }
   if (live && j == 0) noisy::store<S>(T, pair, e, p, x);
@@ -241,19 +190,19 @@ __global__ __launch_bounds__(kQueryWaves * 64) void trajectory_noisy_kernel(DevP
   for (int i = 0; i < S; ++i) x[i] = live ? A.states[(size_t)s * S + i] : 0.;
   (void)Env<ENV>::observe(P, x, obs);
 
-  noisy::Sums e;
-  e.ret = 0; e.disc = 0; e.g = 1; e.steps = 0; e.code = 0;
+  EpisodeSums e;                                       // ties stays 0: the steps that clipped are the policy's count
+  e.ret = 0; e.disc = 0; e.g = 1; e.steps = 0; e.code = 0; e.ties = 0;
   noisy::Policy p;
   noisy::policy_init(P, T, rs, pair, live, p);
   bool active = live;
   for (int step = 0; step < A.max_steps; ++step)
   {
     if (__ballot(active) == 0ull) break;               // wave-uniform
-    if (active) noisy::probe<ENV>(P, tab, rs, obs, j, lane, W);
+    if (active) actor_probe<ENV>(P, tab, rs, obs, j, lane, W);
     wave_sync();
     if (active)
     {
-      const double value = noisy::read_actor(P, W, g);
+      const double value = read_actor(P, W, g);
       bool clip;
       const double action = noisy::act(P, p, value, x[S - 1], clip);
       double before[D];
@@ -263,7 +212,7 @@ __global__ __launch_bounds__(kQueryWaves * 64) void trajectory_noisy_kernel(DevP
       int terminal = 0;
       uint32_t status = 0;
       env_step<ENV, false, NoShare>(P, x, action, obs, reward, terminal, status);
-      active = noisy::account(e, reward, gamma, terminal, status);
+      active = episode_account(e, reward, gamma, terminal, status, false);
       double *at = rec + (size_t)(e.steps - 1) * R;
       if (j < R) at[j] = noisy::record_word<D, S>(j, action, reward, value, e.code, p.noise, clip, before, x);
       if constexpr (R > 16)
@@ -283,20 +232,17 @@ int noisy_trajectory_words(int env)
 // launch_evaluate's grid.  Every output pointer of the kernels is written without a test, so all of them are required here.
 static hipError_t launch_noisy(const DevParams &P, const NoisyArgs &A, bool rec, hipStream_t stream)
 {
-  const long long pairs = (long long)A.e.n_replicas * A.e.n_starts;
-  const unsigned blocks = (unsigned)((pairs + 4 * kQueryWaves - 1) / (4 * kQueryWaves));
+  const unsigned blocks = pair_blocks(A.e);
   if (blocks == 0) return hipSuccess;
   if (P.agent != GRLX_AGENT_AC || !evaluate_built(P.agent, P.env, P.A) || A.e.max_steps < 1 || (rec && !A.records) ||
       !A.streams_out || !A.noise_out || !A.e.ret || !A.e.disc || !A.e.steps || !A.e.terminal || !A.e.ties || !A.e.final_state || !A.e.states)
     return hipErrorInvalidValue;
   const dim3 grid(blocks), block(kQueryWaves * 64);
-  if (rec)
-  {
-    if (P.env == GRLX_ENV_CART_POLE) hipLaunchKernelGGL(trajectory_noisy_kernel<GRLX_ENV_CART_POLE>, grid, block, 0, stream, P, A);
-    else hipLaunchKernelGGL(trajectory_noisy_kernel<GRLX_ENV_PENDULUM>, grid, block, 0, stream, P, A);
-  }
-  else if (P.env == GRLX_ENV_CART_POLE) hipLaunchKernelGGL(evaluate_noisy_kernel<GRLX_ENV_CART_POLE>, grid, block, 0, stream, P, A);
-  else hipLaunchKernelGGL(evaluate_noisy_kernel<GRLX_ENV_PENDULUM>, grid, block, 0, stream, P, A);
+  with_ac_instance(P, [&](auto env) {
+    constexpr int ENV = decltype(env)::value;
+    if (rec) hipLaunchKernelGGL(trajectory_noisy_kernel<ENV>, grid, block, 0, stream, P, A);
+    else hipLaunchKernelGGL(evaluate_noisy_kernel<ENV>, grid, block, 0, stream, P, A);
+  });
   return hipGetLastError();
 }
 

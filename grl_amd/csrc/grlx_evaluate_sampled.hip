@@ -4,8 +4,9 @@
 // -- on two rand48 streams that every episode carries.  The order of draws is eps_greedy_act's (grlx_policy.h), which only the rollout
 // kernels call: the epsilon draw from the sampler's stream, then the global stream for the random action or for the tie break.
 //
-// A unit of its own: grlx_evaluate.hip's kernels stay the machine code they were (its comments record that even sharing a helper with
-// them changed it).  The helpers below are this unit's own copies, in a namespace of their own.
+// A unit of its own beside grlx_evaluate.hip.  The probe, the read and the head of a record are grlx_episode.h's, which every evaluation
+// unit shares; what is below is this unit's alone: the sampler, the record's last word, and what an episode carries and stores -- the
+// bookkeeping mirrors episode_account inline, see Sums.
 //
 // Layout: evaluate_q_kernel's.  A 16-lane group serves one pair, lane = tiling, four pairs per wave, kQueryWaves waves per block, no wave
 // waits for another.  The episode loop is wave-uniform on __ballot(active), bounded by max_steps; finished and dead groups skip loads, LDS
@@ -29,50 +30,20 @@
 #include "grlx_envs.h"
 #include "grlx_query_weights.h"
 #include "grlx_evaluate_sampled.h"
+#include "grlx_episode.h"
 
 namespace grlx {
 namespace sampled {
 
-// what a group carries through the loop besides the model state
+// what a group carries through the loop besides the model state: EpisodeSums' fields (grlx_episode.h), the random actions taken and both
+// streams, in a struct of this unit's.  Deriving it from EpisodeSums, or carrying the extras in a struct beside one, so that the loop
+// could call episode_account and the end episode_store, changed the machine code (the first: two moves of the walker's kernel swap
+// places; the second: every kernel of the unit), so the loop keeps the bookkeeping inline and the end its own store.
 struct Sums {
   double ret, disc, g;
   int steps, code, ties, explored;
   uint64_t S, G;                // the sampler's private stream, the global stream
 };
-
-// project(obs, a_k), k < NA, by the group's 16 lanes (tile_coding.cpp:103-149), query_weights, the lane's NA weights into its column of the
-// wave's tile: grlx_evaluate.hip's member_probe
-template <int ENV, int NA>
-__device__ __forceinline__ void probe(const DevParams &P, const Table &tab, const ReplicaState &rs, const double (&obs)[Env<ENV>::D], int j, int lane, double *W)
-{
-  constexpr int T = kLanesPerReplica, D = Env<ENV>::D;
-  uint32_t hpre = 449u ^ (uint32_t)(D + 2);
-#pragma unroll
-  for (int i = 0; i < D; ++i)
-    hpre = murmur_mix(hpre, tile_coord<T>(P.tile, i, tile_quant(P.tile, i, obs[i]), j));
-  uint32_t slot[NA];
-#pragma unroll
-  for (int a = 0; a < NA; ++a)
-  {
-    uint32_t h = murmur_mix(hpre, tile_coord<T>(P.tile, D, tile_quant(P.tile, D, P.actions[a]), j));
-    h = murmur_mix(h, j);
-    slot[a] = murmur_final(h) % (uint32_t)P.tile.memory;
-  }
-  double w[NA];
-  query_weights<NA>(tab, rs, 0, P.lin, slot, w);
-#pragma unroll
-  for (int a = 0; a < NA; ++a) W[a * kRowStride + lane] = w[a];
-}
-
-// LinearRepresentation::read (linear.cpp:136-184) by lane j < NA of group g: serial sum over the 16 tilings, mean, clamp
-__device__ __forceinline__ double read_q(const DevParams &P, const double *W, int g, int j)
-{
-  double sum = 0;
-#pragma unroll
-  for (int k = 0; k < 16; ++k) sum += W[j * kRowStride + g * 16 + k];
-  sum /= 16;
-  return query_clamp(sum, P.lin.out_min, P.lin.out_max);
-}
 
 // One action of the sampler over q (eps_greedy_act's order of draws, grlx_policy.h); returns the index that acts.
 //   epsilon-greedy: S advances, rnd = drand48; rnd < e: G advances, lrand48 % NA acts, `explored`.
@@ -119,23 +90,13 @@ __device__ __forceinline__ int sample(const double (&q)[NA], int sampler, double
   return mai;
 }
 
-// Word w of a step's record by selects over the values themselves (grlx_evaluate.hip: record_word); the last word is `explored`
+// Word w of a step's record: record_head's words, then `explored`
 template <int D, int S>
 __device__ __forceinline__ double record_word(int w, double action, double reward, double value, int idx, int man, int code, bool explored,
                                               const double (&obs)[D], const double (&x)[S])
 {
-  double out = action;
-  out = (w == GRLX_TRAJ_REWARD) ? reward : out;
-  out = (w == GRLX_TRAJ_VALUE) ? value : out;
-  out = (w == GRLX_TRAJ_ACTION_INDEX) ? (double)idx : out;
-  out = (w == GRLX_TRAJ_N_MAX) ? (double)man : out;
-  out = (w == GRLX_TRAJ_TERMINAL) ? (double)code : out;
-#pragma unroll
-  for (int i = 0; i < D; ++i) out = (w == GRLX_TRAJ_OBS + i) ? obs[i] : out;
-#pragma unroll
-  for (int i = 0; i < S; ++i) out = (w == GRLX_TRAJ_OBS + D + i) ? x[i] : out;
-  out = (w == GRLX_TRAJ_OBS + D + S) ? (explored ? 1.0 : 0.0) : out;
-  return out;
+  const double out = record_head<D, S>(w, action, reward, value, idx, man, code, obs, x);
+  return (w == GRLX_TRAJ_OBS + D + S) ? (explored ? 1.0 : 0.0) : out;
 }
 
 // the episode of one pair by its 16-lane group; REC: with one record per step taken (lane j stores word j, and word j + 16 where R > 16)
@@ -178,9 +139,9 @@ __device__ __forceinline__ void episode(const DevParams &P, const SampledArgs &T
   for (int step = 0; step < A.max_steps; ++step)
   {
     if (__ballot(active) == 0ull) break;               // wave-uniform
-    if (active) probe<ENV, NA>(P, tab, rs, obs, j, lane, W);
+    if (active) member_probe<ENV, NA>(P, tab, rs, obs, j, lane, W);
     wave_sync();
-    if (active && j < NA) Q[g * 8 + j] = read_q(P, W, g, j);
+    if (active && j < NA) Q[g * 8 + j] = member_q(P, W, g, j);
     wave_sync();
     if (active)
     { // the draws sit under the step's predicate: a finished group's streams stand where its last step left them
@@ -207,7 +168,8 @@ __device__ __forceinline__ void episode(const DevParams &P, const SampledArgs &T
       int terminal = 0;
       uint32_t status = 0;
       env_step<ENV, false, NoShare>(P, x, action, obs, reward, terminal, status);
-      e.ret += reward;                                 // online_learning.cpp:202; disc += g * reward; g = g * gamma
+      // episode_account (grlx_episode.h) inline, on this unit's Sums: see there why it is not an EpisodeSums
+      e.ret += reward;
       e.disc += e.g * reward;
       e.g = e.g * gamma;
       e.steps++;
@@ -268,25 +230,18 @@ int sampled_trajectory_words(int env)
 // launch_evaluate's grid.  Every output pointer of the kernels is written without a test, so all of them are required here.
 static hipError_t launch_sampled(const DevParams &P, const SampledArgs &A, bool rec, hipStream_t stream)
 {
-  const long long pairs = (long long)A.e.n_replicas * A.e.n_starts;
-  const unsigned blocks = (unsigned)((pairs + 4 * kQueryWaves - 1) / (4 * kQueryWaves));
+  const unsigned blocks = pair_blocks(A.e);
   if (blocks == 0) return hipSuccess;
   if (P.agent == GRLX_AGENT_AC || !evaluate_built(P.agent, P.env, P.A) || A.e.max_steps < 1 || (rec && !A.records) ||
       (A.sampler != GRLX_SAMPLER_GREEDY && A.sampler != GRLX_SAMPLER_EPSILON_GREEDY) || !A.streams_out || !A.explored ||
       !A.e.ret || !A.e.disc || !A.e.steps || !A.e.terminal || !A.e.ties || !A.e.final_state || !A.e.states)
     return hipErrorInvalidValue;
   const dim3 grid(blocks), block(kQueryWaves * 64);
-#define GRLX_SAMPLED_LAUNCH(ENV, NA)                                                                                   \
-  do {                                                                                                                 \
-    if (rec) hipLaunchKernelGGL((trajectory_sampled_kernel<ENV, NA>), grid, block, 0, stream, P, A);                   \
-    else hipLaunchKernelGGL((evaluate_sampled_kernel<ENV, NA>), grid, block, 0, stream, P, A);                         \
-  } while (0)
-  if (P.env == GRLX_ENV_PENDULUM && P.A == 3) GRLX_SAMPLED_LAUNCH(GRLX_ENV_PENDULUM, 3);
-  else if (P.env == GRLX_ENV_PENDULUM) GRLX_SAMPLED_LAUNCH(GRLX_ENV_PENDULUM, 5);
-  else if (P.env == GRLX_ENV_ACROBOT) GRLX_SAMPLED_LAUNCH(GRLX_ENV_ACROBOT, 3);
-  else if (P.env == GRLX_ENV_CART_POLE) GRLX_SAMPLED_LAUNCH(GRLX_ENV_CART_POLE, 3);
-  else GRLX_SAMPLED_LAUNCH(GRLX_ENV_COMPASS_WALKER, 3);
-#undef GRLX_SAMPLED_LAUNCH
+  with_q_instance(P, [&](auto env, auto na) {
+    constexpr int ENV = decltype(env)::value, NA = decltype(na)::value;
+    if (rec) hipLaunchKernelGGL((trajectory_sampled_kernel<ENV, NA>), grid, block, 0, stream, P, A);
+    else hipLaunchKernelGGL((evaluate_sampled_kernel<ENV, NA>), grid, block, 0, stream, P, A);
+  });
   return hipGetLastError();
 }
 

@@ -105,6 +105,43 @@ def _ptr(arr, ctype):
     return arr.ctypes.data_as(C.POINTER(ctype))
 
 
+# ---- what the evaluation calls of Runner and FqiRunner share
+def _state_rows(states, dims):
+    states = np.ascontiguousarray(states, dtype=np.float64)
+    if states.ndim != 2 or states.shape[1] != dims:
+        raise ValueError(f"expected states of shape (n, {dims}), got {states.shape}")
+    return states
+
+
+_RULES = {"vote": capi.ENSEMBLE_VOTE, "mean": capi.ENSEMBLE_MEAN_Q, "mean_q": capi.ENSEMBLE_MEAN_Q}
+
+
+def _rule(rule):
+    return _RULES[rule] if isinstance(rule, str) else int(rule)
+
+
+_ENSEMBLE_FIELDS = "ret disc steps terminal ties member_ties agreement final_state"
+_SAMPLED_FIELDS = "ret disc steps terminal ties explored final_state streams"
+_NOISY_FIELDS = "ret disc steps terminal clipped final_state streams noise"
+_BASE_OUTPUTS = {"ret": np.float64, "disc": np.float64, "steps": np.int32, "terminal": np.int32, "ties": np.int32}
+_CTYPES = {np.float64: C.c_double, np.int32: C.c_int32, np.int64: C.c_int64, np.uint64: C.c_uint64}
+
+
+def _episode_outputs(rows, n, state_dims, fields, records=None, **extra):
+    """The zeroed output arrays of an evaluation call for `rows` replicas or groups and n start states, in the order of `fields` -- the
+    order of the C call's output pointers and of the result tuple: ret, disc, steps, terminal, ties [rows][n], final_state
+    [rows][n][state_dims], and the variant's own fields, extra[name] = an int32, int64, uint64 or float64 dtype or (dtype, width) for
+    [rows][n][width].  records = (max_steps, words): a last array [rows][n][max_steps][words].  Returns (arrays, their pointers)."""
+    arrays = []
+    for name in fields.split():
+        dtype = (np.float64, state_dims) if name == "final_state" else extra.get(name) or _BASE_OUTPUTS[name]
+        dtype, tail = dtype if isinstance(dtype, tuple) else (dtype, None)
+        arrays.append(np.zeros((rows, n) if tail is None else (rows, n, tail), dtype))
+    if records is not None:
+        arrays.append(np.zeros((rows, n, max(records[0], 0), records[1]), np.float64))
+    return arrays, [_ptr(a, _CTYPES[a.dtype.type]) for a in arrays]
+
+
 class Runner:
     """N independent-seed replicas of one experiment graph on the current GPU
     (the reference's experiment/multi clones, base/src/experiments/multi.cpp:44-75)."""
@@ -566,18 +603,12 @@ class Runner:
         Evaluation(ret, disc, steps, terminal, ties, final_state), each [replica][start] (final_state: [replica][start][state_dims]).
         terminal: 1 timed out, 2 absorbing, 0 cut at max_steps, 3 left the portable math's domain.  ties: steps at which the Q agents'
         maximum was not unique (the first maximum acts; no random draw).  The context is not changed (include/grlx.h: grlx_evaluate)."""
-        states = np.ascontiguousarray(states, dtype=np.float64)
-        if states.ndim != 2 or states.shape[1] != self.state_dims:
-            raise ValueError(f"expected states of shape (n, {self.state_dims}), got {states.shape}")
+        states = _state_rows(states, self.state_dims)
         first, count = self._replica_range(replicas)
         n = states.shape[0]
-        ret, disc = np.zeros((count, n), np.float64), np.zeros((count, n), np.float64)
-        steps, terminal, ties = np.zeros((count, n), np.int32), np.zeros((count, n), np.int32), np.zeros((count, n), np.int32)
-        final_state = np.zeros((count, n, self.state_dims), np.float64)
-        capi.check(self.lib.grlx_evaluate(self._ctx, first, count, _ptr(states, C.c_double), n, int(max_steps), _ptr(ret, C.c_double),
-                                          _ptr(disc, C.c_double), _ptr(steps, C.c_int32), _ptr(terminal, C.c_int32), _ptr(ties, C.c_int32),
-                                          _ptr(final_state, C.c_double)))
-        return Evaluation(ret, disc, steps, terminal, ties, final_state)
+        out, ptrs = _episode_outputs(count, n, self.state_dims, "ret disc steps terminal ties final_state")
+        capi.check(self.lib.grlx_evaluate(self._ctx, first, count, _ptr(states, C.c_double), n, int(max_steps), *ptrs))
+        return Evaluation(*out)
 
     def evaluate_ensemble(self, states, group_size, rule="vote", replicas=None, max_steps=0):
         """One greedy episode per (group of `group_size` consecutive replicas, start state) pair, on the device: at every step the
@@ -586,76 +617,47 @@ class Runner:
         agreement, final_state), each [group][start]: ties = steps at which the combined score had more than one maximum, member_ties =
         member-steps at which a member's own maximum was not unique, agreement = member-steps whose own first maximum was the action
         taken.  disc uses the gamma of a group's first replica.  The context is not changed (include/grlx.h: grlx_evaluate_ensemble)."""
-        rules = {"vote": capi.ENSEMBLE_VOTE, "mean": capi.ENSEMBLE_MEAN_Q, "mean_q": capi.ENSEMBLE_MEAN_Q}
-        rule = rules[rule] if isinstance(rule, str) else int(rule)
-        states = np.ascontiguousarray(states, dtype=np.float64)
-        if states.ndim != 2 or states.shape[1] != self.state_dims:
-            raise ValueError(f"expected states of shape (n, {self.state_dims}), got {states.shape}")
+        rule = _rule(rule)
+        states = _state_rows(states, self.state_dims)
         first, count = self._replica_range(replicas)
         group_size = int(group_size)
         groups = count // group_size if group_size > 0 else 0
         n = states.shape[0]
-        ret, disc = np.zeros((groups, n), np.float64), np.zeros((groups, n), np.float64)
-        steps, terminal, ties = np.zeros((groups, n), np.int32), np.zeros((groups, n), np.int32), np.zeros((groups, n), np.int32)
-        member_ties, agreement = np.zeros((groups, n), np.int64), np.zeros((groups, n), np.int64)
-        final_state = np.zeros((groups, n, self.state_dims), np.float64)
-        capi.check(self.lib.grlx_evaluate_ensemble(self._ctx, first, count, group_size, rule, _ptr(states, C.c_double), n, int(max_steps),
-                                                   _ptr(ret, C.c_double), _ptr(disc, C.c_double), _ptr(steps, C.c_int32), _ptr(terminal, C.c_int32),
-                                                   _ptr(ties, C.c_int32), _ptr(member_ties, C.c_int64), _ptr(agreement, C.c_int64),
-                                                   _ptr(final_state, C.c_double)))
-        return EnsembleEvaluation(ret, disc, steps, terminal, ties, member_ties, agreement, final_state)
+        out, ptrs = _episode_outputs(groups, n, self.state_dims, _ENSEMBLE_FIELDS, member_ties=np.int64, agreement=np.int64)
+        capi.check(self.lib.grlx_evaluate_ensemble(self._ctx, first, count, group_size, rule, _ptr(states, C.c_double), n, int(max_steps), *ptrs))
+        return EnsembleEvaluation(*out)
 
     def trajectory_record_words(self, ensemble=False):
         """R, the doubles of one trajectory record of this context (grlx_trajectory_record_words)"""
-        words = self.lib.grlx_trajectory_record_words(self._ctx, 1 if ensemble else 0)
-        if words < 0:
-            capi.check(words)
-        return words
+        return capi.check(self.lib.grlx_trajectory_record_words(self._ctx, 1 if ensemble else 0))
 
     def evaluate_trajectory(self, states, max_steps, replicas=None):
         """Runner.evaluate with every step of every episode: Trajectory(ret, disc, steps, terminal, ties, final_state, records),
         records[replica][start][max_steps][R] with one record per step taken and zeros behind an episode's end.  The views .action,
         .reward, .value, .action_index, .n_max, .code, .obs and .state cut the records by name; .episode(k, s) gives the records of one
         episode.  max_steps sizes the records, so it has no default (include/grlx.h: grlx_evaluate_trajectory)."""
-        states = np.ascontiguousarray(states, dtype=np.float64)
-        if states.ndim != 2 or states.shape[1] != self.state_dims:
-            raise ValueError(f"expected states of shape (n, {self.state_dims}), got {states.shape}")
+        states = _state_rows(states, self.state_dims)
         first, count = self._replica_range(replicas)
         n, max_steps = states.shape[0], int(max_steps)
-        words = self.trajectory_record_words(False)
-        ret, disc = np.zeros((count, n), np.float64), np.zeros((count, n), np.float64)
-        steps, terminal, ties = np.zeros((count, n), np.int32), np.zeros((count, n), np.int32), np.zeros((count, n), np.int32)
-        final_state = np.zeros((count, n, self.state_dims), np.float64)
-        records = np.zeros((count, n, max(max_steps, 0), words), np.float64)
-        capi.check(self.lib.grlx_evaluate_trajectory(self._ctx, first, count, _ptr(states, C.c_double), n, max_steps, _ptr(ret, C.c_double),
-                                                     _ptr(disc, C.c_double), _ptr(steps, C.c_int32), _ptr(terminal, C.c_int32),
-                                                     _ptr(ties, C.c_int32), _ptr(final_state, C.c_double), _ptr(records, C.c_double)))
-        return Trajectory(ret, disc, steps, terminal, ties, final_state, records)
+        out, ptrs = _episode_outputs(count, n, self.state_dims, "ret disc steps terminal ties final_state",
+                                     records=(max_steps, self.trajectory_record_words(False)))
+        capi.check(self.lib.grlx_evaluate_trajectory(self._ctx, first, count, _ptr(states, C.c_double), n, max_steps, *ptrs))
+        return Trajectory(*out)
 
     def evaluate_ensemble_trajectory(self, states, group_size, max_steps, rule="vote", replicas=None):
         """Runner.evaluate_ensemble with every step of every episode: EnsembleTrajectory(..., records), records[group][start][max_steps][R];
         beside Trajectory's views .step_agreement (votes[mai] of the step) and .step_member_ties (members with a tie at the step), and
         .value is the combined score of the action taken (include/grlx.h: grlx_evaluate_ensemble_trajectory)."""
-        rules = {"vote": capi.ENSEMBLE_VOTE, "mean": capi.ENSEMBLE_MEAN_Q, "mean_q": capi.ENSEMBLE_MEAN_Q}
-        rule = rules[rule] if isinstance(rule, str) else int(rule)
-        states = np.ascontiguousarray(states, dtype=np.float64)
-        if states.ndim != 2 or states.shape[1] != self.state_dims:
-            raise ValueError(f"expected states of shape (n, {self.state_dims}), got {states.shape}")
+        rule = _rule(rule)
+        states = _state_rows(states, self.state_dims)
         first, count = self._replica_range(replicas)
         group_size, max_steps = int(group_size), int(max_steps)
         groups = count // group_size if group_size > 0 else 0
         n = states.shape[0]
-        words = self.trajectory_record_words(True)
-        ret, disc = np.zeros((groups, n), np.float64), np.zeros((groups, n), np.float64)
-        steps, terminal, ties = np.zeros((groups, n), np.int32), np.zeros((groups, n), np.int32), np.zeros((groups, n), np.int32)
-        member_ties, agreement = np.zeros((groups, n), np.int64), np.zeros((groups, n), np.int64)
-        final_state = np.zeros((groups, n, self.state_dims), np.float64)
-        records = np.zeros((groups, n, max(max_steps, 0), words), np.float64)
-        capi.check(self.lib.grlx_evaluate_ensemble_trajectory(self._ctx, first, count, group_size, rule, _ptr(states, C.c_double), n, max_steps,
-                                                              _ptr(ret, C.c_double), _ptr(disc, C.c_double), _ptr(steps, C.c_int32),
-                                                              _ptr(terminal, C.c_int32), _ptr(ties, C.c_int32), _ptr(member_ties, C.c_int64),
-                                                              _ptr(agreement, C.c_int64), _ptr(final_state, C.c_double), _ptr(records, C.c_double)))
-        return EnsembleTrajectory(ret, disc, steps, terminal, ties, member_ties, agreement, final_state, records)
+        out, ptrs = _episode_outputs(groups, n, self.state_dims, _ENSEMBLE_FIELDS, member_ties=np.int64, agreement=np.int64,
+                                     records=(max_steps, self.trajectory_record_words(True)))
+        capi.check(self.lib.grlx_evaluate_ensemble_trajectory(self._ctx, first, count, group_size, rule, _ptr(states, C.c_double), n, max_steps, *ptrs))
+        return EnsembleTrajectory(*out)
 
     # ---- sampled evaluation: the same episodes acted by the reference's samplers on streams the episodes carry (grlx_evaluate_sampled)
     def _sampled_args(self, states, sampler, epsilon, streams, replicas):
@@ -665,9 +667,7 @@ class Runner:
             if epsilon != "own":
                 raise ValueError('epsilon: a number in [0, 1] or "own"')
             epsilon = capi.EPSILON_OWN
-        states = np.ascontiguousarray(states, dtype=np.float64)
-        if states.ndim != 2 or states.shape[1] != self.state_dims:
-            raise ValueError(f"expected states of shape (n, {self.state_dims}), got {states.shape}")
+        states = _state_rows(states, self.state_dims)
         first, count = self._replica_range(replicas)
         n = states.shape[0]
         if streams is not None:
@@ -684,22 +684,14 @@ class Runner:
         SampledEvaluation(ret, disc, steps, terminal, ties, explored, final_state, streams): ties = tie breaks drawn, explored = random
         actions taken, streams = both states after the last step.  The context is not changed (include/grlx.h: grlx_evaluate_sampled)."""
         states, sampler, epsilon, streams, first, count, n = self._sampled_args(states, sampler, epsilon, streams, replicas)
-        ret, disc = np.zeros((count, n), np.float64), np.zeros((count, n), np.float64)
-        steps, terminal, ties, explored = (np.zeros((count, n), np.int32) for _ in range(4))
-        final_state = np.zeros((count, n, self.state_dims), np.float64)
-        out = np.zeros((count, n, 2), np.uint64)
+        out, ptrs = _episode_outputs(count, n, self.state_dims, _SAMPLED_FIELDS, explored=np.int32, streams=(np.uint64, 2))
         capi.check(self.lib.grlx_evaluate_sampled(self._ctx, first, count, _ptr(states, C.c_double), n, int(max_steps), sampler, epsilon,
-                                                  None if streams is None else _ptr(streams, C.c_uint64), _ptr(ret, C.c_double),
-                                                  _ptr(disc, C.c_double), _ptr(steps, C.c_int32), _ptr(terminal, C.c_int32), _ptr(ties, C.c_int32),
-                                                  _ptr(explored, C.c_int32), _ptr(final_state, C.c_double), _ptr(out, C.c_uint64)))
-        return SampledEvaluation(ret, disc, steps, terminal, ties, explored, final_state, out)
+                                                  None if streams is None else _ptr(streams, C.c_uint64), *ptrs))
+        return SampledEvaluation(*out)
 
     def sampled_trajectory_record_words(self):
         """R of evaluate_sampled_trajectory's records: trajectory_record_words() + 1 (grlx_sampled_trajectory_record_words)"""
-        words = self.lib.grlx_sampled_trajectory_record_words(self._ctx)
-        if words < 0:
-            capi.check(words)
-        return words
+        return capi.check(self.lib.grlx_sampled_trajectory_record_words(self._ctx))
 
     def evaluate_sampled_trajectory(self, states, max_steps, sampler="epsilon", epsilon="own", streams=None, replicas=None):
         """Runner.evaluate_sampled with every step of every episode: SampledTrajectory(..., records), records[replica][start][max_steps][R]
@@ -708,18 +700,11 @@ class Runner:
         grlx_evaluate_sampled_trajectory)."""
         states, sampler, epsilon, streams, first, count, n = self._sampled_args(states, sampler, epsilon, streams, replicas)
         max_steps = int(max_steps)
-        words = self.sampled_trajectory_record_words()
-        ret, disc = np.zeros((count, n), np.float64), np.zeros((count, n), np.float64)
-        steps, terminal, ties, explored = (np.zeros((count, n), np.int32) for _ in range(4))
-        final_state = np.zeros((count, n, self.state_dims), np.float64)
-        out = np.zeros((count, n, 2), np.uint64)
-        records = np.zeros((count, n, max(max_steps, 0), words), np.float64)
+        out, ptrs = _episode_outputs(count, n, self.state_dims, _SAMPLED_FIELDS, explored=np.int32, streams=(np.uint64, 2),
+                                     records=(max_steps, self.sampled_trajectory_record_words()))
         capi.check(self.lib.grlx_evaluate_sampled_trajectory(self._ctx, first, count, _ptr(states, C.c_double), n, max_steps, sampler, epsilon,
-                                                             None if streams is None else _ptr(streams, C.c_uint64), _ptr(ret, C.c_double),
-                                                             _ptr(disc, C.c_double), _ptr(steps, C.c_int32), _ptr(terminal, C.c_int32),
-                                                             _ptr(ties, C.c_int32), _ptr(explored, C.c_int32), _ptr(final_state, C.c_double),
-                                                             _ptr(out, C.c_uint64), _ptr(records, C.c_double)))
-        return SampledTrajectory(ret, disc, steps, terminal, ties, explored, final_state, out, records)
+                                                             None if streams is None else _ptr(streams, C.c_uint64), *ptrs))
+        return SampledTrajectory(*out)
 
     # ---- noisy evaluation: the actor-critic's episodes under its exploration, on a stream and a noise state the episodes carry (grlx_evaluate_noisy)
     def _noisy_args(self, states, sigma, theta, streams, noise, replicas):
@@ -731,9 +716,7 @@ class Runner:
             if theta != "own":
                 raise ValueError('theta: a number in [0, 1] or "own"')
             theta = capi.THETA_OWN
-        states = np.ascontiguousarray(states, dtype=np.float64)
-        if states.ndim != 2 or states.shape[1] != self.state_dims:
-            raise ValueError(f"expected states of shape (n, {self.state_dims}), got {states.shape}")
+        states = _state_rows(states, self.state_dims)
         first, count = self._replica_range(replicas)
         n = states.shape[0]
         if streams is not None:
@@ -756,23 +739,15 @@ class Runner:
         the action range, streams / noise = both states after the last step.  The context is not changed (include/grlx.h:
         grlx_evaluate_noisy)."""
         states, sigma, theta, streams, noise, first, count, n = self._noisy_args(states, sigma, theta, streams, noise, replicas)
-        ret, disc = np.zeros((count, n), np.float64), np.zeros((count, n), np.float64)
-        steps, terminal, clipped = (np.zeros((count, n), np.int32) for _ in range(3))
-        final_state = np.zeros((count, n, self.state_dims), np.float64)
-        out, noise_out = np.zeros((count, n), np.uint64), np.zeros((count, n), np.float64)
+        out, ptrs = _episode_outputs(count, n, self.state_dims, _NOISY_FIELDS, clipped=np.int32, streams=np.uint64, noise=np.float64)
         capi.check(self.lib.grlx_evaluate_noisy(self._ctx, first, count, _ptr(states, C.c_double), n, int(max_steps), sigma, theta,
                                                 None if streams is None else _ptr(streams, C.c_uint64),
-                                                None if noise is None else _ptr(noise, C.c_double), _ptr(ret, C.c_double), _ptr(disc, C.c_double),
-                                                _ptr(steps, C.c_int32), _ptr(terminal, C.c_int32), _ptr(clipped, C.c_int32),
-                                                _ptr(final_state, C.c_double), _ptr(out, C.c_uint64), _ptr(noise_out, C.c_double)))
-        return NoisyEvaluation(ret, disc, steps, terminal, clipped, final_state, out, noise_out)
+                                                None if noise is None else _ptr(noise, C.c_double), *ptrs))
+        return NoisyEvaluation(*out)
 
     def noisy_trajectory_record_words(self):
         """R of evaluate_noisy_trajectory's records: trajectory_record_words() + 2 (grlx_noisy_trajectory_record_words)"""
-        words = self.lib.grlx_noisy_trajectory_record_words(self._ctx)
-        if words < 0:
-            capi.check(words)
-        return words
+        return capi.check(self.lib.grlx_noisy_trajectory_record_words(self._ctx))
 
     def evaluate_noisy_trajectory(self, states, max_steps, sigma="own", theta="own", streams=None, noise=None, replicas=None):
         """Runner.evaluate_noisy with every step of every episode: NoisyTrajectory(..., records), records[replica][start][max_steps][R]
@@ -781,19 +756,12 @@ class Runner:
         (include/grlx.h: grlx_evaluate_noisy_trajectory)."""
         states, sigma, theta, streams, noise, first, count, n = self._noisy_args(states, sigma, theta, streams, noise, replicas)
         max_steps = int(max_steps)
-        words = self.noisy_trajectory_record_words()
-        ret, disc = np.zeros((count, n), np.float64), np.zeros((count, n), np.float64)
-        steps, terminal, clipped = (np.zeros((count, n), np.int32) for _ in range(3))
-        final_state = np.zeros((count, n, self.state_dims), np.float64)
-        out, noise_out = np.zeros((count, n), np.uint64), np.zeros((count, n), np.float64)
-        records = np.zeros((count, n, max(max_steps, 0), words), np.float64)
+        out, ptrs = _episode_outputs(count, n, self.state_dims, _NOISY_FIELDS, clipped=np.int32, streams=np.uint64, noise=np.float64,
+                                     records=(max_steps, self.noisy_trajectory_record_words()))
         capi.check(self.lib.grlx_evaluate_noisy_trajectory(self._ctx, first, count, _ptr(states, C.c_double), n, max_steps, sigma, theta,
                                                            None if streams is None else _ptr(streams, C.c_uint64),
-                                                           None if noise is None else _ptr(noise, C.c_double), _ptr(ret, C.c_double),
-                                                           _ptr(disc, C.c_double), _ptr(steps, C.c_int32), _ptr(terminal, C.c_int32),
-                                                           _ptr(clipped, C.c_int32), _ptr(final_state, C.c_double), _ptr(out, C.c_uint64),
-                                                           _ptr(noise_out, C.c_double), _ptr(records, C.c_double)))
-        return NoisyTrajectory(ret, disc, steps, terminal, clipped, final_state, out, noise_out, records)
+                                                           None if noise is None else _ptr(noise, C.c_double), *ptrs))
+        return NoisyTrajectory(*out)
 
 
 Evaluation = collections.namedtuple("Evaluation", "ret disc steps terminal ties final_state")
@@ -997,52 +965,34 @@ class FqiRunner:
 
     STATE_DIMS = 3          # the pendulum's model state: angle, velocity, time
 
-    def _state_rows(self, states):
-        states = np.ascontiguousarray(states, dtype=np.float64)
-        if states.ndim != 2 or states.shape[1] != self.STATE_DIMS:
-            raise ValueError(f"expected states of shape (n, {self.STATE_DIMS}), got {states.shape}")
-        return states
-
     def evaluate(self, states, replicas=None, max_steps=0):
         """One greedy episode of the fitted policy per (replica, start state) pair, on the device, from states[n][3] (the pendulum's
         MODEL state: angle, velocity, time) to its end or to max_steps (0 = GRLX_MAX_EPISODE_STEPS): Evaluation(ret, disc, steps,
         terminal, ties, final_state), each [replica][start].  The first maximum of Q(obs, .) acts; ties counts the steps at which it was
         not unique (no random draw).  terminal: 1 timed out, 0 cut at max_steps, 3 left the portable math's domain.  disc discounts by
         gamma ** control_step per step.  The context is not changed (include/grlx.h: grlx_fqi_evaluate)."""
-        states = self._state_rows(states)
+        states = _state_rows(states, self.STATE_DIMS)
         first, count = self._replica_range(replicas)
         n = states.shape[0]
-        ret, disc = np.zeros((count, n), np.float64), np.zeros((count, n), np.float64)
-        steps, terminal, ties = np.zeros((count, n), np.int32), np.zeros((count, n), np.int32), np.zeros((count, n), np.int32)
-        final_state = np.zeros((count, n, self.STATE_DIMS), np.float64)
-        capi.check(self.lib.grlx_fqi_evaluate(self._ctx, first, count, _ptr(states, C.c_double), n, int(max_steps), _ptr(ret, C.c_double),
-                                              _ptr(disc, C.c_double), _ptr(steps, C.c_int32), _ptr(terminal, C.c_int32), _ptr(ties, C.c_int32),
-                                              _ptr(final_state, C.c_double)))
-        return Evaluation(ret, disc, steps, terminal, ties, final_state)
+        out, ptrs = _episode_outputs(count, n, self.STATE_DIMS, "ret disc steps terminal ties final_state")
+        capi.check(self.lib.grlx_fqi_evaluate(self._ctx, first, count, _ptr(states, C.c_double), n, int(max_steps), *ptrs))
+        return Evaluation(*out)
 
     def trajectory_record_words(self):
         """R = 11, the doubles of one trajectory record (grlx_fqi_trajectory_record_words)"""
-        words = self.lib.grlx_fqi_trajectory_record_words(self._ctx)
-        if words < 0:
-            capi.check(words)
-        return words
+        return capi.check(self.lib.grlx_fqi_trajectory_record_words(self._ctx))
 
     def evaluate_trajectory(self, states, max_steps, replicas=None):
         """FqiRunner.evaluate with every step of every episode: Trajectory(ret, disc, steps, terminal, ties, final_state, records),
         records[replica][start][max_steps][11] with one record per step taken and zeros behind an episode's end; the views and
         .episode(k, s) are Runner.evaluate_trajectory's (include/grlx.h: grlx_fqi_evaluate_trajectory)."""
-        states = self._state_rows(states)
+        states = _state_rows(states, self.STATE_DIMS)
         first, count = self._replica_range(replicas)
         n, max_steps = states.shape[0], int(max_steps)
-        words = self.trajectory_record_words()
-        ret, disc = np.zeros((count, n), np.float64), np.zeros((count, n), np.float64)
-        steps, terminal, ties = np.zeros((count, n), np.int32), np.zeros((count, n), np.int32), np.zeros((count, n), np.int32)
-        final_state = np.zeros((count, n, self.STATE_DIMS), np.float64)
-        records = np.zeros((count, n, max(max_steps, 0), words), np.float64)
-        capi.check(self.lib.grlx_fqi_evaluate_trajectory(self._ctx, first, count, _ptr(states, C.c_double), n, max_steps, _ptr(ret, C.c_double),
-                                                         _ptr(disc, C.c_double), _ptr(steps, C.c_int32), _ptr(terminal, C.c_int32),
-                                                         _ptr(ties, C.c_int32), _ptr(final_state, C.c_double), _ptr(records, C.c_double)))
-        return Trajectory(ret, disc, steps, terminal, ties, final_state, records)
+        out, ptrs = _episode_outputs(count, n, self.STATE_DIMS, "ret disc steps terminal ties final_state",
+                                     records=(max_steps, self.trajectory_record_words()))
+        capi.check(self.lib.grlx_fqi_evaluate_trajectory(self._ctx, first, count, _ptr(states, C.c_double), n, max_steps, *ptrs))
+        return Trajectory(*out)
 
     # ---- the ensemble over groups of `group_size` consecutive replicas (bagged FQI): Runner's calls of the same names restated
     def _groups(self, replicas, group_size):
@@ -1066,54 +1016,36 @@ class FqiRunner:
         group_size = self._groups(replicas, group_size)[2]
         return EnsembleResult(self.query_ensemble_raw(obs, group_size, replicas), group_size, int(self.cfg.action_steps))
 
-    _RULES = {"vote": capi.ENSEMBLE_VOTE, "mean": capi.ENSEMBLE_MEAN_Q, "mean_q": capi.ENSEMBLE_MEAN_Q}
-
     def evaluate_ensemble(self, states, group_size, rule="vote", replicas=None, max_steps=0):
         """One greedy episode per (group of `group_size` consecutive replicas, start state) pair, on the device: at every step the
         members' first maxima are counted and their Q-values summed in ascending replica order, and the episode takes the first maximum
         of the votes (rule "vote") or of the summed Q (rule "mean").  EnsembleEvaluation(ret, disc, steps, terminal, ties, member_ties,
         agreement, final_state), each [group][start], as Runner.evaluate_ensemble defines them; the episode is FqiRunner.evaluate's.
         The context is not changed (include/grlx.h: grlx_fqi_evaluate_ensemble)."""
-        rule = self._RULES[rule] if isinstance(rule, str) else int(rule)
-        states = self._state_rows(states)
+        rule = _rule(rule)
+        states = _state_rows(states, self.STATE_DIMS)
         first, count, group_size, groups = self._groups(replicas, group_size)
         n = states.shape[0]
-        ret, disc = np.zeros((groups, n), np.float64), np.zeros((groups, n), np.float64)
-        steps, terminal, ties = np.zeros((groups, n), np.int32), np.zeros((groups, n), np.int32), np.zeros((groups, n), np.int32)
-        member_ties, agreement = np.zeros((groups, n), np.int64), np.zeros((groups, n), np.int64)
-        final_state = np.zeros((groups, n, self.STATE_DIMS), np.float64)
-        capi.check(self.lib.grlx_fqi_evaluate_ensemble(self._ctx, first, count, group_size, rule, _ptr(states, C.c_double), n, int(max_steps),
-                                                       _ptr(ret, C.c_double), _ptr(disc, C.c_double), _ptr(steps, C.c_int32),
-                                                       _ptr(terminal, C.c_int32), _ptr(ties, C.c_int32), _ptr(member_ties, C.c_int64),
-                                                       _ptr(agreement, C.c_int64), _ptr(final_state, C.c_double)))
-        return EnsembleEvaluation(ret, disc, steps, terminal, ties, member_ties, agreement, final_state)
+        out, ptrs = _episode_outputs(groups, n, self.STATE_DIMS, _ENSEMBLE_FIELDS, member_ties=np.int64, agreement=np.int64)
+        capi.check(self.lib.grlx_fqi_evaluate_ensemble(self._ctx, first, count, group_size, rule, _ptr(states, C.c_double), n, int(max_steps), *ptrs))
+        return EnsembleEvaluation(*out)
 
     def ensemble_trajectory_record_words(self):
         """R = 13, the doubles of one record of the ensemble's trajectory (grlx_fqi_ensemble_trajectory_record_words)"""
-        words = self.lib.grlx_fqi_ensemble_trajectory_record_words(self._ctx)
-        if words < 0:
-            capi.check(words)
-        return words
+        return capi.check(self.lib.grlx_fqi_ensemble_trajectory_record_words(self._ctx))
 
     def evaluate_ensemble_trajectory(self, states, group_size, max_steps, rule="vote", replicas=None):
         """FqiRunner.evaluate_ensemble with every step of every episode: EnsembleTrajectory(..., records), records[group][start][max_steps]
         [13]; the views, .step_agreement, .step_member_ties and .episode(k, s) are Runner.evaluate_ensemble_trajectory's
         (include/grlx.h: grlx_fqi_evaluate_ensemble_trajectory)."""
-        rule = self._RULES[rule] if isinstance(rule, str) else int(rule)
-        states = self._state_rows(states)
+        rule = _rule(rule)
+        states = _state_rows(states, self.STATE_DIMS)
         first, count, group_size, groups = self._groups(replicas, group_size)
         n, max_steps = states.shape[0], int(max_steps)
-        words = self.ensemble_trajectory_record_words()
-        ret, disc = np.zeros((groups, n), np.float64), np.zeros((groups, n), np.float64)
-        steps, terminal, ties = np.zeros((groups, n), np.int32), np.zeros((groups, n), np.int32), np.zeros((groups, n), np.int32)
-        member_ties, agreement = np.zeros((groups, n), np.int64), np.zeros((groups, n), np.int64)
-        final_state = np.zeros((groups, n, self.STATE_DIMS), np.float64)
-        records = np.zeros((groups, n, max(max_steps, 0), words), np.float64)
-        capi.check(self.lib.grlx_fqi_evaluate_ensemble_trajectory(self._ctx, first, count, group_size, rule, _ptr(states, C.c_double), n, max_steps,
-                                                                  _ptr(ret, C.c_double), _ptr(disc, C.c_double), _ptr(steps, C.c_int32),
-                                                                  _ptr(terminal, C.c_int32), _ptr(ties, C.c_int32), _ptr(member_ties, C.c_int64),
-                                                                  _ptr(agreement, C.c_int64), _ptr(final_state, C.c_double), _ptr(records, C.c_double)))
-        return EnsembleTrajectory(ret, disc, steps, terminal, ties, member_ties, agreement, final_state, records)
+        out, ptrs = _episode_outputs(groups, n, self.STATE_DIMS, _ENSEMBLE_FIELDS, member_ties=np.int64, agreement=np.int64,
+                                     records=(max_steps, self.ensemble_trajectory_record_words()))
+        capi.check(self.lib.grlx_fqi_evaluate_ensemble_trajectory(self._ctx, first, count, group_size, rule, _ptr(states, C.c_double), n, max_steps, *ptrs))
+        return EnsembleTrajectory(*out)
 
     def info(self, replica: int):
         n = C.c_int64(); md = C.c_double(); it = C.c_int32(); err = C.c_double(); rng = (C.c_uint64 * 2)()
