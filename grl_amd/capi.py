@@ -11,7 +11,7 @@ from . import _build
 
 MAX_DIMS, MAX_STATE, MAX_ACTIONS = 8, 12, 8
 
-OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_TABLE_FULL, ERR_DOMAIN, ERR_ROWS_FULL, ERR_OOM = 0, -1, -2, -3, -4, -5, -6, -7
+OK, ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_TABLE_FULL, ERR_DOMAIN, ERR_ROWS_FULL, ERR_OOM, ERR_STOPPED = 0, -1, -2, -3, -4, -5, -6, -7, -8
 ENV_PENDULUM, ENV_CART_POLE, ENV_ACROBOT, ENV_COMPASS_WALKER, ENV_CART_POLE_BALANCING, ENV_EXTERNAL = 0, 1, 2, 3, 4, 5
 AGENT_SARSA, AGENT_Q, AGENT_AC, AGENT_EXPECTED_SARSA, AGENT_ADVANTAGE, AGENT_QV = 0, 1, 2, 3, 4, 5
 TRACE_NONE, TRACE_REPLACING, TRACE_ACCUMULATING = 0, 1, 2
@@ -70,6 +70,17 @@ class SnapshotInfo(C.Structure):
                 ("rows", C.c_uint32), ("record_bytes", C.c_uint32), ("trials_run", C.c_int64),
                 ("total_bytes", C.c_uint64), ("header_bytes", C.c_uint64), ("n_records", C.c_uint64), ("checksum", C.c_uint64),
                 ("section_bytes", C.c_uint64 * 5), ("config", Config)]
+
+
+class TrajectoryChunkC(C.Structure):
+    """grlx_trajectory_chunk (include/grlx.h): what the sink of grlx_evaluate_trajectory_stream is handed"""
+    _fields_ = [("struct_size", C.c_int32), ("first_start", C.c_int32), ("n_starts", C.c_int32), ("rows", C.c_int32), ("max_steps", C.c_int32),
+                ("record_words", C.c_int32), ("state_dims", C.c_int32), ("ret", C.POINTER(C.c_double)), ("disc", C.POINTER(C.c_double)),
+                ("steps", C.POINTER(C.c_int32)), ("terminal", C.POINTER(C.c_int32)), ("ties", C.POINTER(C.c_int32)),
+                ("final_state", C.POINTER(C.c_double)), ("records", C.POINTER(C.c_double))]
+
+
+TRAJECTORY_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(TrajectoryChunkC))      # grlx_trajectory_sink
 
 
 class GrlxError(RuntimeError):
@@ -145,6 +156,7 @@ _SIGS = {
     "grlx_evaluate_ensemble_trajectory": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_double), C.c_int, C.c_int, _P(C.c_double),
                                                     _P(C.c_double), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64),
                                                     _P(C.c_double), _P(C.c_double)]),
+    "grlx_evaluate_trajectory_stream": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P(C.c_double), C.c_int, C.c_int, TRAJECTORY_SINK, C.c_void_p]),
     "grlx_evaluate_sampled": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P(C.c_double), C.c_int, C.c_int, C.c_int, C.c_double, _P(C.c_uint64),
                                         _P(C.c_double), _P(C.c_double), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_double),
                                         _P(C.c_uint64)]),
@@ -210,7 +222,8 @@ _NEWER_SIGS = ("grlx_snapshot_size", "grlx_snapshot_save", "grlx_snapshot_load",
                "grlx_fqi_query_ensemble", "grlx_fqi_evaluate_ensemble", "grlx_fqi_ensemble_trajectory_record_words",
                "grlx_fqi_evaluate_ensemble_trajectory",
                "grlx_evaluate_sampled", "grlx_sampled_trajectory_record_words", "grlx_evaluate_sampled_trajectory", "grlx_episode_streams",
-               "grlx_evaluate_noisy", "grlx_noisy_trajectory_record_words", "grlx_evaluate_noisy_trajectory", "grlx_episode_stream_words")
+               "grlx_evaluate_noisy", "grlx_noisy_trajectory_record_words", "grlx_evaluate_noisy_trajectory", "grlx_episode_stream_words",
+               "grlx_evaluate_trajectory_stream")
 # grlx_kernel_plan flags
 PLAN_STAMPS_IN_PLACE, PLAN_STAMPS_DEFERRED, PLAN_SWEEP, PLAN_SERVER_OFF, PLAN_WALKER_SERVER, PLAN_FITS_YES, PLAN_FITS_NO = 1, 2, 4, 8, 16, 32, 64
 ENSEMBLE_VOTE, ENSEMBLE_MEAN_Q = 0, 1       # grlx_evaluate_ensemble's rule

@@ -23,6 +23,10 @@ bool have_device() { return grlx_device_count() > 0; }
 // of the last grlx_run first (its stream may be non-blocking with respect to the NULL stream).
 int drain(grlx_ctx *ctx)
 {
+  // from inside the sink of grlx_evaluate_trajectory_stream: the chunks in flight read the tables, and a copy on the null stream would
+  // wait for them one way or the other -- no call on this context is served until the streamed call has returned
+  if (ctx->streaming)
+    return fail(GRLX_ERR_INVALID, "a streamed call is in progress on this context (grlx_evaluate_trajectory_stream has not returned): no other call on it is served from inside the sink");
   if (ctx->run_pending)
   {
     HIP_TRY(hipStreamSynchronize(ctx->run_stream));
@@ -236,13 +240,15 @@ int grlx_create(const grlx_config *cfg, const int64_t *seeds, grlx_ctx **out)
 
 int grlx_destroy(grlx_ctx *ctx)
 {
-  delete ctx;      // (null: nothing to do) every device allocation, stream and event of the context goes with its owner
+  STREAM_REFUSES(ctx, "grlx_destroy");
+  delete ctx;     // (null: nothing to do) every device allocation, stream and event of the context goes with its owner
   return GRLX_OK;
 }
 
 int grlx_set_diag(grlx_ctx *ctx, int enable)
 {
   if (!ctx) return fail(GRLX_ERR_INVALID, "null ctx");
+  STREAM_REFUSES(ctx, "grlx_set_diag");
   if (enable && ctx->sweep) return fail(GRLX_ERR_INVALID, "diagnostics are not built for a sweep context (grlx_set_replica_params)");
   if (enable == 2 && ctx->cfg.trace == GRLX_TRACE_NONE)
     return fail(GRLX_ERR_INVALID, "stamps of the production ordering (grlx_set_diag 2) are not built for a context without a trace "
@@ -295,6 +301,7 @@ int grlx_grow_tables(grlx_ctx *ctx, uint32_t new_log2)
 int grlx_reset_run(grlx_ctx *ctx)
 {
   if (!ctx) return fail(GRLX_ERR_INVALID, "null ctx");
+  STREAM_REFUSES(ctx, "grlx_reset_run");
   DRAIN(ctx);
   HIP_TRY(hipDeviceSynchronize());
   const size_t N = (size_t)ctx->P.n_replicas;

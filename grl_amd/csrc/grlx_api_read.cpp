@@ -1,9 +1,10 @@
-// grlx_api_read.cpp -- the C ABI declared in include/grlx.h: the read side -- policy queries, greedy, sampled and noisy evaluation episodes, chunked over the caller's observations / start states.
+// grlx_api_read.cpp -- the C ABI declared in include/grlx.h: the read side -- policy queries, greedy, sampled and noisy evaluation episodes, chunked over the caller's observations / start states; the streamed trajectories' two-slot pipeline.
 #include "grlx_host.h"
 #include "grlx_query.h"
 #include "grlx_evaluate.h"
 #include "grlx_evaluate_sampled.h"
 #include "grlx_evaluate_noisy.h"
+#include "grlx_evaluate_stream.h"
 
 // ------------------------------------------------------------------------------------------- policy queries ---
 namespace {
@@ -358,6 +359,143 @@ bool is_q(grlx_ctx *ctx) { return q_agent(ctx->cfg.agent); }
 int greedy_words(int env) { return trajectory_words(env, false); }
 int ensemble_words(int env) { return trajectory_words(env, true); }
 
+// ---- streamed trajectories: grlx_evaluate_trajectory's chunks handed to a sink while the next one runs (grlx_evaluate_stream.hip) ----------
+// The outputs of a chunk of nc start states, on the device and in pinned memory alike: the records, ret, disc, final_state, steps, terminal,
+// ties, one behind the other -- every array [rows][nc]..., the 8-byte ones first -- so that ONE contiguous copy brings a chunk back.
+// bytes = nc * stream_out_bytes (grlx_host_rules.h).
+struct StreamLayout {
+  size_t records, ret, disc, final_state, steps, terminal, ties, bytes;
+  StreamLayout(size_t rows, size_t nc, size_t max_steps, size_t R, size_t S)
+  {
+    const size_t pairs = rows * nc;
+    records = 0;
+    ret = records + pairs * max_steps * R * sizeof(double);
+    disc = ret + pairs * sizeof(double);
+    final_state = disc + pairs * sizeof(double);
+    steps = final_state + pairs * S * sizeof(double);
+    terminal = steps + pairs * sizeof(int32_t);
+    ties = terminal + pairs * sizeof(int32_t);
+    bytes = ties + pairs * sizeof(int32_t);
+  }
+};
+
+// the context's slots with room for a chunk -- both, or the first alone for a call of one chunk: made at the first call that needs them,
+// grown when a call needs more (idle then: every call leaves them so)
+int stream_slots_ready(grlx_ctx *ctx, const char *who, int n_slots, size_t dev_bytes, size_t pinned_bytes)
+{
+  for (int k = 0; k < n_slots; ++k)
+  {
+    StreamSlot &s = ctx->stream_slot[k];
+    if (!s.stream)
+    {
+      HIP_TRY(s.stream.create(hipStreamNonBlocking));
+      HIP_TRY(s.done.create(hipEventDisableTiming));
+      HIP_TRY(s.k0.create(hipEventDefault));
+      HIP_TRY(s.k1.create(hipEventDefault));
+    }
+    if (s.dev_bytes < dev_bytes)
+    {
+      s.dev_bytes = 0;
+      if (s.dev.alloc(dev_bytes) != hipSuccess)
+      {
+        (void)hipGetLastError();
+        return fail(GRLX_ERR_OOM, "%s: no device memory for a staging slot of %zu bytes (lower the bound with grlx_set_query_chunk_bytes)", who, dev_bytes);
+      }
+      s.dev_bytes = dev_bytes;
+    }
+    if (s.pinned_bytes < pinned_bytes)
+    {
+      s.pinned_bytes = 0;
+      if (s.pinned.alloc(pinned_bytes) != hipSuccess)
+      {
+        (void)hipGetLastError();
+        return fail(GRLX_ERR_OOM, "%s: no page-locked host memory for a staging slot of %zu bytes (lower the bound with grlx_set_query_chunk_bytes)", who, pinned_bytes);
+      }
+      s.pinned_bytes = pinned_bytes;
+    }
+  }
+  return GRLX_OK;
+}
+
+// The pipeline.  Chunk k runs on slot k & 1, on the slot's stream: its start states in, (the poison kernel,) its kernel, ONE copy of its
+// outputs to the slot's pinned memory, the slot's event.  Then the host waits for chunk k - 1's event and hands that chunk to the sink:
+// the kernel of chunk k overlaps the copy of chunk k - 1, and the sink overlaps both.
+// Ordering.  Device side: chunk k + 2 is enqueued on the stream chunk k ran on, so its kernel writes the slot's device arrays after chunk
+// k's copy has read them.  Pinned side: chunk k + 2 is enqueued in the iteration after the one that retired chunk k, so its copy writes
+// the pinned arrays after the sink has returned from reading them.  The two streams share nothing but the tables, which both only read.
+// A HIP error or a sink's nonzero return ends the enqueueing; both streams are waited for before the call returns, whatever happened.
+int stream_pipeline(grlx_ctx *ctx, const char *who, int first_replica, int rows, const double *states, int n_starts, int max_steps, int R, int chunk,
+                    grlx_trajectory_sink sink, void *user)
+{
+  const size_t S = (size_t)ctx->S, states_cap = sizeof(double) * S * (size_t)chunk;
+  const int n_chunks = (int)(((int64_t)n_starts + chunk - 1) / chunk);
+  const size_t out_cap = StreamLayout((size_t)rows, (size_t)chunk, (size_t)max_steps, (size_t)R, S).bytes;
+  if (int rc = stream_slots_ready(ctx, who, n_chunks > 1 ? 2 : 1, states_cap + out_cap, out_cap)) return rc;
+  const bool timing = g_read_timing;
+  struct Flag { bool &b; Flag(bool &f) : b(f) { b = true; } ~Flag() { b = false; } } in_progress(ctx->streaming);
+  auto first_of = [&](int k) { return (int)((int64_t)k * chunk); };
+  auto count_of = [&](int k) { return n_starts - first_of(k) < chunk ? n_starts - first_of(k) : chunk; };
+
+  auto enqueue = [&](int k) -> int {
+    StreamSlot &s = ctx->stream_slot[k & 1];
+    hipStream_t q = s.stream.get();
+    const int c0 = first_of(k), nc = count_of(k);
+    const StreamLayout L((size_t)rows, (size_t)nc, (size_t)max_steps, (size_t)R, S);
+    char *out = s.dev.as<char>() + states_cap;
+    HIP_TRY(hipMemcpyAsync(s.dev.get(), states + (size_t)c0 * S, sizeof(double) * (size_t)nc * S, hipMemcpyHostToDevice, q));
+    if (ctx->poison) HIP_TRY(launch_poison_registers(ctx->poison_pattern, q));
+    TrajectoryArgs T{};
+    T.e.first_replica = first_replica; T.e.n_replicas = rows; T.e.n_starts = nc; T.e.max_steps = max_steps;
+    T.e.states = s.dev.as<double>(); T.e.sweep = ctx->sweep ? ctx->sweep_dev.get() : nullptr;
+    T.records = (double *)(out + L.records);
+    T.e.ret = (double *)(out + L.ret); T.e.disc = (double *)(out + L.disc); T.e.final_state = (double *)(out + L.final_state);
+    T.e.steps = (int32_t *)(out + L.steps); T.e.terminal = (int32_t *)(out + L.terminal); T.e.ties = (int32_t *)(out + L.ties);
+    if (timing) HIP_TRY(hipEventRecord(s.k0.get(), q));       // grlx_read_kernel_timing: around the chunk's kernel, read when it is retired
+    HIP_TRY(launch_trajectory_stream(ctx->P, T, q));
+    if (timing) HIP_TRY(hipEventRecord(s.k1.get(), q));
+    HIP_TRY(hipMemcpyAsync(s.pinned.get(), out, L.bytes, hipMemcpyDeviceToHost, q));
+    HIP_TRY(hipEventRecord(s.done.get(), q));
+    return GRLX_OK;
+  };
+  auto retire = [&](int k) -> int {
+    StreamSlot &s = ctx->stream_slot[k & 1];
+    const int c0 = first_of(k), nc = count_of(k);
+    const StreamLayout L((size_t)rows, (size_t)nc, (size_t)max_steps, (size_t)R, S);
+    HIP_TRY(hipEventSynchronize(s.done.get()));
+    if (timing)
+    {
+      float ms = 0;
+      HIP_TRY(hipEventElapsedTime(&ms, s.k0.get(), s.k1.get()));
+      g_read_ms += ms;
+      g_read_chunks++;
+    }
+    const char *in = s.pinned.get();
+    grlx_trajectory_chunk c;
+    c.struct_size = (int32_t)sizeof(c);
+    c.first_start = c0; c.n_starts = nc; c.rows = rows; c.max_steps = max_steps; c.record_words = R; c.state_dims = (int32_t)S;
+    c.ret = (const double *)(in + L.ret); c.disc = (const double *)(in + L.disc);
+    c.steps = (const int32_t *)(in + L.steps); c.terminal = (const int32_t *)(in + L.terminal); c.ties = (const int32_t *)(in + L.ties);
+    c.final_state = (const double *)(in + L.final_state); c.records = (const double *)(in + L.records);
+    if (const int v = sink(user, &c))
+      return fail(GRLX_ERR_STOPPED, "%s: the sink returned %d at chunk %d (start states %d ... %d): nothing further is delivered", who, v, k, c0, c0 + nc - 1);
+    return GRLX_OK;
+  };
+
+  int rc = GRLX_OK;
+  for (int k = 0; k <= n_chunks && rc == GRLX_OK; ++k)
+  {
+    if (k < n_chunks) rc = enqueue(k);
+    if (rc == GRLX_OK && k > 0) rc = retire(k - 1);
+  }
+  for (StreamSlot &s : ctx->stream_slot)
+  {
+    if (!s.stream) continue;                           // a context that has only ever streamed single chunks has one slot
+    const hipError_t e = hipStreamSynchronize(s.stream.get());
+    if (e != hipSuccess && rc == GRLX_OK) rc = fail(GRLX_ERR_HIP, "%s: hipStreamSynchronize failed: %s", who, hipGetErrorString(e));
+  }
+  return rc;
+}
+
 } // namespace
 extern "C" {
 
@@ -466,6 +604,33 @@ int grlx_evaluate_trajectory(grlx_ctx *ctx, int first_replica, int n_replicas, c
 {
   return evaluate_impl(ctx, "grlx_evaluate_trajectory", "grlx_evaluate", first_replica, n_replicas, states, n_starts, max_steps, ret, disc, steps, terminal,
                        ties, final_state, records);
+}
+
+// grlx_evaluate_trajectory's result chunk by chunk (stream_pipeline above); every refusal comes before anything is allocated or launched
+int grlx_evaluate_trajectory_stream(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps,
+                                    grlx_trajectory_sink sink, void *user)
+{
+  const char *who = "grlx_evaluate_trajectory_stream";
+  if (int rc = evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps)) return rc;
+  STREAM_REFUSES(ctx, "grlx_evaluate_trajectory_stream");
+  if (!sink) return fail(GRLX_ERR_INVALID, "%s: sink is null (for the whole result in one array call grlx_evaluate_trajectory)", who);
+  if (max_steps == 0)
+    return fail(GRLX_ERR_INVALID, "%s: max_steps = 0: the records are sized by max_steps, so there is no default here (1 ... GRLX_MAX_EPISODE_STEPS = %d)", who,
+                GRLX_MAX_EPISODE_STEPS);
+  const int S = ctx->S, R = trajectory_words(ctx->cfg.env, false);
+  const int chunk = stream_chunk(g_query_chunk_bytes, n_replicas, max_steps, R, S, n_starts);
+  if (chunk < 0)
+  {
+    const uint64_t column = (uint64_t)n_replicas * (uint64_t)max_steps * (uint64_t)R * sizeof(double);
+    return fail(GRLX_ERR_INVALID, "%s: one start state's column of records is %llu bytes (%d rows x %d steps x %d words x 8; %llu with its sums) and exceeds "
+                "half the staging bound, %llu of %llu bytes (two chunks are staged at a time): ask for fewer replicas per call, a smaller max_steps, or raise the "
+                "bound with grlx_set_query_chunk_bytes", who, (unsigned long long)column, n_replicas, max_steps, R,
+                (unsigned long long)stream_start_bytes(n_replicas, max_steps, R, S), (unsigned long long)(g_query_chunk_bytes / 2),
+                (unsigned long long)g_query_chunk_bytes);
+  }
+  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
+  DRAIN(ctx);
+  return stream_pipeline(ctx, who, first_replica, n_replicas, states, n_starts, max_steps, R, chunk, sink, user);
 }
 
 int grlx_evaluate_ensemble_trajectory(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule, const double *states, int n_starts,

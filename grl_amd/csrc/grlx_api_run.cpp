@@ -27,6 +27,7 @@ static bool env_server_ready(grlx_ctx *ctx, size_t mail_bytes)
 static int run_trials(grlx_ctx *ctx, int n_trials, uint64_t steps_budget, void *stream)
 {
   if (!ctx || n_trials < 0) return fail(GRLX_ERR_INVALID, "bad argument");
+  STREAM_REFUSES(ctx, "grlx_run / grlx_run_steps");
   if (ctx->cfg.env == GRLX_ENV_EXTERNAL) return fail(GRLX_ERR_INVALID, "this context has no environment (GRLX_ENV_EXTERNAL): drive it through grlx_agent_start / _step / _end");
   if (n_trials == 0) return GRLX_OK;
   if (steps_budget != 0 && (ctx->P.tap_capacity > 0 || ctx->P.diag_out))
@@ -356,6 +357,7 @@ int grlx_set_replica_params(grlx_ctx *ctx, int param, const double *values)
 {
   if (!ctx || !values) return fail(GRLX_ERR_INVALID, "null argument");
   if (param < 0 || param > 3) return fail(GRLX_ERR_INVALID, "param %d is not one of GRLX_PARAM_*", param);
+  STREAM_REFUSES(ctx, "grlx_set_replica_params");
   if (ctx->launched) return fail(GRLX_ERR_INVALID, "grlx_set_replica_params is allowed only before the first launch of the context");
   int rc = sweep_admits(ctx->cfg, ctx->P);
   if (rc != GRLX_OK) return rc;

@@ -264,6 +264,7 @@ int grlx_snapshot_load(grlx_ctx *ctx, const void *buf, uint64_t bytes)
 {
   if (!have_device()) return fail(GRLX_ERR_NO_DEVICE, "no HIP device: grlx has no CPU fallback");
   if (!ctx || !buf) return fail(GRLX_ERR_INVALID, "grlx_snapshot_load: null argument");
+  STREAM_REFUSES(ctx, "grlx_snapshot_load");
   if (ctx->launched) return fail(GRLX_ERR_INVALID, "grlx_snapshot_load is allowed only on a context that has launched nothing yet");
   int rc = snapshot_not_built(ctx, "grlx_snapshot_load");
   if (rc != GRLX_OK) return rc;

@@ -95,6 +95,7 @@ int grlx_export_weights(grlx_ctx *ctx, int table, int replica, double *out)
 int grlx_load_weights(grlx_ctx *ctx, int table, int first_replica, int n_replicas, const double *dense, uint64_t count)
 {
   if (!ctx || !dense || table < 0 || table >= ctx->n_tables) return fail(GRLX_ERR_INVALID, "bad argument");
+  STREAM_REFUSES(ctx, "grlx_load_weights");
   const int N = ctx->P.n_replicas;
   if (first_replica < 0 || n_replicas < 0 || first_replica > N || n_replicas > N - first_replica)
     return fail(GRLX_ERR_INVALID, "replica range [%d, %d) outside [0, %d)", first_replica, first_replica + n_replicas, N);

@@ -154,6 +154,18 @@ __device__ __forceinline__ double record_head(int w, double action, double rewar
   return out;
 }
 
+// lane j < 16 of a group writes its words of the single-policy record at rec: word j, and word j + 16 where the record has one
+// (trajectory_q_kernel, trajectory_ac_kernel and their streamed twins in grlx_evaluate_stream.hip)
+template <int D, int S>
+__device__ __forceinline__ void record_store16(double *rec, int j, double action, double reward, double value, int mai, int man, int code,
+                                               const double (&obs)[D], const double (&x)[S])
+{
+  constexpr int R = GRLX_TRAJ_OBS + D + S;
+  if (j < R) rec[j] = record_head<D, S>(j, action, reward, value, mai, man, code, obs, x);
+  if constexpr (R > 16)
+    if (j + 16 < R) rec[j + 16] = record_head<D, S>(j + 16, action, reward, value, mai, man, code, obs, x);
+}
+
 // ---- host: the instantiations ------------------------------------------------------------------------------------------------------------
 // The grid of the single-policy kernels: a 16-lane group per (replica, start state) pair, four pairs per wave
 inline unsigned pair_blocks(const EvaluateArgs &A)

@@ -335,17 +335,6 @@ __device__ __forceinline__ double ensemble_record_word(int w, double action, dou
   return out;
 }
 
-// lane j < 16 of a group writes its words of the single-policy record at rec: word j, and word j + 16 where the record has one
-template <int D, int S>
-__device__ __forceinline__ void record_store16(double *rec, int j, double action, double reward, double value, int mai, int man, int code,
-                                               const double (&obs)[D], const double (&x)[S])
-{
-  constexpr int R = GRLX_TRAJ_OBS + D + S;
-  if (j < R) rec[j] = record_head<D, S>(j, action, reward, value, mai, man, code, obs, x);
-  if constexpr (R > 16)
-    if (j + 16 < R) rec[j + 16] = record_head<D, S>(j + 16, action, reward, value, mai, man, code, obs, x);
-}
-
 // evaluate_q_kernel with records.  After the Q-values are in LDS every lane of the group reads them (broadcast) and runs findmax itself,
 // as the ensemble kernel's threads do: the same bits in every lane, and no word is handed back through LDS.
 template <int ENV, int NA>

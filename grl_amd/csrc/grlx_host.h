@@ -60,6 +60,22 @@ struct DevEvent : Owner<hipEvent_t, hipEventDestroy> {
   hipError_t create(unsigned flags) { reset(); return hipEventCreateWithFlags(&h, flags); }
   hipEvent_t get() const { return h; }
 };
+struct PinnedBuf : Owner<void *, hipHostFree> {      // page-locked host memory: the target of an asynchronous copy
+  hipError_t alloc(size_t bytes) { reset(); return hipHostMalloc(&h, bytes ? bytes : 8, hipHostMallocDefault); }
+  char *get() const { return (char *)h; }
+};
+
+// One of the two staging slots of grlx_evaluate_trajectory_stream (grlx_api_read.cpp): a chunk's device arrays (the start states in, then
+// the outputs in the chunk's layout), the pinned copy of the outputs, the stream the chunk runs on, the event behind its last copy, and
+// the two events around its kernel (grlx_read_kernel_timing).  Made at the first streamed call, grown when a call needs more, released
+// with the context.
+struct StreamSlot {
+  DevBuf    dev;
+  PinnedBuf pinned;
+  size_t    dev_bytes = 0, pinned_bytes = 0;
+  DevStream stream;
+  DevEvent  done, k0, k1;
+};
 } // namespace grlx
 
 struct grlx_ctx {
@@ -120,10 +136,19 @@ struct grlx_ctx {
   bool         no_trace_td = false, no_trace_ac = false;
   double       snap_pack_ms = -1, snap_unpack_ms = -1;   // diagnostic: device time of the snapshot kernels in the last save / load
   bool         launched = false;          // a rollout or per-step kernel has run in this context: its replicas' parameters are fixed
+  // grlx_evaluate_trajectory_stream: its two slots, and whether a call is between its first launch and its return -- that is, whether the
+  // caller's sink may be running (STREAM_REFUSES, drain)
+  StreamSlot   stream_slot[2];
+  bool         streaming = false;
 };
 
-namespace grlx { int drain(grlx_ctx *ctx); }      // wait for the rollouts of the last grlx_run (grlx_api_context.cpp)
+// Wait for the rollouts of the last grlx_run (grlx_api_context.cpp).  Every entry point that reads or writes the context's device memory
+// outside a rollout passes here, so this is also where a call made from inside a streamed call's sink is refused.
+namespace grlx { int drain(grlx_ctx *ctx); }
 #define DRAIN(ctx) do { int rc__ = drain(ctx); if (rc__ != GRLX_OK) return rc__; } while (0)
+// ... and the entry points that change the context without (or before) passing DRAIN say it themselves
+#define STREAM_REFUSES(ctx, who)                                                                                                  \
+  do { if ((ctx) && (ctx)->streaming) return fail(GRLX_ERR_INVALID, who ": a streamed call is in progress on this context (grlx_evaluate_trajectory_stream has not returned)"); } while (0)
 #define SWEEP_REFUSES(ctx, what)                                                                                                  \
   do { if ((ctx) && (ctx)->sweep) return fail(GRLX_ERR_INVALID, what " is not built for a sweep context (grlx_set_replica_params): it would run on the shared values"); } while (0)
 

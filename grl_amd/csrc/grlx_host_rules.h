@@ -56,4 +56,29 @@ inline size_t table_bytes(size_t N, size_t n_tables, uint32_t logC) { return (N 
 inline size_t tval_bytes(size_t N, uint32_t logC) { return (N * sizeof(double)) << logC; }
 inline size_t trace_words(size_t N) { return N * kRuleTraceWords; }
 
+// ---- streamed trajectories (grlx_evaluate_trajectory_stream): what one chunk stages, and how many start states a chunk holds
+// The bytes one start state puts on the device, and the part of them that comes back: its state in (S doubles) and, for each of `rows`
+// replicas, max_steps records of R doubles, ret, disc, the final state (S doubles) and steps, terminal, ties (int32).  The same count
+// grlx_evaluate_trajectory bounds.
+inline uint64_t stream_out_bytes(int rows, int max_steps, int R, int S)
+{
+  return (uint64_t)rows * ((uint64_t)max_steps * (uint64_t)R * 8u + 2u * 8u + (uint64_t)S * 8u + 3u * 4u);
+}
+inline uint64_t stream_start_bytes(int rows, int max_steps, int R, int S) { return (uint64_t)S * 8u + stream_out_bytes(rows, max_steps, R, S); }
+
+// Two slots share the staging bound, so a chunk gets half of it (bound / 2, rounded down).  Start states per chunk: the largest count
+// whose bytes fit the half, at most n_starts, and at most what one launch's grid takes -- a 16-lane group per (row, start state) pair,
+// kRulePairsPerBlock pairs per block, 2^31 - 1 blocks.  -1: a single start state does not fit the half, and the call is refused.
+constexpr uint64_t kRulePairsPerBlock = 16;          // 4 groups per wave x kQueryWaves waves
+constexpr uint64_t kRuleMaxBlocks = 0x7fffffffull;
+inline int stream_chunk(uint64_t bound, int rows, int max_steps, int R, int S, int n_starts)
+{
+  const uint64_t half = bound / 2, one = stream_start_bytes(rows, max_steps, R, S);
+  if (one > half) return -1;
+  uint64_t fit = half / one;
+  if (rows > 0 && fit > kRuleMaxBlocks * kRulePairsPerBlock / (uint64_t)rows) fit = kRuleMaxBlocks * kRulePairsPerBlock / (uint64_t)rows;
+  if (fit > (uint64_t)(n_starts < 0 ? 0 : n_starts)) fit = (uint64_t)(n_starts < 0 ? 0 : n_starts);
+  return (int)fit;
+}
+
 } // namespace grlx

@@ -644,6 +644,47 @@ class Runner:
         capi.check(self.lib.grlx_evaluate_trajectory(self._ctx, first, count, _ptr(states, C.c_double), n, max_steps, *ptrs))
         return Trajectory(*out)
 
+    def evaluate_trajectory_stream(self, states, max_steps, sink, replicas=None) -> int:
+        """Runner.evaluate_trajectory's result chunk by chunk: sink(chunk) is called once per chunk of consecutive start states, in ascending
+        order, with a TrajectoryChunk(first_start, ret, disc, steps, terminal, ties, final_state, records) of READ-ONLY views into the
+        library's staging memory -- [replica][start of the chunk]..., records [replica][start][max_steps][R], the views .action, .reward, ...
+        of a Trajectory -- while the next chunk is computed and copied.  The views are valid only inside the call of the sink: copy what
+        is to be kept.  A truthy return of the sink stops the stream (GrlxError with ERR_STOPPED; an int's value is in the message); an
+        exception raised in the sink stops it too and is raised again once the library has returned.  No other method of this Runner may
+        be called from inside the sink (ERR_INVALID, "a streamed call is in progress").  Returns the number of chunks delivered
+        (include/grlx.h: grlx_evaluate_trajectory_stream)."""
+        states = _state_rows(states, self.state_dims)
+        first, count = self._replica_range(replicas)
+        delivered, raised = [0], []
+
+        def view(ptr, *shape):
+            a = np.ctypeslib.as_array(ptr, shape=shape)
+            a.flags.writeable = False
+            return a
+
+        def on_chunk(_user, cp):
+            try:
+                c = cp.contents
+                rows, n = c.rows, c.n_starts
+                chunk = TrajectoryChunk(c.first_start, view(c.ret, rows, n), view(c.disc, rows, n), view(c.steps, rows, n), view(c.terminal, rows, n),
+                                        view(c.ties, rows, n), view(c.final_state, rows, n, c.state_dims),
+                                        view(c.records, rows, n, c.max_steps, c.record_words))
+                delivered[0] += 1
+                stop = sink(chunk)
+                if not stop:
+                    return 0
+                return stop if type(stop) is int and -2**31 <= stop < 2**31 else 1
+            except BaseException as ex:              # a callback must not raise into the library: stop the stream, raise after it has returned
+                raised.append(ex)
+                return 1
+
+        cb = capi.TRAJECTORY_SINK(on_chunk) if sink is not None else capi.TRAJECTORY_SINK()
+        rc = self.lib.grlx_evaluate_trajectory_stream(self._ctx, first, count, _ptr(states, C.c_double), states.shape[0], int(max_steps), cb, None)
+        if raised:
+            raise raised[0]
+        capi.check(rc)
+        return delivered[0]
+
     def evaluate_ensemble_trajectory(self, states, group_size, max_steps, rule="vote", replicas=None):
         """Runner.evaluate_ensemble with every step of every episode: EnsembleTrajectory(..., records), records[group][start][max_steps][R];
         beside Trajectory's views .step_agreement (votes[mai] of the step) and .step_member_ties (members with a tie at the step), and
@@ -797,6 +838,12 @@ class _RecordViews:
 
 class Trajectory(_RecordViews, collections.namedtuple("Trajectory", "ret disc steps terminal ties final_state records")):
     """What Runner.evaluate_trajectory returns: Evaluation's fields and records[replica][start][max_steps][R]."""
+    __slots__ = ()
+
+
+class TrajectoryChunk(_RecordViews, collections.namedtuple("TrajectoryChunk", "first_start ret disc steps terminal ties final_state records")):
+    """What the sink of Runner.evaluate_trajectory_stream is handed: the start states first_start ... first_start + ret.shape[1] - 1 of the
+    call, Trajectory's fields for them as read-only views that are valid only inside the sink."""
     __slots__ = ()
 
 

@@ -32,7 +32,8 @@ enum {
   GRLX_ERR_TABLE_FULL = -4,    /* a replica's sparse weight table overflowed (raise capacity) */
   GRLX_ERR_DOMAIN = -5,        /* portable sin/cos argument outside |x| < 2^20                */
   GRLX_ERR_ROWS_FULL = -6,     /* more test rows than reserved at create                      */
-  GRLX_ERR_OOM = -7
+  GRLX_ERR_OOM = -7,
+  GRLX_ERR_STOPPED = -8        /* the sink of a streamed call returned nonzero (the message carries its value) */
 };
 
 /* YAML type strings of the reference these enumerators stand for */
@@ -536,7 +537,7 @@ int  grlx_evaluate_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, in
  * refuses, and the three cases above.  Like the siblings they change nothing in the context, wait for the stream of the last grlx_run
  * and do not count as a launch.  The batch path's: grlx_fqi_evaluate_trajectory (at the end of this file), with the same words.
  * Trajectories of the samplers' episodes: grlx_evaluate_sampled_trajectory (below).
- * NOT BUILT: streaming records to a file descriptor. */
+ * The same result chunk by chunk, without one array for all of it: grlx_evaluate_trajectory_stream (below). */
 enum { GRLX_TRAJ_ACTION = 0, GRLX_TRAJ_REWARD = 1, GRLX_TRAJ_VALUE = 2, GRLX_TRAJ_ACTION_INDEX = 3, GRLX_TRAJ_N_MAX = 4, GRLX_TRAJ_TERMINAL = 5,
        GRLX_TRAJ_OBS = 6, GRLX_TRAJ_ENS_AGREEMENT = 6, GRLX_TRAJ_ENS_MEMBER_TIES = 7, GRLX_TRAJ_ENS_OBS = 8 };
 int  grlx_trajectory_record_words(grlx_ctx *ctx, int ensemble);      /* R; a negative status for a context without such episodes */
@@ -548,6 +549,50 @@ int  grlx_evaluate_ensemble_trajectory(grlx_ctx *ctx, int first_replica, int n_r
                                        double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
                                        int64_t *member_ties, int64_t *agreement, double *final_state,
                                        double *records /*[n_replicas / group_size][n_starts][max_steps][R]*/);
+
+/* --- streamed trajectories: grlx_evaluate_trajectory's result handed to a callback chunk by chunk ---------------------------------------
+ * The episodes, the record words and the sums are grlx_evaluate_trajectory's, bit for bit, for the same agents and contexts; the caller
+ * never holds more than one chunk.  The start states are cut into chunks of consecutive ones; for each chunk, in ascending order, the
+ * sink is called once with the chunk's arrays:
+ *   first_start, n_starts   the chunk covers start states first_start ... first_start + n_starts - 1 of the call; the chunks are
+ *                           contiguous, do not overlap and together cover 0 ... n_starts - 1
+ *   rows                    n_replicas;  max_steps, record_words (R), state_dims (S): the call's
+ *   ret, disc, steps, terminal, ties   [rows][n_starts], element (row, s) at row * n_starts + s -- the CHUNK's n_starts
+ *   final_state             [rows][n_starts][state_dims];   records  [rows][n_starts][max_steps][record_words]
+ * Records behind an episode's end are +0.0.  The pointers lead into page-locked staging memory of the context and are valid only until
+ * the sink returns.  The sink runs on the calling thread, never concurrently with itself; while it runs, the next chunk's kernel and copy
+ * are in flight.  The call returns after the last sink call, with nothing in flight.  Nothing in the context changes; like its sibling
+ * the call waits for the stream of the last grlx_run and does not count as a launch.
+ * Staging: two chunks are staged at a time and share grlx_set_query_chunk_bytes' bound, so a chunk holds the start states whose columns
+ * (records, sums, state) fit HALF the bound, and the call never holds more than the bound on the device, nor more than the bound in
+ * page-locked host memory.  The staging belongs to the context: allocated at the first streamed call, grown when a later call needs
+ * more, released by grlx_destroy.
+ * Stopping: a nonzero return of the sink ends the stream -- no further chunk is delivered, nothing more is enqueued, what is in flight
+ * is waited for -- and the call returns GRLX_ERR_STOPPED with the sink's value in the message.  After a HIP error the call likewise
+ * enqueues nothing more, waits, and returns GRLX_ERR_HIP.
+ * Validated on the host before anything is launched or allocated (GRLX_ERR_INVALID, the sink is not called, the reason and this
+ * function named): everything grlx_evaluate_trajectory refuses; sink == NULL; max_steps == 0; a single start state's column that exceeds
+ * half the staging bound (the bytes, the half bound and the remedies named).  n_starts == 0 or n_replicas == 0: GRLX_OK, no sink call.
+ * Calls from inside the sink.  While the streamed call has not returned, the context serves no other call: GRLX_ERR_INVALID, "a streamed
+ * call is in progress".  Checked: grlx_run, grlx_run_steps, grlx_reset_run, grlx_snapshot_load, grlx_destroy, grlx_load_weights,
+ * grlx_set_replica_params, grlx_set_diag, a nested grlx_evaluate_trajectory_stream, and every call that waits for the last grlx_run before
+ * it touches the context's device memory -- which is every other call that reads or writes it (the queries and evaluations, the reads
+ * named grlx_get_..., grlx_read_... and grlx_export_..., grlx_snapshot_size and _save, grlx_grow_tables, grlx_read, _write and _update,
+ * the per-step entry points).  So read-only calls on the SAME context are NOT allowed from inside the sink either; calls that take no context (grlx_project,
+ * grlx_env_step, grlx_math ...) and calls on another context are.
+ * NOT BUILT: the ensemble, sampled, noisy and batch-path trajectories as streams; a file-descriptor sink (the callback is the primitive). */
+typedef struct grlx_trajectory_chunk {
+  int32_t struct_size;
+  int32_t first_start, n_starts;
+  int32_t rows, max_steps, record_words, state_dims;
+  const double *ret, *disc;
+  const int32_t *steps, *terminal, *ties;
+  const double *final_state;
+  const double *records;
+} grlx_trajectory_chunk;
+typedef int (*grlx_trajectory_sink)(void *user, const grlx_trajectory_chunk *chunk);
+int  grlx_evaluate_trajectory_stream(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][state_dims]*/, int n_starts,
+                                     int max_steps, grlx_trajectory_sink sink, void *user);
 
 /* --- sampled evaluation: the episodes of grlx_evaluate acted by the reference's samplers ------------------------------------------------
  * Q agents.  For every (replica, start state) pair one episode, on the device, in one launch: grlx_evaluate's loop, unchanged -- the
