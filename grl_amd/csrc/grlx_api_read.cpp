@@ -31,14 +31,13 @@ int query_admit(grlx_ctx *ctx, const char *who, int first_replica, int n_replica
   if (n_obs < 0) return fail(GRLX_ERR_INVALID, "%s: n_obs = %d", who, n_obs);
   if (int rc = replica_range_ok(ctx, who, first_replica, n_replicas)) return rc;
   if (!obs) return fail(GRLX_ERR_INVALID, "%s: obs is null", who);
-  for (int o = 0; o < n_obs; ++o)
-    for (int i = 0; i < obs_dims; ++i)
-    { // tile_quant casts floor(x * scaling) to int (tile_coding.cpp:121-125)
-      const double x = obs[(size_t)o * obs_dims + i];
-      if (!std::isfinite(x)) return fail(GRLX_ERR_INVALID, "%s: observation row %d, dimension %d is not finite (%g)", who, o, i, x);
-      if (!(fabs(x * tp.scaling[i]) < 1073741824.))
-        return fail(GRLX_ERR_INVALID, "%s: observation row %d, dimension %d (%g) is out of range: |x * scaling| reaches 2^30", who, o, i, x);
-    }
+  int o = 0, i = 0;                                     // quant_admit_rows (grlx_host_rules.h): the rule grlx_project applies too
+  if (int why = quant_admit_rows(obs, n_obs, obs_dims, tp.scaling, &o, &i))
+  {
+    const double x = obs[(size_t)o * obs_dims + i];
+    if (why == 1) return fail(GRLX_ERR_INVALID, "%s: observation row %d, dimension %d is not finite (%g)", who, o, i, x);
+    return fail(GRLX_ERR_INVALID, "%s: observation row %d, dimension %d (%g) is out of range: |x * scaling| reaches 2^30", who, o, i, x);
+  }
   return GRLX_OK;
 }
 

@@ -182,6 +182,13 @@ int grlx_project(const grlx_tile_spec *spec, const double *in, int n, uint32_t *
   int rc = make_tile_params(*spec, &tp);
   if (rc != GRLX_OK) return rc;
   if (spec->safe != 0) return fail(GRLX_ERR_INVALID, "grlx_project is stateless: projector/tile_coding:safe needs the claim table of a context");
+  int o = 0, i = 0;                                     // what the queries admit (quant_admit_rows, grlx_host_rules.h); nothing is written
+  if (int why = quant_admit_rows(in, n, tp.D, tp.scaling, &o, &i))
+  {
+    const double x = in[(size_t)o * (size_t)tp.D + (size_t)i];
+    if (why == 1) return fail(GRLX_ERR_INVALID, "grlx_project: input row %d, dimension %d is not finite (%g)", o, i, x);
+    return fail(GRLX_ERR_INVALID, "grlx_project: input row %d, dimension %d (%g) is out of range: |x * scaling| reaches 2^30", o, i, x);
+  }
   if (!have_device()) return fail(GRLX_ERR_NO_DEVICE, "no HIP device: grlx has no CPU fallback");
   if (n == 0) return GRLX_OK;
   DevBuf din, dout;

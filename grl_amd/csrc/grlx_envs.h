@@ -234,7 +234,7 @@ template <> struct Env<GRLX_ENV_ACROBOT> {
 };
 
 // dynamics/cart_pole (end_stop = 1) + task/cart_pole/swingup (cart_pole.cpp:41-237);
-// state = [x, theta, xd, thetad, time].  parity unpinned by reference tests.
+// state = [x, theta, xd, thetad, time].  Held to the reference's own cart_pole.cpp through recorded answers (tests/test_gpu_ref_envs.py).
 template <> struct Env<GRLX_ENV_CART_POLE> {
   static constexpr int S = 5, D = 4;
   static constexpr bool kAbsorbing = true;      // can observe() report an absorbing state (terminal = 2)?
@@ -338,7 +338,8 @@ template <> struct Env<GRLX_ENV_CART_POLE_BALANCING> : Env<GRLX_ENV_CART_POLE> {
 // model/compass_walker + task/compass_walker/walk: the simplest walking model with its own
 // RK4 (velocities and angles staged separately), angle wrapping and heel-strike events located
 // by a secant search (SWModel.cpp:15-258, SWModel.h:40-59, compass_walker.cpp:63-94, 251-344).
-// state vector (compass_walker.h:40-42).  parity unpinned by reference tests.
+// state vector (compass_walker.h:40-42).  Held to the reference's own SWModel.cpp and compass_walker.cpp through recorded answers
+// (tests/test_gpu_ref_envs.py).
 template <> struct Env<GRLX_ENV_COMPASS_WALKER> {
   static constexpr int S = 11, D = 5;
   static constexpr bool kAbsorbing = true;      // can observe() report an absorbing state (terminal = 2)?

@@ -56,6 +56,29 @@ inline size_t table_bytes(size_t N, size_t n_tables, uint32_t logC) { return (N 
 inline size_t tval_bytes(size_t N, uint32_t logC) { return (N * sizeof(double)) << logC; }
 inline size_t trace_words(size_t N) { return N * kRuleTraceWords; }
 
+// ---- what a projector admits: tile_quant casts floor(x * scaling) to int (tile_coding.cpp:121-125), so every coordinate of a projector's
+// input must be finite with |x * scaling| < 2^30.  0: the rows [n, dims] are admitted; 1: *row, *dim name the first coordinate that is not
+// finite; 2: the first whose product reaches 2^30 (a product that is not finite counts as reaching it).
+constexpr double kRuleQuantBound = 1073741824.;      // 2^30
+inline bool quant_admits(double x, double scaling)
+{
+  const double q = x * scaling;
+  return x - x == 0. && (q < 0 ? -q : q) < kRuleQuantBound;      // x - x: 0 for finite x, NaN otherwise
+}
+inline int quant_admit_rows(const double *in, int n, int dims, const double *scaling, int *row, int *dim)
+{
+  for (int o = 0; o < n; ++o)
+    for (int i = 0; i < dims; ++i)
+    {
+      const double x = in[(size_t)o * (size_t)dims + (size_t)i];
+      if (quant_admits(x, scaling[i])) continue;
+      *row = o;
+      *dim = i;
+      return x - x == 0. ? 2 : 1;
+    }
+  return 0;
+}
+
 // ---- streamed trajectories (grlx_evaluate_trajectory_stream): what one chunk stages, and how many start states a chunk holds
 // The bytes one start state puts on the device, and the part of them that comes back: its state in (S doubles) and, for each of `rows`
 // replicas, max_steps records of R doubles, ret, disc, the final state (S doubles) and steps, terminal, ties (int32).  The same count

@@ -373,7 +373,9 @@ int  grlx_read_taps(grlx_ctx *ctx, grlx_tap *out, int cap, int *n);
  *     HIP kernel, copies out).  They mirror the plug-in interfaces one to one. */
 
 /* Projector::project -> TileCodingProjector::_project (tile_coding.cpp:103-149):
- * in[n][dims] -> out[n][tilings] reference slot indices. */
+ * in[n][dims] -> out[n][tilings] reference slot indices.  A coordinate that is not finite, or whose |x * tilings / resolution|
+ * reaches 2^30 (the quantisation casts its floor to int), is refused with GRLX_ERR_INVALID naming row and dimension, as the
+ * queries refuse it; nothing is written then. */
 int  grlx_project(const grlx_tile_spec *spec, const double *in, int n, uint32_t *out);
 
 /* Environment::step -> ModeledEnvironment::step (modeled.cpp:160-213):

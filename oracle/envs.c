@@ -2,12 +2,17 @@
  *
  * ModeledEnvironment + DynamicalModel (RK4): base/src/environments/modeled.cpp:132-276
  * Pendulum dynamics + swing-up task:          base/src/environments/pendulum.cpp:40-145
+ *   (pinned by the reference's own pendulum.cpp in oracle/_ref/ref_envs, bit for bit: eom, actuate, start, the wrapped observation,
+ *   the reward and the timeout at any angle, rate and time, tests/test_oracle_ref_envs.py; and by the golden learning curve)
  * Acrobot dynamics + balancing task:         base/src/environments/acrobot.cpp:48-151
  *   (pinned by the reference's own acrobot.cpp in oracle/_ref/ref_envs, bit for bit: tests/test_oracle_ref_envs.py)
  * Cart-pole dynamics + swing-up task:        base/src/environments/cart_pole.cpp:58-237
- *   (the swing-up TASK is unpinned; the DYNAMICS -- end_stop = 1, incl. the :65 quirk -- and DynamicalModel::step
- *   are pinned by tests/template/cart_pole_balancing-pid-0.txt through the balancing task below)
+ *   (pinned by the reference's own cart_pole.cpp in oracle/_ref/ref_envs, bit for bit: the dynamics -- end_stop = 1, incl. the :65
+ *   quirk and the four end-stop overrides --, the swing-up task's start, observe, evaluate, failed and potential under every
+ *   penalty setting and randomization, tests/test_oracle_ref_envs.py; the dynamics and DynamicalModel::step also by
+ *   tests/template/cart_pole_balancing-pid-0.txt through the balancing task below)
  * Cart-pole balancing task:                  base/src/environments/cart_pole.cpp:239-320
+ *   (pinned by the same binary, likewise, and by that golden file)
  * Compass walker model + walk task:          base/src/environments/compass_walker/SWModel.cpp:15-258,
  *   base/include/grl/environments/compass_walker/SWModel.h:40-59, compass_walker.cpp:41-95, 198-344
  *   (pinned by the reference's own SWModel.cpp and compass_walker.cpp in oracle/_ref/ref_envs, bit for bit, likewise)

@@ -202,17 +202,9 @@ static void project_sa_claim(orc_exp *e, const double *obs, double action, int c
     abort();
   }
   p->n = ts->tilings;
-  for (int j = 0; j < p->n; ++j)
-  {
-    if (!e->claim) { p->idx[j] = out[j]; continue; }
-    /* getFeatureLocation (tile_coding.h:116-151): linear probing from h % memory over slots claimed by OTHER hash sums */
-    const uint32_t h = out[j], mem = (uint32_t)ts->memory;
-    uint32_t ii = h % mem;
-    while (e->claim[ii] != (int32_t)h && e->claim[ii] != -1)
-      if (++ii >= mem) ii = 0;
-    if (claim) e->claim[ii] = (int32_t)h;
-    p->idx[j] = ii;
-  }
+  if (e->claim)                                                 /* getFeatureLocation's walk over indices_: tile_coding.c */
+    orc_tile_claim(e->claim, ts->memory, out, p->n, claim, out);
+  for (int j = 0; j < p->n; ++j) p->idx[j] = out[j];
 }
 static void project_sa(orc_exp *e, const double *obs, double action, orc_proj *p)
 { /* a SINGLE projection: claims under safe >= 1 (tile_coding.h:62-66) */

@@ -25,10 +25,12 @@
  * configuration with seed 1 reproduces the reference's own golden file
  * tests/template/pendulum-sarsa-tc-0.txt byte for byte (tests/test_oracle_golden.py;
  * fixture committed as tests/golden/pendulum-sarsa-tc-0.txt).  Everything the
- * reference's tests do not pin (Q-learning, actor-critic, the cart-pole swing-up
- * task) is marked "parity unpinned by reference tests" where it is implemented.
- * The acrobot and the compass walker are pinned by the reference's own sources,
- * compiled unmodified into oracle/_ref/ref_envs (oracle/ref, tests/test_oracle_ref_envs.py).
+ * reference's tests do not pin (Q-learning, actor-critic) is marked "parity
+ * unpinned by reference tests" where it is implemented.
+ * All environments (acrobot, cart-pole swing-up and balancing, pendulum, compass
+ * walker) and the tile coding with its claim table are pinned by the reference's
+ * own sources, compiled unmodified into oracle/_ref/ref_envs and oracle/_ref/ref_tiles
+ * (oracle/ref, tests/test_oracle_ref_envs.py, tests/test_oracle_ref_tiles.py).
  *
  * MATH MODES.  ORC_MATH_LIBM calls the host libm (sin/cos/fmod/pow/log) exactly
  * where the reference does.  ORC_MATH_PORTABLE replaces the transcendental calls by
@@ -157,6 +159,9 @@ void orc_spec_cart_pole_balancing_pid(orc_spec *s);
  * -1 when the spec is invalid (wrapping*scaling not an integer). */
 int orc_tile_project(const orc_tile_spec *t, const double *in, uint32_t *out);
 int orc_tile_project_hash(const orc_tile_spec *t, const double *in, uint32_t *out);   /* full hash sums (safe >= 1) */
+/* getFeatureLocation's walk (tile_coding.h:116-151) for n hash sums over a caller-held claim table of `memory` slots (-1 = free);
+ * claim != 0 takes the slots; out[n] (may be hash) receives the slot indices.  The experiments' claim table goes through it. */
+void orc_tile_claim(int32_t *table, int memory, const uint32_t *hash, int n, int claim, uint32_t *out);
 
 /* a3/a4/a5: one ModeledEnvironment::step on an explicit state.
  * state[S] is updated in place; obs[D], *reward, *terminal are outputs.

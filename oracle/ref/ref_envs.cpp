@@ -1,11 +1,12 @@
-/* ref_envs.cpp -- driver around the reference's own acrobot and compass-walker sources (TEST INFRASTRUCTURE).
+/* ref_envs.cpp -- driver around the reference's own acrobot, cart-pole, pendulum and compass-walker sources (TEST INFRASTRUCTURE).
  *
- * oracle/Makefile links this file with the reference's acrobot.cpp, SWModel.cpp and compass_walker.cpp, compiled unmodified by
- * path against the stand-in header shim/grl/environment.h, into oracle/_ref/ref_envs.  The binary is what pins oracle/envs.c's
- * acrobot and compass walker (tests/test_oracle_ref_envs.py, bit for bit in libm arithmetic) and what tools/record_ref_envs.py
- * records into tests/golden/ref_envs_*.npz for the GPU test.  This file restates nothing of either environment: every number it
- * prints comes out of a call into the reference's code, with one exception, acrobot_step, whose RK4 LOOP is ours (the reference's
- * lives in modeled.cpp, which needs Eigen) around the reference's eom; the two golden files pin that loop in the oracle already.
+ * oracle/Makefile links this file with the reference's acrobot.cpp, cart_pole.cpp, pendulum.cpp, SWModel.cpp and
+ * compass_walker.cpp, compiled unmodified by path against the stand-in header shim/grl/environment.h, into oracle/_ref/ref_envs.
+ * The binary is what pins oracle/envs.c's environments (tests/test_oracle_ref_envs.py, bit for bit in libm arithmetic) and what
+ * tools/record_ref_envs.py records into tests/golden/ref_envs_*.npz for the GPU test.  This file restates nothing of any
+ * environment: every number it prints comes out of a call into the reference's code, with one exception, the *_step commands of
+ * the three Dynamics, whose RK4 LOOP is ours (the reference's lives in modeled.cpp, which needs Eigen) around the reference's
+ * eom; the two golden files pin that loop in the oracle already.
  *
  * Protocol: one command per stdin line, a word followed by numbers (doubles as C99 hex floats or decimals, read by strtod);
  * one answer per stdout line, doubles as %a, integers as %d / %llu.  "error <text>" answers a line that cannot be served.
@@ -15,6 +16,23 @@
  *   acrobot_evaluate x[5] u next[5]         -> reward                      AcrobotBalancingTask::evaluate
  *   acrobot_start d1 d2                     -> x[5]                        AcrobotBalancingTask::start; d1, d2: the two RandGen draws
  *   acrobot_step x[5] u h steps             -> next[5]                     `steps` RK4 sub-steps of h, operation order of modeled.cpp:254-276
+ *   cartpole_eom x[5] u                     -> xd[5]                       CartPoleDynamics::eom (end_stop = 1)
+ *   cartpole_observe x[5]                   -> obs[4] terminal             CartPoleSwingupTask::observe
+ *   cartpole_evaluate x[5] u next[5]        -> reward                      CartPoleSwingupTask::evaluate
+ *   cartpole_start d1                       -> x[5]                        CartPoleSwingupTask::start; d1: the RandGen draw
+ *   cartpole_step x[5] u h steps            -> next[5]                     the RK4 loop around CartPoleDynamics::eom
+ *   cartpole_task timeout randomization end_stop_penalty action_penalty -> ok   CartPoleSwingupTask::configure (shaping 0, gamma 1)
+ *   balancing_observe x[5]                  -> obs[4] terminal             CartPoleBalancingTask::observe
+ *   balancing_evaluate x[5] u next[5]       -> reward                      CartPoleBalancingTask::evaluate
+ *   balancing_start d1                      -> x[5]                        CartPoleBalancingTask::start
+ *   balancing_task timeout                  -> ok                          CartPoleBalancingTask::configure
+ *   pendulum_eom x[3] u                     -> xd[3]                       PendulumDynamics::eom
+ *   pendulum_observe x[3]                   -> obs[2] terminal             PendulumSwingupTask::observe
+ *   pendulum_evaluate x[3] u next[3]        -> reward                      PendulumSwingupTask::evaluate
+ *   pendulum_start d1 test                  -> x[3]                        PendulumSwingupTask::start
+ *   pendulum_actuate u                      -> actuation                   PendulumSwingupTask::actuate (the clamp to +-3)
+ *   pendulum_step x[3] u h steps            -> next[3]                     the RK4 loop around PendulumDynamics::eom
+ *   pendulum_task timeout randomization     -> ok                          PendulumSwingupTask::configure
  *   walker_step slope tau steps sla ha slar har footx torque -> sla ha slar har footx changed      CSWModel::singleStep
  *   walker_model slope tau steps            -> ok                          CompassWalkerModel::configure
  *   walker_task timeout variation slope negative_reward -> ok              CompassWalkerWalkTask::configure (observe 1 1 1 1 1 0 0, steps 0)
@@ -24,7 +42,8 @@
  *   walker_start seed test                  -> x[11] X                     srand48(seed), CompassWalkerWalkTask::start; X: drand48's 48-bit state after it
  *   walker_start_at X test                  -> x[11] X                     the same from the stream position X (seed48)
  * At start-up the model is configured with slope 0.004, tau 0.2, 20 steps and the task with timeout 100, variation 0.2,
- * slope 0.004, negative reward -100.
+ * slope 0.004, negative reward -100; the cart-pole swing-up task with timeout 9.99, randomization 0 and no penalties, the
+ * balancing task with timeout 9.99, the pendulum's with timeout 2.99 and randomization 0.
  * CompassWalkerModel::step never writes next[8] (the step distance): the reference leaves it uninitialised, the stand-in's
  * resize leaves it 0, and the tests do not compare it.
  */
@@ -36,6 +55,8 @@
 #include <vector>
 
 #include <grl/environments/acrobot.h>
+#include <grl/environments/cart_pole.h>
+#include <grl/environments/pendulum.h>
 #include <grl/environments/compass_walker/compass_walker.h>
 
 using namespace grl;
@@ -111,9 +132,21 @@ struct Driver
   AcrobotBalancingTask balancing;
   CompassWalkerModel walker;
   CompassWalkerWalkTask walk;
+  CartPoleDynamics cart_pole;
+  CartPoleSwingupTask swingup;
+  CartPoleBalancingTask cart_balancing;
+  PendulumDynamics pendulum;
+  PendulumSwingupTask pendulum_swingup;
 
   Driver()
   {
+    Configuration c;
+    c.set("end_stop", 1);
+    cart_pole.configure(c);
+    pendulum.configure(c);
+    configure_swingup(9.99, 0, 0, 0);
+    configure_cart_balancing(9.99);
+    configure_pendulum(2.99, 0);
     configure_model(0.004, 0.2, 20);
     configure_task(100, 0.2, 0.004, -100);
   }
@@ -139,8 +172,124 @@ struct Driver
     walk.configure(c);
   }
 
+  void configure_swingup(double timeout, int randomization, int end_stop_penalty, int action_penalty)
+  {
+    Configuration c;
+    c.set("timeout", timeout);
+    c.set("randomization", randomization);
+    c.set("shaping", 0);
+    c.set("gamma", 1.0);
+    c.set("end_stop_penalty", end_stop_penalty);
+    c.set("action_penalty", action_penalty);
+    swingup.configure(c);
+  }
+
+  void configure_cart_balancing(double timeout)
+  {
+    Configuration c;
+    c.set("timeout", timeout);
+    cart_balancing.configure(c);
+  }
+
+  void configure_pendulum(double timeout, double randomization)
+  {
+    Configuration c;
+    c.set("timeout", timeout);
+    c.set("randomization", randomization);
+    pendulum_swingup.configure(c);
+  }
+
+  /* Task::observe / evaluate / start of any task, and Dynamics::eom / the RK4 loop of any dynamics, on S state dimensions */
+  void observe(const Task &task, const std::vector<double> &a, size_t S)
+  {
+    Observation obs; int terminal = -1;
+    task.observe(take(a, 0, S), &obs, &terminal);
+    print(obs.v); printf(" %d", terminal);
+  }
+
+  void evaluate(const Task &task, const std::vector<double> &a, size_t S)
+  {
+    double reward = 0;
+    task.evaluate(take(a, 0, S), action_of(a[S]), take(a, S + 1, S), &reward);
+    printf("%a", reward);
+  }
+
+  void start(Task &task, const std::vector<double> &draws, int test)
+  {
+    Vector x;
+    g_draws.assign(draws.begin(), draws.end());
+    task.start(test, &x);
+    if (!g_draws.empty())
+      throw Exception("the reference left a thread-local draw unused");
+    print(x);
+  }
+
+  bool serve_dynamical(const std::string &cmd, const std::vector<double> &a)
+  {
+    if (cmd == "cartpole_eom" && a.size() == 6)
+    {
+      Vector xd;
+      cart_pole.eom(take(a, 0, 5), take(a, 5, 1), &xd);
+      print(xd);
+    }
+    else if (cmd == "cartpole_observe" && a.size() == 5)
+      observe(swingup, a, 5);
+    else if (cmd == "cartpole_evaluate" && a.size() == 11)
+      evaluate(swingup, a, 5);
+    else if (cmd == "cartpole_start" && a.size() == 1)
+      start(swingup, a, 0);
+    else if (cmd == "cartpole_step" && a.size() == 8)
+      print(rk4(cart_pole, take(a, 0, 5), take(a, 5, 1), a[6], (int)a[7]));
+    else if (cmd == "cartpole_task" && a.size() == 4)
+    {
+      configure_swingup(a[0], (int)a[1], (int)a[2], (int)a[3]);
+      printf("ok");
+    }
+    else if (cmd == "balancing_observe" && a.size() == 5)
+      observe(cart_balancing, a, 5);
+    else if (cmd == "balancing_evaluate" && a.size() == 11)
+      evaluate(cart_balancing, a, 5);
+    else if (cmd == "balancing_start" && a.size() == 1)
+      start(cart_balancing, a, 0);
+    else if (cmd == "balancing_task" && a.size() == 1)
+    {
+      configure_cart_balancing(a[0]);
+      printf("ok");
+    }
+    else if (cmd == "pendulum_eom" && a.size() == 4)
+    {
+      Vector xd;
+      pendulum.eom(take(a, 0, 3), take(a, 3, 1), &xd);
+      print(xd);
+    }
+    else if (cmd == "pendulum_observe" && a.size() == 3)
+      observe(pendulum_swingup, a, 3);
+    else if (cmd == "pendulum_evaluate" && a.size() == 7)
+      evaluate(pendulum_swingup, a, 3);
+    else if (cmd == "pendulum_start" && a.size() == 2)
+      start(pendulum_swingup, std::vector<double>(1, a[0]), (int)a[1]);
+    else if (cmd == "pendulum_actuate" && a.size() == 1)
+    {
+      Vector actuation;
+      pendulum_swingup.actuate(Vector(), Vector(), action_of(a[0]), &actuation);
+      print(actuation);
+    }
+    else if (cmd == "pendulum_step" && a.size() == 6)
+      print(rk4(pendulum, take(a, 0, 3), take(a, 3, 1), a[4], (int)a[5]));
+    else if (cmd == "pendulum_task" && a.size() == 2)
+    {
+      configure_pendulum(a[0], a[1]);
+      printf("ok");
+    }
+    else
+      return false;
+    return true;
+  }
+
   bool serve(const std::string &cmd, const std::vector<double> &a)
   {
+    if (serve_dynamical(cmd, a))
+      return true;
     if (cmd == "acrobot_eom" && a.size() == 6)
     {
       Vector xd;

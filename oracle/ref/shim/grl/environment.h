@@ -1,12 +1,14 @@
 /* grl/environment.h -- STAND-IN for the reference's header of that name (TEST INFRASTRUCTURE).
  *
- * oracle/Makefile compiles three of the reference's environment sources UNMODIFIED, by path, into oracle/_ref/ref_envs:
- *   base/src/environments/acrobot.cpp, base/src/environments/compass_walker/SWModel.cpp and .../compass_walker/compass_walker.cpp.
- * Their own headers (acrobot.h, SWModel.h, compass_walker.h) come from the reference's include directory; this file takes the
- * place of the framework header they all ask for, which needs Eigen and the configuration machinery.  It is our own text, written
- * from what the compiler asks for when it compiles those three files: every name below is here because one of them uses it, and
- * does the least that lets the code under test (eom, start, observe, evaluate, step, singleStep, configure) run as written.
- * Nothing here computes a number the tests compare, except Vector's element access.
+ * oracle/Makefile compiles five of the reference's environment sources UNMODIFIED, by path, into oracle/_ref/ref_envs:
+ *   base/src/environments/acrobot.cpp, cart_pole.cpp, pendulum.cpp, compass_walker/SWModel.cpp and compass_walker/compass_walker.cpp
+ * (and, through the stand-in grl/projector.h beside this file, base/src/projectors/tile_coding.cpp into oracle/_ref/ref_tiles).
+ * Their own headers (acrobot.h, cart_pole.h, pendulum.h, SWModel.h, compass_walker.h, tile_coding.h) come from the reference's
+ * include directory; this file takes the place of the framework header they all ask for, which needs Eigen and the configuration
+ * machinery.  It is our own text, written from what the compiler asks for when it compiles those files: every name below is here
+ * because one of them uses it, and does the least that lets the code under test (eom, start, observe, evaluate, step, singleStep,
+ * configure, _project) run as written.  Nothing here computes a number the tests compare, except Vector's element access and
+ * `extend` (a concatenation).
  */
 #ifndef GRL_ORACLE_REF_SHIM_ENVIRONMENT_H_
 #define GRL_ORACLE_REF_SHIM_ENVIRONMENT_H_
@@ -19,6 +21,8 @@
 #include <deque>
 #include <initializer_list>
 #include <iostream>
+#include <cstdint>
+#include <cstring>
 #include <map>
 #include <string>
 #include <vector>
@@ -53,6 +57,7 @@ class Vector
     };
 
     Vector() { }
+    explicit Vector(size_t n) : d_(n) { }
     size_t size() const { return d_.size(); }
     void resize(size_t n) { d_.resize(n); }
     double &operator[](size_t i) { return d_.at(i); }
@@ -63,6 +68,18 @@ class Vector
   private:
     std::vector<double> d_;
 };
+
+inline std::ostream &operator<<(std::ostream &os, const Vector &v)
+{
+  for (size_t i = 0; i < v.size(); ++i) os << (i ? " " : "") << v[i];
+  return os;
+}
+inline Vector extend(const Vector &head, const Vector &tail)
+{
+  Vector v = head;
+  for (size_t i = 0; i < tail.size(); ++i) v.push(tail[i]);
+  return v;
+}
 
 inline void fill_vector(Vector *) { }
 template<class T, class... Rest> void fill_vector(Vector *v, T first, Rest... rest)
@@ -88,10 +105,18 @@ struct Observation
   Vector v;
   bool absorbing;
   Observation() : absorbing(false) { }
+  operator Vector() const { return v; }
   size_t size() const { return v.size(); }
   double &operator[](size_t i) { return v[i]; }
   const double &operator[](size_t i) const { return v[i]; }
 };
+
+/* what rewardHessian returns: never looked at */
+struct Matrix
+{
+  static Matrix Identity(size_t, size_t) { return Matrix(); }
+};
+inline Matrix diagonal(const Vector &) { return Matrix(); }
 
 struct Action
 {
@@ -146,7 +171,9 @@ struct ConfigurationValue
 {
   double scalar;
   Vector vector;
+  std::string string;
   ConfigurationValue() : scalar(0) { }
+  const std::string &str() const { return string; }
   template<class T> operator T() const { return (T)scalar; }
   Vector v() const { return vector; }
   void *ptr() const { return NULL; }
@@ -155,7 +182,15 @@ class Configuration
 {
   public:
     ConfigurationValue &operator[](const std::string &key) { return values_[key]; }
+    ConfigurationValue operator[](const std::string &key) const { return has(key) ? values_.find(key)->second : ConfigurationValue(); }
+    bool has(const std::string &key) const { return values_.count(key) != 0; }
+    template<class T> bool get(const std::string &key, T &x) const
+    {
+      if (has(key)) x = (T)values_.find(key)->second.scalar;
+      return has(key);
+    }
     void set(const std::string &key, const Vector &v) { values_[key].vector = v; }
+    void set(const std::string &key, const char *text) { values_[key].string = text; }
     template<class T> void set(const std::string &key, T x) { values_[key].scalar = (double)x; }
   private:
     std::map<std::string, ConfigurationValue> values_;
@@ -168,6 +203,7 @@ class Configurable
     virtual void request(ConfigurationRequest *) { }
     virtual void configure(Configuration &) { }
     virtual void reconfigure(const Configuration &) { }
+    virtual Configurable &copy(const Configurable &) { return *this; }
 };
 class Dynamics : public Configurable
 {

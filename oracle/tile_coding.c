@@ -3,7 +3,13 @@
  * Follows base/src/projectors/tile_coding.cpp:45-80 (configure: scaling,
  * integer wrapping), :103-149 (_project) and
  * base/include/grl/projectors/tile_coding.h:78-118 (MurmurHash2 over the
- * coordinate tuple with seed 449, index = hash % memory), safe = 0 only.
+ * coordinate tuple with seed 449, index = hash % memory) and :116-151 (getFeatureLocation: the claim table of safe = 1 / 2,
+ * orc_tile_claim below, which the experiments walk their table with).
+ *
+ * PINNED by the reference's own tile_coding.cpp and tile_coding.h, compiled unmodified into oracle/_ref/ref_tiles (oracle/ref):
+ * tests/test_oracle_ref_tiles.py holds orc_tile_project, orc_tile_project_hash and orc_tile_claim to that binary index by index
+ * on 1 to 8 dimensions, 1 to 32 tilings, wrapping on any dimension, memories that are no power of two, negative coordinates and
+ * inputs on tile edges, and the specs configure() refuses; the golden learning curve pins the pendulum's projector besides.
  */
 #include <math.h>
 #include "oracle.h"
@@ -80,4 +86,22 @@ static int tile_project_impl(const orc_tile_spec *t, const double *in, uint32_t 
     if (!full_hash) out[j] %= (uint32_t)t->memory;
   }
   return 0;
+}
+
+/* getFeatureLocation (tile_coding.h:116-151) over a caller-held claim table (indices_: `memory` slots, -1 = free): each of the n
+ * hash sums walks from h % memory, wrapping at the table's end, past slots claimed by OTHER hash sums, to a free slot or its
+ * own; with `claim` it takes the slot (project(in) always, project(base, variants) under safe = 2 only: tile_coding.h:62-73).
+ * out may be hash.  Like the reference's, the walk does not end on a table without a free slot. */
+void orc_tile_claim(int32_t *table, int memory, const uint32_t *hash, int n, int claim, uint32_t *out)
+{
+  const uint32_t mem = (uint32_t)memory;
+  for (int j = 0; j < n; ++j)
+  {
+    const uint32_t h = hash[j];
+    uint32_t ii = h % mem;
+    while (table[ii] != (int32_t)h && table[ii] != -1)
+      if (++ii >= mem) ii = 0;
+    if (claim) table[ii] = (int32_t)h;
+    out[j] = ii;
+  }
 }

@@ -96,6 +96,8 @@ def load():
     L.orc_spec_pendulum_sarsa.argtypes = [P(Spec)]
     L.orc_spec_cart_pole_balancing_pid.argtypes = [P(Spec)]
     L.orc_tile_project.argtypes = [P(TileSpec), P(C.c_double), P(C.c_uint32)]; L.orc_tile_project.restype = C.c_int
+    L.orc_tile_project_hash.argtypes = [P(TileSpec), P(C.c_double), P(C.c_uint32)]; L.orc_tile_project_hash.restype = C.c_int
+    L.orc_tile_claim.argtypes = [P(C.c_int32), C.c_int, P(C.c_uint32), C.c_int, C.c_int, P(C.c_uint32)]; L.orc_tile_claim.restype = None
     L.orc_env_step.argtypes = [P(Spec), P(C.c_double), C.c_double, P(C.c_double), P(C.c_double), P(C.c_int)]
     L.orc_env_step.restype = C.c_double
     L.orc_env_state_dims.argtypes = [C.c_int]; L.orc_env_obs_dims.argtypes = [C.c_int]

@@ -1,9 +1,10 @@
-"""Case sets that hold the acrobot and the compass walker against the reference's OWN sources (oracle/_ref/ref_envs, built by
-oracle/Makefile from the unmodified reference files), shared by tests/test_oracle_ref_envs.py (CPU: oracle against the binary),
+"""Case sets that hold the acrobot, the cart-pole swing-up, the pendulum and the compass walker against the reference's OWN sources
+(oracle/_ref/ref_envs, built by oracle/Makefile from the unmodified reference files), shared by tests/test_oracle_ref_envs.py (CPU: oracle against the binary),
 tools/record_ref_envs.py (writes the fixtures under tests/golden/) and tests/test_gpu_ref_envs.py (GPU: kernels against the
 fixtures).  Fixed seeds, no clock; the configurations are those of tests/configs.py.
 
-A case set is a dict: state [n, S], action [n], tag [n] (index into TAGS: what the row is there for).  The reference's answers
+A case set is a dict: state [n, S], action [n], tag [n] (index into TAGS: what the row is there for) and, for the cart-pole, variant [n]
+(bit 0: end_stop_penalty, bit 1: action_penalty: the task a row runs under).  The reference's answers
 and the oracle's answers to a case set are dicts with the same keys (ANSWER_KEYS), so that every comparison is one loop.
 """
 import ctypes as C
@@ -20,9 +21,10 @@ REF_BIN = os.path.join(ob.ORACLE_DIR, "_ref", "ref_envs")
 REF_BIN_FUSED = os.path.join(ob.ORACLE_DIR, "_ref", "ref_envs_fused")        # the same sources at plain -O2 (sin/cos fused into sincos)
 REFERENCE = os.environ.get("REFERENCE", "/root/reference")                   # oracle/Makefile's default
 REF_SOURCES = [os.path.join(REFERENCE, "base", "src", "environments", f) for f in
-               ("acrobot.cpp", os.path.join("compass_walker", "SWModel.cpp"), os.path.join("compass_walker", "compass_walker.cpp"))]
+               ("acrobot.cpp", "cart_pole.cpp", "pendulum.cpp", os.path.join("compass_walker", "SWModel.cpp"),
+                os.path.join("compass_walker", "compass_walker.cpp"))]
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-FIXTURE = {"acrobot": os.path.join(GOLDEN, "ref_envs_acrobot.npz"), "walker": os.path.join(GOLDEN, "ref_envs_walker.npz")}
+FIXTURE = {env: os.path.join(GOLDEN, f"ref_envs_{env}.npz") for env in ("acrobot", "walker", "cart_pole", "pendulum")}
 BOUNDS = os.path.join(GOLDEN, "ref_envs_bounds.json")
 
 MAX_ROWS = 512
@@ -37,17 +39,44 @@ WALKER_COMPARED = [i for i in range(11) if i != STEPDIST]
 
 TAGS = ["balancing", "angle1_threshold", "angle2_threshold", "rate1_limit", "rate2_limit", "timeout", "swinging",
         "walking", "strike", "refused_hip_sign", "refused_stance_rate", "refused_hip_angle", "wrap", "fallen_stance", "fallen_hip",
-        "search_exhausted"]
+        "search_exhausted",
+        "episode", "end_stop", "end_stop_edge", "failed_threshold", "observe_wrap", "potential_wrap", "action_penalty", "far",
+        "rate_range", "turns", "observe_wrap_step", "clamped"]
 TAG = {t: i for i, t in enumerate(TAGS)}
 
+DYNAMICAL = {"acrobot": dict(S=5, D=4, prefix="acrobot"), "cart_pole": dict(S=5, D=4, prefix="cartpole"), "pendulum": dict(S=3, D=2, prefix="pendulum")}
+THREAD_LOCAL_STARTS = ("acrobot", "cart_pole", "pendulum")                   # environments whose start draws from RandGen, not from drand48
 ANSWER_KEYS = {"acrobot": ("xd", "obs0", "term0", "next", "obs", "term", "reward"),
+               "cart_pole": ("xd", "obs0", "term0", "next", "obs", "term", "reward"),
+               "pendulum": ("xd", "obs0", "term0", "next", "obs", "term", "reward"),
                "walker": ("model", "changed", "obs0", "term0", "next", "obs", "term", "reward")}
 
 
-def spec_of(env, math):
-    spec = (configs.acrobot if env == "acrobot" else configs.compass_walker)(None, 1)[1]
+CONFIGS = {"acrobot": configs.acrobot, "walker": configs.compass_walker, "cart_pole": configs.cart_pole_ac, "pendulum": configs.pendulum}
+
+
+def spec_of(env, math, variant=0, randomization=None):
+    spec = CONFIGS[env](None, 1)[1]
     spec.math = math
+    if env == "cart_pole":
+        spec.end_stop_penalty, spec.action_penalty = int(variant) & 1, (int(variant) >> 1) & 1
+    if randomization is not None:
+        spec.randomization = float(randomization)
     return spec
+
+
+def _per_variant(answer, cases):
+    """answer(rows of one variant, variant) for every variant of the case set, put back in the rows' order"""
+    variant = cases.get("variant")
+    if variant is None:
+        return answer(cases, 0)
+    out = {}
+    for v in np.unique(variant):
+        rows = np.nonzero(variant == v)[0]
+        part = answer({k: a[rows] for k, a in cases.items()}, int(v))
+        for k, a in part.items():
+            out.setdefault(k, np.zeros((len(variant),) + a.shape[1:], a.dtype))[rows] = a
+    return out
 
 
 def reference_sources_present():
@@ -72,21 +101,43 @@ def floats(words):
     return [float.fromhex(w) for w in words]
 
 
+def task_lines(env, spec):
+    """the commands that configure the reference's task as the spec says"""
+    if env == "cart_pole":
+        return [f"cartpole_task {hexes(spec.timeout)} {int(spec.randomization)} {spec.end_stop_penalty} {spec.action_penalty}"]
+    if env == "pendulum":
+        return [f"pendulum_task {hexes(spec.timeout)} {hexes(spec.randomization)}"]
+    return []
+
+
+def _reference_dynamical(env, cases, variant, binary):
+    """eom, the task's observation of the state, control_step / integration_steps RK4 sub-steps around the reference's eom (under
+    the task's actuation), the observation of the result and the reward of the transition"""
+    state, action = cases["state"], cases["action"]
+    spec = spec_of(env, ob.MATH_LIBM, variant)
+    p, D = DYNAMICAL[env]["prefix"], DYNAMICAL[env]["D"]
+    h, steps = spec.control_step / spec.integration_steps, spec.integration_steps
+    setup = task_lines(env, spec)
+    actuation = action
+    if env == "pendulum":                                                 # Task::actuate: the others pass the action through (environment.h:94)
+        actuation = np.array([floats(a)[0] for a in ask([f"pendulum_actuate {hexes(u)}" for u in action], binary)])
+    first = ask(setup + [c for x, u in zip(state, actuation) for c in
+                         (f"{p}_eom {hexes(x)} {hexes(u)}", f"{p}_observe {hexes(x)}", f"{p}_step {hexes(x)} {hexes(u)} {hexes(h)} {steps}")], binary)[len(setup):]
+    xd = np.array([floats(a) for a in first[0::3]])
+    obs0 = np.array([floats(a[:D]) for a in first[1::3]]); term0 = np.array([int(a[D]) for a in first[1::3]], np.int32)
+    nxt = np.array([floats(a) for a in first[2::3]])
+    second = ask(setup + [c for x, u, y in zip(state, action, nxt) for c in
+                          (f"{p}_observe {hexes(y)}", f"{p}_evaluate {hexes(x)} {hexes(u)} {hexes(y)}")], binary)[len(setup):]
+    obs = np.array([floats(a[:D]) for a in second[0::2]]); term = np.array([int(a[D]) for a in second[0::2]], np.int32)
+    reward = np.array([floats(a)[0] for a in second[1::2]])
+    return dict(xd=xd, obs0=obs0, term0=term0, next=nxt, obs=obs, term=term, reward=reward)
+
+
 def reference_answers(env, cases, binary=REF_BIN):
     state, action = cases["state"], cases["action"]
     n = len(action)
-    if env == "acrobot":
-        h, steps = 0.05 / 5, 5                                           # control_step / integration_steps of configs.acrobot
-        first = ask([c for x, u in zip(state, action) for c in
-                     (f"acrobot_eom {hexes(x)} {hexes(u)}", f"acrobot_observe {hexes(x)}", f"acrobot_step {hexes(x)} {hexes(u)} {hexes(h)} {steps}")], binary)
-        xd = np.array([floats(a) for a in first[0::3]])
-        obs0 = np.array([floats(a[:4]) for a in first[1::3]]); term0 = np.array([int(a[4]) for a in first[1::3]], np.int32)
-        nxt = np.array([floats(a) for a in first[2::3]])
-        second = ask([c for x, u, y in zip(state, action, nxt) for c in
-                      (f"acrobot_observe {hexes(y)}", f"acrobot_evaluate {hexes(x)} {hexes(u)} {hexes(y)}")], binary)
-        obs = np.array([floats(a[:4]) for a in second[0::2]]); term = np.array([int(a[4]) for a in second[0::2]], np.int32)
-        reward = np.array([floats(a)[0] for a in second[1::2]])
-        return dict(xd=xd, obs0=obs0, term0=term0, next=nxt, obs=obs, term=term, reward=reward)
+    if env in DYNAMICAL:
+        return _per_variant(lambda part, variant: _reference_dynamical(env, part, variant, binary), cases)
     spec = spec_of("walker", ob.MATH_LIBM)
     setup = [f"walker_model {hexes(spec.slope_angle)} {hexes(spec.control_step)} {spec.integration_steps}",
              f"walker_task {hexes(spec.timeout)} {hexes(spec.initial_state_variation)} {hexes(spec.slope_angle)} {hexes(spec.negative_reward)}"]
@@ -118,6 +169,20 @@ def reference_starts(env, starts, binary=REF_BIN):
         x = np.array([floats(a) for a in ask(lines, binary)])
         obs = np.array([floats(a[:4]) for a in ask([f"acrobot_observe {hexes(r)}" for r in x], binary)])
         return dict(x=x, obs=obs, position_after=np.array(after, np.uint64))
+    if env in DYNAMICAL:                                                  # one RandGen draw; the task re-configured where the randomization changes
+        p, D = DYNAMICAL[env]["prefix"], DYNAMICAL[env]["D"]
+        lines, after, answers_at = [], [], []
+        for pos, test, rand in zip(starts["position"], starts["test"], starts["randomization"]):
+            g = ob.Rand48(int(pos))
+            d = L.orc_drand48(C.byref(g))
+            lines += task_lines(env, spec_of(env, ob.MATH_LIBM, randomization=rand))
+            answers_at.append(len(lines))
+            lines.append(f"{p}_start {hexes(d)}" + (f" {int(test)}" if env == "pendulum" else ""))
+            after.append(g.x)
+        answers = ask(lines, binary)
+        x = np.array([floats(answers[i]) for i in answers_at])
+        obs = np.array([floats(a[:D]) for a in ask(task_lines(env, spec_of(env, ob.MATH_LIBM)) + [f"{p}_observe {hexes(r)}" for r in x], binary)[1:]])
+        return dict(x=x, obs=obs, position_after=np.array(after, np.uint64))
     spec = spec_of("walker", ob.MATH_LIBM)
     setup = [f"walker_task {hexes(spec.timeout)} {hexes(spec.initial_state_variation)} {hexes(spec.slope_angle)} {hexes(spec.negative_reward)}"]
     answers = ask(setup + [f"walker_start_at {int(p)} {int(t)}" for p, t in zip(starts["position"], starts["test"])], binary)[1:]
@@ -138,8 +203,12 @@ def _arr(n):
 
 
 def oracle_answers(env, cases, math):
+    return _per_variant(lambda part, variant: _oracle_answers(env, part, math, variant), cases)
+
+
+def _oracle_answers(env, cases, math, variant):
     L = ob.load()
-    spec = spec_of(env, math)
+    spec = spec_of(env, math, variant)
     state, action = cases["state"], cases["action"]
     n, S, D = len(action), state.shape[1], L.orc_env_obs_dims(spec.env)
     obs0 = np.zeros((n, D)); term0 = np.zeros(n, np.int32)
@@ -148,12 +217,14 @@ def oracle_answers(env, cases, math):
         term0[i] = L.orc_env_observe(C.byref(spec), (C.c_double * S)(*state[i]), o); obs0[i] = o[:]
     nxt, obs, reward, term = ob.env_step(spec, state, action)             # the composed step, as the kernels restate it
     out = dict(obs0=obs0, term0=term0, next=nxt, obs=obs, term=term, reward=reward)
-    if env == "acrobot":
-        xd = np.zeros((n, 5)); integrated = np.zeros((n, 5)); evaluated = np.zeros(n)
+    if env in DYNAMICAL:
+        xd = np.zeros((n, S)); integrated = np.zeros((n, S)); evaluated = np.zeros(n)
+        h, steps = spec.control_step / spec.integration_steps, spec.integration_steps
         for i in range(n):
-            x = (C.c_double * S)(*state[i]); d = _arr(5); y = _arr(5)
-            L.orc_env_eom(C.byref(spec), x, float(action[i]), d); xd[i] = d[:]
-            L.orc_env_integrate(C.byref(spec), x, float(action[i]), 0.05 / 5, 5, y); integrated[i] = y[:]
+            x = (C.c_double * S)(*state[i]); d = _arr(S); y = _arr(S)
+            u = min(max(float(action[i]), -3.0), 3.0) if env == "pendulum" else float(action[i])    # the step's own actuation is inside orc_env_step
+            L.orc_env_eom(C.byref(spec), x, u, d); xd[i] = d[:]
+            L.orc_env_integrate(C.byref(spec), x, u, h, steps, y); integrated[i] = y[:]
             evaluated[i] = L.orc_env_evaluate(C.byref(spec), x, float(action[i]), y)
         assert (integrated.view(np.uint64) == nxt.view(np.uint64)).all() and (evaluated == reward).all(), "orc_env_step is not its pieces"
         out["xd"] = xd
@@ -169,13 +240,16 @@ def oracle_starts(env, starts, math):
     S, D = L.orc_env_state_dims(spec.env), L.orc_env_obs_dims(spec.env)
     n = len(starts["position"])
     x = np.zeros((n, S)); obs = np.zeros((n, D)); after = np.zeros(n, np.uint64)
+    thread_local = env in THREAD_LOCAL_STARTS
     for i, (pos, test) in enumerate(zip(starts["position"], starts["test"])):
+        if "randomization" in starts:
+            spec.randomization = float(starts["randomization"][i])
         g, tl = C.c_uint64(0), C.c_uint64(0)
-        (tl if env == "acrobot" else g).value = int(pos)
+        (tl if thread_local else g).value = int(pos)
         xs, o = _arr(S), _arr(D)
         L.orc_env_start_at(C.byref(spec), C.byref(g), C.byref(tl), int(test), xs)
         L.orc_env_observe(C.byref(spec), xs, o)
-        x[i] = xs[:]; obs[i] = o[:]; after[i] = (tl if env == "acrobot" else g).value
+        x[i] = xs[:]; obs[i] = o[:]; after[i] = (tl if thread_local else g).value
     return dict(x=x, obs=obs, position_after=after)
 
 
@@ -192,20 +266,42 @@ def seeded_starts():
     return dict(position=np.concatenate([pos, pos]), test=np.repeat([0, 1], N_STARTS).astype(np.int32))
 
 
+START_RANDOMIZATION = {"cart_pole": (0.0, 1.0), "pendulum": (0.0, 1.0)}     # the tasks that have one: a context per value
+
+
+def seeded_starts_of(env):
+    """seeded_starts, once per randomization where the task has one"""
+    starts = seeded_starts()
+    if env not in START_RANDOMIZATION:
+        return starts
+    rands = START_RANDOMIZATION[env]
+    return dict(position=np.tile(starts["position"], len(rands)), test=np.tile(starts["test"], len(rands)),
+                randomization=np.repeat(rands, len(starts["test"])))
+
+
 def context_starts(env):
     """The first learning start and the test start after it of a 64-replica context (seeds START_SEEDS, tables of START_MEMORY
-    slots): the stream positions at which grlx_env_start draws, which are the oracle experiment's after its construction."""
-    spec = spec_of(env, ob.MATH_LIBM)
-    spec.projector.memory = START_MEMORY
-    which = 1 if env == "acrobot" else 0                                  # thread-local / global stream (orc_rng_states)
-    pos = {0: [], 1: []}
-    for seed in START_SEEDS:
-        e = ob.Experiment(spec, seed=int(seed))
-        for test in (0, 1):
-            pos[test].append(e.rng()[which])
-            e.env_start(test)
-        e.close()
-    return dict(position=np.array(pos[0] + pos[1], np.uint64), test=np.repeat([0, 1], N_STARTS).astype(np.int32))
+    slots): the stream positions at which grlx_env_start draws, which are the oracle experiment's after its construction.  Where the
+    task has a randomization, one context per value of START_RANDOMIZATION, one after the other."""
+    out = dict(position=[], test=[])
+    for rand in START_RANDOMIZATION.get(env, (None,)):
+        spec = spec_of(env, ob.MATH_LIBM, randomization=rand)
+        spec.projector.memory = spec.actor_projector.memory = START_MEMORY
+        which = 1 if env in THREAD_LOCAL_STARTS else 0                    # thread-local / global stream (orc_rng_states)
+        pos = {0: [], 1: []}
+        for seed in START_SEEDS:
+            e = ob.Experiment(spec, seed=int(seed))
+            for test in (0, 1):
+                pos[test].append(e.rng()[which])
+                e.env_start(test)
+            e.close()
+        out["position"] += pos[0] + pos[1]; out["test"] += [0] * N_STARTS + [1] * N_STARTS
+        if rand is not None:
+            out.setdefault("randomization", []).extend([rand] * (2 * N_STARTS))
+    starts = dict(position=np.array(out["position"], np.uint64), test=np.array(out["test"], np.int32))
+    if "randomization" in out:
+        starts["randomization"] = np.array(out["randomization"], np.float64)
+    return starts
 
 
 # ------------------------------------------------------------------------------------------- groups and bounds ---
@@ -219,6 +315,12 @@ def groups(env, answers, rows=None):
         return {"angles": np.concatenate([nxt[:, 0:2].ravel(), obs[:, 0:2].ravel()]),
                 "rates": np.concatenate([nxt[:, 2:4].ravel(), obs[:, 2:4].ravel()]),
                 "time": nxt[:, 4].ravel(), "reward": reward.ravel()}
+    if env == "cart_pole":
+        return {"positions": np.concatenate([nxt[:, 0].ravel(), obs[:, 0].ravel()]), "angles": np.concatenate([nxt[:, 1].ravel(), obs[:, 1].ravel()]),
+                "rates": np.concatenate([nxt[:, 2:4].ravel(), obs[:, 2:4].ravel()]), "time": nxt[:, 4].ravel(), "reward": reward.ravel()}
+    if env == "pendulum":
+        return {"angles": np.concatenate([nxt[:, 0].ravel(), obs[:, 0].ravel()]), "rates": np.concatenate([nxt[:, 1].ravel(), obs[:, 1].ravel()]),
+                "time": nxt[:, 2].ravel(), "reward": reward.ravel()}
     return {"angles": np.concatenate([nxt[:, [SLA, HA]].ravel(), obs[:, [0, 1]].ravel()]),
             "rates": np.concatenate([nxt[:, [SLAR, HAR, HIPVEL]].ravel(), obs[:, [2, 3]].ravel()]),
             "positions": nxt[:, [SFX, LASTHIPX]].ravel(), "time": nxt[:, [TIME, TIMEOUT]].ravel(), "reward": reward.ravel()}
@@ -234,9 +336,15 @@ def start_groups(env, answers, rows=None):
     return g
 
 
+WRAPPED_OBS = {"cart_pole": 1, "pendulum": 0}
+
+
 def discrete_mismatch(env, ref, got):
-    """rows on which two answers differ in a discrete outcome: a terminal code or the strike flag"""
+    """rows on which two answers differ in a discrete outcome: a terminal code, the strike flag, or the turn the wrapped angle of the
+    cart-pole's and the pendulum's observation was taken on (the two sides of the wrap are 2 pi apart)"""
     bad = ref["term"] != got["term"]
+    if env in WRAPPED_OBS:
+        bad |= np.abs(ref["obs"][:, WRAPPED_OBS[env]] - got["obs"][:, WRAPPED_OBS[env]]) > np.pi
     if env == "walker":
         bad |= (ref["next"][:, CHANGED] != got["next"][:, CHANGED]) | (ref["obs"][:, 4] != got["obs"][:, 4])
     return bad
@@ -247,7 +355,7 @@ def deviations(env, ref, got, excluded):
     def dev(rows):
         a, b = groups(env, ref, rows), groups(env, got, rows)
         return {k: float(np.max(np.abs(a[k] - b[k]))) if a[k].size else 0.0 for k in a}
-    if env == "acrobot":
+    if env != "walker":
         return dev(~excluded)
     strike = ref["next"][:, CHANGED] > 0.5
     return {"strike": dev(strike & ~excluded), "no_strike": dev(~strike & ~excluded)}
@@ -261,7 +369,7 @@ def start_deviations(env, ref, got, excluded):
 def within(env, ref, got, excluded, bounds, factor):
     """[(what, deviation, allowed)] for every group that exceeds factor * its recorded bound"""
     found = deviations(env, ref, got, excluded)
-    pairs = [(k, found[k], bounds[k]) for k in found] if env == "acrobot" else \
+    pairs = [(k, found[k], bounds[k]) for k in found] if env != "walker" else \
             [(f"{s}/{k}", found[s][k], bounds[s][k]) for s in found for k in found[s]]
     return [(k, d, factor * b) for k, d, b in pairs if not d <= factor * b]
 
@@ -521,4 +629,251 @@ def _check_walker_coverage(cases, spec):
     assert set(np.round(action[np.isin(action, WALKER_TORQUES[:3])], 1)) == {-1.2, 0.0, 1.2} and (~np.isin(action, WALKER_TORQUES[:3])).sum() > 20
 
 
-CASES = {"acrobot": acrobot_cases, "walker": walker_cases}
+# ---------------------------------------------------------------------------------------------- cart-pole cases ---
+CART_FORCES = [-15.0, 0.0, 15.0, 6.31, -11.7, 0.875]                     # the actor-critic's range: its ends, its middle and three off-grid forces
+END_STOP = 2.4
+
+
+def _finish(rows, tags, S, variants=None):
+    a = np.array(rows)
+    cases = dict(state=np.ascontiguousarray(a[:, :S]), action=np.ascontiguousarray(a[:, S]), tag=np.array(tags, np.int32))
+    if variants is not None:
+        cases["variant"] = np.array(variants, np.int32)
+    assert len(tags) <= MAX_ROWS
+    return cases
+
+
+def cart_pole_cases():
+    rng = np.random.default_rng(19830913)
+    spec = spec_of("cart_pole", ob.MATH_LIBM)
+    timeout = spec.timeout
+    rows, tags, variants = [], [], []
+
+    def add(tag, x, u, variant=None):
+        rows.append(list(x) + [u]); tags.append(TAG[tag]); variants.append(len(tags) % 4 if variant is None else variant)
+
+    def step(x, u):
+        return ob.env_step(spec, [x], [u])[0][0]
+
+    def force(i):
+        return CART_FORCES[i % 6] if i % 4 else float(rng.uniform(-15, 15))
+
+    # swing-up episodes from the task's start under forces from the whole range (no penalty: they run on through the end stops)
+    for ep in range(8):
+        x = np.array([0.0, np.pi + rng.uniform(-0.05, 0.05), 0.0, 0.0, 0.0])
+        for k in range(190):
+            u = force(int(rng.integers(1000)))
+            if k % 9 == ep % 9:
+                add("episode", x, u)
+            x = step(x, u)
+    # the end stops: position excess on either side x velocity into / out of the stop x acceleration of either sign
+    for side in (1.0, -1.0):
+        for vsign in (1.0, -1.0):
+            for asign in (1.0, -1.0):
+                found = 0
+                while found < 4:
+                    x = np.array([side * (END_STOP + rng.uniform(1e-6, 0.4)), rng.uniform(-8, 8), vsign * rng.uniform(0.01, 6), rng.uniform(-8, 8), rng.uniform(0, 9)])
+                    u = float(rng.uniform(-15, 15))
+                    if _cart_acc(spec, x, u) * asign > 0:
+                        add("end_stop", x, u); found += 1
+        for value in (END_STOP, np.nextafter(END_STOP, 0), np.nextafter(END_STOP, 3)):      # at, just inside and just beyond the stop, moving into it
+            for asign in (1.0, -1.0):
+                x = np.array([side * value, rng.uniform(-3, 3), side * rng.uniform(0.5, 3), rng.uniform(-3, 3), rng.uniform(0, 9)])
+                add("end_stop_edge", x, side * asign * 15.0)
+    # failed(): the next position lands just inside / just outside |x| = 2.4, under every task variant
+    for side in (1.0, -1.0):
+        for k in range(4):
+            base = np.array([0.0, rng.uniform(-3, 3), side * rng.uniform(0.8, 1.5), rng.uniform(-2, 2), rng.uniform(0, 9)])
+            u = CART_FORCES[k]
+
+            def at(p):
+                x = base.copy(); x[0] = side * p
+                return x
+            lo, hi = _bisect(lambda p: abs(step(at(p), u)[0]) - END_STOP, 2.0, END_STOP)
+            add("failed_threshold", at(lo), u, k); add("failed_threshold", at(hi), u, k)
+    # time on both sides of the timeout, stepped there and given
+    for k in range(4):
+        base = np.array([rng.uniform(-1, 1), rng.uniform(-3, 3), rng.uniform(-1, 1), rng.uniform(-2, 2), 0.0])
+
+        def at(p):
+            x = base.copy(); x[4] = p
+            return x
+        lo, hi = _bisect(lambda p: step(at(p), CART_FORCES[k])[4] - timeout, timeout - 0.09, timeout)
+        add("timeout", at(lo), CART_FORCES[k], k); add("timeout", at(hi), CART_FORCES[k], k)
+    for t in (timeout - 0.06, np.nextafter(timeout - 0.05, 0), timeout - 0.05, np.nextafter(timeout - 0.05, 10), np.nextafter(timeout, 0), timeout, np.nextafter(timeout, 10), timeout + 0.01):
+        add("timeout", [rng.uniform(-1, 1), rng.uniform(-3, 3), rng.uniform(-1, 1), rng.uniform(-2, 2), t], force(len(tags)))
+    # observe: state[1] + pi on either side of multiples of 2 pi, the negative ones (the `a < 0` branch) included
+    for turn in range(-3, 4):
+        edge = 2 * np.pi * turn - np.pi
+        for value in (edge, np.nextafter(edge, -np.inf), np.nextafter(edge, np.inf), edge - 1e-9, edge + 1e-9):
+            add("observe_wrap", [rng.uniform(-2, 2), value, rng.uniform(-1, 1), rng.uniform(-0.5, 0.5), rng.uniform(0, 9)], force(len(tags)))
+    # potential: |theta| mod 2 pi of the next state lands on either side of pi
+    for centre in (np.pi, -np.pi, 3 * np.pi, -3 * np.pi, 5 * np.pi, -7 * np.pi):
+        base = np.array([rng.uniform(-1, 1), 0.0, rng.uniform(-1, 1), rng.uniform(-1, 1), rng.uniform(0, 9)])
+        u = force(len(tags))
+
+        def at(p):
+            x = base.copy(); x[1] = centre + p
+            return x
+        lo, hi = _bisect(lambda p: np.fmod(abs(step(at(p), u)[1]), 2 * np.pi) - np.pi, -0.3, 0.3)
+        add("potential_wrap", at(lo), u); add("potential_wrap", at(hi), u)
+    for i in range(24):                                                   # the action penalty at forces up to the range's ends, with and without it
+        add("action_penalty", [rng.uniform(-2, 2), rng.uniform(-7, 7), rng.uniform(-3, 3), rng.uniform(-5, 5), rng.uniform(0, 9)], force(i), 2 * (i % 2) + (i // 2) % 2)
+    for i in range(64):                                                   # far from any episode: many turns, rates beyond the observation's range
+        add("far", [rng.uniform(-3.5, 3.5), rng.uniform(-40, 40), rng.uniform(-12, 12), rng.uniform(-20, 20), rng.uniform(0, 9.9)], force(i))
+    cases = _finish(rows, tags, 5, variants)
+    _check_cart_pole_coverage(cases)
+    return cases
+
+
+def _cart_acc(spec, x, u):
+    """the cart's acceleration before the end stops override it: it does not depend on the cart's position or velocity"""
+    free = np.array(x, np.float64); free[0] = 0.0; free[2] = 0.0
+    d = _arr(5)
+    ob.load().orc_env_eom(C.byref(spec), (C.c_double * 5)(*free), float(u), d)
+    return d[2]
+
+
+def _check_cart_pole_coverage(cases):
+    got = oracle_answers("cart_pole", cases, ob.MATH_LIBM)
+    spec = spec_of("cart_pole", ob.MATH_LIBM)
+    tag, state, action, variant = cases["tag"], cases["state"], cases["action"], cases["variant"]
+    esp, ap = (variant & 1).astype(bool), (variant & 2).astype(bool)
+    assert set(variant) == {0, 1, 2, 3}
+    rows = tag == TAG["episode"]
+    assert rows.sum() >= 120 and (np.abs(state[rows, 0]) > END_STOP).any() and np.isin(action[rows], CART_FORCES[:3]).any() and (~np.isin(action[rows], CART_FORCES)).any()
+    # the four overrides of eom: xd[0] = 0 on either side, xd[2] = 0 with it where the acceleration pushes further in, and neither where the cart moves out
+    rows = np.nonzero(tag == TAG["end_stop"])[0]
+    seen = set()
+    for i in rows:
+        side, v, acc = np.sign(state[i, 0]), np.sign(state[i, 2]), np.sign(_cart_acc(spec, state[i], action[i]))
+        seen.add((side, v, acc))
+        into = side == v
+        assert (got["xd"][i, 0] == 0) == into and (got["xd"][i, 2] == 0) == (into and acc == side)
+        assert into or got["xd"][i, 0] == state[i, 2]
+    assert len(seen) == 8
+    rows = tag == TAG["end_stop_edge"]
+    beyond = np.abs(state[rows, 0]) > END_STOP
+    assert beyond.sum() == 4 and (np.abs(state[rows, 0]) == END_STOP).sum() == 4 and ((got["xd"][rows, 0] == 0) == beyond).all()
+    rows = tag == TAG["failed_threshold"]
+    margin = np.abs(got["next"][rows, 0]) - END_STOP
+    assert (np.abs(margin) < 1e-8).all() and (margin > 0).sum() == (margin < 0).sum() == 8
+    assert (got["next"][rows, 0] > 0).sum() == (got["next"][rows, 0] < 0).sum() == 8
+    assert ((got["term"][rows] == 2) == ((margin > 0) & esp[rows])).all() and (got["term"][rows] == 2).sum() == 4
+    assert ((got["reward"][rows] < -9000) == ((margin > 0) & esp[rows])).all()
+    rows = tag == TAG["timeout"]
+    assert (got["term"][rows] == 1).sum() >= 6 and (got["term"][rows] == 0).sum() >= 6 and (got["term0"][rows] == 1).any() and (got["term0"][rows] == 0).any()
+    assert (np.abs(got["next"][rows, 4] - spec.timeout) < 1e-8).sum() >= 8
+    rows = tag == TAG["observe_wrap"]
+    z = state[rows, 1] + np.pi
+    assert (z < 0).sum() >= 10 and (z > 0).sum() >= 10 and (got["obs0"][rows, 1] < 1e-6).any() and (got["obs0"][rows, 1] > 2 * np.pi - 1e-6).any()
+    assert ((got["obs0"][rows, 1] >= 0) & (got["obs0"][rows, 1] <= 2 * np.pi)).all()
+    rows = tag == TAG["potential_wrap"]
+    m = np.fmod(np.abs(got["next"][rows, 1]), 2 * np.pi) - np.pi
+    assert (np.abs(m) < 1e-8).all() and (m > 0).sum() == (m < 0).sum() == 6 and (got["next"][rows, 1] < 0).any() and (got["next"][rows, 1] > 0).any()
+    rows = tag == TAG["action_penalty"]
+    assert set(variant[rows]) == {0, 1, 2, 3} and (np.abs(action[rows]) == 15).any()
+    assert np.abs(state[tag == TAG["far"], 1]).max() > 39
+
+
+# ----------------------------------------------------------------------------------------------- pendulum cases ---
+PENDULUM_TORQUES = [-3.0, 0.0, 3.0, 1.37, -2.231, 0.0521]                 # the grid of the yaml and three off-grid torques
+RATE_RANGE = 12 * np.pi
+
+
+def pendulum_cases():
+    rng = np.random.default_rng(20150122)
+    spec = spec_of("pendulum", ob.MATH_LIBM)
+    timeout = spec.timeout
+    rows, tags = [], []
+
+    def add(tag, x, u):
+        rows.append(list(x) + [u]); tags.append(TAG[tag])
+
+    def step(x, u):
+        return ob.env_step(spec, [x], [u])[0][0]
+
+    def torque(i):
+        return PENDULUM_TORQUES[i % 6] if i % 4 else float(rng.uniform(-3, 3))
+
+    for ep in range(8):                                                   # episodes from learning starts (any angle) and the test start
+        x = np.array([np.pi + (ep % 4 != 0) * rng.uniform(0, 2 * np.pi), 0.0, 0.0])
+        for k in range(99):
+            u = torque(int(rng.integers(1000)))
+            if k % 5 == ep % 5:
+                add("episode", x, u)
+            x = step(x, u)
+    for sign in (1.0, -1.0):                                              # rates to and beyond +-12 pi
+        for value in (RATE_RANGE, np.nextafter(RATE_RANGE, 0), np.nextafter(RATE_RANGE, 100), 30.0, 45.0, 60.0, 90.0):
+            for k in range(3):
+                add("rate_range", [rng.uniform(-7, 7), sign * value, rng.uniform(0, 2.9)], torque(len(tags)))
+    for i in range(64):                                                   # angles many turns either way
+        add("turns", [rng.uniform(-300, 300), rng.uniform(-40, 40), rng.uniform(0, 2.9)], torque(i))
+    for u in (-4.5, 4.5, np.nextafter(3.0, 4), np.nextafter(-3.0, -4), 100.0, -100.0):        # actuate clamps what moves the pendulum, the reward sees the action
+        for k in range(2):
+            add("clamped", [rng.uniform(-7, 7), rng.uniform(-10, 10), rng.uniform(0, 2.9)], u)
+    for turn in range(-3, 4):                                             # observe: state[0] + pi on either side of multiples of 2 pi, given ...
+        edge = 2 * np.pi * turn - np.pi
+        for value in (edge, np.nextafter(edge, -np.inf), np.nextafter(edge, np.inf), edge - 1e-9, edge + 1e-9):
+            add("observe_wrap", [value, rng.uniform(-5, 5), rng.uniform(0, 2.9)], torque(len(tags)))
+    for turn in (-2, -1, 0, 1, 2, 3):                                     # ... and stepped to
+        edge = 2 * np.pi * turn - np.pi
+        base = np.array([0.0, rng.uniform(-5, 5), rng.uniform(0, 2.9)])
+        u = torque(len(tags))
+
+        def at(p):
+            x = base.copy(); x[0] = edge + p
+            return x
+        lo, hi = _bisect(lambda p: step(at(p), u)[0] - edge, -0.6, 0.6)
+        add("observe_wrap_step", at(lo), u); add("observe_wrap_step", at(hi), u)
+    for centre in (np.pi, -np.pi, 3 * np.pi, -5 * np.pi):                # evaluate: |angle| mod 2 pi of the next state on either side of pi
+        base = np.array([0.0, rng.uniform(-5, 5), rng.uniform(0, 2.9)])
+        u = torque(len(tags))
+
+        def at(p):
+            x = base.copy(); x[0] = centre + p + 1e-4                     # off observe's wrap, which sits at the same angles
+            return x
+        lo, hi = _bisect(lambda p: np.fmod(abs(step(at(p), u)[0]), 2 * np.pi) - np.pi, -0.6, 0.6)
+        add("potential_wrap", at(lo), u); add("potential_wrap", at(hi), u)
+    for k in range(4):                                                    # time on both sides of the timeout, stepped there and given
+        base = np.array([rng.uniform(-7, 7), rng.uniform(-10, 10), 0.0])
+
+        def at(p):
+            x = base.copy(); x[2] = p
+            return x
+        lo, hi = _bisect(lambda p: step(at(p), PENDULUM_TORQUES[k])[2] - timeout, timeout - 0.05, timeout)
+        add("timeout", at(lo), PENDULUM_TORQUES[k]); add("timeout", at(hi), PENDULUM_TORQUES[k])
+    for t in (timeout - 0.04, np.nextafter(timeout - 0.03, 0), timeout - 0.03, np.nextafter(timeout - 0.03, 10), np.nextafter(timeout, 0), timeout, np.nextafter(timeout, 10), timeout + 0.01):
+        add("timeout", [rng.uniform(-7, 7), rng.uniform(-10, 10), t], torque(len(tags)))
+    cases = _finish(rows, tags, 3)
+    _check_pendulum_coverage(cases)
+    return cases
+
+
+def _check_pendulum_coverage(cases):
+    got = oracle_answers("pendulum", cases, ob.MATH_LIBM)
+    spec = spec_of("pendulum", ob.MATH_LIBM)
+    tag, state, action = cases["tag"], cases["state"], cases["action"]
+    rows = tag == TAG["episode"]
+    assert rows.sum() >= 120 and set(action[rows][np.isin(action[rows], PENDULUM_TORQUES[:3])]) == {-3.0, 0.0, 3.0} and (~np.isin(action[rows], PENDULUM_TORQUES)).sum() > 20
+    rows = tag == TAG["rate_range"]
+    assert (np.abs(state[rows, 1]) == RATE_RANGE).sum() == 6 and (np.abs(state[rows, 1]) > 2 * RATE_RANGE).any() and (state[rows, 1] < 0).any()
+    assert np.abs(state[tag == TAG["turns"], 0]).max() > 250 and (state[tag == TAG["turns"], 0] < -100).any()
+    rows = tag == TAG["clamped"]
+    assert (np.abs(action[rows]) > 3).all() and (got["reward"][rows] < -9).all() and (got["reward"][rows] < -9000).any()
+    rows = tag == TAG["observe_wrap"]
+    z = state[rows, 0] + np.pi
+    assert (z < 0).sum() >= 10 and (z > 0).sum() >= 10 and (got["obs0"][rows, 0] < 1e-6).any() and (got["obs0"][rows, 0] > 2 * np.pi - 1e-6).any()
+    rows = tag == TAG["observe_wrap_step"]
+    assert ((got["obs"][rows, 0] < 1e-8) | (got["obs"][rows, 0] > 2 * np.pi - 1e-8)).all()
+    assert (got["obs"][rows, 0] < 1e-8).sum() == (got["obs"][rows, 0] > 1).sum() == 6 and (got["next"][rows, 0] < -np.pi).any()
+    rows = tag == TAG["potential_wrap"]
+    m = np.fmod(np.abs(got["next"][rows, 0]), 2 * np.pi) - np.pi
+    assert (np.abs(m) < 1e-8).all() and (m > 0).sum() == (m < 0).sum() == 4
+    rows = tag == TAG["timeout"]
+    assert (got["term"][rows] == 1).sum() >= 6 and (got["term"][rows] == 0).sum() >= 6 and (got["term0"][rows] == 1).any() and (got["term0"][rows] == 0).any()
+    assert (np.abs(got["next"][rows, 2] - spec.timeout) < 1e-8).sum() >= 8
+    assert ((got["obs"][:, 0] >= 0) & (got["obs"][:, 0] <= 2 * np.pi)).all() and ((got["term"] == 0) | (got["term"] == 1)).all()
+
+
+CASES = {"acrobot": acrobot_cases, "walker": walker_cases, "cart_pole": cart_pole_cases, "pendulum": pendulum_cases}

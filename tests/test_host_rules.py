@@ -1,5 +1,5 @@
 """The host-side rules that need no device, checked by stand-alone programs under the host sanitizers: those of the C ABI
-(grl_amd/csrc/grlx_host_rules.h: table growth, the stream distance of the initial parameters, the byte counts of tables, target values
+(grl_amd/csrc/grlx_host_rules.h: what a projector admits -- finite, |x * scaling| < 2^30 --, table growth, the stream distance of the initial parameters, the byte counts of tables, target values
 and traces; tools/host_rules_check.cpp) and those of the host layer above it (grl_amd/csrc/host/report_rules.h: file names, row texts,
 the simple regret, row caps and the statistics of the report files; tools/host_report_check.cpp).  Nothing is loaded into Python."""
 import os

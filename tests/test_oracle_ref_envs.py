@@ -1,9 +1,11 @@
-"""The oracle's acrobot and compass walker against the reference's OWN sources, bit for bit.
+"""The oracle's acrobot, cart-pole (swing-up and balancing tasks), pendulum and compass walker against the reference's OWN sources,
+bit for bit.
 
-oracle/_ref/ref_envs is the reference's acrobot.cpp, SWModel.cpp and compass_walker.cpp, compiled unmodified against a stand-in
-framework header (oracle/ref) with -fno-builtin, i.e. evaluated call by call.  In libm arithmetic the oracle must give that
-binary's bits on every case of tests/ref_env_cases.py and every command: derivatives, RK4 steps, model steps through heel strikes
-and refused strikes, observations, rewards, terminal codes, the strike flag, start states and the draws a start consumes.
+oracle/_ref/ref_envs is the reference's acrobot.cpp, cart_pole.cpp, pendulum.cpp, SWModel.cpp and compass_walker.cpp, compiled
+unmodified against a stand-in framework header (oracle/ref) with -fno-builtin, i.e. evaluated call by call.  In libm arithmetic the
+oracle must give that binary's bits on every case of tests/ref_env_cases.py and every command: derivatives (the cart-pole's end-stop
+overrides included), RK4 steps, model steps through heel strikes and refused strikes, observations and their wraps, rewards under
+every penalty setting, terminal codes, the strike flag, start states under every randomization and the draws a start consumes.
 
 The fixtures under tests/golden/ (what the GPU test reads) must equal a fresh run of the binary, and the portable-mode oracle
 (what the kernels reproduce) must stay inside the bounds recorded with them: tools/record_ref_envs.py rewrites all three.
@@ -19,7 +21,7 @@ import pytest
 from tests import oracle_binding as ob
 from tests import ref_env_cases as rc
 
-ENVS = ("acrobot", "walker")
+ENVS = ("acrobot", "walker", "cart_pole", "pendulum")
 
 
 @pytest.fixture(scope="module")
@@ -84,7 +86,7 @@ def test_libm_oracle_starts_equal_the_reference_binarys(binary, env):
     """64 seeds x {learn, test} from srand48(seed): start states, first observations and the stream position after the start
     (the draws the walker's rejection sampling consumed).  The walker's go through `walker_start seed test` (srand48 inside the
     binary) as well as through the position."""
-    starts = rc.seeded_starts()
+    starts = rc.seeded_starts_of(env)
     ref = rc.reference_starts(env, starts)
     got = rc.oracle_starts(env, starts, ob.MATH_LIBM)
     assert_same_bits(ref, got, ("x", "obs", "position_after"), f"{env} starts")
@@ -118,11 +120,11 @@ def test_fixtures_equal_a_fresh_run_and_the_portable_oracle_stays_inside_the_rec
     with open(rc.BOUNDS) as f:
         recorded = json.load(f)[env]
     cases, ref = cases_of(env), reference_of(env)
-    assert_same_bits(cases, fx, ("state", "action", "tag"), f"{env} fixture inputs")
+    assert_same_bits(cases, fx, tuple(cases), f"{env} fixture inputs")
     assert_same_bits(ref, fx, ("next", "obs", "reward", "term"), f"{env} fixture outputs")
     starts = context_starts_of(env)
     sref = rc.reference_starts(env, starts)
-    assert_same_bits(dict(starts, **sref), {k[6:]: fx[k] for k in fx.files if k.startswith("start_")}, ("position", "test", "x", "obs", "position_after"), f"{env} fixture starts")
+    assert_same_bits(dict(starts, **sref), {k[6:]: fx[k] for k in fx.files if k.startswith("start_")}, tuple(starts) + ("x", "obs", "position_after"), f"{env} fixture starts")
     # the portable oracle: discrete outcomes equal on all but 1 % of the rows, by the oracle alone, and the rest inside the bounds
     portable = rc.oracle_answers(env, cases, ob.MATH_PORTABLE)
     excluded = rc.discrete_mismatch(env, ref, portable)
@@ -135,3 +137,56 @@ def test_fixtures_equal_a_fresh_run_and_the_portable_oracle_stays_inside_the_rec
     assert rc.starts_within(env, sref, sportable, sexcluded, recorded["start_bounds"], 1.0) == []
     for path in (rc.FIXTURE[env], rc.BOUNDS):
         assert os.path.getsize(path) < 100 * 1024
+
+
+def test_randomized_starts_vary_and_plain_ones_do_not(binary):
+    """the cases of the start tests are what they are there for: the cart-pole's and the pendulum's starts under randomization 1 differ
+    from seed to seed (the pendulum's test starts do not), and under randomization 0 the draw is consumed all the same"""
+    for env in ("cart_pole", "pendulum"):
+        starts = rc.seeded_starts_of(env)
+        ref = rc.reference_starts(env, starts)
+        angle = ref["x"][:, 1 if env == "cart_pole" else 0]
+        plain, learn = starts["randomization"] == 0, starts["test"] == 0
+        assert (angle[plain] == np.pi).all() and (ref["position_after"] != starts["position"]).all()
+        varies = ~plain & (learn | (env == "cart_pole"))
+        assert len(set(angle[varies])) == len(set(starts["position"][varies])) == rc.N_STARTS and (angle[~plain & ~varies] == np.pi).all()
+
+
+def test_cart_pole_balancing_task_equals_the_reference_binarys(binary):
+    """task/cart_pole/balancing's source is in the binary too: observe, evaluate and start on the cart-pole's cases, whose positions
+    and angles lie on both sides of its two failure thresholds"""
+    import ctypes as C
+    L = ob.load()
+    spec = ob.cart_pole_balancing_pid_spec(math=ob.MATH_LIBM)
+    cases, ref = cases_of("cart_pole"), reference_of("cart_pole")
+    state = np.concatenate([cases["state"], cases["state"] * [1, 0.01, 1, 1, 1]])          # the second half: angles about the 12 degrees
+    nxt = np.concatenate([ref["next"], ref["next"] * [1, 0.01, 1, 1, 1]])
+    action = np.concatenate([cases["action"], cases["action"]])
+    lines = [f"balancing_task {rc.hexes(spec.timeout)}"]
+    for x, u, y in zip(state, action, nxt):
+        lines += [f"balancing_observe {rc.hexes(y)}", f"balancing_evaluate {rc.hexes(x)} {rc.hexes(u)} {rc.hexes(y)}"]
+    answers = rc.ask(lines)[1:]
+    want = dict(obs=np.array([rc.floats(a[:4]) for a in answers[0::2]]), term=np.array([int(a[4]) for a in answers[0::2]], np.int32),
+                reward=np.array([rc.floats(a)[0] for a in answers[1::2]]))
+    got = dict(obs=np.zeros((len(state), 4)), term=np.zeros(len(state), np.int32), reward=np.zeros(len(state)))
+    for i, (x, u, y) in enumerate(zip(state, action, nxt)):
+        o = (C.c_double * 4)()
+        got["term"][i] = L.orc_env_observe(C.byref(spec), (C.c_double * 5)(*y), o); got["obs"][i] = o[:]
+        got["reward"][i] = L.orc_env_evaluate(C.byref(spec), (C.c_double * 5)(*x), float(u), (C.c_double * 5)(*y))
+    assert_same_bits(want, got, ("obs", "term", "reward"), "balancing task")
+    assert {0, 1, 2} <= set(want["term"]) and (want["reward"] == 0).any() and ((want["reward"] > 0) & (want["reward"] < 1)).any()
+    fallen = np.abs(nxt[:, 1]) > 12 * np.pi / 180
+    assert (fallen & (np.abs(nxt[:, 0]) <= 2.4)).any() and (~fallen & (np.abs(nxt[:, 0]) > 2.4)).any() and (~fallen & (np.abs(nxt[:, 0]) <= 2.4)).any()
+    starts = rc.seeded_starts()
+    draws, after = [], []
+    for pos in starts["position"][: rc.N_STARTS]:
+        g = ob.Rand48(int(pos))
+        draws.append(L.orc_drand48(C.byref(g))); after.append(g.x)
+    x = np.array([rc.floats(a) for a in rc.ask([f"balancing_start {rc.hexes(d)}" for d in draws])])
+    mine = np.zeros((rc.N_STARTS, 5)); mine_after = []
+    for i, pos in enumerate(starts["position"][: rc.N_STARTS]):
+        g, tl, xs = C.c_uint64(0), C.c_uint64(int(pos)), (C.c_double * 5)()
+        L.orc_env_start_at(C.byref(spec), C.byref(g), C.byref(tl), 0, xs)
+        mine[i] = xs[:]; mine_after.append(tl.value)
+    assert_same_bits({"x": x}, {"x": mine}, ("x",), "balancing starts")
+    assert mine_after == after and len(set(x[:, 1])) == rc.N_STARTS and (np.abs(x[:, 1]) <= 0.05).all()

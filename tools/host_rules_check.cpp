@@ -1,6 +1,9 @@
 // host_rules_check.cpp -- the host-side rules of the C ABI (grl_amd/csrc/grlx_host_rules.h) checked as a program of their own, built
 // with the host sanitizers (tests/test_host_rules.py).  Each rule is held to the property it states, not to a second copy of its code.
+#include <cmath>
 #include <cstdio>
+#include <initializer_list>
+#include <limits>
 #include <cstring>
 #include "../grl_amd/csrc/grlx_host_rules.h"
 
@@ -79,8 +82,48 @@ static void check_bytes()
   printf("byte counts: no 32-bit overflow at 2^26 entries x 65536 replicas\n");
 }
 
+static void check_quant()
+{ // the property the rule is there for: an admitted coordinate's floor(x * scaling) is an int of magnitude at most 2^30, so tile_quant's
+  // cast is defined and the displacement 1 + 2 i added over 32 tilings stays inside int; the first product at the bound is refused
+  const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
+  const double scalings[5] = {1., 16. / 0.31415, 16. / 2.5, 32. / 0.1, 1. / 1024.};
+  long cases = 0;
+  for (double sc : scalings)
+  {
+    double inside = 1073741824. / sc;                   // walk down to the largest x whose product is below 2^30, up to the first at it
+    while (!(inside * sc < 1073741824.)) inside = std::nextafter(inside, 0.);
+    while (std::nextafter(inside, inf) * sc < 1073741824.) inside = std::nextafter(inside, inf);
+    const double outside = std::nextafter(inside, inf);
+    for (double sign : {1., -1.})
+    {
+      ++cases;
+      CHECK(quant_admits(sign * inside, sc), "scaling %g: %a is inside the bound", sc, sign * inside);
+      CHECK(!quant_admits(sign * outside, sc), "scaling %g: %a is the first value outside the bound", sc, sign * outside);
+      const double q = std::floor(sign * inside * sc);
+      CHECK(q >= -1073741824. && q < 1073741824. && (double)(int)q == q, "scaling %g: floor(%a * scaling) = %.17g does not fit", sc, sign * inside, q);
+    }
+    for (double x : {0., -0., 1e-300, -1e-12, 40., -40.}) CHECK(quant_admits(x, sc), "scaling %g: %g is admitted", sc, x);
+    for (double x : {inf, -inf, nan, 1e300, -1e300}) CHECK(!quant_admits(x, sc), "scaling %g: %g is refused", sc, x);
+  }
+  // rows: the first offender is named by row and dimension, and by kind (1 not finite, 2 out of range); clean rows give 0
+  const double sc3[3] = {1., 2., 4.};
+  double rows[4 * 3] = {0, 1, 2, -3, 4, 5, 6, 7, 8, 9, 10, 11};
+  int row = -1, dim = -1;
+  CHECK(quant_admit_rows(rows, 4, 3, sc3, &row, &dim) == 0 && row == -1 && dim == -1, "clean rows");
+  CHECK(quant_admit_rows(rows, 0, 3, sc3, &row, &dim) == 0, "no rows");
+  rows[2 * 3 + 1] = 536870912.;                         // x 2 = 2^30
+  rows[3 * 3 + 0] = nan;
+  CHECK(quant_admit_rows(rows, 4, 3, sc3, &row, &dim) == 2 && row == 2 && dim == 1, "out of range at (2, 1): got (%d, %d)", row, dim);
+  rows[2 * 3 + 1] = std::nextafter(536870912., 0.);
+  CHECK(quant_admit_rows(rows, 4, 3, sc3, &row, &dim) == 1 && row == 3 && dim == 0, "not finite at (3, 0): got (%d, %d)", row, dim);
+  rows[3 * 3 + 0] = -inf;
+  CHECK(quant_admit_rows(rows, 4, 3, sc3, &row, &dim) == 1 && row == 3 && dim == 0, "-inf at (3, 0): got (%d, %d)", row, dim);
+  printf("quant_admits: %ld bounds\n", cases);
+}
+
 int main()
 {
+  check_quant();
   check_growth();
   check_draws();
   check_bytes();

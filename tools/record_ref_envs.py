@@ -1,14 +1,18 @@
 #!/usr/bin/env python3
-"""Record what the reference's own acrobot and compass-walker code answers on the case sets of tests/ref_env_cases.py.
+"""Record what the reference's own acrobot, cart-pole, pendulum and compass-walker code answers on the case sets of
+tests/ref_env_cases.py, and its tile coding on those of tests/ref_tile_cases.py.
 
-Needs oracle/_ref/ref_envs and oracle/_ref/ref_envs_fused (`make -C oracle` on a machine with a checkout of the reference).
+Needs oracle/_ref/ref_envs, oracle/_ref/ref_envs_fused and oracle/_ref/ref_tiles (`make -C oracle` on a machine with a checkout of
+the reference).
 Writes
-  tests/golden/ref_envs_acrobot.npz, tests/golden/ref_envs_walker.npz   inputs and the binary's outputs: data only
+  tests/golden/ref_envs_{acrobot,walker,cart_pole,pendulum}.npz   inputs and the binary's outputs: data only
+  tests/golden/ref_tiles.npz   tile coding specs, inputs and the indices oracle/_ref/ref_tiles answered: data only
   tests/golden/ref_envs_bounds.json   per environment and output group the largest absolute deviation of the PORTABLE-mode
       oracle (what the kernels reproduce bit for bit) from the binary on those rows -- measured against the reference, never
       against a kernel --, the rows excluded for a different discrete outcome, the rows on which a binary built at plain -O2
       (g++ fuses sin/cos into sincos) differs from the call-by-call one, and the compiler and C library that built both.
-tests/test_oracle_ref_envs.py holds the three files against a fresh run; tests/test_gpu_ref_envs.py reads them on the GPU.
+tests/test_oracle_ref_envs.py and tests/test_oracle_ref_tiles.py hold the files against a fresh run; tests/test_gpu_ref_envs.py and
+tests/test_gpu_ref_tiles.py read them on the GPU.
 Run:  python tools/record_ref_envs.py
 """
 import json
@@ -22,6 +26,10 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from tests import oracle_binding as ob  # noqa: E402
 from tests import ref_env_cases as rc  # noqa: E402
+from tests import ref_tile_cases as tc  # noqa: E402
+
+
+ENVS = ("acrobot", "walker", "cart_pole", "pendulum")
 
 
 def differing_rows(a, b, keys):
@@ -45,10 +53,11 @@ def record(env):
     sexcluded = sref["position_after"] != sportable["position_after"]
     fused = rc.reference_answers(env, cases, rc.REF_BIN_FUSED)
     sfused = rc.reference_starts(env, starts, rc.REF_BIN_FUSED)
-    np.savez_compressed(rc.FIXTURE[env], state=cases["state"], action=cases["action"], tag=cases["tag"],
-                        next=ref["next"], obs=ref["obs"], reward=ref["reward"], term=ref["term"], excluded=excluded,
-                        start_position=starts["position"], start_test=starts["test"], start_x=sref["x"], start_obs=sref["obs"],
-                        start_position_after=sref["position_after"], start_excluded=sexcluded)
+    out = dict(cases)                                                     # state, action, tag (and the cart-pole's variant)
+    out.update(next=ref["next"], obs=ref["obs"], reward=ref["reward"], term=ref["term"], excluded=excluded)
+    out.update({"start_" + k: v for k, v in starts.items()})              # position, test (and the randomization where there is one)
+    out.update(start_x=sref["x"], start_obs=sref["obs"], start_position_after=sref["position_after"], start_excluded=sexcluded)
+    np.savez_compressed(rc.FIXTURE[env], **out)
     keys = rc.ANSWER_KEYS[env]
     return {"rows": int(len(excluded)), "excluded_rows": int(excluded.sum()),
             "bounds": rc.deviations(env, ref, portable, excluded),
@@ -58,8 +67,33 @@ def record(env):
             "starts_differing_at_plain_O2": int(differing_rows(sref, sfused, ("x", "obs", "position_after")).sum())}
 
 
+def record_tiles():
+    """tests/golden/ref_tiles.npz: per spec k its shape, its inputs x{k}, their tags tag{k} and what oracle/_ref/ref_tiles answered, idx{k};
+    the names of the specs configure() refuses, those a fixed-size spec can say with their shapes.  Data only."""
+    specs, refused = tc.specs(), tc.refused_specs()
+    for s in refused:
+        assert tc.reference_refuses(s), s["name"]
+
+    def shapes(which):
+        res, wrap = np.zeros((len(which), tc.MAX_DIMS)), np.zeros((len(which), tc.MAX_DIMS))
+        for k, s in enumerate(which):
+            res[k, :len(s["res"])] = s["res"]; wrap[k, :len(s["wrap"])] = s["wrap"]
+        return dict(names=np.array([s["name"] for s in which]), tilings=np.array([s["tilings"] for s in which], np.int32),
+                    memory=np.array([s["memory"] for s in which], np.int32), dims=np.array([len(s["res"]) for s in which], np.int32),
+                    wrap_len=np.array([len(s["wrap"]) for s in which], np.int32), res=res, wrap=wrap)
+    out = shapes(specs)
+    out.update({"refused_" + k: v for k, v in shapes(refused).items()})
+    rows = 0
+    for k, s in enumerate(specs):
+        cases = tc.inputs(s, seed=7000 + k)
+        out[f"x{k}"], out[f"tag{k}"], out[f"idx{k}"] = cases["x"], cases["tag"], tc.reference_indices(s, cases["x"])
+        rows += len(cases["tag"])
+    np.savez_compressed(tc.FIXTURE, **out)
+    return {"specs": len(specs), "refused_specs": len(refused), "rows": rows}
+
+
 def main():
-    out = {env: record(env) for env in ("acrobot", "walker")}
+    out = {env: record(env) for env in ENVS}
     pool = rc.walker_pool()                                              # the 12 k steps the walker's rows are chosen from
     call_by_call, fused = rc.reference_answers("walker", pool), rc.reference_answers("walker", pool, rc.REF_BIN_FUSED)
     differ = differing_rows(call_by_call, fused, rc.ANSWER_KEYS["walker"])
@@ -68,6 +102,7 @@ def main():
     out["walker"]["pool_rows_differing_at_plain_O2"] = int(differ.sum())
     out["walker"]["pool_largest_difference_at_plain_O2"] = largest
     out["walker"]["pool_discrete_differences_at_plain_O2"] = int(rc.discrete_mismatch("walker", call_by_call, fused).sum())
+    out["tiles"] = record_tiles()
     out["toolchain"] = {"compiler": subprocess.run(["g++", "--version"], capture_output=True, text=True, check=True).stdout.splitlines()[0],
                         "libc": " ".join(platform.libc_ver()),
                         "flags": "-O2 -std=c++11 -ffp-contract=off -fno-builtin (plain -O2: without -fno-builtin)"}
@@ -75,7 +110,8 @@ def main():
         json.dump(out, f, indent=2, sort_keys=True)
         f.write("\n")
     print(json.dumps(out, indent=2, sort_keys=True))
-    for env in ("acrobot", "walker"):
+    print(tc.FIXTURE, os.path.getsize(tc.FIXTURE), "bytes")
+    for env in ENVS:
         print(rc.FIXTURE[env], os.path.getsize(rc.FIXTURE[env]), "bytes")
 
 
