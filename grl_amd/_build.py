@@ -14,7 +14,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libgrlx.so")
 # the C ABI (include/grlx.h), one unit per subject; they share grlx_host.h
 API_UNITS = ["grlx_api_config.cpp", "grlx_api_context.cpp", "grlx_api_run.cpp", "grlx_api_tables.cpp", "grlx_api_step.cpp", "grlx_api_read.cpp", "grlx_api_snapshot.cpp"]
-SOURCES = ["grlx_kernels.hip", "grlx_fqi.hip", "grlx_snapshot.hip", "grlx_query.hip", "grlx_evaluate.hip", "grlx_evaluate_sampled.hip", "grlx_evaluate_noisy.hip", "grlx_evaluate_stream.hip"] + API_UNITS + ["grlx_plan.cpp", "grlx_snapshot_format.cpp"]
+SOURCES = ["grlx_kernels.hip", "grlx_fqi.hip", "grlx_snapshot.hip", "grlx_query.hip", "grlx_evaluate.hip", "grlx_evaluate_sampled.hip", "grlx_evaluate_noisy.hip", "grlx_evaluate_actor_ensemble.hip", "grlx_evaluate_stream.hip"] + API_UNITS + ["grlx_plan.cpp", "grlx_snapshot_format.cpp"]
 GRLX_H = os.path.join("..", "..", "include", "grlx.h")
 # what grlx_kernels.hip includes
 HEADERS = ["grlx_internal.h", "grlx_math.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_envs.h", "grlx_policy.h", "grlx_update.h", "grlx_frame.h",
@@ -110,9 +110,9 @@ def _build_hip_object(hipcc, src, tmp, flags, verbose, report):
 
 # what each translation unit includes (besides itself): an object whose inputs did not change is taken from the object cache
 # (outside the tree: $GRLX_OBJCACHE or /tmp/grlx_objcache), so that editing a unit of the C ABI does not recompile the kernels
-API_DEPS = ["grlx_host.h", "grlx_host_rules.h", "grlx_internal.h", "grlx_snapshot.h", "grlx_snapshot_format.h", "grlx_query.h", "grlx_evaluate.h", "grlx_evaluate_sampled.h", "grlx_evaluate_noisy.h", "grlx_evaluate_stream.h", GRLX_H,
+API_DEPS = ["grlx_host.h", "grlx_host_rules.h", "grlx_internal.h", "grlx_snapshot.h", "grlx_snapshot_format.h", "grlx_query.h", "grlx_evaluate.h", "grlx_evaluate_sampled.h", "grlx_evaluate_noisy.h", "grlx_evaluate_actor_ensemble.h", "grlx_evaluate_stream.h", GRLX_H,
             os.path.join("..", "..", "include", "grlx_diag.h")]
-# what the four units of the evaluation episodes share; grlx_episode.h: their common device helpers and dispatch
+# what the five units of the evaluation episodes share; grlx_episode.h: their common device helpers and dispatch
 EVALUATE_DEPS = ["grlx_internal.h", "grlx_math.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_envs.h", "grlx_query_weights.h", "grlx_evaluate.h",
                  "grlx_episode.h", GRLX_H]
 UNIT_DEPS = {
@@ -123,6 +123,7 @@ UNIT_DEPS = {
     "grlx_evaluate.hip": EVALUATE_DEPS,
     "grlx_evaluate_sampled.hip": EVALUATE_DEPS + ["grlx_evaluate_sampled.h"],
     "grlx_evaluate_noisy.hip": EVALUATE_DEPS + ["grlx_evaluate_noisy.h"],
+    "grlx_evaluate_actor_ensemble.hip": EVALUATE_DEPS + ["grlx_evaluate_actor_ensemble.h"],
     "grlx_evaluate_stream.hip": EVALUATE_DEPS + ["grlx_evaluate_stream.h", "grlx_host_rules.h"],
     **{unit: API_DEPS for unit in API_UNITS},
     "grlx_snapshot_format.cpp": ["grlx_snapshot_format.h", GRLX_H],

@@ -173,6 +173,13 @@ _SIGS = {
                                                  _P(C.c_double), _P(C.c_double), _P(C.c_double), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32),
                                                  _P(C.c_double), _P(C.c_uint64), _P(C.c_double), _P(C.c_double)]),
     "grlx_episode_stream_words": (None, [C.c_long, C.c_int64, C.c_int64, _P(C.c_uint64)]),
+    "grlx_evaluate_actor_ensemble": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _P(C.c_double), C.c_int, C.c_int,
+                                               _P(C.c_double), _P(C.c_double), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64), _P(C.c_double),
+                                               _P(C.c_double)]),
+    "grlx_actor_ensemble_trajectory_record_words": (C.c_int, [C.c_void_p]),
+    "grlx_evaluate_actor_ensemble_trajectory": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _P(C.c_double), C.c_int,
+                                                          C.c_int, _P(C.c_double), _P(C.c_double), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32),
+                                                          _P(C.c_int64), _P(C.c_double), _P(C.c_double), _P(C.c_double)]),
     "grlx_math": (C.c_int, [C.c_int, _P(C.c_double), _P(C.c_double), C.c_int, _P(C.c_double)]),
     "grlx_rand48_at": (C.c_int, [C.c_int64, _P(C.c_uint64), C.c_int, _P(C.c_double)]),
     "grlx_fqi_config_pendulum": (None, [_P(FqiConfig)]),
@@ -223,7 +230,8 @@ _NEWER_SIGS = ("grlx_snapshot_size", "grlx_snapshot_save", "grlx_snapshot_load",
                "grlx_fqi_evaluate_ensemble_trajectory",
                "grlx_evaluate_sampled", "grlx_sampled_trajectory_record_words", "grlx_evaluate_sampled_trajectory", "grlx_episode_streams",
                "grlx_evaluate_noisy", "grlx_noisy_trajectory_record_words", "grlx_evaluate_noisy_trajectory", "grlx_episode_stream_words",
-               "grlx_evaluate_trajectory_stream")
+               "grlx_evaluate_trajectory_stream",
+               "grlx_evaluate_actor_ensemble", "grlx_actor_ensemble_trajectory_record_words", "grlx_evaluate_actor_ensemble_trajectory")
 # grlx_kernel_plan flags
 PLAN_STAMPS_IN_PLACE, PLAN_STAMPS_DEFERRED, PLAN_SWEEP, PLAN_SERVER_OFF, PLAN_WALKER_SERVER, PLAN_FITS_YES, PLAN_FITS_NO = 1, 2, 4, 8, 16, 32, 64
 ENSEMBLE_VOTE, ENSEMBLE_MEAN_Q = 0, 1       # grlx_evaluate_ensemble's rule
@@ -233,6 +241,8 @@ TRAJ_ENS_AGREEMENT, TRAJ_ENS_MEMBER_TIES, TRAJ_ENS_OBS = 6, 7, 8
 SAMPLER_GREEDY, SAMPLER_EPSILON_GREEDY = 0, 1      # grlx_evaluate_sampled's sampler
 EPSILON_OWN = -1.0                                 # ... and its epsilon that means eps_decay * epsilon of the replica (GRLX_EPSILON_OWN)
 SIGMA_OWN, THETA_OWN = -1.0, -1.0                  # grlx_evaluate_noisy: ac_decay * sigma of the replica, the configuration's theta
+# grlx_evaluate_actor_ensemble's rule and the largest group it serves (GRLX_ACTOR_ENSEMBLE_*)
+ACTOR_ENSEMBLE_MEAN, ACTOR_ENSEMBLE_BINNING, ACTOR_ENSEMBLE_DATA_CENTER, ACTOR_ENSEMBLE_DENSITY, ACTOR_ENSEMBLE_MAX = 0, 1, 2, 3, 256
 ABI_VERSION = 2        # include/grlx.h: GRLX_ABI_VERSION
 
 

@@ -1,9 +1,10 @@
-// grlx_api_read.cpp -- the C ABI declared in include/grlx.h: the read side -- policy queries, greedy, sampled and noisy evaluation episodes, chunked over the caller's observations / start states; the streamed trajectories' two-slot pipeline.
+// grlx_api_read.cpp -- the C ABI declared in include/grlx.h: the read side -- policy queries, greedy, sampled, noisy and actor-ensemble evaluation episodes, chunked over the caller's observations / start states; the streamed trajectories' two-slot pipeline.
 #include "grlx_host.h"
 #include "grlx_query.h"
 #include "grlx_evaluate.h"
 #include "grlx_evaluate_sampled.h"
 #include "grlx_evaluate_noisy.h"
+#include "grlx_evaluate_actor_ensemble.h"
 #include "grlx_evaluate_stream.h"
 
 // ------------------------------------------------------------------------------------------- policy queries ---
@@ -190,7 +191,8 @@ int evaluate_admit(grlx_ctx *ctx, const char *who, int first_replica, int n_repl
 int ensemble_admit(grlx_ctx *ctx, const char *who, int n_replicas, int group_size, int rule)
 {
   if (!q_agent(ctx->cfg.agent))
-    return fail(GRLX_ERR_INVALID, "%s is not built for the actor-critic agent (a vote over continuous actions is mapping/policy/multi's); it serves agents with a policy/discrete/q", who);
+    return fail(GRLX_ERR_INVALID, "%s is not built for the actor-critic agent (a vote over continuous actions is mapping/policy/multi's: "
+                "grlx_evaluate_actor_ensemble combines them); it serves agents with a policy/discrete/q", who);
   if (group_size < 1) return fail(GRLX_ERR_INVALID, "%s: group_size = %d is below 1", who, group_size);
   if (n_replicas % group_size != 0) return fail(GRLX_ERR_INVALID, "%s: group_size %d does not divide the %d replicas", who, group_size, n_replicas);
   if (rule != GRLX_ENSEMBLE_VOTE && rule != GRLX_ENSEMBLE_MEAN_Q)
@@ -259,6 +261,36 @@ int noisy_admit(grlx_ctx *ctx, const char *who, int n_replicas, int n_starts, do
     if (noise && !std::isfinite(noise[row]))
       return fail(GRLX_ERR_INVALID, "%s: noise row %lld (replica %lld, start state %lld) is not finite (%g)", who, (long long)row, (long long)(row / n_starts),
                   (long long)(row % n_starts), noise[row]);
+  }
+  return GRLX_OK;
+}
+
+// ---- actor-critic ensembles: episodes on the members' combined action (grlx_evaluate_actor_ensemble.hip) -------------------------------------
+// what both calls check beyond evaluate_admit
+int actor_ensemble_admit(grlx_ctx *ctx, const char *who, int n_replicas, int group_size, int rule, int bins, double r)
+{
+  if (q_agent(ctx->cfg.agent))
+    return fail(GRLX_ERR_INVALID, "%s serves the actor-critic only (it combines continuous actions, mapping/policy/multi); the vote and the mean Q of agents "
+                "with a policy/discrete/q are grlx_evaluate_ensemble's", who);
+  if (group_size < 1) return fail(GRLX_ERR_INVALID, "%s: group_size = %d is below 1", who, group_size);
+  if (n_replicas % group_size != 0) return fail(GRLX_ERR_INVALID, "%s: group_size %d does not divide the %d replicas", who, group_size, n_replicas);
+  if (group_size > GRLX_ACTOR_ENSEMBLE_MAX)
+    return fail(GRLX_ERR_INVALID, "%s: group_size = %d exceeds GRLX_ACTOR_ENSEMBLE_MAX (%d)", who, group_size, GRLX_ACTOR_ENSEMBLE_MAX);
+  switch (rule)
+  {
+    case GRLX_ACTOR_ENSEMBLE_MEAN: break;
+    case GRLX_ACTOR_ENSEMBLE_BINNING:
+      if (bins < 1 || bins > 64) return fail(GRLX_ERR_INVALID, "%s: bins = %d is outside 1 ... 64 (GRLX_ACTOR_ENSEMBLE_BINNING)", who, bins);
+      break;
+    case GRLX_ACTOR_ENSEMBLE_DATA_CENTER:
+      if (bins < 1) return fail(GRLX_ERR_INVALID, "%s: bins = %d, the members kept, is below 1 (GRLX_ACTOR_ENSEMBLE_DATA_CENTER)", who, bins);
+      break;
+    case GRLX_ACTOR_ENSEMBLE_DENSITY:
+      if (!std::isfinite(r)) return fail(GRLX_ERR_INVALID, "%s: r is not finite (%g) (GRLX_ACTOR_ENSEMBLE_DENSITY)", who, r);
+      if (!(r > 0.)) return fail(GRLX_ERR_INVALID, "%s: r = %g is not above 0 (GRLX_ACTOR_ENSEMBLE_DENSITY)", who, r);
+      break;
+    default:
+      return fail(GRLX_ERR_INVALID, "%s: unknown rule %d (GRLX_ACTOR_ENSEMBLE_MEAN = 0, _BINNING = 1, _DATA_CENTER = 2, _DENSITY = 3)", who, rule);
   }
   return GRLX_OK;
 }
@@ -748,6 +780,46 @@ int grlx_evaluate_noisy_trajectory(grlx_ctx *ctx, int first_replica, int n_repli
 {
   return evaluate_noisy_impl(ctx, "grlx_evaluate_noisy_trajectory", "grlx_evaluate_noisy", first_replica, n_replicas, states, n_starts, max_steps, sigma,
                              theta, streams, noise, ret, disc, steps, terminal, clipped, final_state, streams_out, noise_out, records);
+}
+
+// ---- actor-critic ensembles (grlx_evaluate_actor_ensemble.hip); sibling null: the sums alone
+static int evaluate_actor_ensemble_impl(grlx_ctx *ctx, const char *who, const char *sibling, int first_replica, int n_replicas, int group_size, int rule,
+                                        int bins, double r, const double *states, int n_starts, int max_steps, double *ret, double *disc, int32_t *steps,
+                                        int32_t *terminal, int32_t *ties, int64_t *kept, double *spread, double *final_state, double *records)
+{
+  EpisodeCall c{who, first_replica, n_replicas, group_size, states, n_starts, max_steps, ret, disc, steps, terminal, ties, final_state};
+  c.extra[0] = {kept, sizeof(int64_t)}; c.extra[1] = {spread, sizeof(double)}; c.n_extra = 2;
+  c.extra_bytes = sizeof(int64_t) + sizeof(double);
+  c.sibling = sibling; c.records = records; c.record_words = actor_ensemble_trajectory_words;
+  return episode_read<ActorEnsembleArgs>(ctx, c, [&] { return actor_ensemble_admit(ctx, who, n_replicas, group_size, rule, bins, r); },
+                                         [&](ActorEnsembleArgs &A, const DevBuf *extra, double *rec) {
+    A.group_size = group_size; A.rule = rule; A.bins = bins; A.r = r;
+    A.kept = extra[0].as<int64_t>(); A.spread = extra[1].as<double>();
+    A.records = rec;
+    return rec ? launch_trajectory_actor_ensemble(ctx->P, A, nullptr) : launch_evaluate_actor_ensemble(ctx->P, A, nullptr);
+  });
+}
+
+int grlx_evaluate_actor_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule, int bins, double r, const double *states,
+                                 int n_starts, int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, int64_t *kept,
+                                 double *spread, double *final_state)
+{
+  return evaluate_actor_ensemble_impl(ctx, "grlx_evaluate_actor_ensemble", nullptr, first_replica, n_replicas, group_size, rule, bins, r, states, n_starts,
+                                      max_steps, ret, disc, steps, terminal, ties, kept, spread, final_state, nullptr);
+}
+
+int grlx_actor_ensemble_trajectory_record_words(grlx_ctx *ctx)
+{
+  if (int rc = record_words_admit(ctx, "grlx_actor_ensemble_trajectory_record_words", is_q, "the actor ensemble serves the actor-critic only")) return rc;
+  return actor_ensemble_trajectory_words(ctx->cfg.env);
+}
+
+int grlx_evaluate_actor_ensemble_trajectory(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule, int bins, double r,
+                                            const double *states, int n_starts, int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal,
+                                            int32_t *ties, int64_t *kept, double *spread, double *final_state, double *records)
+{
+  return evaluate_actor_ensemble_impl(ctx, "grlx_evaluate_actor_ensemble_trajectory", "grlx_evaluate_actor_ensemble", first_replica, n_replicas, group_size,
+                                      rule, bins, r, states, n_starts, max_steps, ret, disc, steps, terminal, ties, kept, spread, final_state, records);
 }
 
 // host only: stream k = srand48(seed) advanced by k * 2^20 draws, k = 2 * pair + which

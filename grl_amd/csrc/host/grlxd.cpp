@@ -21,6 +21,9 @@
 // -N SIGMA|own: with -E on an actor-critic, also one NOISY episode per (clone, start state) with grlx_evaluate_noisy -- the exploring policy on a
 // standard deviation SIGMA >= 0 or on every clone's own decayed sigma, on the configuration's theta -- on the streams of
 // grlx_episode_stream_words(-s seed), written to <output>-<run>-noisy.txt, and with -T the steps in <output>-<run>-noisy-trajectories.txt (objects.h),
+// -A mean|binning[:bins]|data_center[:keep]|density[:r]: with -E on an actor-critic, also one episode per start state of the ensemble of ALL clones
+// acting on the members' combined action (grlx_evaluate_actor_ensemble; the parameters default to the reference's 10, 10 and 0.001), written to
+// <output>-<run>-actor-ensemble.txt, and with -T the steps in <output>-<run>-actor-ensemble-trajectories.txt (objects.h),
 // -n: print the plan (one line per clone: i seed alpha gamma lambda epsilon) and exit before anything touches HIP, and
 // -g N: one process per GPU (rank r on the r-th visible device, started before anything touches HIP), every rank running -r replicas
 // (clones r * replicas ..., seeds and "@i" identities counted over the whole job), the learning curves reduced with one RCCL all-reduce
@@ -85,9 +88,9 @@ int main(int argc, char **argv)
   int c;
   std::vector<std::string> sweep_args;
   std::string ensemble_arg;
-  bool ensemble = false, trajectory = false, sampled = false, noisy = false;
+  bool ensemble = false, trajectory = false, sampled = false, noisy = false, actors = false;
   int trajectory_steps = 0;
-  while ((c = getopt(argc, argv, "vs:r:t:lqc:g:p:nk:K:Q:E:V:T:e:N:")) != -1)
+  while ((c = getopt(argc, argv, "vs:r:t:lqc:g:p:nk:K:Q:E:V:T:e:N:A:")) != -1)
   {
     switch (c)
     {
@@ -109,12 +112,13 @@ int main(int argc, char **argv)
       case 'T': trajectory_steps = atoi(optarg); trajectory = true; break;
       case 'e': opt.sampled_arg = optarg; sampled = true; break;
       case 'N': opt.noisy_arg = optarg; noisy = true; break;
+      case 'A': opt.actor_arg = optarg; actors = true; break;
       default: return 1;
     }
   }
   if (optind > argc - 1)
   {
-    log(0, std::string("Usage: \n  ") + argv[0] + " [-v] [-s seed] [-r replicas] [-g gpus] [-t trials] [-l] [-q] [-p path=v1,v2,...]... [-n] [-k snapshot] [-K snapshot] [-Q observations] [-E states] [-V vote|mean] [-T steps] [-e epsilon|own|greedy] [-N sigma|own] <yaml file> [yaml file...]");
+    log(0, std::string("Usage: \n  ") + argv[0] + " [-v] [-s seed] [-r replicas] [-g gpus] [-t trials] [-l] [-q] [-p path=v1,v2,...]... [-n] [-k snapshot] [-K snapshot] [-Q observations] [-E states] [-V vote|mean] [-T steps] [-e epsilon|own|greedy] [-N sigma|own] [-A mean|binning[:bins]|data_center[:keep]|density[:r]] <yaml file> [yaml file...]");
     return 1;
   }
   if (opt.seed == 0)
@@ -213,6 +217,37 @@ int main(int argc, char **argv)
     if (gpus > 1) { log(0, "-N: a noisy policy evaluation runs on one GPU (-g " + std::to_string(gpus) + " is not built)"); return 1; }
     if (!sweep_args.empty()) { log(0, "-N: a noisy evaluation is the actor-critic's, for which per-replica parameters (-p) are not built"); return 1; }
     if (opt.replicas < 2) { log(0, "-N: -E needs -r >= 2: the standard deviation over the clones divides by n - 1"); return 1; }
+  }
+  if (actors)
+  { // -A needs -E's states, one of the four rules and a well-formed parameter: refused before any process is forked or any device looked for
+    const std::string &arg = opt.actor_arg;
+    const size_t colon = arg.find(':');
+    const std::string name = arg.substr(0, colon), value = colon == std::string::npos ? "" : arg.substr(colon + 1);
+    const bool given = colon != std::string::npos;
+    char *stop = nullptr;
+    if (name == "mean") opt.actor_rule = GRLX_ACTOR_ENSEMBLE_MEAN;
+    else if (name == "binning") opt.actor_rule = GRLX_ACTOR_ENSEMBLE_BINNING;
+    else if (name == "data_center") opt.actor_rule = GRLX_ACTOR_ENSEMBLE_DATA_CENTER;
+    else if (name == "density") opt.actor_rule = GRLX_ACTOR_ENSEMBLE_DENSITY;
+    else { log(0, "-A: unknown rule '" + name + "' (mean, binning[:bins], data_center[:keep], density[:r]: mapping/policy/multi's strategies)"); return 1; }
+    if (given && opt.actor_rule == GRLX_ACTOR_ENSEMBLE_MEAN) { log(0, "-A " + arg + ": the rule mean takes no parameter"); return 1; }
+    if (given && opt.actor_rule == GRLX_ACTOR_ENSEMBLE_DENSITY)
+    {
+      opt.actor_r = strtod(value.c_str(), &stop);
+      if (value.empty() || *stop != 0 || !std::isfinite(opt.actor_r) || !(opt.actor_r > 0.))
+      { log(0, "-A " + arg + ": '" + value + "' is not a finite radius above 0"); return 1; }
+    }
+    else if (given)
+    {
+      const long v = strtol(value.c_str(), &stop, 10);
+      const long most = opt.actor_rule == GRLX_ACTOR_ENSEMBLE_BINNING ? 64 : 0x7fffffffl;
+      if (value.empty() || *stop != 0 || v < 1 || v > most)
+      { log(0, "-A " + arg + ": '" + value + "' is not " + (opt.actor_rule == GRLX_ACTOR_ENSEMBLE_BINNING ? "a number of bins in 1 ... 64" : "a number of members kept >= 1")); return 1; }
+      opt.actor_bins = (int)v;
+    }
+    if (opt.evaluate_file.empty()) { log(0, "-A " + arg + ": an actor ensemble's evaluation needs the start states of -E <states file>"); return 1; }
+    if (gpus > 1) { log(0, "-A: an actor ensemble's evaluation runs on one GPU (-g " + std::to_string(gpus) + " is not built)"); return 1; }
+    if (!sweep_args.empty()) { log(0, "-A: an actor ensemble is the actor-critic's, for which per-replica parameters (-p) are not built"); return 1; }
   }
   if (!opt.evaluate_file.empty())
   { // likewise: the state file is read, and -g and -r 1 refused, before any process is forked or any device looked for

@@ -81,6 +81,15 @@ struct RunOptions {
   bool noisy = false;
   double noisy_sigma = 0;
   std::string noisy_arg;
+  // -A mean|binning[:bins]|data_center[:keep]|density[:r] (needs -E, an actor-critic): also one episode per start state of the ensemble of ALL
+  // clones on the members' combined action (grlx_evaluate_actor_ensemble).  <output>-<run>-actor-ensemble.txt: per start state one line
+  // "ret disc steps terminal ties kept spread".  With -T also <output>-<run>-actor-ensemble-trajectories.txt
+  // (grlx_evaluate_actor_ensemble_trajectory): the trajectories file's lines for group 0, with the record's two last words, the step's kept
+  // and spread.  actor_rule: GRLX_ACTOR_ENSEMBLE_*, -1 without -A.
+  int actor_rule = -1;
+  int actor_bins = 10;
+  double actor_r = 0.001;
+  std::string actor_arg;
 };
 // ... the same for opt.evaluate_file -> opt.evaluate_states / _rows / _cols (messages begin with -E)
 void read_evaluate_file(RunOptions *opt);

@@ -236,6 +236,8 @@ struct BatchLearningExperimentImpl : Experiment {
       throw Exception(path() + ": a policy query (-Q) is built for experiment/online_learning, not for experiment/batch_learning");
     if (opt.trajectory_steps != 0)
       throw Exception(path() + ": per-step trajectories (-T) are built for experiment/online_learning, not for experiment/batch_learning");
+    if (opt.actor_rule >= 0)
+      throw Exception(path() + ": an actor ensemble's evaluation (-A) is built for experiment/online_learning, not for experiment/batch_learning");
     if (opt.noisy)
       throw Exception(path() + ": a noisy policy evaluation (-N) is built for experiment/online_learning, not for experiment/batch_learning");
     if (opt.sampled_sampler >= 0)

@@ -315,6 +315,7 @@ struct OnlineLearningExperimentImpl : OnlineLearningExperiment, StepwiseExperime
   void write_trajectory_files(const RunPlan &p, grlx_ctx *ctx, int run) const;
   void write_sampled_files(const RunPlan &p, grlx_ctx *ctx, int run) const;
   void write_noisy_files(const RunPlan &p, grlx_ctx *ctx, int run) const;
+  void write_actor_ensemble_files(const RunPlan &p, grlx_ctx *ctx, int run) const;
   void write_mean_file(const RunPlan &p, grlx_ctx *ctx, int run, const RunRows &rows) const;
 };
 

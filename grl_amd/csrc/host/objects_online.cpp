@@ -273,6 +273,14 @@ RunPlan OnlineImpl::plan(const RunOptions &opt) const
     if (c.agent != GRLX_AGENT_AC)
       throw Exception(path() + ": -N: a noisy evaluation serves the actor-critic agent only; the samplers of an agent with a policy/discrete/q are -e <epsilon | own | greedy>'s");
   }
+  if (opt.actor_rule >= 0)
+  { // -A rides on -E: refused here with its own name, before -E's checks say the same without it
+    if (opt.evaluate_file.empty()) throw Exception(path() + ": -A: an actor ensemble's evaluation needs the start states of -E <states file>");
+    if (opt.world > 1) throw Exception(path() + ": -A: an actor ensemble's evaluation runs on one GPU (-g " + std::to_string(opt.world) + " is not built)");
+    if (p.sweep) throw Exception(path() + ": -A: an actor ensemble is the actor-critic's, for which per-replica parameters (-p) are not built");
+    if (c.agent != GRLX_AGENT_AC)
+      throw Exception(path() + ": -A: an actor ensemble serves the actor-critic agent only; the vote and the mean Q of an agent with a policy/discrete/q are -V <vote | mean>'s");
+  }
   p.evaluate = !opt.evaluate_file.empty();
   if (p.evaluate)
   { // (grlx_evaluate validates the states themselves, and what it is built for, before it launches)
@@ -285,7 +293,7 @@ RunPlan OnlineImpl::plan(const RunOptions &opt) const
                       " (the time included)");
     if (output.empty()) throw Exception(path() + ": -E writes <output>-<run>-returns.txt: the experiment has no output");
     if (opt.ensemble_rule >= 0 && c.agent == GRLX_AGENT_AC)
-      throw Exception(path() + ": -V: an ensemble evaluation is not built for the actor-critic agent (a vote over continuous actions is mapping/policy/multi's)");
+      throw Exception(path() + ": -V: an ensemble evaluation is not built for the actor-critic agent (a vote over continuous actions is mapping/policy/multi's: -A <rule> combines them)");
   }
   if (p.sweep)
   {
@@ -483,6 +491,7 @@ std::vector<double> OnlineImpl::run(const RunOptions &opt)
     write_trajectory_files(p, ctx, rr);
     write_sampled_files(p, ctx, rr);
     write_noisy_files(p, ctx, rr);
+    write_actor_ensemble_files(p, ctx, rr);
     write_mean_file(p, ctx, rr, rows);
     if (save_every == "run" && !output.empty()) save_policy(p, ctx, output + "-run" + std::to_string(rr));      // online_learning.cpp:294-302
 

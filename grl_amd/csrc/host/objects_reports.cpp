@@ -314,6 +314,41 @@ void OnlineImpl::write_noisy_files(const RunPlan &p, grlx_ctx *ctx, int run) con
   write_record_lines(ofs, records, tsteps, opt.replicas, NS, T, R);
 }
 
+// -E -A, <output>-<run>-actor-ensemble.txt: the returns file's start states for the ensemble of ALL clones of an actor-critic on the members'
+// combined action (grlx_evaluate_actor_ensemble), one line per start state: ret disc steps terminal ties kept spread.  With -T also
+// <output>-<run>-actor-ensemble-trajectories.txt, the first -T steps of the same episodes, step by step, as group 0's lines.
+void OnlineImpl::write_actor_ensemble_files(const RunPlan &p, grlx_ctx *ctx, int run) const
+{
+  const RunOptions &opt = *p.opt;
+  if (!p.evaluate || opt.rank != 0 || opt.actor_rule < 0) return;
+  const int NS = opt.evaluate_rows, G = opt.replicas;
+  std::vector<double> ret((size_t)NS), disc((size_t)NS), spread((size_t)NS);
+  std::vector<int32_t> esteps((size_t)NS), eterm((size_t)NS), eties((size_t)NS);
+  std::vector<int64_t> kept((size_t)NS);
+  check(grlx_evaluate_actor_ensemble(ctx, 0, G, G, opt.actor_rule, opt.actor_bins, opt.actor_r, opt.evaluate_states.data(), NS, 0, ret.data(), disc.data(),
+                                     esteps.data(), eterm.data(), eties.data(), kept.data(), spread.data(), nullptr),
+        "-A " + opt.actor_arg + ": ");
+  {
+    std::ofstream ofs(rules::output_name(output, run, false, 0, "-actor-ensemble"));
+    for (int s = 0; s < NS; ++s)
+    {
+      char line[416];
+      snprintf(line, sizeof(line), "%.17g %.17g %d %d %d %lld %.17g", ret[s], disc[s], esteps[s], eterm[s], eties[s], (long long)kept[s], spread[s]);
+      ofs << line << std::endl;
+    }
+  }
+  if (opt.trajectory_steps < 1) return;
+  const int T = opt.trajectory_steps, R = grlx_actor_ensemble_trajectory_record_words(ctx);
+  check(R < 0 ? R : GRLX_OK, "-A -T: ");
+  std::vector<double> records((size_t)NS * (size_t)T * (size_t)R);
+  std::vector<int32_t> tsteps((size_t)NS);
+  check(grlx_evaluate_actor_ensemble_trajectory(ctx, 0, G, G, opt.actor_rule, opt.actor_bins, opt.actor_r, opt.evaluate_states.data(), NS, T, nullptr, nullptr,
+                                                tsteps.data(), nullptr, nullptr, nullptr, nullptr, nullptr, records.data()),
+        "-A " + opt.actor_arg + " -T " + std::to_string(T) + ": ");
+  std::ofstream ofs(rules::output_name(output, run, false, 0, "-actor-ensemble-trajectories"));
+  write_record_lines(ofs, records, tsteps, 1, NS, T, R);
+}
+
 // `grlxd -g N`, <output>-<run>-mean.txt: the learning curve over the clones of ALL ranks: per row {sum, sum of squares, count} of this
 // device's replicas (grlx_curve_stats, fixed reduction order), ONE all-reduce over the ranks, mean and standard deviation on rank 0.
 // (Trial-bounded runs write the same rows on every rank; a steps budget with more than one clone is refused by the plan.)

@@ -123,6 +123,9 @@ def _rule(rule):
 _ENSEMBLE_FIELDS = "ret disc steps terminal ties member_ties agreement final_state"
 _SAMPLED_FIELDS = "ret disc steps terminal ties explored final_state streams"
 _NOISY_FIELDS = "ret disc steps terminal clipped final_state streams noise"
+_ACTOR_ENSEMBLE_FIELDS = "ret disc steps terminal ties kept spread final_state"
+_ACTOR_RULES = {"mean": capi.ACTOR_ENSEMBLE_MEAN, "binning": capi.ACTOR_ENSEMBLE_BINNING, "data_center": capi.ACTOR_ENSEMBLE_DATA_CENTER,
+                "density": capi.ACTOR_ENSEMBLE_DENSITY}
 _BASE_OUTPUTS = {"ret": np.float64, "disc": np.float64, "steps": np.int32, "terminal": np.int32, "ties": np.int32}
 _CTYPES = {np.float64: C.c_double, np.int32: C.c_int32, np.int64: C.c_int64, np.uint64: C.c_uint64}
 
@@ -804,6 +807,52 @@ class Runner:
                                                            None if noise is None else _ptr(noise, C.c_double), *ptrs))
         return NoisyTrajectory(*out)
 
+    # ---- actor-critic ensembles: episodes on the members' combined action (grlx_evaluate_actor_ensemble)
+    def _actor_ensemble_args(self, states, group_size, rule, bins, r, replicas):
+        if isinstance(rule, str):
+            if rule not in _ACTOR_RULES:
+                raise ValueError(f"rule {rule!r}: one of {sorted(_ACTOR_RULES)}")
+            rule = _ACTOR_RULES[rule]
+        states = _state_rows(states, self.state_dims)
+        first, count = self._replica_range(replicas)
+        group_size = int(group_size)
+        groups = count // group_size if group_size > 0 else 0
+        return states, first, count, group_size, groups, int(rule), int(bins), float(r)
+
+    def evaluate_actor_ensemble(self, states, group_size, rule="mean", bins=10, r=0.001, replicas=None, max_steps=0):
+        """One episode per (group of `group_size` consecutive actor-critic replicas, start state) pair, on the device: at every step the
+        members' noise-free actions (each what Runner.evaluate would act on for that replica) are combined in ascending replica order by
+        mapping/policy/multi's rule "mean", "binning" (`bins` bins, 1 ... 64), "data_center" (`bins` = the members kept) or "density"
+        (radius `r`), and the episode acts on the result.  ActorEnsembleEvaluation(ret, disc, steps, terminal, ties, kept, spread,
+        final_state), each [group][start]: ties = steps at which the rule's selection tied (the first candidate acts; no random draw), kept
+        = member-steps that entered the action taken, spread = the steps' max - min over the members, added up.  The defaults are the
+        reference's; at its r = 0.001 nearly every density is exactly 1, so nearly every step ties and the group's first member acts.
+        group_size 1 is Runner.evaluate.  The context is not changed (include/grlx.h: grlx_evaluate_actor_ensemble)."""
+        states, first, count, group_size, groups, rule, bins, r = self._actor_ensemble_args(states, group_size, rule, bins, r, replicas)
+        n = states.shape[0]
+        out, ptrs = _episode_outputs(groups, n, self.state_dims, _ACTOR_ENSEMBLE_FIELDS, kept=np.int64, spread=np.float64)
+        capi.check(self.lib.grlx_evaluate_actor_ensemble(self._ctx, first, count, group_size, rule, bins, r, _ptr(states, C.c_double), n, int(max_steps),
+                                                         *ptrs))
+        return ActorEnsembleEvaluation(*out)
+
+    def actor_ensemble_trajectory_record_words(self):
+        """R of evaluate_actor_ensemble_trajectory's records: trajectory_record_words() + 2 (grlx_actor_ensemble_trajectory_record_words)"""
+        return capi.check(self.lib.grlx_actor_ensemble_trajectory_record_words(self._ctx))
+
+    def evaluate_actor_ensemble_trajectory(self, states, group_size, max_steps, rule="mean", bins=10, r=0.001, replicas=None):
+        """Runner.evaluate_actor_ensemble with every step of every episode: ActorEnsembleTrajectory(..., records),
+        records[group][start][max_steps][R] with Trajectory's views -- .action the combined action, .value the members' arithmetic mean under
+        every rule, .action_index the selected member ("density"), the winning bin ("binning") or -1, .n_max the tied candidates -- and
+        .kept and .spread, per step; the per-episode sums are the fields n_kept and total_spread
+        (include/grlx.h: grlx_evaluate_actor_ensemble_trajectory)."""
+        states, first, count, group_size, groups, rule, bins, r = self._actor_ensemble_args(states, group_size, rule, bins, r, replicas)
+        n, max_steps = states.shape[0], int(max_steps)
+        out, ptrs = _episode_outputs(groups, n, self.state_dims, _ACTOR_ENSEMBLE_FIELDS, kept=np.int64, spread=np.float64,
+                                     records=(max_steps, self.actor_ensemble_trajectory_record_words()))
+        capi.check(self.lib.grlx_evaluate_actor_ensemble_trajectory(self._ctx, first, count, group_size, rule, bins, r, _ptr(states, C.c_double), n,
+                                                                    max_steps, *ptrs))
+        return ActorEnsembleTrajectory(*out)
+
 
 Evaluation = collections.namedtuple("Evaluation", "ret disc steps terminal ties final_state")
 EnsembleEvaluation = collections.namedtuple("EnsembleEvaluation", "ret disc steps terminal ties member_ties agreement final_state")
@@ -891,6 +940,22 @@ class NoisyTrajectory(_RecordViews, collections.namedtuple("NoisyTrajectory",
     state = property(lambda self: self._cut(self.records.shape[-1] - 2 - self.final_state.shape[-1], self.records.shape[-1] - 2))
     noise = property(lambda self: self._cut(self.records.shape[-1] - 2))
     clipped = property(lambda self: self._cut(self.records.shape[-1] - 1))
+
+
+ActorEnsembleEvaluation = collections.namedtuple("ActorEnsembleEvaluation", _ACTOR_ENSEMBLE_FIELDS)
+
+
+class ActorEnsembleTrajectory(_RecordViews, collections.namedtuple("ActorEnsembleTrajectory",
+                                                                   "ret disc steps terminal ties n_kept total_spread final_state records")):
+    """What Runner.evaluate_actor_ensemble_trajectory returns: ActorEnsembleEvaluation's fields and records[group][start][max_steps][R], whose
+    two last words (after the model state) are the members that entered the step's action and the step's max - min over the members: the
+    views .kept and .spread, per step.  The per-episode sums that ActorEnsembleEvaluation calls kept and spread are the fields n_kept and
+    total_spread here."""
+    __slots__ = ()
+    obs = property(lambda self: self._cut(self._OBS, self.records.shape[-1] - 2 - self.final_state.shape[-1]))
+    state = property(lambda self: self._cut(self.records.shape[-1] - 2 - self.final_state.shape[-1], self.records.shape[-1] - 2))
+    kept = property(lambda self: self._cut(self.records.shape[-1] - 2))
+    spread = property(lambda self: self._cut(self.records.shape[-1] - 1))
 
 
 def episode_stream_words(seed: int, n_replicas: int, n_starts: int, first_pair: int = 0):

@@ -712,6 +712,69 @@ int  grlx_evaluate_noisy_trajectory(grlx_ctx *ctx, int first_replica, int n_repl
  * by pair * 2^21 draws -- one per pair, for calls whose episodes carry one stream.  first_pair < 0 or out == NULL: nothing is written. */
 void grlx_episode_stream_words(long seed, int64_t first_pair, int64_t n_pairs, uint64_t *out /*[n_pairs]*/);
 
+/* --- actor-critic ensembles: episodes on the members' combined action ------------------------------------------------------------------
+ * The ACTOR-CRITIC's counterpart of grlx_evaluate_ensemble.  One episode runs per (group, start state): a group is group_size CONSECUTIVE
+ * replicas of [first_replica, first_replica + n_replicas) sharing ONE environment state.  Grouping, the pair index group * n_starts +
+ * start, the staging in chunks, max_steps (0 = GRLX_MAX_EPISODE_STEPS), the terminal codes 0 / 1 / 2 / 3, ret, disc and final_state are
+ * exactly grlx_evaluate_ensemble's; disc uses the context's gamma (an actor-critic context has no sweep).  Reference:
+ * mapping/policy/multi (base/src/policies/multi.cpp), which combines the continuous actions of several policies.
+ *   At every step, for the members m in ASCENDING replica order, a_m is the action grlx_evaluate would hand the environment for that
+ *   replica at this observation: the actor's read after the representation's clamp, then clipped to [action_min, action_max]; noise-free,
+ *   ActionPolicy::act(in, out) with sigma 0.  The rule combines a_0 ... a_{G-1} into the action that acts.  No clip follows the
+ *   combination (the reference has none, and the task's actuate does its own).  No random draw is made anywhere: where the reference
+ *   draws rand() among tied candidates, the FIRST acts and `ties` counts the step.  lo / hi are the context's action_min / action_max.
+ * GRLX_ACTOR_ENSEMBLE_MEAN (csMean, multi.cpp:507-523):
+ *   m = a_0; m = m + a_i for i = 1 ... G-1; action = m / (double)G.
+ * GRLX_ACTOR_ENSEMBLE_BINNING (csBinning, :126-181), parameter `bins` B with 1 <= B <= 64:
+ *   bin(a) = min((int)floor(((double)B * (a - lo)) / (hi - lo)), B - 1).  Build the histogram of the members' bins.  binmax is the first
+ *   bin of strictly greatest count, found by an ascending scan with cnt < hist[b] from cnt = 0.  Then s = 0.0, n = 0; for i ascending, if
+ *   hist[bin(a_i)] == hist[binmax] then s += a_i and ++n; action = s / n.  Members of ANOTHER bin with the same count are included: that is
+ *   what the reference does.  Tie: more than one bin holds that count.
+ * GRLX_ACTOR_ENSEMBLE_DATA_CENTER (csDataCenter, :251-336), parameter `bins` K >= 1, the number of members kept:
+ *   All members start alive.  mean is the serial sum of the alive members in ascending order, starting from the first one and not from
+ *   0.0, divided by their count.  While more than K are alive: d_i = (a_i - mean) * (a_i - mean) for the alive i; the first alive member
+ *   with the greatest d is removed (if every d is 0, that is the first alive member); mean is recomputed the same way.  action = mean.
+ *   Tie: at some removal of this step more than one alive member had the greatest d; it counts once per step.  Deviation: the reference
+ *   never clears its tie list between removals and indexes it with rand().
+ * GRLX_ACTOR_ENSEMBLE_DENSITY (csDensityBased, :183-248), parameter `r` > 0:
+ *   n_i = -1 + 2 * ((a_i - lo) / (hi - lo)).  rho_i is the sum over j ascending, from 0.0, of pexp((-1 * ((n_i - n_j) * (n_i - n_j))) /
+ *   (r * r)), pexp the portable exponential (GRLX_MATH's, specified by the oracle's orc_pexp).  The first i of strictly greatest rho is
+ *   selected, scanning from -inf; action = a_i.  Tie: more than one member has that rho.  At the reference's default r = 0.001 nearly
+ *   every rho is exactly 1.0, nearly every step ties and the group's first member acts.
+ * Outputs per pair, [n_replicas / group_size][n_starts] (final_state has [state_dims] more); host pointers, any may be NULL:
+ *   ret, disc, steps, terminal, final_state   as grlx_evaluate_ensemble defines them
+ *   ties    (int32)   the steps at which the rule's selection tied; 0 under MEAN
+ *   kept    (int64)   per step, the members that entered the action taken: G under MEAN, n under BINNING, min(G, K) under DATA_CENTER,
+ *                     1 under DENSITY; added up over the steps
+ *   spread  (double)  per step max_m a_m - min_m a_m, added up in step order: where the members stop agreeing
+ * With group_size == 1 every rule hands the member's own action on (a / 1): the episode is grlx_evaluate's, bit for bit.
+ *   Records.  grlx_evaluate_actor_ensemble_trajectory: records[group][start][max_steps][R], R = grlx_actor_ensemble_trajectory_record_words(ctx)
+ *   = grlx_trajectory_record_words(ctx, 0) + 2.  Every word of the actor-critic's record keeps its index: GRLX_TRAJ_ACTION is the combined
+ *   action; GRLX_TRAJ_VALUE the members' arithmetic mean, MEAN's expression, under every rule; GRLX_TRAJ_ACTION_INDEX the selected member's
+ *   index in the group under DENSITY, binmax under BINNING, -1 otherwise; GRLX_TRAJ_N_MAX the number of tied candidates -- the members of
+ *   greatest rho (DENSITY), the bins of greatest count (BINNING), the greatest number of members tied at one removal of the step
+ *   (DATA_CENTER) --, 1 where the rule selects nothing; the two new last words are the step's kept (R - 2) and its spread (R - 1).
+ *   Records behind an episode's end are zeros.  The staging rule and its refusals are grlx_evaluate_ensemble_trajectory's.
+ * Validated on the host before anything is launched (GRLX_ERR_INVALID, nothing written, the function and the reason named): everything
+ * grlx_evaluate refuses; a Q agent ("actor-critic only": grlx_evaluate_ensemble serves those); group_size < 1; n_replicas % group_size
+ * != 0; group_size > GRLX_ACTOR_ENSEMBLE_MAX; an unknown rule; bins outside its range for the two rules that read it; r not finite or
+ * <= 0 for DENSITY.  n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.  The calls change nothing in the context, do not count
+ * as a launch and wait for the stream of the last grlx_run.
+ * NOT BUILT: the reference's other strategies (mean_mov, data_center_mean_mov, random, static, value_based), a noisy ensemble, the
+ * draws among tied candidates, groups above GRLX_ACTOR_ENSEMBLE_MAX, a streamed variant. */
+#define GRLX_ACTOR_ENSEMBLE_MAX 256
+enum { GRLX_ACTOR_ENSEMBLE_MEAN = 0, GRLX_ACTOR_ENSEMBLE_BINNING = 1, GRLX_ACTOR_ENSEMBLE_DATA_CENTER = 2, GRLX_ACTOR_ENSEMBLE_DENSITY = 3 };
+int  grlx_evaluate_actor_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule, int bins, double r,
+                                  const double *states /*[n_starts][state_dims]*/, int n_starts, int max_steps,
+                                  double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                                  int64_t *kept, double *spread, double *final_state);
+int  grlx_actor_ensemble_trajectory_record_words(grlx_ctx *ctx);      /* R = grlx_trajectory_record_words(ctx, 0) + 2; a negative status otherwise */
+int  grlx_evaluate_actor_ensemble_trajectory(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule, int bins, double r,
+                                             const double *states /*[n_starts][state_dims]*/, int n_starts, int max_steps,
+                                             double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                                             int64_t *kept, double *spread, double *final_state,
+                                             double *records /*[n_replicas / group_size][n_starts][max_steps][R]*/);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * The per-step plug-in interfaces on the replicas of a context: one call of the reference's interface for EVERY replica per
  * call, for graphs in which only one side of the loop of OnlineLearningExperiment::run (online_learning.cpp:172-213) lives on the
