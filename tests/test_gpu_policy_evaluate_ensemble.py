@@ -4,7 +4,8 @@ tables -- and against the project's own grlx_evaluate, grlx_query_ensemble and t
 bit patterns, all eight outputs.  An evaluation must change nothing in the context.
 
 Shapes: 10 replicas in two groups of 5 x 5 start states where nothing else is said; max_steps 40 at most.  One block serves one episode
-with 16 members per round: 16 | 17 members are the two sides of the second round, 19 and 13 are no multiple of anything.  The oracle's
+with 16 members per round: 16 | 17 members are the two sides of the second round, 19 and 13 are no multiple of anything; 33, 48, 49
+and 64 members of one 64-replica context are three and four rounds.  The oracle's
 half is computed once per case (every GPU test runs clean and with poisoned registers)."""
 import os
 import subprocess
@@ -159,6 +160,45 @@ def test_many_members(grlx):
         for name, _ in RULES:
             got = r.evaluate_ensemble(states, G, name, replicas=range(0, count), max_steps=12)
             check(got, {f: want[name][f][at:at + count // G] for f in ens.FIELDS}, f"{count} replicas in groups of {G}, {name}")
+        at += count // G
+    r.close()
+
+
+# ---- 4b: three and four rounds per step ----------------------------------------------------------------------------------------------
+LARGE = [(0, 33, 33), (0, 48, 48), (0, 49, 49), (0, 64, 64), (0, 64, 32), (16, 48, 48)]      # (first replica, replicas, group size)
+
+
+@pytest.mark.parametrize("graph,trials", [("pendulum_sarsa", 6), ("pendulum_q_five_actions", 6), ("ties", 0)])
+def test_three_and_four_rounds(grlx, graph, trials):
+    """64 replicas on a 32768-slot memory, 2 start states, 12 steps: one group each of 33 (three rounds, one member in the last), 48, 49
+    and 64 (four full rounds), two groups of 32, and replicas 16 ... 63 as one group of 48.  An odd number of rounds flips the parity of
+    the members' LDS buffer from step to step.  pendulum_q_five_actions: five Q-values per member slot.  The combination must be
+    exercised (asserted on the reference alone): members that disagree, a tied vote, and the two rules parting.  The learned members
+    never tie among their own Q-values (member_ties is 0 throughout), so the `ties` graph is run before any launch: init_min =
+    init_max = 0, every member of every round ties at every step."""
+    n = 64
+    cfg, spec = build(grlx, graph, n)
+    states = five_states(graph, spec)[1:3]
+    small_memory(cfg, spec)
+    seeds = np.arange(SEED0, SEED0 + n)
+    groups = [g for first, count, G in LARGE for g in consecutive(count, G, first)]
+    want = oracle_groups(("large", graph, n), [spec] * n, seeds, states, (trials,), 12, groups)[0]
+    sizes = np.array([len(g) for g in groups], np.int64)[:, None]
+    assert want["vote"]["steps"].max() == 12
+    if graph == "ties":
+        assert all((want[name]["member_ties"] == want[name]["steps"] * sizes).all() for name, _ in RULES), "ties: every member was meant to tie at every step"
+    else:
+        assert all((want[name]["agreement"] < want[name]["steps"] * sizes).any() for name, _ in RULES), f"{graph}: the members never disagree"
+        assert (want["vote"]["ties"] > 0).any(), f"{graph}: the vote never ties"
+        assert any(want["vote"][f].tobytes() != want["mean"][f].tobytes() for f in ens.FIELDS), f"{graph}: the two rules never part"
+    r = grlx.Runner(cfg, seeds)
+    if trials:
+        r.run(trials); r.sync()
+    at = 0
+    for first, count, G in LARGE:
+        for name, _ in RULES:
+            got = r.evaluate_ensemble(states, G, name, replicas=range(first, first + count), max_steps=12)
+            check(got, {f: want[name][f][at:at + count // G] for f in ens.FIELDS}, f"{graph}: replicas {first} ... {first + count - 1} in groups of {G}, {name}")
         at += count // G
     r.close()
 

@@ -4,7 +4,7 @@ same context and against the queries.  Every comparison is on the bit patterns. 
 
 Shapes: those of test_gpu_policy_evaluate.py -- 3 replicas (actor-critic 5) x 7 start states, never a multiple of 4 pairs, 6 trials of
 training, max_steps 40 at most.  Record widths: pendulum 11, acrobot and cart-pole 15, walker 22 (two stores per step); ensemble 13, 17
-(two stores), 24.  The oracle's half is computed once per case (every GPU test runs clean and with poisoned registers)."""
+(two stores), 24; the ensemble's round loop beyond its first round on 64 replicas in groups of 17, 33, 64 and 32.  The oracle's half is computed once per case (every GPU test runs clean and with poisoned registers)."""
 import ctypes as C
 import os
 import subprocess
@@ -171,6 +171,74 @@ def test_ensemble_against_the_reference(grlx, graph):
         same_bits(got.step_member_ties.sum(axis=2).astype(np.int64), got.member_ties, f"{what}: the member_ties column summed")
     steps = np.stack([w["steps"] for w in want["vote"]])
     assert (steps <= 2).any() and steps.max() == ms
+    r.close()
+
+
+ROUNDS = [(17, 17), (33, 33), (64, 64), (64, 32)]              # (replicas, group size): 2, 3 and 4 rounds of 16 members, two groups of 2 rounds
+
+
+def many_members(grlx, graph, n, trials, groups, max_steps):
+    """(configuration, seeds, start states, [rule name] -> list over groups of the reference's dict, does a member of a round after the
+    first tie?) of one context of n replicas on a 32768-slot memory, which lets the oracle hold a dense vector per member"""
+    if ("rounds", graph) not in _ref_cache:
+        cfg, spec = build(grlx, graph, n)
+        states = start_states(graph, spec)[1:3]
+        for obj in (cfg, spec):
+            obj.projector.memory = 32768
+        seeds = np.arange(SEED0, SEED0 + n)
+        exps = [ob.Experiment(spec, seed=int(seed)) for seed in seeds]
+        for e in exps:
+            if trials:
+                e.run(trials)
+        tables = [ref.dense(e, 0) for e in exps]
+        want = {name: [tr.evaluate_ensemble([tables[m] for m in g], spec, states, rule, max_steps) for g in groups] for name, rule in RULES}
+        D = tr.dims(spec)[0]
+        later = False                                           # step_member_ties > 0 with a tied member of index >= 16 in its group
+        for g, w in zip(groups, want["vote"]):
+            for rec in w["records"].reshape(-1, w["records"].shape[-1]):
+                if rec[tr.ENS_MEMBER_TIES] > 0 and not later:
+                    later = any(int(ref.query_q(tables[m], spec, [rec[tr.ENS_OBS:tr.ENS_OBS + D]])[3][0]) > 1 for m in g[16:])
+        for e in exps:
+            e.close()
+        _ref_cache[("rounds", graph)] = (cfg, seeds, states, want, later)
+    return _ref_cache[("rounds", graph)]
+
+
+@pytest.mark.parametrize("graph,trials", [("pendulum_sarsa", 6), ("pendulum_q_five_actions", 6), ("ties", 0)])
+def test_ensemble_of_more_than_one_round(grlx, graph, trials):
+    """64 replicas on a 32768-slot memory, 2 start states, 12 steps, both rules: one group each of 17, 33 and 64 members and two groups of
+    32 -- the kernel's round loop beyond its first round: the members' double buffer, the partial last round, and the step's member ties
+    counted across the rounds.  Asserted on the reference alone: the learned members disagree, their vote ties, the two rules part.  The
+    learned tables give no member of a later round that ties (their weights are drawn, no two Q-values agree), so that precondition is
+    the `ties` graph's, before any launch: init_min = init_max = 0, every member ties at every step."""
+    n, ms = 64, 12
+    groups = [list(range(g * G, (g + 1) * G)) for count, G in ROUNDS for g in range(count // G)]
+    cfg, seeds, states, want, later = many_members(grlx, graph, n, trials, groups, ms)
+    sizes = np.array([len(g) for g in groups], np.float64)[:, None, None]
+    agreement = np.stack([w["records"][..., tr.ENS_AGREEMENT] for w in want["vote"]])
+    steps = np.stack([w["steps"] for w in want["vote"]])
+    live = np.arange(ms)[None, None, :] < steps[:, :, None]
+    assert steps.max() == ms
+    if graph == "ties":
+        member_ties = np.stack([w["records"][..., tr.ENS_MEMBER_TIES] for w in want["vote"]])
+        assert later and (member_ties == sizes)[live].all(), "ties: every member was meant to tie at every step"
+    else:
+        assert (agreement < sizes)[live].any(), f"{graph}: the members never disagree"
+        assert any((w["ties"] > 0).any() for w in want["vote"]), f"{graph}: the vote never ties"
+        assert any(v["records"].tobytes() != m["records"].tobytes() for v, m in zip(want["vote"], want["mean"])), f"{graph}: the two rules never part"
+    r = grlx.Runner(cfg, seeds)
+    if trials:
+        r.run(trials); r.sync()
+    at = 0
+    for count, G in ROUNDS:
+        for name, _ in RULES:
+            what = f"{graph}: {count} replicas in groups of {G}, {name}"
+            got = r.evaluate_ensemble_trajectory(states, G, ms, name, replicas=range(count))
+            check_trajectory(got, want[name][at:at + count // G], what, tr.ENSEMBLE_FIELDS)
+            check_shape_of_the_records(got, what)
+            same_bits(got.step_agreement.sum(axis=2).astype(np.int64), got.agreement, f"{what}: the agreement column summed")
+            same_bits(got.step_member_ties.sum(axis=2).astype(np.int64), got.member_ties, f"{what}: the member_ties column summed")
+        at += count // G
     r.close()
 
 
