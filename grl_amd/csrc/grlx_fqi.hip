@@ -740,7 +740,8 @@ struct grlx_fqi_ctx {
   int batches_run = 0;
   int replicas_per_launch = 1;       // how many replicas' blocks are resident at once
   int blocks_per_replica = 16, block_threads = 256;      // FqiShape<hidden>
-  bool plain_launch = false;         // diagnostic: GRLX_FQI_NO_COOP=1 launches the epochs kernel without hipLaunchCooperativeKernel
+  bool plain_launch = false;         // the epochs kernel without hipLaunchCooperativeKernel: GRLX_FQI_NO_COOP=1 (diagnostic), or the runtime
+                                     // refused the cooperative launch because another process holds the device's cooperative queue
 };
 
 namespace {
@@ -963,10 +964,22 @@ int grlx_fqi_run_batch(grlx_fqi_ctx *ctx, void *stream_)
       void *args[] = {&Fa, &r_first, &epochs};
       const dim3 grid(nr * ctx->blocks_per_replica), block(ctx->block_threads);
       hipError_t le = hipSuccess;
-      if (ctx->plain_launch)      // diagnostic (GRLX_FQI_NO_COOP=1): the same grid without the runtime's residency check
+      if (!ctx->plain_launch)
+      {
+        FQI_FOR_H(F.H, le = hipLaunchCooperativeKernel((const void *)fqi_epochs_kernel<HH>, grid, block, args, 0, stream));
+        // A device may lend its queue for cooperative launches to one process at a time: while another process holds it (a parent
+        // that ran the batch path, the other rank on a shared GPU) the runtime answers hipErrorIllegalState and has launched nothing.
+        // The kernel needs nothing of that queue but the residency check, and create() sized the grid to be resident
+        // (replicas_per_launch); the spins are bounded either way.  So this context launches the same grid plainly from here on.
+        if (le == hipErrorIllegalState)
+        {
+          (void)hipGetLastError();
+          ctx->plain_launch = true;
+          le = hipSuccess;
+        }
+      }
+      if (ctx->plain_launch)      // also GRLX_FQI_NO_COOP=1 (diagnostic): the same grid without the runtime's residency check
       { FQI_FOR_H(F.H, hipLaunchKernelGGL(fqi_epochs_kernel<HH>, grid, block, 0, stream, Fa, r_first, epochs)); }
-      else
-      { FQI_FOR_H(F.H, le = hipLaunchCooperativeKernel((const void *)fqi_epochs_kernel<HH>, grid, block, args, 0, stream)); }
       FQI_TRY(le);
     }
   }
