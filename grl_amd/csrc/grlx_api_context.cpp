@@ -15,8 +15,6 @@ int fail(int code, const char *fmt, ...)
   return code;
 }
 
-void set_last_error(const char *msg) { g_err = msg; }     // other translation units of the library (grlx_fqi.hip)
-
 bool have_device() { return grlx_device_count() > 0; }
 
 // Read-back and fine-grained entry points run on the NULL stream or copy synchronously: wait for the rollouts

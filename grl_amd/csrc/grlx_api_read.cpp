@@ -1,5 +1,6 @@
 // grlx_api_read.cpp -- the C ABI declared in include/grlx.h: the read side -- policy queries, greedy, sampled, noisy and actor-ensemble evaluation episodes, chunked over the caller's observations / start states; the streamed trajectories' two-slot pipeline.
 #include "grlx_host.h"
+#include "grlx_read.h"
 #include "grlx_query.h"
 #include "grlx_evaluate.h"
 #include "grlx_evaluate_sampled.h"
@@ -10,19 +11,10 @@
 // ------------------------------------------------------------------------------------------- policy queries ---
 namespace {
 
-constexpr uint64_t kQueryChunkDefault = 256ull << 20;
-uint64_t g_query_chunk_bytes = kQueryChunkDefault;
-
 bool q_agent(int agent) { return agent != GRLX_AGENT_AC; }      // every other agent acts through a policy/discrete/q on table 0
 
-// the replica range every read names: [first_replica, first_replica + n_replicas) inside the context
-int replica_range_ok(grlx_ctx *ctx, const char *who, int first_replica, int n_replicas)
-{
-  if (first_replica < 0 || n_replicas < 0 || (int64_t)first_replica + n_replicas > ctx->P.n_replicas)
-    return fail(GRLX_ERR_INVALID, "%s: replica range [%d, %lld) is outside the context's %d replicas", who, first_replica,
-                (long long)first_replica + n_replicas, ctx->P.n_replicas);
-  return GRLX_OK;
-}
+// what a context's reads add around a chunk's kernels (chunked_read): its poison launch, and their time in grlx_read_kernel_timing's sum
+ReadHooks read_hooks(const grlx_ctx *ctx) { return {ctx->poison, ctx->poison_pattern, true}; }
 
 // what every query checks before it touches the device; tp: the projector of the table read, obs_dims: its share of the observation
 int query_admit(grlx_ctx *ctx, const char *who, int first_replica, int n_replicas, const double *obs, int n_obs, const TileParams &tp, int obs_dims)
@@ -30,7 +22,7 @@ int query_admit(grlx_ctx *ctx, const char *who, int first_replica, int n_replica
   if (ctx->P.tile_safe >= 1)
     return fail(GRLX_ERR_INVALID, "%s is not built for projector/tile_coding:safe >= 1 (a read would have to walk the claim table without claiming)", who);
   if (n_obs < 0) return fail(GRLX_ERR_INVALID, "%s: n_obs = %d", who, n_obs);
-  if (int rc = replica_range_ok(ctx, who, first_replica, n_replicas)) return rc;
+  if (int rc = replica_range_ok(who, ctx->P.n_replicas, first_replica, n_replicas)) return rc;
   if (!obs) return fail(GRLX_ERR_INVALID, "%s: obs is null", who);
   int o = 0, i = 0;                                     // quant_admit_rows (grlx_host_rules.h): the rule grlx_project applies too
   if (int why = quant_admit_rows(obs, n_obs, obs_dims, tp.scaling, &o, &i))
@@ -38,94 +30,6 @@ int query_admit(grlx_ctx *ctx, const char *who, int first_replica, int n_replica
     const double x = obs[(size_t)o * obs_dims + i];
     if (why == 1) return fail(GRLX_ERR_INVALID, "%s: observation row %d, dimension %d is not finite (%g)", who, o, i, x);
     return fail(GRLX_ERR_INVALID, "%s: observation row %d, dimension %d (%g) is out of range: |x * scaling| reaches 2^30", who, o, i, x);
-  }
-  return GRLX_OK;
-}
-
-// observations per chunk so that one chunk's device arrays stay within the bound; at least one
-int query_chunk(int n_obs, size_t bytes_per_obs)
-{
-  const uint64_t fit = g_query_chunk_bytes / (bytes_per_obs ? bytes_per_obs : 1);
-  return (int)(fit < 1 ? 1 : fit > (uint64_t)n_obs ? (uint64_t)n_obs : fit);
-}
-
-// rows [n_replicas] of `elem` bytes per observation: device [r][chunk] -> host [r][n_obs] at observation o0
-hipError_t query_copy_out(void *host, const void *dev, size_t elem, int n_replicas, int n_obs, int o0, int nc)
-{
-  return hipMemcpy2D((char *)host + (size_t)o0 * elem, (size_t)n_obs * elem, dev, (size_t)nc * elem, (size_t)nc * elem, (size_t)n_replicas,
-                     hipMemcpyDeviceToHost);
-}
-
-// grlx_read_kernel_timing (include/grlx_diag.h): the device time of the chunks' launches, summed since timing was enabled
-bool g_read_timing = false;
-double g_read_ms = 0;
-int g_read_chunks = 0;
-
-struct ReadTimer {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  ~ReadTimer()
-  {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
-  hipError_t start()
-  {
-    if (hipError_t err = hipEventCreate(&e0)) return err;
-    if (hipError_t err = hipEventCreate(&e1)) return err;
-    return hipEventRecord(e0, nullptr);
-  }
-  hipError_t stop()
-  {
-    if (hipError_t err = hipEventRecord(e1, nullptr)) return err;
-    if (hipError_t err = hipEventSynchronize(e1)) return err;
-    float ms = 0;
-    if (hipError_t err = hipEventElapsedTime(&ms, e0, e1)) return err;
-    g_read_ms += ms;
-    g_read_chunks++;
-    return hipSuccess;
-  }
-};
-
-// One output of a chunked read: `rows` rows of `elem` bytes per column, copied to `host` when that is not null; `on_device`: the kernels
-// write it (or a reduction reads it) whether the caller asked for it or not.
-struct ReadOut { void *host; size_t elem; int rows; bool on_device; };
-constexpr int kMaxReadOuts = 9;
-// A second per-column input of a chunked read, laid out like an output: host [rows][cols] of `elem` bytes -> `dev` [rows][chunk], so that
-// a chunk's rows begin at its first column for EVERY row (a strided copy, not a contiguous one).  host null: nothing is staged.
-struct ReadIn { const void *host; size_t elem; int rows; DevBuf *dev; };
-
-// The skeleton of every read: the columns of `in` (observations or start states, `in_dims` doubles each) go through the device `chunk` at a
-// time.  Per chunk: the input in, launch(nc, input, outputs) -- device pointers, null for an output neither asked for nor needed -- and out
-// what the caller asked for.  `sync_each`: every output may be null, so the next chunk's copy-in must not overtake the launch.
-// `extra`: a second input staged beside the first (ReadIn), or null.
-template <typename Launch>
-int chunked_read(grlx_ctx *ctx, const ReadOut *outs, int n_outs, int cols, const double *in, int in_dims, int chunk, bool sync_each, Launch launch,
-                 const ReadIn *extra = nullptr)
-{
-  DevBuf din, dout[kMaxReadOuts];
-  HIP_TRY(din.alloc(sizeof(double) * (size_t)chunk * in_dims));
-  if (extra && extra->host) HIP_TRY(extra->dev->alloc(extra->elem * (size_t)extra->rows * (size_t)chunk));
-  for (int k = 0; k < n_outs; ++k)
-    if (outs[k].host || outs[k].on_device) HIP_TRY(dout[k].alloc(outs[k].elem * (size_t)outs[k].rows * (size_t)chunk));
-  for (int c0 = 0; c0 < cols; c0 += chunk)
-  {
-    const int nc = cols - c0 < chunk ? cols - c0 : chunk;
-    HIP_TRY(hipMemcpy(din.get(), in + (size_t)c0 * in_dims, sizeof(double) * (size_t)nc * in_dims, hipMemcpyHostToDevice));
-    if (extra && extra->host)
-      HIP_TRY(hipMemcpy2D(extra->dev->get(), (size_t)nc * extra->elem, (const char *)extra->host + (size_t)c0 * extra->elem, (size_t)cols * extra->elem,
-                          (size_t)nc * extra->elem, (size_t)extra->rows, hipMemcpyHostToDevice));
-    if (ctx->poison) HIP_TRY(launch_poison_registers(ctx->poison_pattern, nullptr));
-    if (g_read_timing)
-    { // grlx_read_kernel_timing: events around the chunk's launches, waited for here
-      ReadTimer timer;
-      HIP_TRY(timer.start());
-      if (int rc = launch(nc, din.as<double>(), dout)) return rc;
-      HIP_TRY(timer.stop());
-    }
-    else if (int rc = launch(nc, din.as<double>(), dout)) return rc;
-    for (int k = 0; k < n_outs; ++k)
-      if (outs[k].host) HIP_TRY(query_copy_out(outs[k].host, dout[k].get(), outs[k].elem, outs[k].rows, cols, c0, nc));
-    if (sync_each) HIP_TRY(hipDeviceSynchronize());
   }
   return GRLX_OK;
 }
@@ -149,7 +53,7 @@ int query_q_impl(grlx_ctx *ctx, const char *who, int first_replica, int n_replic
   const bool e = ensemble != nullptr;              // the reduction reads q, value and greedy; the caller of grlx_query_ensemble gets only its result
   const ReadOut outs[5] = {{q, sizeof(double) * NA, n_replicas, e}, {value, sizeof(double), n_replicas, e}, {greedy, sizeof(int32_t), n_replicas, e},
                            {n_max, sizeof(int32_t), n_replicas, false}, {ensemble, sizeof(double) * cols, n_groups, false}};
-  return chunked_read(ctx, outs, 5, n_obs, obs, D, chunk, false, [&](int nc, const double *dobs, const DevBuf *d) -> int {
+  return chunked_read(read_hooks(ctx), outs, 5, n_obs, obs, D, chunk, false, [&](int nc, const double *dobs, const DevPtr *d) -> int {
     QueryArgs A;
     A.first_replica = first_replica; A.n_replicas = n_replicas; A.n_obs = nc;
     A.obs = dobs; A.q = d[0].as<double>(); A.value = d[1].as<double>(); A.greedy = d[2].as<int32_t>(); A.n_max = d[3].as<int32_t>();
@@ -171,20 +75,7 @@ int evaluate_admit(grlx_ctx *ctx, const char *who, int first_replica, int n_repl
   if (!evaluate_built(ctx->cfg.agent, ctx->cfg.env, ctx->P.A))
     return fail(GRLX_ERR_INVALID, "%s is not built for environment %d with %d actions (Q agents: pendulum x {3, 5}, acrobot, cart-pole, walker x 3; actor-critic: cart-pole, pendulum)", who,
                 ctx->cfg.env, ctx->cfg.agent == GRLX_AGENT_AC ? 0 : ctx->P.A);
-  if (n_starts < 0) return fail(GRLX_ERR_INVALID, "%s: n_starts = %d", who, n_starts);
-  if (int rc = replica_range_ok(ctx, who, first_replica, n_replicas)) return rc;
-  if (!states) return fail(GRLX_ERR_INVALID, "%s: states is null", who);
-  if (max_steps < 0 || max_steps > GRLX_MAX_EPISODE_STEPS)
-    return fail(GRLX_ERR_INVALID, "%s: max_steps = %d is outside 1 ... GRLX_MAX_EPISODE_STEPS (%d; 0 = that cap)", who, max_steps, GRLX_MAX_EPISODE_STEPS);
-  const int S = ctx->S;
-  for (int s = 0; s < n_starts; ++s)
-    for (int i = 0; i < S; ++i)
-    { // below 2^17 the RK4 stages of one step stay inside the branch-free sine's domain (the cart-pole's case)
-      const double v = states[(size_t)s * S + i];
-      if (!std::isfinite(v)) return fail(GRLX_ERR_INVALID, "%s: state row %d, component %d is not finite (%g)", who, s, i, v);
-      if (!(fabs(v) < 0x1p17)) return fail(GRLX_ERR_INVALID, "%s: state row %d, component %d (%g) is out of range: its magnitude reaches 2^17", who, s, i, v);
-    }
-  return GRLX_OK;
+  return episode_pairs_ok(who, ctx->P.n_replicas, ctx->S, first_replica, n_replicas, states, n_starts, max_steps);
 }
 
 // what both ensemble evaluations check beyond evaluate_admit
@@ -193,30 +84,10 @@ int ensemble_admit(grlx_ctx *ctx, const char *who, int n_replicas, int group_siz
   if (!q_agent(ctx->cfg.agent))
     return fail(GRLX_ERR_INVALID, "%s is not built for the actor-critic agent (a vote over continuous actions is mapping/policy/multi's: "
                 "grlx_evaluate_actor_ensemble combines them); it serves agents with a policy/discrete/q", who);
-  if (group_size < 1) return fail(GRLX_ERR_INVALID, "%s: group_size = %d is below 1", who, group_size);
+  if (int rc = group_size_ok(who, group_size)) return rc;
   if (n_replicas % group_size != 0) return fail(GRLX_ERR_INVALID, "%s: group_size %d does not divide the %d replicas", who, group_size, n_replicas);
   if (rule != GRLX_ENSEMBLE_VOTE && rule != GRLX_ENSEMBLE_MEAN_Q)
     return fail(GRLX_ERR_INVALID, "%s: unknown rule %d (GRLX_ENSEMBLE_VOTE = 0, GRLX_ENSEMBLE_MEAN_Q = 1)", who, rule);
-  return GRLX_OK;
-}
-
-// ---- per-step trajectories: the two evaluations with a record per step (grlx_evaluate.hip: trajectory_*_kernel) -----------------------------
-// What a trajectory call checks beyond its sibling, after the sibling's own checks; gives the start states per chunk.  `rows`: replicas or
-// groups; `in_and_sums`: a start state's other staged bytes (its state and its rows' sums).  Unlike the other reads a chunk never exceeds
-// the bound: the records are what the bound is for, so a column that does not fit is refused instead of staged as "at least one".
-int trajectory_admit(const char *who, const char *sibling, const void *records, int max_steps, int rows, int n_starts,
-                            int R, size_t in_and_sums, int *chunk)
-{
-  if (!records) return fail(GRLX_ERR_INVALID, "%s: records is null (for the sums alone call %s)", who, sibling);
-  if (max_steps == 0)
-    return fail(GRLX_ERR_INVALID, "%s: max_steps = 0: the records are sized by max_steps, so there is no default here (1 ... GRLX_MAX_EPISODE_STEPS = %d)", who,
-                GRLX_MAX_EPISODE_STEPS);
-  const uint64_t column = (uint64_t)rows * (uint64_t)max_steps * (uint64_t)R * sizeof(double);
-  if (column + in_and_sums > g_query_chunk_bytes)
-    return fail(GRLX_ERR_INVALID, "%s: one start state's column of records is %llu bytes (%d rows x %d steps x %d words x 8; %llu with its sums) and exceeds "
-                "the staging bound of %llu bytes: ask for fewer replicas per call, a smaller max_steps, or raise the bound with grlx_set_query_chunk_bytes", who,
-                (unsigned long long)column, rows, max_steps, R, (unsigned long long)(column + in_and_sums), (unsigned long long)g_query_chunk_bytes);
-  *chunk = rows ? query_chunk(n_starts, (size_t)column + in_and_sums) : n_starts;
   return GRLX_OK;
 }
 
@@ -272,7 +143,7 @@ int actor_ensemble_admit(grlx_ctx *ctx, const char *who, int n_replicas, int gro
   if (q_agent(ctx->cfg.agent))
     return fail(GRLX_ERR_INVALID, "%s serves the actor-critic only (it combines continuous actions, mapping/policy/multi); the vote and the mean Q of agents "
                 "with a policy/discrete/q are grlx_evaluate_ensemble's", who);
-  if (group_size < 1) return fail(GRLX_ERR_INVALID, "%s: group_size = %d is below 1", who, group_size);
+  if (int rc = group_size_ok(who, group_size)) return rc;
   if (n_replicas % group_size != 0) return fail(GRLX_ERR_INVALID, "%s: group_size %d does not divide the %d replicas", who, group_size, n_replicas);
   if (group_size > GRLX_ACTOR_ENSEMBLE_MAX)
     return fail(GRLX_ERR_INVALID, "%s: group_size = %d exceeds GRLX_ACTOR_ENSEMBLE_MAX (%d)", who, group_size, GRLX_ACTOR_ENSEMBLE_MAX);
@@ -311,7 +182,7 @@ struct EpisodeCall {
   ReadOut       extra[2];                   // the variant's own outputs: host and elem; the rows are filled in here
   int           n_extra;
   size_t        extra_bytes;                // per pair, what the variant stages beyond the six outputs: part of what cuts the chunks
-  const ReadIn *in;                         // the variant's second input, or null
+  ReadIn       *in;                         // the variant's second input, or null
   // trajectory calls only: the call that gives the sums alone (named in a refusal), the caller's records, R of an environment's record
   const char   *sibling;
   double       *records;
@@ -334,7 +205,7 @@ int episode_outs(const EpisodeCall &c, int rows, int S, size_t rec_elem, ReadOut
 
 // the base fields of a chunk's argument block (EvaluateArgs, EnsembleArgs: the same member names) for nc start states at dst
 template <class Args>
-void episode_args(Args &A, grlx_ctx *ctx, const EpisodeCall &c, int max_steps, int nc, const double *dst, const DevBuf *d)
+void episode_args(Args &A, grlx_ctx *ctx, const EpisodeCall &c, int max_steps, int nc, const double *dst, const DevPtr *d)
 {
   A.first_replica = c.first_replica; A.n_replicas = c.n_replicas; A.n_starts = nc; A.max_steps = max_steps;
   A.states = dst; A.sweep = ctx->sweep ? ctx->sweep_dev.get() : nullptr;
@@ -351,8 +222,7 @@ int episode_read(grlx_ctx *ctx, const EpisodeCall &c, Admit admit, Launch launch
   if (int rc = evaluate_admit(ctx, c.who, c.first_replica, c.n_replicas, c.states, c.n_starts, max_steps)) return rc;
   if (int rc = admit()) return rc;
   const int S = ctx->S, rows = c.group_size ? c.n_replicas / c.group_size : c.n_replicas, R = c.sibling ? c.record_words(ctx->cfg.env) : 0;
-  const size_t per_pair = 2 * sizeof(double) + 3 * sizeof(int32_t) + sizeof(double) * (size_t)S + c.extra_bytes;
-  const size_t in_and_sums = sizeof(double) * (size_t)S + per_pair * (size_t)rows;
+  const size_t in_and_sums = episode_start_bytes(S, rows, c.extra_bytes);
   int chunk = 0;
   if (c.sibling)
   {
@@ -366,7 +236,7 @@ int episode_read(grlx_ctx *ctx, const EpisodeCall &c, Admit admit, Launch launch
   const size_t rec_elem = sizeof(double) * (size_t)R * (size_t)max_steps;
   ReadOut outs[kMaxReadOuts];
   const int n_outs = episode_outs(c, rows, S, rec_elem, outs);
-  return chunked_read(ctx, outs, n_outs, c.n_starts, c.states, S, chunk, true, [&](int nc, const double *dst, const DevBuf *d) -> int {
+  return chunked_read(read_hooks(ctx), outs, n_outs, c.n_starts, c.states, S, chunk, true, [&](int nc, const double *dst, const DevPtr *d) -> int {
     Args A{};
     episode_args(A, ctx, c, max_steps, nc, dst, d);
     double *records = rec_elem ? d[n_outs - 1].as<double>() : nullptr;
@@ -533,7 +403,6 @@ extern "C" {
 int grlx_set_query_chunk_bytes(uint64_t bytes)
 {
   g_query_chunk_bytes = bytes ? bytes : kQueryChunkDefault;
-  set_fqi_query_chunk_bytes(bytes);
   return GRLX_OK;
 }
 
@@ -571,7 +440,7 @@ int grlx_query_state(grlx_ctx *ctx, int table, int first_replica, int n_replicas
   const int D = tp.D;
   const int chunk = query_chunk(n_obs, sizeof(double) * (size_t)D + sizeof(double) * (size_t)n_replicas);
   const ReadOut outs[1] = {{out, sizeof(double), n_replicas, true}};
-  return chunked_read(ctx, outs, 1, n_obs, obs, D, chunk, false, [&](int nc, const double *dobs, const DevBuf *d) -> int {
+  return chunked_read(read_hooks(ctx), outs, 1, n_obs, obs, D, chunk, false, [&](int nc, const double *dobs, const DevPtr *d) -> int {
     QueryArgs A;
     A.first_replica = first_replica; A.n_replicas = n_replicas; A.n_obs = nc;
     A.obs = dobs; A.q = nullptr; A.value = d[0].as<double>(); A.greedy = nullptr; A.n_max = nullptr;
@@ -587,7 +456,7 @@ static int evaluate_impl(grlx_ctx *ctx, const char *who, const char *sibling, in
 {
   EpisodeCall c{who, first_replica, n_replicas, 0, states, n_starts, max_steps, ret, disc, steps, terminal, ties, final_state};
   c.sibling = sibling; c.records = records; c.record_words = greedy_words;
-  return episode_read<EvaluateArgs>(ctx, c, [] { return GRLX_OK; }, [&](EvaluateArgs &A, const DevBuf *, double *rec) {
+  return episode_read<EvaluateArgs>(ctx, c, [] { return GRLX_OK; }, [&](EvaluateArgs &A, const DevPtr *, double *rec) {
     return rec ? launch_trajectory(ctx->P, TrajectoryArgs{A, rec}, nullptr) : launch_evaluate(ctx->P, A, nullptr);
   });
 }
@@ -601,7 +470,7 @@ static int evaluate_ensemble_impl(grlx_ctx *ctx, const char *who, const char *si
   c.extra_bytes = 2 * sizeof(int64_t);
   c.sibling = sibling; c.records = records; c.record_words = ensemble_words;
   return episode_read<EnsembleArgs>(ctx, c, [&] { return ensemble_admit(ctx, who, n_replicas, group_size, rule); },
-                                    [&](EnsembleArgs &A, const DevBuf *extra, double *rec) {
+                                    [&](EnsembleArgs &A, const DevPtr *extra, double *rec) {
     A.group_size = group_size; A.rule = rule;
     A.member_ties = extra[0].as<int64_t>(); A.agreement = extra[1].as<int64_t>();
     return rec ? launch_trajectory_ensemble(ctx->P, EnsembleTrajectoryArgs{A, rec}, nullptr) : launch_evaluate_ensemble(ctx->P, A, nullptr);
@@ -677,18 +546,17 @@ static int evaluate_sampled_impl(grlx_ctx *ctx, const char *who, const char *sib
                                  int max_steps, int sampler, double epsilon, const uint64_t *streams, double *ret, double *disc, int32_t *steps,
                                  int32_t *terminal, int32_t *ties, int32_t *explored, double *final_state, uint64_t *streams_out, double *records)
 {
-  DevBuf dstreams;
-  const ReadIn in_streams = {streams, 2 * sizeof(uint64_t), n_replicas, &dstreams};     // [replica][start][2]: a chunk is strided, not contiguous
+  ReadIn in_streams = {streams, 2 * sizeof(uint64_t), n_replicas, nullptr};     // [replica][start][2]: a chunk is strided, not contiguous
   EpisodeCall c{who, first_replica, n_replicas, 0, states, n_starts, max_steps, ret, disc, steps, terminal, ties, final_state};
   c.extra[0] = {explored, sizeof(int32_t)}; c.extra[1] = {streams_out, 2 * sizeof(uint64_t)}; c.n_extra = 2;
   c.extra_bytes = sizeof(int32_t) + 4 * sizeof(uint64_t);     // explored, both streams in and out
   c.in = &in_streams;
   c.sibling = sibling; c.records = records; c.record_words = sampled_trajectory_words;
   return episode_read<EvaluateArgs>(ctx, c, [&] { return sampled_admit(ctx, who, n_replicas, n_starts, sampler, epsilon, streams); },
-                                    [&](EvaluateArgs &A, const DevBuf *extra, double *rec) {
+                                    [&](EvaluateArgs &A, const DevPtr *extra, double *rec) {
     SampledArgs T;
     T.e = A; T.sampler = sampler; T.epsilon = epsilon;
-    T.streams = streams ? dstreams.as<uint64_t>() : nullptr;
+    T.streams = (uint64_t *)in_streams.dev;
     T.explored = extra[0].as<int32_t>(); T.streams_out = extra[1].as<uint64_t>();
     T.records = rec;
     return rec ? launch_trajectory_sampled(ctx->P, T, nullptr) : launch_evaluate_sampled(ctx->P, T, nullptr);
@@ -726,8 +594,7 @@ static int evaluate_noisy_impl(grlx_ctx *ctx, const char *who, const char *sibli
   // the two 8-byte inputs of a pair travel as one 16-byte column of the staging skeleton: [replica][start]{stream, bits of the noise};
   // an absent array is filled with what the kernel takes as its default (kNoisyOwnStream: the replica's own stream; +0.0)
   std::vector<uint64_t> packed;
-  DevBuf dinputs;
-  ReadIn in_pairs = {nullptr, 2 * sizeof(uint64_t), n_replicas, &dinputs};
+  ReadIn in_pairs = {nullptr, 2 * sizeof(uint64_t), n_replicas, nullptr};
   EpisodeCall c{who, first_replica, n_replicas, 0, states, n_starts, max_steps, ret, disc, steps, terminal, clipped, final_state};
   c.extra[0] = {streams_out, sizeof(uint64_t)}; c.extra[1] = {noise_out, sizeof(double)}; c.n_extra = 2;
   c.extra_bytes = 4 * sizeof(uint64_t);     // stream and noise in and out
@@ -750,10 +617,10 @@ static int evaluate_noisy_impl(grlx_ctx *ctx, const char *who, const char *sibli
     }
     in_pairs.host = packed.empty() ? nullptr : packed.data();
     return GRLX_OK;
-  }, [&](EvaluateArgs &A, const DevBuf *extra, double *rec) {
+  }, [&](EvaluateArgs &A, const DevPtr *extra, double *rec) {
     NoisyArgs T;
     T.e = A; T.sigma = sigma; T.theta = theta;
-    T.inputs = packed.empty() ? nullptr : dinputs.as<uint64_t>();
+    T.inputs = (uint64_t *)in_pairs.dev;
     T.streams_out = extra[0].as<uint64_t>(); T.noise_out = extra[1].as<double>();
     T.records = rec;
     return rec ? launch_trajectory_noisy(ctx->P, T, nullptr) : launch_evaluate_noisy(ctx->P, T, nullptr);
@@ -792,7 +659,7 @@ static int evaluate_actor_ensemble_impl(grlx_ctx *ctx, const char *who, const ch
   c.extra_bytes = sizeof(int64_t) + sizeof(double);
   c.sibling = sibling; c.records = records; c.record_words = actor_ensemble_trajectory_words;
   return episode_read<ActorEnsembleArgs>(ctx, c, [&] { return actor_ensemble_admit(ctx, who, n_replicas, group_size, rule, bins, r); },
-                                         [&](ActorEnsembleArgs &A, const DevBuf *extra, double *rec) {
+                                         [&](ActorEnsembleArgs &A, const DevPtr *extra, double *rec) {
     A.group_size = group_size; A.rule = rule; A.bins = bins; A.r = r;
     A.kept = extra[0].as<int64_t>(); A.spread = extra[1].as<double>();
     A.records = rec;

@@ -12,12 +12,8 @@
 // (K = 3 and K = 20, N = 1; a 16x16x4 f64 tile would be 80 % padding) and the chain is bound by launch latency and
 // the reduction, not by FLOPs: see DESIGN.md section 4.3 for the measurement.
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <string>
-#include <vector>
 #include "grlx_internal.h"
 #include "grlx_math.h"
 #include "grlx_math_batch.h"
@@ -25,47 +21,9 @@
 #include "grlx_tile.h"
 #include "grlx_table.h"
 #include "grlx_envs.h"
+#include "grlx_fqi.h"
 
 namespace grlx {
-void set_last_error(const char *msg);      // grlx_api.cpp
-
-constexpr int kFqiNIn = 3;                 // task/pendulum/swingup: observation (2) ++ action (1)
-constexpr int kFqiD = 2;
-constexpr int kFqiS = 3;
-
-struct FqiRep {                            // per-replica state between launches
-  uint64_t G, TL;                          // global / thread-local streams (fqi.c: orc_fqi_create)
-  int64_t  n;                              // transitions stored
-  int64_t  batches_done;
-  unsigned long long maxdelta_bits;        // max |target - previous target| of the running iteration (non-negative double)
-  double   maxdelta_last;
-  int32_t  done;                           // the rebuild's iteration loop has ended (maxdelta <= 0.001)
-  int32_t  iterations;                     // iterations executed by the last rebuild
-  uint32_t status;
-  uint32_t rows;
-  double   last_error;
-};
-
-struct FqiParams {
-  DevParams env;                           // h, integration_steps, timeout, randomization of the pendulum
-  int32_t  R, H, P, A, batch_size, cap, chunks_cap;
-  double   actions[kMaxActions];
-  double   in_min[kFqiNIn], in_scale[kFqiNIn], obs_min[kFqiD], obs_range[kFqiD];
-  double   action_min, action_range;
-  double   gamma_tau;
-  double   eta;                                     // representation/parameterized/ann:eta (0: RPROP, > 0: gradient descent, < 0: RMSprop)
-  FqiRep  *rep;
-  double  *in, *next_obs, *reward, *targets;        // [R][cap][...]
-  int32_t *absorbing;
-  double  *net;                                     // [R][4][P]: params, eta, Delta (unused), prev_Delta
-  double  *vL;                                      // [2][R][P + 1][64]: the 64 partial sums of level 2 per parameter, double-buffered by epoch parity
-  unsigned long long *stamps;                       // diagnostic (GRLX_FQI_STAMPS=1): [R][16][4 epochs][8] shader-clock stamps, else null
-  unsigned int *sync;                               // [R][4]: arrival counter of the replica's blocks (16-byte slots), zeroed per launch
-  double  *row_reward;                              // [R][max_rows]
-  int64_t *row_batch, *row_transitions;
-  int32_t  max_rows;
-};
-
 // ANNRepresentation::read (ann.cpp:133-160): net input ((w0 a0 + w1 a1) + w2 a2) + bias, logistic hidden layer, linear output.
 // Written stage by stage over the hidden units (per unit the operations and their order are those of the scalar text:
 // oracle/fqi.c ann_forward): independent chains for the wave to overlap -- a branchy exp per unit serialises them.  Up to 20
@@ -259,7 +217,6 @@ __global__ __launch_bounds__(256) void fqi_targets_kernel(FqiParams F, int first
 typedef __attribute__((address_space(1))) unsigned int fqi_gu32;
 typedef __attribute__((address_space(1))) unsigned long long fqi_gu64;
 #define FQI_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-constexpr uint32_t ST_SYNC_TIMEOUT = 32u;
 constexpr unsigned kFqiSpinLimit = 4u << 20;            // x (s_sleep 2 + one L2 round trip) = seconds
 
 __device__ __forceinline__ void fqi_publish(double *p, double x)
@@ -318,7 +275,6 @@ template <int H> struct FqiShape {
   static_assert(KP <= 6 && RS * SPB <= 12 && SPB >= 1, "reads per batch");
   static_assert((size_t)WAVES * 64 * COLS * 8 + 3 * P * 8 + 64 <= 160 * 1024, "factor tiles exceed the LDS");
 };
-constexpr int kFqiStampBlocks = 16;
 
 // s_waitcnt lgkmcnt(N) that the compiler may not move the uses of x[] across
 template <int N>
@@ -728,344 +684,10 @@ __global__ __launch_bounds__(64) void fqi_test_kernel(FqiParams F)
   rep.status |= status;
 }
 
-} // namespace grlx
-
-using namespace grlx;
-
-struct grlx_fqi_ctx {
-  grlx_fqi_config cfg;
-  FqiParams F;
-  std::vector<void *> bufs;
-  uint64_t *r0 = nullptr;
-  int batches_run = 0;
-  int replicas_per_launch = 1;       // how many replicas' blocks are resident at once
-  int blocks_per_replica = 16, block_threads = 256;      // FqiShape<hidden>
-  bool plain_launch = false;         // the epochs kernel without hipLaunchCooperativeKernel: GRLX_FQI_NO_COOP=1 (diagnostic), or the runtime
-                                     // refused the cooperative launch because another process holds the device's cooperative queue
-};
-
-namespace {
-// the instantiated widths of the hidden layer (representation/parameterized/ann:hiddens = [H])
-#define FQI_FOR_H(H_, ...)                                           \
-  switch (H_)                                                        \
-  {                                                                  \
-    case 8:  { constexpr int HH = 8;  __VA_ARGS__; } break;          \
-    case 16: { constexpr int HH = 16; __VA_ARGS__; } break;          \
-    case 20: { constexpr int HH = 20; __VA_ARGS__; } break;          \
-    case 32: { constexpr int HH = 32; __VA_ARGS__; } break;          \
-    case 64: { constexpr int HH = 64; __VA_ARGS__; } break;          \
-    default: break;                                                  \
-  }
-inline bool fqi_width_built(int H) { return H == 8 || H == 16 || H == 20 || H == 32 || H == 64; }
-
-int ffail(int code, const char *fmt, ...)
-{
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  set_last_error(buf);
-  return code;
-}
-#define FQI_TRY(expr)                                                                              \
-  do {                                                                                             \
-    hipError_t e__ = (expr);                                                                       \
-    if (e__ != hipSuccess) return ffail(GRLX_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e__)); \
-  } while (0)
-
-constexpr uint64_t kA = 0x5DEECE66DULL, kC = 0xBULL, kM = (1ULL << 48) - 1;
-inline uint64_t h_seed(long s) { return ((((uint64_t)s) & 0xFFFFFFFFULL) << 16) | 0x330EULL; }
-inline uint64_t h_next(uint64_t x) { return (kA * x + kC) & kM; }
-
-template <typename T> int dev_alloc(grlx_fqi_ctx *ctx, T **p, size_t n)
-{
-  void *q = nullptr;
-  if (hipMalloc(&q, n * sizeof(T) ? n * sizeof(T) : 8) != hipSuccess) return ffail(GRLX_ERR_OOM, "out of device memory (%zu bytes)", n * sizeof(T));
-  if (hipMemset(q, 0, n * sizeof(T)) != hipSuccess) return ffail(GRLX_ERR_HIP, "hipMemset failed");
-  ctx->bufs.push_back(q);
-  *p = (T *)q;
-  return GRLX_OK;
-}
-} // namespace
-
-extern "C" {
-
-void grlx_fqi_config_pendulum(grlx_fqi_config *c)
-{ // the reference's tests/pendulum-fqi-ann.yaml
-  memset(c, 0, sizeof(*c));
-  c->struct_size = sizeof(grlx_fqi_config);
-  c->n_replicas = 1;
-  c->env = GRLX_ENV_PENDULUM;
-  c->control_step = 0.03;
-  c->integration_steps = 5;
-  c->timeout = 2.99;
-  c->action_min = -3;
-  c->action_max = 3;
-  c->action_steps = 3;
-  c->gamma = 0.97;
-  c->batch_size = 1000;
-  c->max_batches = 2;
-  c->iterations = 10;
-  c->epochs = 500;
-  c->hidden = 20;
-}
-
-int grlx_fqi_create(const grlx_fqi_config *cfg, const int64_t *seeds, grlx_fqi_ctx **out)
-{
-  if (!cfg || !seeds || !out) return ffail(GRLX_ERR_INVALID, "null argument");
-  *out = nullptr;
-  if (cfg->struct_size != sizeof(grlx_fqi_config)) return ffail(GRLX_ERR_INVALID, "grlx_fqi_config.struct_size mismatch");
-  if (cfg->env != GRLX_ENV_PENDULUM) return ffail(GRLX_ERR_INVALID, "experiment/batch_learning: the task must support invert(); built for task/pendulum/swingup");
-  if (!(cfg->eta >= -2. && cfg->eta <= 2.)) return ffail(GRLX_ERR_INVALID, "representation/parameterized/ann:eta = %g outside [-2, 2] (ann.cpp:61)", cfg->eta);
-  if (!fqi_width_built(cfg->hidden))
-    return ffail(GRLX_ERR_INVALID, "representation/parameterized/ann:hiddens = [%d] is not built (instantiated: [8], [16], [20], [32], [64])", cfg->hidden);
-  if (cfg->n_replicas < 1 || cfg->batch_size < 1 || cfg->max_batches < 1 || cfg->iterations < 1 || cfg->epochs < 0)
-    return ffail(GRLX_ERR_INVALID, "n_replicas, batch_size, max_batches, iterations must be >= 1");
-  if (cfg->action_steps < 1 || cfg->action_steps > GRLX_MAX_ACTIONS) return ffail(GRLX_ERR_INVALID, "discretizer/uniform:steps");
-  if (!(cfg->action_min < cfg->action_max) || !(cfg->control_step > 0) || cfg->integration_steps < 1 || !std::isfinite(cfg->timeout) || cfg->timeout < 0)
-    return ffail(GRLX_ERR_INVALID, "model / task parameters");
-  if (std::ceil(cfg->timeout / cfg->control_step) + 1 > (double)GRLX_MAX_EPISODE_STEPS) return ffail(GRLX_ERR_INVALID, "task:timeout exceeds GRLX_MAX_EPISODE_STEPS");
-  if ((double)cfg->batch_size * cfg->max_batches > 2e8) return ffail(GRLX_ERR_INVALID, "transition store too large");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { (void)hipGetLastError(); return ffail(GRLX_ERR_NO_DEVICE, "no HIP device: grlx has no CPU fallback"); }
-
-  grlx_fqi_ctx *ctx = new grlx_fqi_ctx();
-  ctx->cfg = *cfg;
-  FqiParams &F = ctx->F;
-  memset(&F, 0, sizeof(F));
-  F.env.env = GRLX_ENV_PENDULUM;
-  F.env.integration_steps = cfg->integration_steps;
-  F.env.h = cfg->control_step / (double)(size_t)cfg->integration_steps;
-  F.env.timeout = cfg->timeout;
-  F.env.randomization = 0;
-  F.R = cfg->n_replicas;
-  F.H = cfg->hidden;
-  F.P = (kFqiNIn + 1) * F.H + F.H + 1;
-  F.A = cfg->action_steps;
-  F.batch_size = cfg->batch_size;
-  F.cap = cfg->batch_size * cfg->max_batches;
-  F.chunks_cap = (F.cap + 63) / 64;
-  F.max_rows = cfg->max_batches;
-  {
-    const double range = cfg->action_max - cfg->action_min;
-    double delta = range / ((double)cfg->action_steps - 1);
-    if (std::isnan(delta)) delta = 0.;
-    for (int k = 0; k < cfg->action_steps; ++k) F.actions[k] = cfg->action_min + delta * k;
-  }
-  const double omin[2] = {0., -12 * M_PI}, omax[2] = {2 * M_PI, 12 * M_PI};      // pendulum.cpp:84-85
-  for (int i = 0; i < kFqiD; ++i)
-  {
-    F.obs_min[i] = omin[i];
-    F.obs_range[i] = omax[i] - omin[i];
-    F.in_min[i] = omin[i];
-    F.in_scale[i] = 1. / (omax[i] - omin[i]) * (1 + 0);
-  }
-  F.action_min = cfg->action_min;
-  F.action_range = cfg->action_max - cfg->action_min;
-  F.in_min[kFqiD] = cfg->action_min;
-  F.in_scale[kFqiD] = 1. / (cfg->action_max - cfg->action_min) * (1 + 0);
-  F.gamma_tau = pow(cfg->gamma, cfg->control_step);                               // pow(gamma_, tau), tau = control_step
-  F.eta = cfg->eta;
-
-  const size_t R = (size_t)F.R, cap = (size_t)F.cap;
-  int rc = GRLX_OK;
-  if ((rc = dev_alloc(ctx, &F.rep, R)) != GRLX_OK || (rc = dev_alloc(ctx, &F.in, R * cap * kFqiNIn)) != GRLX_OK ||
-      (rc = dev_alloc(ctx, &F.next_obs, R * cap * kFqiD)) != GRLX_OK || (rc = dev_alloc(ctx, &F.reward, R * cap)) != GRLX_OK ||
-      (rc = dev_alloc(ctx, &F.targets, R * cap)) != GRLX_OK || (rc = dev_alloc(ctx, &F.absorbing, R * cap)) != GRLX_OK ||
-      (rc = dev_alloc(ctx, &F.net, R * 4 * (size_t)F.P)) != GRLX_OK ||
-      (rc = dev_alloc(ctx, &F.vL, 2 * R * 64 * (size_t)(F.P + 1))) != GRLX_OK || (rc = dev_alloc(ctx, &F.sync, R * 4)) != GRLX_OK ||
-      (rc = dev_alloc(ctx, &F.row_reward, R * (size_t)F.max_rows)) != GRLX_OK || (rc = dev_alloc(ctx, &F.row_batch, R * (size_t)F.max_rows)) != GRLX_OK ||
-      (rc = dev_alloc(ctx, &F.row_transitions, R * (size_t)F.max_rows)) != GRLX_OK || (rc = dev_alloc(ctx, &ctx->r0, R)) != GRLX_OK)
-  {
-    grlx_fqi_destroy(ctx);
-    return rc;
-  }
-  // instantiate order of the yaml (oracle/fqi.c: orc_fqi_create): sampler/greedy Rand = global lrand48 #1, the
-  // thread-local RandGen = global lrand48 #2; the weight-initialisation stream of deviation D1 = srand48_r(seed)
-  std::vector<FqiRep> hr(R);
-  std::vector<uint64_t> hr0(R);
-  for (size_t r = 0; r < R; ++r)
-  {
-    memset(&hr[r], 0, sizeof(FqiRep));
-    uint64_t G = h_seed((long)seeds[r]);
-    G = h_next(G);                                   // sampler's private Rand (never drawn from: ties use the global stream)
-    G = h_next(G);
-    hr[r].TL = h_seed((long)(G >> 17));
-    hr[r].G = G;
-    hr0[r] = h_seed((long)seeds[r]);
-  }
-  if (hipMemcpy(F.rep, hr.data(), sizeof(FqiRep) * R, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(ctx->r0, hr0.data(), sizeof(uint64_t) * R, hipMemcpyHostToDevice) != hipSuccess)
-  {
-    grlx_fqi_destroy(ctx);
-    return ffail(GRLX_ERR_HIP, "hipMemcpy failed");
-  }
-  {
-    int dev = 0, cus = 0, per_cu = 0;
-    hipError_t occ = hipErrorInvalidValue;
-    FQI_FOR_H(F.H, ctx->blocks_per_replica = FqiShape<HH>::BLOCKS; ctx->block_threads = FqiShape<HH>::WAVES * 64;
-              occ = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fqi_epochs_kernel<HH>, FqiShape<HH>::WAVES * 64, 0));
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        occ != hipSuccess || cus * per_cu < ctx->blocks_per_replica)
-    {
-      const int need = ctx->blocks_per_replica;
-      grlx_fqi_destroy(ctx);
-      return ffail(GRLX_ERR_HIP, "fqi_epochs_kernel: the device cannot hold the %d resident blocks of one replica", need);
-    }
-    ctx->replicas_per_launch = (cus * per_cu) / ctx->blocks_per_replica;
-  }
-  if (const char *nc = getenv("GRLX_FQI_NO_COOP")) ctx->plain_launch = nc[0] && nc[0] != '0';
-  if (const char *st = getenv("GRLX_FQI_STAMPS"))
-    if (st[0] && st[0] != '0' && (rc = dev_alloc(ctx, &F.stamps, R * kFqiStampBlocks * 4 * 8)) != GRLX_OK)
-    {
-      grlx_fqi_destroy(ctx);
-      return rc;
-    }
-  hipLaunchKernelGGL(fqi_init_kernel, dim3((F.P + 127) / 128, F.R), dim3(128), 0, nullptr, F, ctx->r0);
-  if (hipDeviceSynchronize() != hipSuccess)
-  {
-    grlx_fqi_destroy(ctx);
-    return ffail(GRLX_ERR_HIP, "fqi_init_kernel failed");
-  }
-  *out = ctx;
-  return GRLX_OK;
-}
-
-int grlx_fqi_destroy(grlx_fqi_ctx *ctx)
-{
-  if (!ctx) return GRLX_OK;
-  for (void *p : ctx->bufs) (void)hipFree(p);
-  delete ctx;
-  return GRLX_OK;
-}
-
-int grlx_fqi_run_batch(grlx_fqi_ctx *ctx, void *stream_)
-{
-  if (!ctx) return ffail(GRLX_ERR_INVALID, "null ctx");
-  if (ctx->batches_run >= ctx->cfg.max_batches) return ffail(GRLX_ERR_ROWS_FULL, "more batches than max_batches");
-  hipStream_t stream = (hipStream_t)stream_;
-  const FqiParams &F = ctx->F;
-  const int n_after = (ctx->batches_run + 1) * F.batch_size;
-  const int chunks = (n_after + 255) / 256;
-  hipLaunchKernelGGL(fqi_generate_kernel, dim3((F.batch_size + 255) / 256, F.R), dim3(256), 0, stream, F);
-  hipLaunchKernelGGL(fqi_batch_begin_kernel, dim3((F.R + 63) / 64), dim3(64), 0, stream, F);
-  for (int ii = 0; ii < ctx->cfg.iterations; ++ii)
-  {
-    hipLaunchKernelGGL(fqi_iter_begin_kernel, dim3((F.R + 63) / 64), dim3(64), 0, stream, F, ii);
-    FQI_FOR_H(F.H, hipLaunchKernelGGL(fqi_targets_kernel<HH>, dim3(chunks, F.R), dim3(256), 0, stream, F, ii == 0 ? 1 : 0));
-    // the epochs of the iteration: one cooperative launch per group of replicas that fills the chip (16 blocks per replica for [20])
-    for (int r0 = 0; r0 < F.R; r0 += ctx->replicas_per_launch)
-    {
-      const int nr = (F.R - r0 < ctx->replicas_per_launch) ? F.R - r0 : ctx->replicas_per_launch;
-      FQI_TRY(hipMemsetAsync(F.sync + (size_t)r0 * 4, 0, (size_t)nr * 4 * sizeof(unsigned int), stream));
-      FqiParams Fa = F;
-      int r_first = r0, epochs = ctx->cfg.epochs;
-      void *args[] = {&Fa, &r_first, &epochs};
-      const dim3 grid(nr * ctx->blocks_per_replica), block(ctx->block_threads);
-      hipError_t le = hipSuccess;
-      if (!ctx->plain_launch)
-      {
-        FQI_FOR_H(F.H, le = hipLaunchCooperativeKernel((const void *)fqi_epochs_kernel<HH>, grid, block, args, 0, stream));
-        // A device may lend its queue for cooperative launches to one process at a time: while another process holds it (a parent
-        // that ran the batch path, the other rank on a shared GPU) the runtime answers hipErrorIllegalState and has launched nothing.
-        // The kernel needs nothing of that queue but the residency check, and create() sized the grid to be resident
-        // (replicas_per_launch); the spins are bounded either way.  So this context launches the same grid plainly from here on.
-        if (le == hipErrorIllegalState)
-        {
-          (void)hipGetLastError();
-          ctx->plain_launch = true;
-          le = hipSuccess;
-        }
-      }
-      if (ctx->plain_launch)      // also GRLX_FQI_NO_COOP=1 (diagnostic): the same grid without the runtime's residency check
-      { FQI_FOR_H(F.H, hipLaunchKernelGGL(fqi_epochs_kernel<HH>, grid, block, 0, stream, Fa, r_first, epochs)); }
-      FQI_TRY(le);
-    }
-  }
-  FQI_FOR_H(F.H, hipLaunchKernelGGL(fqi_test_kernel<HH>, dim3((F.R + 63) / 64), dim3(64), 0, stream, F));
-  FQI_TRY(hipGetLastError());
-  ctx->batches_run++;
-  return GRLX_OK;
-}
-
-int grlx_fqi_sync(grlx_fqi_ctx *ctx, void *stream)
-{
-  if (!ctx) return ffail(GRLX_ERR_INVALID, "null ctx");
-  FQI_TRY(hipStreamSynchronize((hipStream_t)stream));
-  std::vector<FqiRep> hr((size_t)ctx->F.R);
-  FQI_TRY(hipMemcpy(hr.data(), ctx->F.rep, sizeof(FqiRep) * hr.size(), hipMemcpyDeviceToHost));
-  uint32_t st = 0;
-  for (const FqiRep &r : hr) st |= r.status;
-  if (st & ST_DOMAIN) return ffail(GRLX_ERR_DOMAIN, "sin/cos argument outside |x| < 2^20");
-  if (st & ST_ROWS_FULL) return ffail(GRLX_ERR_ROWS_FULL, "more batches than max_batches");
-  if (st & ST_SYNC_TIMEOUT) return ffail(GRLX_ERR_HIP, "fqi_epochs_kernel: a wait between the blocks of a replica timed out (were all of its blocks resident?)");
-  return GRLX_OK;
-}
-
-int grlx_fqi_read_rows(grlx_fqi_ctx *ctx, int replica, int first, int count, int64_t *batch, int64_t *transitions, double *reward)
-{
-  if (!ctx || replica < 0 || replica >= ctx->F.R || first < 0 || count < 0 || first + count > ctx->F.max_rows) return ffail(GRLX_ERR_INVALID, "bad argument");
-  if (count == 0) return GRLX_OK;
-  FQI_TRY(hipDeviceSynchronize());
-  const size_t at = (size_t)replica * (size_t)ctx->F.max_rows + (size_t)first;
-  if (batch) FQI_TRY(hipMemcpy(batch, ctx->F.row_batch + at, sizeof(int64_t) * (size_t)count, hipMemcpyDeviceToHost));
-  if (transitions) FQI_TRY(hipMemcpy(transitions, ctx->F.row_transitions + at, sizeof(int64_t) * (size_t)count, hipMemcpyDeviceToHost));
-  if (reward) FQI_TRY(hipMemcpy(reward, ctx->F.row_reward + at, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost));
-  return GRLX_OK;
-}
-
-int grlx_fqi_get_params(grlx_fqi_ctx *ctx, int replica, double *out, int n)
-{
-  if (!ctx || !out || replica < 0 || replica >= ctx->F.R || n != ctx->F.P) return ffail(GRLX_ERR_INVALID, "bad argument (the network has %d parameters)", ctx ? ctx->F.P : 0);
-  FQI_TRY(hipDeviceSynchronize());
-  FQI_TRY(hipMemcpy(out, ctx->F.net + (size_t)replica * 4 * (size_t)ctx->F.P, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-  return GRLX_OK;
-}
-
-int grlx_fqi_get_transitions(grlx_fqi_ctx *ctx, int replica, int first, int count, double *in, double *next_obs, double *reward, double *targets)
-{
-  if (!ctx || replica < 0 || replica >= ctx->F.R || first < 0 || count < 0 || first + count > ctx->F.cap) return ffail(GRLX_ERR_INVALID, "bad argument");
-  if (count == 0) return GRLX_OK;
-  FQI_TRY(hipDeviceSynchronize());
-  const size_t at = (size_t)replica * (size_t)ctx->F.cap + (size_t)first;
-  if (in) FQI_TRY(hipMemcpy(in, ctx->F.in + at * kFqiNIn, sizeof(double) * (size_t)count * kFqiNIn, hipMemcpyDeviceToHost));
-  if (next_obs) FQI_TRY(hipMemcpy(next_obs, ctx->F.next_obs + at * kFqiD, sizeof(double) * (size_t)count * kFqiD, hipMemcpyDeviceToHost));
-  if (reward) FQI_TRY(hipMemcpy(reward, ctx->F.reward + at, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost));
-  if (targets) FQI_TRY(hipMemcpy(targets, ctx->F.targets + at, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost));
-  return GRLX_OK;
-}
-
-// diagnostic, not part of include/grlx.h: the stamps of the LAST fqi_epochs_kernel launch (GRLX_FQI_STAMPS=1 at create)
-int grlx_fqi_debug_stamps(grlx_fqi_ctx *ctx, unsigned long long *out, int count)
-{
-  if (!ctx || !out || !ctx->F.stamps || count != ctx->F.R * kFqiStampBlocks * 4 * 8) return ffail(GRLX_ERR_INVALID, "no stamps (GRLX_FQI_STAMPS=1 at create; count = R * 512)");
-  FQI_TRY(hipDeviceSynchronize());
-  FQI_TRY(hipMemcpy(out, ctx->F.stamps, sizeof(unsigned long long) * (size_t)count, hipMemcpyDeviceToHost));
-  return GRLX_OK;
-}
-
-int grlx_fqi_info(grlx_fqi_ctx *ctx, int replica, int64_t *n_transitions, double *maxdelta, int32_t *iterations, double *error, uint64_t rng[2])
-{
-  if (!ctx || replica < 0 || replica >= ctx->F.R) return ffail(GRLX_ERR_INVALID, "bad argument");
-  FQI_TRY(hipDeviceSynchronize());
-  FqiRep r;
-  FQI_TRY(hipMemcpy(&r, ctx->F.rep + replica, sizeof(r), hipMemcpyDeviceToHost));
-  if (n_transitions) *n_transitions = r.n;
-  if (maxdelta) *maxdelta = r.done ? r.maxdelta_last : __builtin_bit_cast(double, r.maxdelta_bits);
-  if (iterations) *iterations = r.iterations;
-  if (error) *error = r.last_error;
-  if (rng) { rng[0] = r.G; rng[1] = r.TL; }
-  return GRLX_OK;
-}
-
-} // extern "C"
-
 // ------------------------------------------------------------------------------------------- policy query ---
 // grlx_fqi_query: the batch path's Q(s, a_k) at observations of the caller's choice -- the projector's normalisation and the network's
 // forward pass on the replica's CURRENT parameters, the operations of fqi_test_kernel's policy.  Reads F.net only: nothing of the
-// context changes.  Appended after everything else of the unit: the kernels above keep their instruction streams.
-namespace grlx {
+// context changes.
 
 // one thread per (replica, observation), looping over the actions; q[(replica - first_replica) * n_obs + observation][F.A]
 template <int H>
@@ -1086,65 +708,11 @@ __global__ __launch_bounds__(64) void fqi_query_kernel(FqiParams F, int first_re
   }
 }
 
-} // namespace grlx
-
-namespace {
-uint64_t g_fqi_query_chunk_bytes = 256ull << 20;      // device staging one query holds at most
-}
-namespace grlx { void set_fqi_query_chunk_bytes(uint64_t bytes) { g_fqi_query_chunk_bytes = bytes ? bytes : (256ull << 20); } }     // grlx_set_query_chunk_bytes
-
-extern "C" int grlx_fqi_query(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, const double *obs, int n_obs, double *q)
-{
-  if (!ctx || !q) return ffail(GRLX_ERR_INVALID, "bad argument");
-  if (!obs) return ffail(GRLX_ERR_INVALID, "grlx_fqi_query: obs is null");
-  if (n_obs < 0) return ffail(GRLX_ERR_INVALID, "grlx_fqi_query: n_obs = %d", n_obs);
-  if (first_replica < 0 || n_replicas < 0 || (int64_t)first_replica + n_replicas > ctx->F.R)
-    return ffail(GRLX_ERR_INVALID, "grlx_fqi_query: replica range [%d, %lld) is outside the context's %d replicas", first_replica,
-                 (long long)first_replica + n_replicas, ctx->F.R);
-  for (int o = 0; o < n_obs; ++o)
-    for (int d = 0; d < kFqiD; ++d)
-      if (!std::isfinite(obs[(size_t)o * kFqiD + d]))
-        return ffail(GRLX_ERR_INVALID, "grlx_fqi_query: observation row %d, dimension %d is not finite", o, d);
-  if (n_obs == 0 || n_replicas == 0) return GRLX_OK;
-  FQI_TRY(hipDeviceSynchronize());
-  const int A = ctx->F.A;
-  const uint64_t per_obs = sizeof(double) * kFqiD + sizeof(double) * (uint64_t)A * (uint64_t)n_replicas;
-  const uint64_t fit = g_fqi_query_chunk_bytes / per_obs;
-  const int chunk = (int)(fit < 1 ? 1 : fit > (uint64_t)n_obs ? (uint64_t)n_obs : fit);
-  double *dobs = nullptr, *dq = nullptr;
-  if (hipMalloc((void **)&dobs, sizeof(double) * kFqiD * (size_t)chunk) != hipSuccess ||
-      hipMalloc((void **)&dq, sizeof(double) * (size_t)A * (size_t)n_replicas * (size_t)chunk) != hipSuccess)
-  {
-    if (dobs) (void)hipFree(dobs);
-    return ffail(GRLX_ERR_OOM, "grlx_fqi_query: out of device memory");
-  }
-  hipError_t err = hipSuccess;
-  for (int o0 = 0; o0 < n_obs && err == hipSuccess; o0 += chunk)
-  {
-    const int nc = n_obs - o0 < chunk ? n_obs - o0 : chunk;
-    const long long pairs = (long long)n_replicas * nc;
-    err = hipMemcpy(dobs, obs + (size_t)o0 * kFqiD, sizeof(double) * kFqiD * (size_t)nc, hipMemcpyHostToDevice);
-    if (err != hipSuccess) break;
-    FQI_FOR_H(ctx->F.H, hipLaunchKernelGGL(fqi_query_kernel<HH>, dim3((unsigned)((pairs + 63) / 64)), dim3(64), 0, nullptr, ctx->F, first_replica,
-                                           n_replicas, dobs, nc, dq));
-    err = hipGetLastError();
-    if (err != hipSuccess) break;
-    const size_t elem = sizeof(double) * (size_t)A;                       // device [replica][nc][A] -> host [replica][n_obs][A] at o0
-    err = hipMemcpy2D((char *)q + (size_t)o0 * elem, (size_t)n_obs * elem, dq, (size_t)nc * elem, (size_t)nc * elem, (size_t)n_replicas,
-                      hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(dobs);
-  (void)hipFree(dq);
-  if (err != hipSuccess) return ffail(GRLX_ERR_HIP, "grlx_fqi_query failed: %s", hipGetErrorString(err));
-  return GRLX_OK;
-}
-
 // ----------------------------------------------------------------------------------- greedy evaluation episodes ---
 // grlx_fqi_evaluate, grlx_fqi_evaluate_trajectory: for every (replica, start state) pair one greedy episode of the batch path's policy
 // from a MODEL state of the caller's choice -- fqi_test_kernel's loop with the caller's state in place of Task::start and without the
 // tie-breaking draw (the first maximum acts; `ties` counts the steps with more than one).  Reads F.net, F.env and the projector's
-// constants only: no row, no batches_done, no stream, no status bit, no parameter changes.  Appended after the query: every kernel above
-// keeps its instruction stream.
+// constants only: no row, no batches_done, no stream, no status bit, no parameter changes.
 //
 // Layout.  The policy is A small dense forward passes per step, so ONE LANE is one pair; blockIdx.y is the replica, which makes the
 // network block-uniform: its P = 5 H + 1 parameters (the first of the replica's four P-blocks in F.net) are staged once into LDS, as
@@ -1157,20 +725,6 @@ extern "C" int grlx_fqi_query(grlx_fqi_ctx *ctx, int first_replica, int n_replic
 // operations each time, so a compiler that forms them once changes no bit; ann_forward itself is not re-associated.
 // RECORD: one record of GRLX_TRAJ_OBS + 2 + 3 doubles per step taken, and -- behind the lane's own episode's end -- zeros up to
 // max_steps, written by the lane itself: the staging buffer is never filled twice.
-namespace grlx {
-
-constexpr int kFqiTrajWords = GRLX_TRAJ_OBS + kFqiD + kFqiS;
-constexpr int kFqiEvalDomain = 3;          // terminal code of a step that ended outside Env<PENDULUM>::in_domain (grlx_evaluate's)
-
-struct FqiEvalArgs {
-  int32_t first_replica, n_starts, max_steps;      // n_starts: of this chunk; max_steps: 1 ... GRLX_MAX_EPISODE_STEPS
-  const double *states;                            // [n_starts][3]
-  double  *ret, *disc;                             // [n_replicas][n_starts], as are steps, terminal and ties
-  int32_t *steps, *terminal, *ties;
-  double  *final_state;                            // [n_replicas][n_starts][3]
-  double  *records;                                // RECORD: [n_replicas][n_starts][max_steps][kFqiTrajWords]
-};
-
 template <int H, bool RECORD>
 __global__ __launch_bounds__(64) void fqi_evaluate_kernel(FqiParams F, FqiEvalArgs A)
 {
@@ -1252,137 +806,13 @@ __global__ __launch_bounds__(64) void fqi_evaluate_kernel(FqiParams F, FqiEvalAr
   for (int i = 0; i < kFqiS; ++i) A.final_state[pair * kFqiS + i] = x[i];
 }
 
-} // namespace grlx
-
-namespace {
-
-// what both evaluations check before they touch the device
-int fqi_evaluate_admit(grlx_fqi_ctx *ctx, const char *who, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps)
-{
-  if (!ctx) return ffail(GRLX_ERR_INVALID, "%s: ctx is null", who);
-  if (n_starts < 0) return ffail(GRLX_ERR_INVALID, "%s: n_starts = %d", who, n_starts);
-  if (first_replica < 0 || n_replicas < 0 || (int64_t)first_replica + n_replicas > ctx->F.R)
-    return ffail(GRLX_ERR_INVALID, "%s: replica range [%d, %lld) is outside the context's %d replicas", who, first_replica,
-                 (long long)first_replica + n_replicas, ctx->F.R);
-  if (!states) return ffail(GRLX_ERR_INVALID, "%s: states is null", who);
-  if (max_steps < 0 || max_steps > GRLX_MAX_EPISODE_STEPS)
-    return ffail(GRLX_ERR_INVALID, "%s: max_steps = %d is outside 1 ... GRLX_MAX_EPISODE_STEPS (%d; 0 = that cap)", who, max_steps, GRLX_MAX_EPISODE_STEPS);
-  for (int s = 0; s < n_starts; ++s)
-    for (int i = 0; i < kFqiS; ++i)
-    { // below 2^17 the RK4 stages of one step stay inside the branch-free sine's domain (grlx_evaluate's bound)
-      const double v = states[(size_t)s * kFqiS + i];
-      if (!std::isfinite(v)) return ffail(GRLX_ERR_INVALID, "%s: state row %d, component %d is not finite (%g)", who, s, i, v);
-      if (!(std::fabs(v) < 0x1p17)) return ffail(GRLX_ERR_INVALID, "%s: state row %d, component %d (%g) is out of range: its magnitude reaches 2^17", who, s, i, v);
-    }
-  return GRLX_OK;
-}
-
-// the episodes of admitted arguments, in chunks of start states of at most per_start bytes of staging each; records == nullptr: the sums alone
-int fqi_evaluate_run(grlx_fqi_ctx *ctx, const char *who, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps,
-                     uint64_t per_start, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state, double *records)
-{
-  FQI_TRY(hipDeviceSynchronize());
-  const uint64_t fit = g_fqi_query_chunk_bytes / per_start;
-  const int chunk = (int)(fit < 1 ? 1 : fit > (uint64_t)n_starts ? (uint64_t)n_starts : fit);
-  const size_t rows = (size_t)n_replicas, pairs = rows * (size_t)chunk;
-  const size_t rec_elem = records ? sizeof(double) * (size_t)kFqiTrajWords * (size_t)max_steps : 0;
-  // one allocation, the doubles first: states, ret, disc, final_state, records, then the three int32 arrays
-  const size_t n_double = (size_t)chunk * kFqiS + 2 * pairs + pairs * kFqiS + pairs * (rec_elem / sizeof(double));
-  char *dev = nullptr;
-  if (hipMalloc((void **)&dev, n_double * sizeof(double) + 3 * pairs * sizeof(int32_t)) != hipSuccess)
-  {
-    (void)hipGetLastError();
-    return ffail(GRLX_ERR_OOM, "%s: out of device memory (%zu bytes of staging)", who, n_double * sizeof(double) + 3 * pairs * sizeof(int32_t));
-  }
-  double *dstates = (double *)dev, *dret = dstates + (size_t)chunk * kFqiS, *ddisc = dret + pairs, *dfinal = ddisc + pairs, *drec = dfinal + pairs * kFqiS;
-  int32_t *dsteps = (int32_t *)(drec + pairs * (rec_elem / sizeof(double))), *dterm = dsteps + pairs, *dties = dterm + pairs;
-  hipError_t err = hipSuccess;
-  for (int s0 = 0; s0 < n_starts && err == hipSuccess; s0 += chunk)
-  {
-    const int nc = n_starts - s0 < chunk ? n_starts - s0 : chunk;
-    err = hipMemcpy(dstates, states + (size_t)s0 * kFqiS, sizeof(double) * kFqiS * (size_t)nc, hipMemcpyHostToDevice);
-    if (err != hipSuccess) break;
-    FqiEvalArgs A;
-    A.first_replica = first_replica; A.n_starts = nc; A.max_steps = max_steps; A.states = dstates;
-    A.ret = dret; A.disc = ddisc; A.steps = dsteps; A.terminal = dterm; A.ties = dties; A.final_state = dfinal; A.records = records ? drec : nullptr;
-    const dim3 grid((unsigned)((nc + 63) / 64), (unsigned)n_replicas), block(64);
-    if (records) { FQI_FOR_H(ctx->F.H, hipLaunchKernelGGL((fqi_evaluate_kernel<HH, true>), grid, block, 0, nullptr, ctx->F, A)); }
-    else { FQI_FOR_H(ctx->F.H, hipLaunchKernelGGL((fqi_evaluate_kernel<HH, false>), grid, block, 0, nullptr, ctx->F, A)); }
-    err = hipGetLastError();
-    // device [replica][nc] -> host [replica][n_starts] at s0
-    const struct { void *host; const void *dev; size_t elem; } outs[7] = {
-        {ret, dret, sizeof(double)}, {disc, ddisc, sizeof(double)}, {steps, dsteps, sizeof(int32_t)}, {terminal, dterm, sizeof(int32_t)},
-        {ties, dties, sizeof(int32_t)}, {final_state, dfinal, sizeof(double) * kFqiS}, {records, drec, rec_elem}};
-    for (int o = 0; o < 7 && err == hipSuccess; ++o)
-      if (outs[o].host)
-        err = hipMemcpy2D((char *)outs[o].host + (size_t)s0 * outs[o].elem, (size_t)n_starts * outs[o].elem, outs[o].dev, (size_t)nc * outs[o].elem,
-                          (size_t)nc * outs[o].elem, rows, hipMemcpyDeviceToHost);
-  }
-  if (err == hipSuccess) err = hipDeviceSynchronize();
-  (void)hipFree(dev);
-  if (err != hipSuccess) return ffail(GRLX_ERR_HIP, "%s failed: %s", who, hipGetErrorString(err));
-  return GRLX_OK;
-}
-
-// a start state's staged bytes besides its records: the state and its rows' sums
-inline uint64_t fqi_evaluate_sums_bytes(int n_replicas)
-{
-  return sizeof(double) * kFqiS + (2 * sizeof(double) + 3 * sizeof(int32_t) + sizeof(double) * kFqiS) * (uint64_t)n_replicas;
-}
-
-} // namespace
-
-extern "C" {
-
-int grlx_fqi_evaluate(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, double *ret, double *disc,
-                      int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state)
-{
-  const char *who = "grlx_fqi_evaluate";
-  int rc = fqi_evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps);
-  if (rc != GRLX_OK) return rc;
-  if (max_steps == 0) max_steps = GRLX_MAX_EPISODE_STEPS;
-  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
-  return fqi_evaluate_run(ctx, who, first_replica, n_replicas, states, n_starts, max_steps, fqi_evaluate_sums_bytes(n_replicas), ret, disc, steps, terminal,
-                          ties, final_state, nullptr);
-}
-
-int grlx_fqi_trajectory_record_words(grlx_fqi_ctx *ctx)
-{
-  if (!ctx) return ffail(GRLX_ERR_INVALID, "grlx_fqi_trajectory_record_words: ctx is null");
-  return kFqiTrajWords;
-}
-
-int grlx_fqi_evaluate_trajectory(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, double *ret,
-                                 double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state, double *records)
-{
-  const char *who = "grlx_fqi_evaluate_trajectory";
-  int rc = fqi_evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps);
-  if (rc != GRLX_OK) return rc;
-  if (!records) return ffail(GRLX_ERR_INVALID, "%s: records is null (for the sums alone call grlx_fqi_evaluate)", who);
-  if (max_steps == 0)
-    return ffail(GRLX_ERR_INVALID, "%s: max_steps = 0: the records are sized by max_steps, so there is no default here (1 ... GRLX_MAX_EPISODE_STEPS = %d)", who,
-                 GRLX_MAX_EPISODE_STEPS);
-  // unlike the sums, a chunk with records never exceeds the bound: a column that does not fit is refused instead of staged as "at least one"
-  const uint64_t column = (uint64_t)n_replicas * (uint64_t)max_steps * (uint64_t)kFqiTrajWords * sizeof(double);
-  const uint64_t per_start = column + fqi_evaluate_sums_bytes(n_replicas);
-  if (per_start > g_fqi_query_chunk_bytes)
-    return ffail(GRLX_ERR_INVALID, "%s: one start state's column of records is %llu bytes (%d rows x %d steps x %d words x 8; %llu with its sums) and exceeds "
-                 "the staging bound of %llu bytes: ask for fewer replicas per call, a smaller max_steps, or raise the bound with grlx_set_query_chunk_bytes", who,
-                 (unsigned long long)column, n_replicas, max_steps, kFqiTrajWords, (unsigned long long)per_start, (unsigned long long)g_fqi_query_chunk_bytes);
-  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
-  return fqi_evaluate_run(ctx, who, first_replica, n_replicas, states, n_starts, max_steps, per_start, ret, disc, steps, terminal, ties, final_state, records);
-}
-
-} // extern "C"
-
 // ---------------------------------------------------------------------------- the ensemble over groups of replicas ---
 // grlx_fqi_query_ensemble, grlx_fqi_evaluate_ensemble, grlx_fqi_evaluate_ensemble_trajectory: the replicas [first_replica, first_replica +
 // n_replicas) in groups of group_size consecutive ones (bagged FQI: every replica is a network of its own fitted to transitions of its
 // own).  Per observation the members are visited in ASCENDING replica order: q_m[k] by the operations of fqi_query_kernel, (mai_m, man_m)
 // by findmax, votes[mai_m] += 1, sumq[k] += q_m[k] into one accumulator per action from 0.0 -- that order is the specification.  The
 // episode is fqi_evaluate_kernel's with the first maximum of votes (GRLX_ENSEMBLE_VOTE) or sumq (GRLX_ENSEMBLE_MEAN_Q) acting.  Reads
-// F.net, F.env and the projector's constants only.  Appended after everything else of the unit: the kernels above keep their
-// instruction streams.
+// F.net, F.env and the projector's constants only.
 //
 // Layout of the episodes.  One lane is one (group, start state) pair, blockIdx.y the group, the block one wave: the member loop is
 // block-uniform, and a lane walks its group's members one after the other.  A member's P = 5 H + 1 parameters (the first of the replica's
@@ -1391,20 +821,6 @@ int grlx_fqi_evaluate_trajectory(grlx_fqi_ctx *ctx, int first_replica, int n_rep
 // section 4.2i.)  The step loop is wave-uniform: it runs while a ballot finds an active lane; finished and dead lanes skip the step.
 // Nothing is indexed at run time by a lane's value or by a loop counter that is not unrolled: the action of pass k, q[k] -> q[], the
 // member's vote, the chosen action and its score are selects over the kMaxActions actions.  ann_forward is called as it is.
-namespace grlx {
-
-constexpr int kFqiEnsTrajWords = GRLX_TRAJ_ENS_OBS + kFqiD + kFqiS;
-
-struct FqiEnsArgs {
-  int32_t first_replica, group_size, rule, n_starts, max_steps;      // n_starts: of this chunk; max_steps: 1 ... GRLX_MAX_EPISODE_STEPS
-  const double *states;                            // [n_starts][3]
-  double  *ret, *disc;                             // [groups][n_starts], as are steps, terminal, ties, member_ties and agreement
-  int32_t *steps, *terminal, *ties;
-  int64_t *member_ties, *agreement;
-  double  *final_state;                            // [groups][n_starts][3]
-  double  *records;                                // RECORD: [groups][n_starts][max_steps][kFqiEnsTrajWords]
-};
-
 // one member at obs: q[k] = Q(obs, a_k) for k < F.A (the others stay 0), sumq[k] += q[k], and findmax over them (greedy.cpp:47-61) as
 // they are produced.  A caller that does not read q[] pays nothing for it.
 template <int H>
@@ -1570,189 +986,109 @@ __global__ __launch_bounds__(64) void fqi_query_ensemble_kernel(FqiParams F, int
     }
 }
 
+// ------------------------------------------------------------------------------------------------ host launchers ---
+// What grlx_api_fqi.cpp needs from the kernel symbols above (grlx_fqi.h).  Host code does not live in this unit beyond this block, and
+// kernels are appended above it, not inserted: every kernel keeps its instruction stream.
+
+// the instantiated widths of the hidden layer (representation/parameterized/ann:hiddens = [H])
+#define FQI_FOR_H(H_, ...)                                           \
+  switch (H_)                                                        \
+  {                                                                  \
+    case 8:  { constexpr int HH = 8;  __VA_ARGS__; } break;          \
+    case 16: { constexpr int HH = 16; __VA_ARGS__; } break;          \
+    case 20: { constexpr int HH = 20; __VA_ARGS__; } break;          \
+    case 32: { constexpr int HH = 32; __VA_ARGS__; } break;          \
+    case 64: { constexpr int HH = 64; __VA_ARGS__; } break;          \
+    default: return hipErrorInvalidValue;                            \
+  }
+bool fqi_width_built(int H) { return H == 8 || H == 16 || H == 20 || H == 32 || H == 64; }
+
+hipError_t fqi_epochs_shape(int H, FqiLaunchPlan *plan, int *blocks_per_cu)
+{
+  FQI_FOR_H(H, plan->blocks_per_replica = FqiShape<HH>::BLOCKS; plan->block_threads = FqiShape<HH>::WAVES * 64;
+            return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, fqi_epochs_kernel<HH>, FqiShape<HH>::WAVES * 64, 0));
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_fqi_init(const FqiParams &F, const uint64_t *r0, hipStream_t stream)
+{
+  hipLaunchKernelGGL(fqi_init_kernel, dim3((F.P + 127) / 128, F.R), dim3(128), 0, stream, F, r0);
+  return hipGetLastError();
+}
+
+hipError_t launch_fqi_batch(const FqiParams &F, FqiLaunchPlan &plan, int batches_run, int iterations, int epochs_, hipStream_t stream)
+{
+  const int n_after = (batches_run + 1) * F.batch_size;
+  const int chunks = (n_after + 255) / 256;
+  hipLaunchKernelGGL(fqi_generate_kernel, dim3((F.batch_size + 255) / 256, F.R), dim3(256), 0, stream, F);
+  hipLaunchKernelGGL(fqi_batch_begin_kernel, dim3((F.R + 63) / 64), dim3(64), 0, stream, F);
+  for (int ii = 0; ii < iterations; ++ii)
+  {
+    hipLaunchKernelGGL(fqi_iter_begin_kernel, dim3((F.R + 63) / 64), dim3(64), 0, stream, F, ii);
+    FQI_FOR_H(F.H, hipLaunchKernelGGL(fqi_targets_kernel<HH>, dim3(chunks, F.R), dim3(256), 0, stream, F, ii == 0 ? 1 : 0));
+    // the epochs of the iteration: one cooperative launch per group of replicas that fills the chip (16 blocks per replica for [20])
+    for (int r0 = 0; r0 < F.R; r0 += plan.replicas_per_launch)
+    {
+      const int nr = (F.R - r0 < plan.replicas_per_launch) ? F.R - r0 : plan.replicas_per_launch;
+      if (hipError_t e = hipMemsetAsync(F.sync + (size_t)r0 * 4, 0, (size_t)nr * 4 * sizeof(unsigned int), stream)) return e;
+      FqiParams Fa = F;
+      int r_first = r0, epochs = epochs_;
+      void *args[] = {&Fa, &r_first, &epochs};
+      const dim3 grid(nr * plan.blocks_per_replica), block(plan.block_threads);
+      hipError_t le = hipSuccess;
+      if (!plan.plain_launch)
+      {
+        FQI_FOR_H(F.H, le = hipLaunchCooperativeKernel((const void *)fqi_epochs_kernel<HH>, grid, block, args, 0, stream));
+        // A device may lend its queue for cooperative launches to one process at a time: while another process holds it (a parent
+        // that ran the batch path, the other rank on a shared GPU) the runtime answers hipErrorIllegalState and has launched nothing.
+        // The kernel needs nothing of that queue but the residency check, and create() sized the grid to be resident
+        // (replicas_per_launch); the spins are bounded either way.  So this context launches the same grid plainly from here on.
+        if (le == hipErrorIllegalState)
+        {
+          (void)hipGetLastError();
+          plan.plain_launch = true;
+          le = hipSuccess;
+        }
+      }
+      if (plan.plain_launch)      // also GRLX_FQI_NO_COOP=1 (diagnostic): the same grid without the runtime's residency check
+      { FQI_FOR_H(F.H, hipLaunchKernelGGL(fqi_epochs_kernel<HH>, grid, block, 0, stream, Fa, r_first, epochs)); }
+      if (le != hipSuccess) return le;
+    }
+  }
+  FQI_FOR_H(F.H, hipLaunchKernelGGL(fqi_test_kernel<HH>, dim3((F.R + 63) / 64), dim3(64), 0, stream, F));
+  return hipGetLastError();
+}
+
+hipError_t launch_fqi_query(const FqiParams &F, int first_replica, int n_replicas, const double *obs, int n_obs, double *q, hipStream_t stream)
+{
+  const long long pairs = (long long)n_replicas * n_obs;
+  FQI_FOR_H(F.H, hipLaunchKernelGGL(fqi_query_kernel<HH>, dim3((unsigned)((pairs + 63) / 64)), dim3(64), 0, stream, F, first_replica, n_replicas, obs,
+                                    n_obs, q));
+  return hipGetLastError();
+}
+
+hipError_t launch_fqi_evaluate(const FqiParams &F, const FqiEvalArgs &A, int rows, hipStream_t stream)
+{
+  const dim3 grid((unsigned)((A.n_starts + 63) / 64), (unsigned)rows), block(64);
+  if (A.records) { FQI_FOR_H(F.H, hipLaunchKernelGGL((fqi_evaluate_kernel<HH, true>), grid, block, 0, stream, F, A)); }
+  else { FQI_FOR_H(F.H, hipLaunchKernelGGL((fqi_evaluate_kernel<HH, false>), grid, block, 0, stream, F, A)); }
+  return hipGetLastError();
+}
+
+hipError_t launch_fqi_evaluate_ensemble(const FqiParams &F, const FqiEnsArgs &A, int rows, hipStream_t stream)
+{
+  const dim3 grid((unsigned)((A.n_starts + 63) / 64), (unsigned)rows), block(64);
+  if (A.records) { FQI_FOR_H(F.H, hipLaunchKernelGGL((fqi_evaluate_ensemble_kernel<HH, true>), grid, block, 0, stream, F, A)); }
+  else { FQI_FOR_H(F.H, hipLaunchKernelGGL((fqi_evaluate_ensemble_kernel<HH, false>), grid, block, 0, stream, F, A)); }
+  return hipGetLastError();
+}
+
+hipError_t launch_fqi_query_ensemble(const FqiParams &F, int first_replica, int groups, int group_size, const double *obs, int n_obs, double *out,
+                                     hipStream_t stream)
+{
+  const dim3 grid((unsigned)((n_obs + 63) / 64), (unsigned)groups), block(64);
+  FQI_FOR_H(F.H, hipLaunchKernelGGL(fqi_query_ensemble_kernel<HH>, grid, block, 0, stream, F, first_replica, group_size, obs, n_obs, out));
+  return hipGetLastError();
+}
+
 } // namespace grlx
-
-namespace {
-
-// what the three grouped calls check after their single-policy sibling's rules
-int fqi_ensemble_admit(const char *who, int n_replicas, int group_size)
-{
-  if (group_size < 1) return ffail(GRLX_ERR_INVALID, "%s: group_size = %d (at least 1)", who, group_size);
-  if (n_replicas % group_size != 0)
-    return ffail(GRLX_ERR_INVALID, "%s: n_replicas = %d is not a multiple of group_size = %d", who, n_replicas, group_size);
-  return GRLX_OK;
-}
-
-int fqi_evaluate_ensemble_admit(grlx_fqi_ctx *ctx, const char *who, int first_replica, int n_replicas, int group_size, int rule, const double *states,
-                                int n_starts, int max_steps)
-{
-  int rc = fqi_evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps);
-  if (rc != GRLX_OK) return rc;
-  if ((rc = fqi_ensemble_admit(who, n_replicas, group_size)) != GRLX_OK) return rc;
-  if (rule != GRLX_ENSEMBLE_VOTE && rule != GRLX_ENSEMBLE_MEAN_Q)
-    return ffail(GRLX_ERR_INVALID, "%s: rule = %d is neither GRLX_ENSEMBLE_VOTE (0) nor GRLX_ENSEMBLE_MEAN_Q (1)", who, rule);
-  return GRLX_OK;
-}
-
-// a start state's staged bytes besides its records: the state and its groups' sums
-inline uint64_t fqi_ensemble_sums_bytes(int groups)
-{
-  return sizeof(double) * kFqiS + (2 * sizeof(double) + 3 * sizeof(int32_t) + 2 * sizeof(int64_t) + sizeof(double) * kFqiS) * (uint64_t)groups;
-}
-
-struct FqiEnsOut {
-  double *ret, *disc;
-  int32_t *steps, *terminal, *ties;
-  int64_t *member_ties, *agreement;
-  double *final_state, *records;
-};
-
-// the episodes of admitted arguments, in chunks of start states of at most per_start bytes of staging each; records == nullptr: the sums alone
-int fqi_ensemble_run(grlx_fqi_ctx *ctx, const char *who, int first_replica, int groups, int group_size, int rule, const double *states, int n_starts,
-                     int max_steps, uint64_t per_start, const FqiEnsOut &out)
-{
-  FQI_TRY(hipDeviceSynchronize());
-  const uint64_t fit = g_fqi_query_chunk_bytes / per_start;
-  const int chunk = (int)(fit < 1 ? 1 : fit > (uint64_t)n_starts ? (uint64_t)n_starts : fit);
-  const size_t rows = (size_t)groups, pairs = rows * (size_t)chunk;
-  const size_t rec_elem = out.records ? sizeof(double) * (size_t)kFqiEnsTrajWords * (size_t)max_steps : 0;
-  // one allocation, the 8-byte types first: states, ret, disc, final_state, records, member_ties, agreement, then the three int32 arrays
-  const size_t n_double = (size_t)chunk * kFqiS + 2 * pairs + pairs * kFqiS + pairs * (rec_elem / sizeof(double));
-  const size_t bytes = n_double * sizeof(double) + 2 * pairs * sizeof(int64_t) + 3 * pairs * sizeof(int32_t);
-  char *dev = nullptr;
-  if (hipMalloc((void **)&dev, bytes) != hipSuccess)
-  {
-    (void)hipGetLastError();
-    return ffail(GRLX_ERR_OOM, "%s: out of device memory (%zu bytes of staging)", who, bytes);
-  }
-  double *dstates = (double *)dev, *dret = dstates + (size_t)chunk * kFqiS, *ddisc = dret + pairs, *dfinal = ddisc + pairs, *drec = dfinal + pairs * kFqiS;
-  int64_t *dmties = (int64_t *)(drec + pairs * (rec_elem / sizeof(double))), *dagree = dmties + pairs;
-  int32_t *dsteps = (int32_t *)(dagree + pairs), *dterm = dsteps + pairs, *dties = dterm + pairs;
-  hipError_t err = hipSuccess;
-  for (int s0 = 0; s0 < n_starts && err == hipSuccess; s0 += chunk)
-  {
-    const int nc = n_starts - s0 < chunk ? n_starts - s0 : chunk;
-    err = hipMemcpy(dstates, states + (size_t)s0 * kFqiS, sizeof(double) * kFqiS * (size_t)nc, hipMemcpyHostToDevice);
-    if (err != hipSuccess) break;
-    FqiEnsArgs A;
-    A.first_replica = first_replica; A.group_size = group_size; A.rule = rule; A.n_starts = nc; A.max_steps = max_steps; A.states = dstates;
-    A.ret = dret; A.disc = ddisc; A.steps = dsteps; A.terminal = dterm; A.ties = dties; A.member_ties = dmties; A.agreement = dagree;
-    A.final_state = dfinal; A.records = out.records ? drec : nullptr;
-    const dim3 grid((unsigned)((nc + 63) / 64), (unsigned)groups), block(64);
-    if (out.records) { FQI_FOR_H(ctx->F.H, hipLaunchKernelGGL((fqi_evaluate_ensemble_kernel<HH, true>), grid, block, 0, nullptr, ctx->F, A)); }
-    else { FQI_FOR_H(ctx->F.H, hipLaunchKernelGGL((fqi_evaluate_ensemble_kernel<HH, false>), grid, block, 0, nullptr, ctx->F, A)); }
-    err = hipGetLastError();
-    // device [group][nc] -> host [group][n_starts] at s0
-    const struct { void *host; const void *dev; size_t elem; } outs[9] = {
-        {out.ret, dret, sizeof(double)}, {out.disc, ddisc, sizeof(double)}, {out.steps, dsteps, sizeof(int32_t)}, {out.terminal, dterm, sizeof(int32_t)},
-        {out.ties, dties, sizeof(int32_t)}, {out.member_ties, dmties, sizeof(int64_t)}, {out.agreement, dagree, sizeof(int64_t)},
-        {out.final_state, dfinal, sizeof(double) * kFqiS}, {out.records, drec, rec_elem}};
-    for (int o = 0; o < 9 && err == hipSuccess; ++o)
-      if (outs[o].host)
-        err = hipMemcpy2D((char *)outs[o].host + (size_t)s0 * outs[o].elem, (size_t)n_starts * outs[o].elem, outs[o].dev, (size_t)nc * outs[o].elem,
-                          (size_t)nc * outs[o].elem, rows, hipMemcpyDeviceToHost);
-  }
-  if (err == hipSuccess) err = hipDeviceSynchronize();
-  (void)hipFree(dev);
-  if (err != hipSuccess) return ffail(GRLX_ERR_HIP, "%s failed: %s", who, hipGetErrorString(err));
-  return GRLX_OK;
-}
-
-} // namespace
-
-extern "C" {
-
-int grlx_fqi_query_ensemble(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, int group_size, const double *obs, int n_obs, double *out)
-{
-  const char *who = "grlx_fqi_query_ensemble";
-  if (!ctx) return ffail(GRLX_ERR_INVALID, "%s: ctx is null", who);
-  if (!out) return ffail(GRLX_ERR_INVALID, "%s: out is null", who);
-  if (!obs) return ffail(GRLX_ERR_INVALID, "%s: obs is null", who);
-  if (n_obs < 0) return ffail(GRLX_ERR_INVALID, "%s: n_obs = %d", who, n_obs);
-  if (first_replica < 0 || n_replicas < 0 || (int64_t)first_replica + n_replicas > ctx->F.R)
-    return ffail(GRLX_ERR_INVALID, "%s: replica range [%d, %lld) is outside the context's %d replicas", who, first_replica,
-                 (long long)first_replica + n_replicas, ctx->F.R);
-  for (int o = 0; o < n_obs; ++o)
-    for (int d = 0; d < kFqiD; ++d)
-      if (!std::isfinite(obs[(size_t)o * kFqiD + d]))
-        return ffail(GRLX_ERR_INVALID, "%s: observation row %d, dimension %d is not finite", who, o, d);
-  int rc = fqi_ensemble_admit(who, n_replicas, group_size);
-  if (rc != GRLX_OK) return rc;
-  if (n_obs == 0 || n_replicas == 0) return GRLX_OK;
-  FQI_TRY(hipDeviceSynchronize());
-  const int groups = n_replicas / group_size;
-  const size_t cols = 2 + 2 * (size_t)ctx->F.A;
-  const uint64_t per_obs = sizeof(double) * kFqiD + sizeof(double) * cols * (uint64_t)groups;
-  const uint64_t fit = g_fqi_query_chunk_bytes / per_obs;
-  const int chunk = (int)(fit < 1 ? 1 : fit > (uint64_t)n_obs ? (uint64_t)n_obs : fit);
-  double *dobs = nullptr;
-  if (hipMalloc((void **)&dobs, sizeof(double) * (kFqiD + cols * (size_t)groups) * (size_t)chunk) != hipSuccess)
-  {
-    (void)hipGetLastError();
-    return ffail(GRLX_ERR_OOM, "%s: out of device memory", who);
-  }
-  double *dout = dobs + (size_t)kFqiD * (size_t)chunk;
-  hipError_t err = hipSuccess;
-  for (int o0 = 0; o0 < n_obs && err == hipSuccess; o0 += chunk)
-  {
-    const int nc = n_obs - o0 < chunk ? n_obs - o0 : chunk;
-    err = hipMemcpy(dobs, obs + (size_t)o0 * kFqiD, sizeof(double) * kFqiD * (size_t)nc, hipMemcpyHostToDevice);
-    if (err != hipSuccess) break;
-    const dim3 grid((unsigned)((nc + 63) / 64), (unsigned)groups), block(64);
-    FQI_FOR_H(ctx->F.H, hipLaunchKernelGGL(fqi_query_ensemble_kernel<HH>, grid, block, 0, nullptr, ctx->F, first_replica, group_size, dobs, nc, dout));
-    err = hipGetLastError();
-    if (err != hipSuccess) break;
-    const size_t elem = sizeof(double) * cols;                            // device [group][nc][cols] -> host [group][n_obs][cols] at o0
-    err = hipMemcpy2D((char *)out + (size_t)o0 * elem, (size_t)n_obs * elem, dout, (size_t)nc * elem, (size_t)nc * elem, (size_t)groups,
-                      hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(dobs);
-  if (err != hipSuccess) return ffail(GRLX_ERR_HIP, "%s failed: %s", who, hipGetErrorString(err));
-  return GRLX_OK;
-}
-
-int grlx_fqi_evaluate_ensemble(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule, const double *states, int n_starts,
-                               int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, int64_t *member_ties,
-                               int64_t *agreement, double *final_state)
-{
-  const char *who = "grlx_fqi_evaluate_ensemble";
-  int rc = fqi_evaluate_ensemble_admit(ctx, who, first_replica, n_replicas, group_size, rule, states, n_starts, max_steps);
-  if (rc != GRLX_OK) return rc;
-  if (max_steps == 0) max_steps = GRLX_MAX_EPISODE_STEPS;
-  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
-  const int groups = n_replicas / group_size;
-  const FqiEnsOut out = {ret, disc, steps, terminal, ties, member_ties, agreement, final_state, nullptr};
-  return fqi_ensemble_run(ctx, who, first_replica, groups, group_size, rule, states, n_starts, max_steps, fqi_ensemble_sums_bytes(groups), out);
-}
-
-int grlx_fqi_ensemble_trajectory_record_words(grlx_fqi_ctx *ctx)
-{
-  if (!ctx) return ffail(GRLX_ERR_INVALID, "grlx_fqi_ensemble_trajectory_record_words: ctx is null");
-  return kFqiEnsTrajWords;
-}
-
-int grlx_fqi_evaluate_ensemble_trajectory(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule, const double *states, int n_starts,
-                                          int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
-                                          int64_t *member_ties, int64_t *agreement, double *final_state, double *records)
-{
-  const char *who = "grlx_fqi_evaluate_ensemble_trajectory";
-  int rc = fqi_evaluate_ensemble_admit(ctx, who, first_replica, n_replicas, group_size, rule, states, n_starts, max_steps);
-  if (rc != GRLX_OK) return rc;
-  if (!records) return ffail(GRLX_ERR_INVALID, "%s: records is null (for the sums alone call grlx_fqi_evaluate_ensemble)", who);
-  if (max_steps == 0)
-    return ffail(GRLX_ERR_INVALID, "%s: max_steps = 0: the records are sized by max_steps, so there is no default here (1 ... GRLX_MAX_EPISODE_STEPS = %d)", who,
-                 GRLX_MAX_EPISODE_STEPS);
-  // a chunk with records never exceeds the bound: a column that does not fit is refused instead of staged as "at least one"
-  const int groups = n_replicas / group_size;
-  const uint64_t column = (uint64_t)groups * (uint64_t)max_steps * (uint64_t)kFqiEnsTrajWords * sizeof(double);
-  const uint64_t per_start = column + fqi_ensemble_sums_bytes(groups);
-  if (per_start > g_fqi_query_chunk_bytes)
-    return ffail(GRLX_ERR_INVALID, "%s: one start state's column of records is %llu bytes (%d groups x %d steps x %d words x 8; %llu with its sums) and exceeds "
-                 "the staging bound of %llu bytes: ask for fewer replicas per call, a smaller max_steps, or raise the bound with grlx_set_query_chunk_bytes", who,
-                 (unsigned long long)column, groups, max_steps, kFqiEnsTrajWords, (unsigned long long)per_start, (unsigned long long)g_fqi_query_chunk_bytes);
-  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
-  const FqiEnsOut out = {ret, disc, steps, terminal, ties, member_ties, agreement, final_state, records};
-  return fqi_ensemble_run(ctx, who, first_replica, groups, group_size, rule, states, n_starts, max_steps, per_start, out);
-}
-
-} // extern "C"

@@ -23,8 +23,6 @@ using namespace grlx;
 
 namespace grlx {
 int fail(int code, const char *fmt, ...);                  // sets the thread's message (grlx_last_error), returns `code`
-void set_last_error(const char *msg);                      // other translation units of the library (grlx_fqi.hip)
-void set_fqi_query_chunk_bytes(uint64_t bytes);            // grlx_fqi.hip: the staging bound of grlx_fqi_query
 bool have_device();
 static_assert(sizeof(Entry) == kRuleEntryBytes && 16 * kMaxTrace * 2 == kRuleTraceWords, "grlx_host_rules.h: kRuleEntryBytes, kRuleTraceWords");
 }

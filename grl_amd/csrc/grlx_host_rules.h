@@ -79,6 +79,22 @@ inline int quant_admit_rows(const double *in, int n, int dims, const double *sca
   return 0;
 }
 
+// ---- chunked reads: the columns (observations or start states) of a call go through the device a chunk at a time
+// Columns per chunk so that a chunk's device arrays stay within `bound`: the floor of the quotient, at most n, and at least one -- a
+// column larger than the bound is staged alone.
+inline int query_chunk(uint64_t bound, int n, size_t bytes_per_column)
+{
+  const uint64_t fit = bound / (bytes_per_column ? bytes_per_column : 1);
+  return (int)(fit < 1 ? 1 : fit > (uint64_t)n ? (uint64_t)n : fit);
+}
+
+// The bytes one start state of an evaluation call stages besides its records: its state in (S doubles) and, for each of `rows` replicas
+// or groups, ret, disc, the final state (S doubles), steps, terminal, ties (int32) and `extra` bytes of the variant's own.
+inline uint64_t episode_start_bytes(int S, int rows, size_t extra)
+{
+  return (uint64_t)S * 8u + (2u * 8u + 3u * 4u + (uint64_t)S * 8u + extra) * (uint64_t)rows;
+}
+
 // ---- streamed trajectories (grlx_evaluate_trajectory_stream): what one chunk stages, and how many start states a chunk holds
 // The bytes one start state puts on the device, and the part of them that comes back: its state in (S doubles) and, for each of `rows`
 // replicas, max_steps records of R doubles, ret, disc, the final state (S doubles) and steps, terminal, ties (int32).  The same count

@@ -13,6 +13,7 @@ episode without a tie, an episode with ties -- is asserted on the reference's ou
 No domain-exit case: the pendulum's damping keeps the angle inside Env::in_domain from every admitted state (DESIGN.md section 7)."""
 import ctypes as C
 import math
+import os
 
 import numpy as np
 import pytest
@@ -204,6 +205,15 @@ def test_chunked_staging(grlx):
         got = r.evaluate(states)
         for k in fr.FIELDS:
             same_bits(getattr(got, k), getattr(whole, k), f"chunked evaluate: {k}")
+        # the batch path's reads are neither poisoned nor counted by grlx_read_kernel_timing: four chunks, none of them in the sum
+        assert "GRLX_POISON_REGISTERS" not in os.environ
+        ms, chunks = C.c_double(-1.0), C.c_int(-1)
+        lib.grlx_read_kernel_timing(1, None, None)
+        try:
+            r.evaluate(states)
+        finally:
+            lib.grlx_read_kernel_timing(0, C.byref(ms), C.byref(chunks))
+        assert chunks.value == 0 and ms.value == 0.0, (chunks.value, ms.value)
         lib.grlx_set_query_chunk_bytes(2 * (column + sums) + sums)
         got = r.evaluate_trajectory(states, FULL)
         for k in fr.FIELDS + ("records",):

@@ -538,6 +538,14 @@ def test_batch_path_query(grlx, hidden):
     try:
         lib.grlx_set_query_chunk_bytes(4 * (16 + 8 * len(acts) * len(seeds)))
         same_bits(r.query(obs), want, "chunked staging")
+        if hidden == 8:
+            # a ragged last chunk: 5 observations two at a time on 2 replicas' initial networks, against the one-chunk result
+            fresh = grlx.FqiRunner(grlx.pendulum_fqi_config(2, max_batches=1, hidden=8), [1, 2])
+            lib.grlx_set_query_chunk_bytes(0)
+            one_chunk = fresh.query(obs[:5])
+            lib.grlx_set_query_chunk_bytes(2 * (16 + 8 * len(acts) * 2) + 8)
+            same_bits(fresh.query(obs[:5]), one_chunk, "chunks of 2, 2 and 1 observations")
+            fresh.close()
     finally:
         lib.grlx_set_query_chunk_bytes(0)
     bad = obs.copy(); bad[2, 1] = np.inf

@@ -121,8 +121,28 @@ static void check_quant()
   printf("quant_admits: %ld bounds\n", cases);
 }
 
+static void check_staging()
+{ // the figures the episode tests compute for themselves: a start state's staged bytes without records
+  CHECK(episode_start_bytes(3, 2, 0) == 8 * 3 + (2 * 8 + 3 * 4 + 8 * 3) * 2, "plain, S = 3, 2 rows: %llu", (unsigned long long)episode_start_bytes(3, 2, 0));
+  CHECK(episode_start_bytes(3, 2, 16) == 8 * 3 + (2 * 8 + 3 * 4 + 2 * 8 + 8 * 3) * 2, "ensemble, S = 3, 2 groups, 16 bytes of its own: %llu",
+        (unsigned long long)episode_start_bytes(3, 2, 16));
+  CHECK(episode_start_bytes(4, 0, 16) == 8 * 4, "no rows: the state alone");
+  CHECK(episode_start_bytes(6, 65536, 40) == 48ull + 116ull * 65536ull, "65536 rows");
+  // a chunk: one column for a bound below a column, n for a bound above n columns, the floor in between
+  const int n = 7;
+  const size_t column = 128;
+  CHECK(query_chunk(column - 1, n, column) == 1 && query_chunk(0, n, column) == 1, "a bound below one column stages one");
+  CHECK(query_chunk(n * column, n, column) == n && query_chunk(n * column + 1, n, column) == n && query_chunk(1ull << 62, n, column) == n, "a bound above n columns stages n");
+  for (int k = 1; k < n; ++k)
+    for (uint64_t over : {(uint64_t)0, (uint64_t)1, (uint64_t)column - 1})
+      CHECK(query_chunk(k * column + over, n, column) == k, "bound %llu: %d columns, not %d", (unsigned long long)(k * column + over), query_chunk(k * column + over, n, column), k);
+  CHECK(query_chunk(1000, n, 0) == n, "a column of no bytes");
+  printf("staging: episode_start_bytes, query_chunk\n");
+}
+
 int main()
 {
+  check_staging();
   check_quant();
   check_growth();
   check_draws();
