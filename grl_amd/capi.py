@@ -180,6 +180,14 @@ _SIGS = {
     "grlx_evaluate_actor_ensemble_trajectory": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _P(C.c_double), C.c_int,
                                                           C.c_int, _P(C.c_double), _P(C.c_double), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32),
                                                           _P(C.c_int64), _P(C.c_double), _P(C.c_double), _P(C.c_double)]),
+    "grlx_evaluate_ensemble_sampled": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _P(C.c_double), C.c_int,
+                                                 C.c_int, _P(C.c_uint64), _P(C.c_double), _P(C.c_double), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32),
+                                                 _P(C.c_int64), _P(C.c_int64), _P(C.c_int32), _P(C.c_double), _P(C.c_uint64)]),
+    "grlx_ensemble_sampled_trajectory_record_words": (C.c_int, [C.c_void_p]),
+    "grlx_evaluate_ensemble_sampled_trajectory": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _P(C.c_double),
+                                                            C.c_int, C.c_int, _P(C.c_uint64), _P(C.c_double), _P(C.c_double), _P(C.c_int32), _P(C.c_int32),
+                                                            _P(C.c_int32), _P(C.c_int64), _P(C.c_int64), _P(C.c_int32), _P(C.c_double), _P(C.c_uint64),
+                                                            _P(C.c_double)]),
     "grlx_math": (C.c_int, [C.c_int, _P(C.c_double), _P(C.c_double), C.c_int, _P(C.c_double)]),
     "grlx_rand48_at": (C.c_int, [C.c_int64, _P(C.c_uint64), C.c_int, _P(C.c_double)]),
     "grlx_fqi_config_pendulum": (None, [_P(FqiConfig)]),
@@ -231,7 +239,8 @@ _NEWER_SIGS = ("grlx_snapshot_size", "grlx_snapshot_save", "grlx_snapshot_load",
                "grlx_evaluate_sampled", "grlx_sampled_trajectory_record_words", "grlx_evaluate_sampled_trajectory", "grlx_episode_streams",
                "grlx_evaluate_noisy", "grlx_noisy_trajectory_record_words", "grlx_evaluate_noisy_trajectory", "grlx_episode_stream_words",
                "grlx_evaluate_trajectory_stream",
-               "grlx_evaluate_actor_ensemble", "grlx_actor_ensemble_trajectory_record_words", "grlx_evaluate_actor_ensemble_trajectory")
+               "grlx_evaluate_actor_ensemble", "grlx_actor_ensemble_trajectory_record_words", "grlx_evaluate_actor_ensemble_trajectory",
+               "grlx_evaluate_ensemble_sampled", "grlx_ensemble_sampled_trajectory_record_words", "grlx_evaluate_ensemble_sampled_trajectory")
 # grlx_kernel_plan flags
 PLAN_STAMPS_IN_PLACE, PLAN_STAMPS_DEFERRED, PLAN_SWEEP, PLAN_SERVER_OFF, PLAN_WALKER_SERVER, PLAN_FITS_YES, PLAN_FITS_NO = 1, 2, 4, 8, 16, 32, 64
 ENSEMBLE_VOTE, ENSEMBLE_MEAN_Q = 0, 1       # grlx_evaluate_ensemble's rule
@@ -243,6 +252,9 @@ EPSILON_OWN = -1.0                                 # ... and its epsilon that me
 SIGMA_OWN, THETA_OWN = -1.0, -1.0                  # grlx_evaluate_noisy: ac_decay * sigma of the replica, the configuration's theta
 # grlx_evaluate_actor_ensemble's rule and the largest group it serves (GRLX_ACTOR_ENSEMBLE_*)
 ACTOR_ENSEMBLE_MEAN, ACTOR_ENSEMBLE_BINNING, ACTOR_ENSEMBLE_DATA_CENTER, ACTOR_ENSEMBLE_DENSITY, ACTOR_ENSEMBLE_MAX = 0, 1, 2, 3, 256
+# grlx_evaluate_ensemble_sampled's strategy and its members' sampler (GRLX_ENSEMBLE_MAJORITY / _RANK, GRLX_MEMBER_*)
+ENSEMBLE_MAJORITY, ENSEMBLE_RANK = 0, 1
+MEMBER_GREEDY, MEMBER_EPSILON, MEMBER_SOFTMAX = 0, 1, 2
 ABI_VERSION = 2        # include/grlx.h: GRLX_ABI_VERSION
 
 

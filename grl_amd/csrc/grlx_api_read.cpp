@@ -1,4 +1,4 @@
-// grlx_api_read.cpp -- the C ABI declared in include/grlx.h: the read side -- policy queries, greedy, sampled, noisy and actor-ensemble evaluation episodes, chunked over the caller's observations / start states; the streamed trajectories' two-slot pipeline.
+// grlx_api_read.cpp -- the C ABI declared in include/grlx.h: the read side -- policy queries, greedy, sampled, noisy, actor-ensemble and sampled-ensemble evaluation episodes, chunked over the caller's observations / start states; the streamed trajectories' two-slot pipeline.
 #include "grlx_host.h"
 #include "grlx_read.h"
 #include "grlx_query.h"
@@ -6,6 +6,7 @@
 #include "grlx_evaluate_sampled.h"
 #include "grlx_evaluate_noisy.h"
 #include "grlx_evaluate_actor_ensemble.h"
+#include "grlx_evaluate_ensemble_sampled.h"
 #include "grlx_evaluate_stream.h"
 
 // ------------------------------------------------------------------------------------------- policy queries ---
@@ -166,9 +167,45 @@ int actor_ensemble_admit(grlx_ctx *ctx, const char *who, int n_replicas, int gro
   return GRLX_OK;
 }
 
+// ---- sampled ensemble episodes: the draw from the majority and rank votes (grlx_evaluate_ensemble_sampled.hip) ---------------------------------
+// what both calls check beyond evaluate_admit: grlx_evaluate_ensemble's group checks, then the strategy, the samplers and the streams
+int ensemble_sampled_admit(grlx_ctx *ctx, const char *who, int n_replicas, int group_size, int n_starts, int strategy, double tau, int member,
+                           double member_param, const uint64_t *streams)
+{
+  if (!q_agent(ctx->cfg.agent))
+    return fail(GRLX_ERR_INVALID, "%s is not built for the actor-critic agent (grlx_evaluate_actor_ensemble combines its continuous actions, and such a "
+                "context has no epsilon-greedy exploration for GRLX_EPSILON_OWN to read); it serves agents with a policy/discrete/q", who);
+  if (int rc = group_size_ok(who, group_size)) return rc;
+  if (n_replicas % group_size != 0) return fail(GRLX_ERR_INVALID, "%s: group_size %d does not divide the %d replicas", who, group_size, n_replicas);
+  if (strategy != GRLX_ENSEMBLE_MAJORITY && strategy != GRLX_ENSEMBLE_RANK)
+    return fail(GRLX_ERR_INVALID, "%s: unknown strategy %d (GRLX_ENSEMBLE_MAJORITY = 0, GRLX_ENSEMBLE_RANK = 1)", who, strategy);
+  if (!std::isfinite(tau) || !(tau > 0.)) return fail(GRLX_ERR_INVALID, "%s: tau = %g is not a finite temperature above 0", who, tau);
+  switch (member)
+  {
+    case GRLX_MEMBER_GREEDY: break;
+    case GRLX_MEMBER_EPSILON:
+      if (!std::isfinite(member_param)) return fail(GRLX_ERR_INVALID, "%s: epsilon is not finite (%g) (GRLX_MEMBER_EPSILON)", who, member_param);
+      if (member_param != GRLX_EPSILON_OWN && !(member_param >= 0. && member_param <= 1.))
+        return fail(GRLX_ERR_INVALID, "%s: epsilon = %g is outside [0, 1] and is not GRLX_EPSILON_OWN (-1) (GRLX_MEMBER_EPSILON)", who, member_param);
+      break;
+    case GRLX_MEMBER_SOFTMAX:
+      if (!std::isfinite(member_param) || !(member_param > 0.))
+        return fail(GRLX_ERR_INVALID, "%s: tau_m = %g is not a finite temperature above 0 (GRLX_MEMBER_SOFTMAX)", who, member_param);
+      break;
+    default:
+      return fail(GRLX_ERR_INVALID, "%s: unknown member sampler %d (GRLX_MEMBER_GREEDY = 0, GRLX_MEMBER_EPSILON = 1, GRLX_MEMBER_SOFTMAX = 2)", who, member);
+  }
+  if (streams)
+    for (int64_t row = 0; row < (int64_t)(n_replicas / group_size) * n_starts; ++row)
+      if (streams[row] >> 48)
+        return fail(GRLX_ERR_INVALID, "%s: stream row %lld (group %lld, start state %lld) is 0x%llx: a rand48 state is below 2^48", who, (long long)row,
+                    (long long)(row / n_starts), (long long)(row % n_starts), (unsigned long long)streams[row]);
+  return GRLX_OK;
+}
+
 // ---- one description of an episode call: what the evaluation entry points share around their launch -----------------------------------------
 // Every variant has the six base outputs -- ret, disc, steps, terminal, ties (the noisy variant: clipped) and final_state -- for `rows`
-// replicas or groups, up to two outputs of its own, and, as a trajectory, the records.  An entry point fills this in and keeps its admit
+// replicas or groups, up to four outputs of its own, and, as a trajectory, the records.  An entry point fills this in and keeps its admit
 // and its launch.
 struct EpisodeCall {
   const char   *who;
@@ -179,7 +216,7 @@ struct EpisodeCall {
   double       *ret, *disc;
   int32_t      *steps, *terminal, *ties;
   double       *final_state;
-  ReadOut       extra[2];                   // the variant's own outputs: host and elem; the rows are filled in here
+  ReadOut       extra[4];                   // the variant's own outputs: host and elem; the rows are filled in here
   int           n_extra;
   size_t        extra_bytes;                // per pair, what the variant stages beyond the six outputs: part of what cuts the chunks
   ReadIn       *in;                         // the variant's second input, or null
@@ -687,6 +724,60 @@ int grlx_evaluate_actor_ensemble_trajectory(grlx_ctx *ctx, int first_replica, in
 {
   return evaluate_actor_ensemble_impl(ctx, "grlx_evaluate_actor_ensemble_trajectory", "grlx_evaluate_actor_ensemble", first_replica, n_replicas, group_size,
                                       rule, bins, r, states, n_starts, max_steps, ret, disc, steps, terminal, ties, kept, spread, final_state, records);
+}
+
+// ---- sampled ensemble episodes (grlx_evaluate_ensemble_sampled.hip); sibling null: the sums alone
+static int evaluate_ensemble_sampled_impl(grlx_ctx *ctx, const char *who, const char *sibling, int first_replica, int n_replicas, int group_size, int strategy,
+                                          double tau, int member, double member_param, const double *states, int n_starts, int max_steps,
+                                          const uint64_t *streams, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                                          int64_t *member_ties, int64_t *agreement, int32_t *explored, double *final_state, uint64_t *streams_out,
+                                          double *records)
+{
+  ReadIn in_streams = {streams, sizeof(uint64_t), group_size > 0 ? n_replicas / group_size : 0, nullptr};     // [group][start]: a chunk is strided
+  EpisodeCall c{who, first_replica, n_replicas, group_size, states, n_starts, max_steps, ret, disc, steps, terminal, ties, final_state};
+  c.extra[0] = {member_ties, sizeof(int64_t)}; c.extra[1] = {agreement, sizeof(int64_t)};
+  c.extra[2] = {explored, sizeof(int32_t)}; c.extra[3] = {streams_out, sizeof(uint64_t)}; c.n_extra = 4;
+  c.extra_bytes = 2 * sizeof(int64_t) + sizeof(int32_t) + 2 * sizeof(uint64_t);     // the ensemble's two, explored, the stream in and out
+  c.in = &in_streams;
+  c.sibling = sibling; c.records = records; c.record_words = ensemble_sampled_trajectory_words;
+  return episode_read<EnsembleArgs>(ctx, c, [&] { return ensemble_sampled_admit(ctx, who, n_replicas, group_size, n_starts, strategy, tau, member, member_param, streams); },
+                                    [&](EnsembleArgs &A, const DevPtr *extra, double *rec) {
+    A.group_size = group_size; A.rule = strategy;
+    A.member_ties = extra[0].as<int64_t>(); A.agreement = extra[1].as<int64_t>();
+    EnsembleSampledArgs T;
+    T.e = A; T.tau = tau; T.member = member; T.member_param = member_param;
+    T.streams = (uint64_t *)in_streams.dev;
+    T.explored = extra[2].as<int32_t>(); T.streams_out = extra[3].as<uint64_t>();
+    T.records = rec;
+    return rec ? launch_trajectory_ensemble_sampled(ctx->P, T, nullptr) : launch_evaluate_ensemble_sampled(ctx->P, T, nullptr);
+  });
+}
+
+int grlx_evaluate_ensemble_sampled(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int strategy, double tau, int member, double member_param,
+                                   const double *states, int n_starts, int max_steps, const uint64_t *streams, double *ret, double *disc, int32_t *steps,
+                                   int32_t *terminal, int32_t *ties, int64_t *member_ties, int64_t *agreement, int32_t *explored, double *final_state,
+                                   uint64_t *streams_out)
+{
+  return evaluate_ensemble_sampled_impl(ctx, "grlx_evaluate_ensemble_sampled", nullptr, first_replica, n_replicas, group_size, strategy, tau, member,
+                                        member_param, states, n_starts, max_steps, streams, ret, disc, steps, terminal, ties, member_ties, agreement, explored,
+                                        final_state, streams_out, nullptr);
+}
+
+int grlx_ensemble_sampled_trajectory_record_words(grlx_ctx *ctx)
+{
+  if (int rc = record_words_admit(ctx, "grlx_ensemble_sampled_trajectory_record_words", is_ac, "the sampled ensemble is not built for the actor-critic agent"))
+    return rc;
+  return ensemble_sampled_trajectory_words(ctx->cfg.env);
+}
+
+int grlx_evaluate_ensemble_sampled_trajectory(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int strategy, double tau, int member,
+                                              double member_param, const double *states, int n_starts, int max_steps, const uint64_t *streams, double *ret,
+                                              double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, int64_t *member_ties, int64_t *agreement,
+                                              int32_t *explored, double *final_state, uint64_t *streams_out, double *records)
+{
+  return evaluate_ensemble_sampled_impl(ctx, "grlx_evaluate_ensemble_sampled_trajectory", "grlx_evaluate_ensemble_sampled", first_replica, n_replicas,
+                                        group_size, strategy, tau, member, member_param, states, n_starts, max_steps, streams, ret, disc, steps, terminal,
+                                        ties, member_ties, agreement, explored, final_state, streams_out, records);
 }
 
 // host only: stream k = srand48(seed) advanced by k * 2^20 draws, k = 2 * pair + which

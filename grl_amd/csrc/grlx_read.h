@@ -48,7 +48,7 @@ struct ReadTimer {
 // One output of a chunked read: `rows` rows of `elem` bytes per column, copied to `host` when that is not null; `on_device`: the kernels
 // write it (or a reduction reads it) whether the caller asked for it or not.
 struct ReadOut { void *host; size_t elem; int rows; bool on_device; };
-constexpr int kMaxReadOuts = 9;
+constexpr int kMaxReadOuts = 11;
 // A second per-column input of a chunked read, laid out like an output: host [rows][cols] of `elem` bytes -> `dev` [rows][chunk], so that
 // a chunk's rows begin at its first column for EVERY row (a strided copy, not a contiguous one).  host null: nothing is staged.  `dev`:
 // where the skeleton put it, for the launch to read.

@@ -126,6 +126,9 @@ _NOISY_FIELDS = "ret disc steps terminal clipped final_state streams noise"
 _ACTOR_ENSEMBLE_FIELDS = "ret disc steps terminal ties kept spread final_state"
 _ACTOR_RULES = {"mean": capi.ACTOR_ENSEMBLE_MEAN, "binning": capi.ACTOR_ENSEMBLE_BINNING, "data_center": capi.ACTOR_ENSEMBLE_DATA_CENTER,
                 "density": capi.ACTOR_ENSEMBLE_DENSITY}
+_SAMPLED_ENSEMBLE_FIELDS = "ret disc steps terminal ties member_ties agreement explored final_state streams"
+_STRATEGIES = {"majority": capi.ENSEMBLE_MAJORITY, "rank": capi.ENSEMBLE_RANK}
+_MEMBERS = {"greedy": capi.MEMBER_GREEDY, "epsilon": capi.MEMBER_EPSILON, "softmax": capi.MEMBER_SOFTMAX}
 _BASE_OUTPUTS = {"ret": np.float64, "disc": np.float64, "steps": np.int32, "terminal": np.int32, "ties": np.int32}
 _CTYPES = {np.float64: C.c_double, np.int32: C.c_int32, np.int64: C.c_int64, np.uint64: C.c_uint64}
 
@@ -853,8 +856,70 @@ class Runner:
                                                                     max_steps, *ptrs))
         return ActorEnsembleTrajectory(*out)
 
+    # ---- sampled ensemble episodes: the draw from the majority and rank votes (grlx_evaluate_ensemble_sampled)
+    def _ensemble_sampled_args(self, states, group_size, strategy, tau, member, member_param, streams, replicas):
+        if isinstance(strategy, str):
+            if strategy not in _STRATEGIES:
+                raise ValueError(f"strategy {strategy!r}: one of {sorted(_STRATEGIES)}")
+            strategy = _STRATEGIES[strategy]
+        if isinstance(member, str):
+            if member not in _MEMBERS:
+                raise ValueError(f"member {member!r}: one of {sorted(_MEMBERS)}")
+            member = _MEMBERS[member]
+        if member_param is None:         # the reference's defaults: no epsilon is configured there, the members' own stands in; softmax tau 1
+            member_param = {capi.MEMBER_EPSILON: capi.EPSILON_OWN, capi.MEMBER_SOFTMAX: 1.0}.get(int(member), 0.0)
+        elif isinstance(member_param, str):
+            if member_param != "own":
+                raise ValueError('member_param: a number or "own"')
+            member_param = capi.EPSILON_OWN
+        states = _state_rows(states, self.state_dims)
+        first, count = self._replica_range(replicas)
+        group_size = int(group_size)
+        groups = count // group_size if group_size > 0 else 0
+        n = states.shape[0]
+        if streams is not None:
+            streams = np.ascontiguousarray(streams, dtype=np.uint64)
+            if streams.shape != (groups, n):
+                raise ValueError(f"expected streams of shape ({groups}, {n}), got {streams.shape}")
+        head = (self._ctx, first, count, group_size, int(strategy), float(tau), int(member), float(member_param), _ptr(states, C.c_double), n)
+        return head, None if streams is None else _ptr(streams, C.c_uint64), groups, n, (states, streams)
 
-Evaluation = collections.namedtuple("Evaluation", "ret disc steps terminal ties final_state")
+    def evaluate_ensemble_sampled(self, states, group_size, strategy="majority", tau=0.1, member="greedy", member_param=None, streams=None, replicas=None,
+                                  max_steps=0):
+        """Runner.evaluate_ensemble's episodes acted as the reference's ensemble policy acts: at every step the action is DRAWN from
+        softmax(score / tau), the score being the members' votes (strategy "majority") or their summed ranks ("rank").  member: the
+        members' distribution, "greedy", "epsilon" (member_param: e in [0, 1] or "own", the default) or "softmax" (member_param: its
+        temperature, default 1).  streams[group][start]: the rand48 state every episode draws from, one draw per step; None = a copy of
+        the global stream of the group's first replica (see episode_stream_words).  SampledEnsembleEvaluation(ret, disc, steps, terminal,
+        ties, member_ties, agreement, explored, final_state, streams), each [group][start]: ties = steps at which the score's maximum was
+        not unique, agreement = member-steps whose vote was the action drawn, explored = steps at which the draw left the score's first
+        maximum, streams = the states after the last step.  The context is not changed (include/grlx.h: grlx_evaluate_ensemble_sampled)."""
+        head, streams, groups, n, _keep = self._ensemble_sampled_args(states, group_size, strategy, tau, member, member_param, streams, replicas)
+        out, ptrs = _episode_outputs(groups, n, self.state_dims, _SAMPLED_ENSEMBLE_FIELDS, member_ties=np.int64, agreement=np.int64, explored=np.int32,
+                                     streams=np.uint64)
+        capi.check(self.lib.grlx_evaluate_ensemble_sampled(*head, int(max_steps), streams, *ptrs))
+        return SampledEnsembleEvaluation(*out)
+
+    def ensemble_sampled_trajectory_record_words(self):
+        """R of evaluate_ensemble_sampled_trajectory's records: trajectory_record_words(True) + 2 (grlx_ensemble_sampled_trajectory_record_words)"""
+        return capi.check(self.lib.grlx_ensemble_sampled_trajectory_record_words(self._ctx))
+
+    def evaluate_ensemble_sampled_trajectory(self, states, group_size, max_steps, strategy="majority", tau=0.1, member="greedy", member_param=None,
+                                             streams=None, replicas=None):
+        """Runner.evaluate_ensemble_sampled with every step of every episode: SampledEnsembleTrajectory(..., records),
+        records[group][start][max_steps][R] with EnsembleTrajectory's views -- .action_index the index drawn, .value its score, .n_max the
+        maxima of the score, .step_agreement the votes for the action drawn -- and .explored (1.0 where the draw left the score's first
+        maximum) and .prob (the combined distribution's entry for the action drawn); the per-episode count is the field n_explored
+        (include/grlx.h: grlx_evaluate_ensemble_sampled_trajectory)."""
+        head, streams, groups, n, _keep = self._ensemble_sampled_args(states, group_size, strategy, tau, member, member_param, streams, replicas)
+        max_steps = int(max_steps)
+        out, ptrs = _episode_outputs(groups, n, self.state_dims, _SAMPLED_ENSEMBLE_FIELDS, member_ties=np.int64, agreement=np.int64, explored=np.int32,
+                                     streams=np.uint64, records=(max_steps, self.ensemble_sampled_trajectory_record_words()))
+        capi.check(self.lib.grlx_evaluate_ensemble_sampled_trajectory(*head, max_steps, streams, *ptrs))
+        return SampledEnsembleTrajectory(*out)
+
+
+Evaluation =collections.namedtuple("Evaluation", "ret disc steps terminal ties final_state")
 EnsembleEvaluation = collections.namedtuple("EnsembleEvaluation", "ret disc steps terminal ties member_ties agreement final_state")
 
 
@@ -956,6 +1021,25 @@ class ActorEnsembleTrajectory(_RecordViews, collections.namedtuple("ActorEnsembl
     state = property(lambda self: self._cut(self.records.shape[-1] - 2 - self.final_state.shape[-1], self.records.shape[-1] - 2))
     kept = property(lambda self: self._cut(self.records.shape[-1] - 2))
     spread = property(lambda self: self._cut(self.records.shape[-1] - 1))
+
+
+SampledEnsembleEvaluation = collections.namedtuple("SampledEnsembleEvaluation", _SAMPLED_ENSEMBLE_FIELDS)
+
+
+class SampledEnsembleTrajectory(_RecordViews, collections.namedtuple("SampledEnsembleTrajectory",
+                                                                     "ret disc steps terminal ties member_ties agreement n_explored final_state streams records")):
+    """What Runner.evaluate_ensemble_sampled_trajectory returns: SampledEnsembleEvaluation's fields and records[group][start][max_steps][R]:
+    EnsembleTrajectory's record with two words more (after the model state), whether the step's draw left the score's first maximum and
+    the combined distribution's entry for the action drawn: the views .explored and .prob, per step.  The per-episode count that
+    SampledEnsembleEvaluation calls explored is the field n_explored here."""
+    __slots__ = ()
+    _OBS = capi.TRAJ_ENS_OBS
+    step_agreement = property(lambda self: self._cut(capi.TRAJ_ENS_AGREEMENT))
+    step_member_ties = property(lambda self: self._cut(capi.TRAJ_ENS_MEMBER_TIES))
+    obs = property(lambda self: self._cut(self._OBS, self.records.shape[-1] - 2 - self.final_state.shape[-1]))
+    state = property(lambda self: self._cut(self.records.shape[-1] - 2 - self.final_state.shape[-1], self.records.shape[-1] - 2))
+    explored = property(lambda self: self._cut(self.records.shape[-1] - 2))
+    prob = property(lambda self: self._cut(self.records.shape[-1] - 1))
 
 
 def episode_stream_words(seed: int, n_replicas: int, n_starts: int, first_pair: int = 0):

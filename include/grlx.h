@@ -501,8 +501,8 @@ int  grlx_evaluate(grlx_ctx *ctx, int first_replica, int n_replicas, const doubl
  * continuous actions is mapping/policy/multi's).  n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
  * The steps of these episodes: grlx_evaluate_ensemble_trajectory (below).
  * The batch path's: grlx_fqi_evaluate_ensemble (at the end of this file).
- * NOT BUILT: the reference's other discrete strategies (multiply, rank voting, density based), sampling from the combined
- * distribution. */
+ * The reference's own act -- the draw from softmax(votes / tau), and rank voting: grlx_evaluate_ensemble_sampled (below).
+ * NOT BUILT: the reference's other discrete strategies (add and multiply of the members' distributions, density based). */
 enum { GRLX_ENSEMBLE_VOTE = 0, GRLX_ENSEMBLE_MEAN_Q = 1 };
 int  grlx_evaluate_ensemble(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule,
                             const double *states /*[n_starts][state_dims]*/, int n_starts, int max_steps,
@@ -636,8 +636,8 @@ int  grlx_evaluate_trajectory_stream(grlx_ctx *ctx, int first_replica, int n_rep
  * grlx_evaluate refuses; an unknown sampler; epsilon that is not finite; epsilon outside [0, 1] that is not exactly GRLX_EPSILON_OWN;
  * a stream word >= 2^48 (row and word named); the actor-critic ("not built": its Gaussian / Ornstein-Uhlenbeck exploration needs the
  * policy's noise state, which grlx_evaluate_noisy below carries).  n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
- * NOT BUILT: a sampled ensemble (softmax(votes)), the tie-breaking draw of grlx_fqi_evaluate, the
- * decay at episode time 0. */
+ * A sampled ENSEMBLE, the draw from softmax(votes / tau): grlx_evaluate_ensemble_sampled (below).
+ * NOT BUILT: a softmax sampler for a single policy, the tie-breaking draw of grlx_fqi_evaluate, the decay at episode time 0. */
 enum { GRLX_SAMPLER_GREEDY = 0, GRLX_SAMPLER_EPSILON_GREEDY = 1 };
 #define GRLX_EPSILON_OWN (-1.0)
 int  grlx_evaluate_sampled(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][state_dims]*/, int n_starts,
@@ -774,6 +774,81 @@ int  grlx_evaluate_actor_ensemble_trajectory(grlx_ctx *ctx, int first_replica, i
                                              double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
                                              int64_t *kept, double *spread, double *final_state,
                                              double *records /*[n_replicas / group_size][n_starts][max_steps][R]*/);
+
+/* --- sampled ensemble episodes: the draw from the majority and rank votes ----------------------------------------------------------------
+ * Q agents.  grlx_evaluate_ensemble's episodes -- one per (group of group_size CONSECUTIVE replicas, start state), the members sharing ONE
+ * environment state; the grouping, the pair index group * n_starts + start, the ignored terminal code of the start state, the terminal
+ * codes 0 / 1 / 2 / 3, max_steps (0 = GRLX_MAX_EPISODE_STEPS), the 2^17 bound, ret, disc (the gamma of the group's FIRST replica) and
+ * final_state are that call's -- in which the action is DRAWN from the distribution the reference's ensemble policy builds, as
+ * DiscreteMultiPolicy::act does (multi_discrete.cpp:88-105), instead of taken at the first maximum of the votes.  What it answers: what
+ * the ensemble policy the reference would deploy does, what its temperature costs in return, how often the draw leaves the vote's maximum.
+ *   Stream.     Every episode carries ONE rand48 state in and out, streams[n_replicas / group_size][n_starts].  streams == NULL: every
+ *               episode of a group starts from a COPY of the global stream of the group's first replica as it stands (grlx_get_rng's
+ *               word 0); the context's own streams do not move.  streams_out receives the state after the episode's last step; it may
+ *               be NULL.  grlx_episode_stream_words (above) makes disjoint streams from one seed.  One drand48 per step taken, nothing else.
+ *   A step, exactly.  NA = action_steps.  Member m, in any order, reads q_m = grlx_query_q's Q-values of that replica at the observation.
+ *     Its distribution d_m over the NA actions follows `member`:
+ *       GRLX_MEMBER_GREEDY   (mai, man) = findmax(q_m); d[i] = 1 / man where q[i] == q[mai], else 0 (greedy.cpp:88-98).  member_param is
+ *                            ignored.
+ *       GRLX_MEMBER_EPSILON  the greedy d; then for i ascending: if d[i] == 1 then d[i] = 1 - e; d[i] += e / NA (greedy.cpp:229-236).  e is
+ *                            member_param in [0, 1], or with GRLX_EPSILON_OWN every member's own eps_decay * epsilon as it stands (in a
+ *                            sweep context that replica's own), read and never advanced, as grlx_evaluate_sampled reads it.
+ *       GRLX_MEMBER_SOFTMAX  softmax(q_m, tau_m), tau_m = member_param > 0 (softmax.cpp:65-110).
+ *     softmax(v, t): p_i = v_i / t; maxp = their maximum, taken ascending from -DBL_MAX with maxp < p ? p : maxp; minp = maxp + (-100);
+ *       center = (maxp + minp) / 2.0; for i ascending from sum = 0: if p_i > minp then e_i = pexp(p_i - center) and sum += e_i, otherwise
+ *       entry i is dropped; the result is e_i / sum for the entries kept and 0 for those dropped.  pexp is the portable exponential
+ *       (GRLX_MATH's, specified by the oracle's orc_pexp); its arguments here lie in (-50, 50].
+ *     vote_m: best = 0.0, idx = NA - 1; for j ascending, d_m[j] > best takes idx = j and best = d_m[j] (multi_discrete.cpp:218-229).
+ *       It is computed under both strategies, for `agreement`.
+ *     The score, per action from 0:   GRLX_ENSEMBLE_MAJORITY (:201-235)  score[vote_m] += 1;
+ *                                     GRLX_ENSEMBLE_RANK (:237-281)      for every i, score[i] += 1 + #{k : d_m[i] > d_m[k]}.
+ *       Every score is an integer below 2^31, so the sums are exact in any order.
+ *     The combined distribution is softmax(score, tau), tau > 0.  The draw is grl::sample (utils.h:227-250): s = the sum of its entries,
+ *       ascending from 0.0; r = drand48(stream) * s; accumulate ascending from 0.0, the first i with r < acc acts, otherwise NA - 1.
+ *   ties        += (the score's maximum is not unique) per step
+ *   member_ties += the members with man_m > 1, per step
+ *   explored    += (the action drawn is not the first maximum of the score) per step
+ *   agreement   += #{m : vote_m == the action drawn} per step
+ * ret, disc, steps, terminal, ties, member_ties, agreement, explored, streams_out: [n_replicas / group_size][n_starts]; final_state has
+ * [state_dims] more.  Host pointers; any output may be NULL.  At tau = 0.1, the reference's default, one vote of difference is a factor
+ * e^10 and the draw almost never leaves the maximum.
+ *   Records.    grlx_evaluate_ensemble_sampled_trajectory: records[group][start][max_steps][R], R =
+ *               grlx_ensemble_sampled_trajectory_record_words(ctx) = grlx_trajectory_record_words(ctx, 1) + 2.  Every word of
+ *               grlx_evaluate_ensemble_trajectory keeps its index: GRLX_TRAJ_ACTION_INDEX is the index DRAWN, GRLX_TRAJ_VALUE its score as
+ *               a double, GRLX_TRAJ_N_MAX the number of maxima of the score, GRLX_TRAJ_ENS_AGREEMENT the votes for the action drawn; the
+ *               two new last words are 1.0 where the action drawn was not the score's first maximum (R - 2) and the combined
+ *               distribution's entry for the action drawn (R - 1).  Records behind an episode's end are zeros.  The staging rule and its
+ *               refusals are grlx_evaluate_ensemble_trajectory's.
+ * Deviations from the reference.  Its act(time, ...) first calls every member's own act, which advances the members' samplers: those
+ * draws are not made.  policy_strategy_add_prob and policy_strategy_multiply_prob are not built: their normalized_function is
+ * pow(x, 50), and the portable math has no pow.  policy_strategy_density_based belongs to continuous actions: it is
+ * grlx_evaluate_actor_ensemble's.
+ * The calls change nothing in the context, wait for the stream of the last grlx_run, do not count as a launch and stage in chunks of
+ * start states under grlx_set_query_chunk_bytes' bound.
+ * Validated on the host before anything is launched (GRLX_ERR_INVALID, nothing written, the function and the reason named): everything
+ * grlx_evaluate refuses; group_size < 1; n_replicas % group_size != 0; an actor-critic context ("not built":
+ * grlx_evaluate_actor_ensemble combines continuous actions, and such a context has no epsilon-greedy exploration for GRLX_EPSILON_OWN
+ * to read); an unknown strategy or member sampler; tau, or tau_m under GRLX_MEMBER_SOFTMAX, that is not finite or <= 0; under
+ * GRLX_MEMBER_EPSILON an e that is not finite, or outside [0, 1] and not exactly GRLX_EPSILON_OWN; a stream word >= 2^48 (row named).
+ * n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
+ * NOT BUILT: add / multiply; the members' own draws; a sampled ensemble of FQI replicas; a streamed variant. */
+enum { GRLX_ENSEMBLE_MAJORITY = 0, GRLX_ENSEMBLE_RANK = 1 };
+enum { GRLX_MEMBER_GREEDY = 0, GRLX_MEMBER_EPSILON = 1, GRLX_MEMBER_SOFTMAX = 2 };
+int  grlx_evaluate_ensemble_sampled(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int strategy, double tau, int member,
+                                    double member_param, const double *states /*[n_starts][state_dims]*/, int n_starts, int max_steps,
+                                    const uint64_t *streams /*[n_replicas / group_size][n_starts] or NULL*/,
+                                    double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                                    int64_t *member_ties, int64_t *agreement, int32_t *explored, double *final_state,
+                                    uint64_t *streams_out /*[n_replicas / group_size][n_starts]*/);
+int  grlx_ensemble_sampled_trajectory_record_words(grlx_ctx *ctx);      /* R = grlx_trajectory_record_words(ctx, 1) + 2; a negative status otherwise */
+int  grlx_evaluate_ensemble_sampled_trajectory(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int strategy, double tau,
+                                               int member, double member_param, const double *states /*[n_starts][state_dims]*/,
+                                               int n_starts, int max_steps,
+                                               const uint64_t *streams /*[n_replicas / group_size][n_starts] or NULL*/,
+                                               double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                                               int64_t *member_ties, int64_t *agreement, int32_t *explored, double *final_state,
+                                               uint64_t *streams_out /*[n_replicas / group_size][n_starts]*/,
+                                               double *records /*[n_replicas / group_size][n_starts][max_steps][R]*/);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * The per-step plug-in interfaces on the replicas of a context: one call of the reference's interface for EVERY replica per
