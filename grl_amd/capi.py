@@ -212,6 +212,21 @@ _SIGS = {
     "grlx_fqi_evaluate_ensemble_trajectory": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_double), C.c_int, C.c_int, _P(C.c_double),
                                                         _P(C.c_double), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64),
                                                         _P(C.c_double), _P(C.c_double)]),
+    "grlx_fqi_evaluate_sampled": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P(C.c_double), C.c_int, C.c_int, C.c_int, C.c_double, _P(C.c_uint64),
+                                            _P(C.c_double), _P(C.c_double), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_double),
+                                            _P(C.c_uint64)]),
+    "grlx_fqi_sampled_trajectory_record_words": (C.c_int, [C.c_void_p]),
+    "grlx_fqi_evaluate_sampled_trajectory": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P(C.c_double), C.c_int, C.c_int, C.c_int, C.c_double, _P(C.c_uint64),
+                                                       _P(C.c_double), _P(C.c_double), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32),
+                                                       _P(C.c_double), _P(C.c_uint64), _P(C.c_double)]),
+    "grlx_fqi_evaluate_ensemble_sampled": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _P(C.c_double), C.c_int,
+                                                     C.c_int, _P(C.c_uint64), _P(C.c_double), _P(C.c_double), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32),
+                                                     _P(C.c_int64), _P(C.c_int64), _P(C.c_int32), _P(C.c_double), _P(C.c_uint64)]),
+    "grlx_fqi_ensemble_sampled_trajectory_record_words": (C.c_int, [C.c_void_p]),
+    "grlx_fqi_evaluate_ensemble_sampled_trajectory": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,
+                                                                _P(C.c_double), C.c_int, C.c_int, _P(C.c_uint64), _P(C.c_double), _P(C.c_double),
+                                                                _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64), _P(C.c_int32),
+                                                                _P(C.c_double), _P(C.c_uint64), _P(C.c_double)]),
 }
 
 # include/grlx_diag.h: diagnostic exports (tools, tests, bench.py), not part of the boundary
@@ -240,7 +255,10 @@ _NEWER_SIGS = ("grlx_snapshot_size", "grlx_snapshot_save", "grlx_snapshot_load",
                "grlx_evaluate_noisy", "grlx_noisy_trajectory_record_words", "grlx_evaluate_noisy_trajectory", "grlx_episode_stream_words",
                "grlx_evaluate_trajectory_stream",
                "grlx_evaluate_actor_ensemble", "grlx_actor_ensemble_trajectory_record_words", "grlx_evaluate_actor_ensemble_trajectory",
-               "grlx_evaluate_ensemble_sampled", "grlx_ensemble_sampled_trajectory_record_words", "grlx_evaluate_ensemble_sampled_trajectory")
+               "grlx_evaluate_ensemble_sampled", "grlx_ensemble_sampled_trajectory_record_words", "grlx_evaluate_ensemble_sampled_trajectory",
+               "grlx_fqi_evaluate_sampled", "grlx_fqi_sampled_trajectory_record_words", "grlx_fqi_evaluate_sampled_trajectory",
+               "grlx_fqi_evaluate_ensemble_sampled", "grlx_fqi_ensemble_sampled_trajectory_record_words",
+               "grlx_fqi_evaluate_ensemble_sampled_trajectory")
 # grlx_kernel_plan flags
 PLAN_STAMPS_IN_PLACE, PLAN_STAMPS_DEFERRED, PLAN_SWEEP, PLAN_SERVER_OFF, PLAN_WALKER_SERVER, PLAN_FITS_YES, PLAN_FITS_NO = 1, 2, 4, 8, 16, 32, 64
 ENSEMBLE_VOTE, ENSEMBLE_MEAN_Q = 0, 1       # grlx_evaluate_ensemble's rule

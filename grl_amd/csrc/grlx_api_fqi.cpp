@@ -57,16 +57,23 @@ int fqi_evaluate_admit(grlx_fqi_ctx *ctx, const char *who, int first_replica, in
 }
 
 // An admitted episode call over `rows` replicas or groups, as the skeleton takes it: the start states per chunk and the outputs -- the six
-// every call has, `own` (the ensemble's two), the records of `words` doubles per step.  sibling null: the sums alone, max_steps = 0 is
-// the cap; else trajectory_admit's checks come first.
+// every call has, `own` (the ensemble's two), `more` (the sampled calls': explored, the streams after), the records of `words` doubles per
+// step.  sibling null: the sums alone, max_steps = 0 is the cap; else trajectory_admit's checks come first.  in_bytes: what a pair stages
+// beside its start state (the streams that go in).
 struct FqiEpisodes {
   int     chunk = 0, n_outs = 0;
   ReadOut outs[kMaxReadOuts];
 };
 int fqi_episodes(FqiEpisodes &e, const char *who, const char *sibling, int rows, int n_starts, int *max_steps, double *ret, double *disc, int32_t *steps,
-                 int32_t *terminal, int32_t *ties, double *final_state, std::initializer_list<int64_t *> own, double *records, int words)
+                 int32_t *terminal, int32_t *ties, double *final_state, std::initializer_list<int64_t *> own, double *records, int words,
+                 std::initializer_list<ReadOut> more = {}, size_t in_bytes = 0)
 {
-  const size_t in_and_sums = episode_start_bytes(kFqiS, rows, own.size() * sizeof(int64_t));
+  size_t extra = own.size() * sizeof(int64_t) + in_bytes;
+  for (const ReadOut &o : more) extra += o.elem;
+  const size_t in_and_sums = episode_start_bytes(kFqiS, rows, extra);
+  // the launches read d[6 + own + more] for the records whether they were asked for or not: that slot exists in the skeleton's arrays
+  if (6 + own.size() + more.size() + 1 > (size_t)kMaxReadOuts)
+    return fail(GRLX_ERR_INVALID, "%s: %zu outputs exceed the read skeleton's kMaxReadOuts = %d", who, 6 + own.size() + more.size() + 1, kMaxReadOuts);
   if (sibling)
   {
     if (int rc = trajectory_admit(who, sibling, records, *max_steps, rows, n_starts, words, in_and_sums, &e.chunk)) return rc;
@@ -81,6 +88,7 @@ int fqi_episodes(FqiEpisodes &e, const char *who, const char *sibling, int rows,
                            ReadOut{final_state, sizeof(double) * kFqiS, rows, true}})
     e.outs[e.n_outs++] = o;
   for (int64_t *p : own) e.outs[e.n_outs++] = {p, sizeof(int64_t), rows, true};
+  for (const ReadOut &o : more) e.outs[e.n_outs++] = o;
   if (sibling) e.outs[e.n_outs++] = {records, sizeof(double) * (size_t)words * (size_t)*max_steps, rows, true};
   return GRLX_OK;
 }
@@ -127,6 +135,120 @@ int fqi_evaluate_ensemble_impl(grlx_fqi_ctx *ctx, const char *who, const char *s
     HIP_TRY(launch_fqi_evaluate_ensemble(ctx->F, A, groups, nullptr));
     return GRLX_OK;
   });
+}
+
+// ---- sampled episodes: the samplers of one network, the draw from a group's majority or rank votes.  What they check beyond their greedy
+// siblings follows grlx_api_read.cpp's sampled_admit / ensemble_sampled_admit; a batch context has no sampler stream and no epsilon of
+// its own, so what would read them is refused by name.
+int fqi_epsilon_ok(const char *who, double e, const char *of)
+{
+  if (!std::isfinite(e)) return fail(GRLX_ERR_INVALID, "%s: epsilon is not finite (%g)%s", who, e, of);
+  if (e == GRLX_EPSILON_OWN)
+    return fail(GRLX_ERR_INVALID, "%s: GRLX_EPSILON_OWN (-1) is refused: a batch context has no epsilon of its own; name a number in [0, 1]%s", who, of);
+  if (!(e >= 0. && e <= 1.)) return fail(GRLX_ERR_INVALID, "%s: epsilon = %g is outside [0, 1]%s", who, e, of);
+  return GRLX_OK;
+}
+
+int fqi_sampled_admit(const char *who, int n_replicas, int n_starts, int sampler, double epsilon, const uint64_t *streams)
+{
+  if (sampler != GRLX_SAMPLER_GREEDY && sampler != GRLX_SAMPLER_EPSILON_GREEDY)
+    return fail(GRLX_ERR_INVALID, "%s: unknown sampler %d (GRLX_SAMPLER_GREEDY = 0, GRLX_SAMPLER_EPSILON_GREEDY = 1)", who, sampler);
+  if (int rc = fqi_epsilon_ok(who, epsilon, "")) return rc;
+  if (!streams && sampler == GRLX_SAMPLER_EPSILON_GREEDY)
+    return fail(GRLX_ERR_INVALID, "%s: streams is null under GRLX_SAMPLER_EPSILON_GREEDY: a batch context has no sampler stream of its own to copy "
+                "(grlx_episode_streams makes them)", who);
+  if (streams)
+    for (int64_t row = 0; row < (int64_t)n_replicas * n_starts; ++row)
+      for (int w = 0; w < 2; ++w)
+        if (streams[row * 2 + w] >> 48)
+          return fail(GRLX_ERR_INVALID, "%s: stream row %lld (replica %lld, start state %lld), word %d is 0x%llx: a rand48 state is below 2^48", who,
+                      (long long)row, (long long)(row / n_starts), (long long)(row % n_starts), w, (unsigned long long)streams[row * 2 + w]);
+  return GRLX_OK;
+}
+
+int fqi_evaluate_sampled_impl(grlx_fqi_ctx *ctx, const char *who, const char *sibling, int first_replica, int n_replicas, const double *states, int n_starts,
+                              int max_steps, int sampler, double epsilon, const uint64_t *streams, double *ret, double *disc, int32_t *steps,
+                              int32_t *terminal, int32_t *ties, int32_t *explored, double *final_state, uint64_t *streams_out, double *records)
+{
+  if (int rc = fqi_evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps)) return rc;
+  if (int rc = fqi_sampled_admit(who, n_replicas, n_starts, sampler, epsilon, streams)) return rc;
+  FqiEpisodes e;
+  if (int rc = fqi_episodes(e, who, sibling, n_replicas, n_starts, &max_steps, ret, disc, steps, terminal, ties, final_state, {}, records, kFqiSampledTrajWords,
+                            {ReadOut{explored, sizeof(int32_t), n_replicas, true}, ReadOut{streams_out, 2 * sizeof(uint64_t), n_replicas, true}},
+                            2 * sizeof(uint64_t)))
+    return rc;
+  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  ReadIn in_streams = {streams, 2 * sizeof(uint64_t), n_replicas, nullptr};      // [replica][start][2]: a chunk is strided, not contiguous
+  return chunked_read(kPlainRead, e.outs, e.n_outs, n_starts, states, kFqiS, e.chunk, true, [&](int nc, const double *dst, const DevPtr *d) -> int {
+    FqiSampledArgs T;
+    FqiEvalArgs &A = T.e;
+    A.first_replica = first_replica; A.n_starts = nc; A.max_steps = max_steps; A.states = dst;
+    A.ret = d[0].as<double>(); A.disc = d[1].as<double>(); A.steps = d[2].as<int32_t>(); A.terminal = d[3].as<int32_t>(); A.ties = d[4].as<int32_t>();
+    A.final_state = d[5].as<double>(); A.records = d[8].as<double>();      // (past the outputs: null, the sums alone)
+    T.sampler = sampler; T.epsilon = epsilon; T.streams = (const uint64_t *)in_streams.dev;
+    T.explored = d[6].as<int32_t>(); T.streams_out = d[7].as<uint64_t>();
+    HIP_TRY(launch_fqi_evaluate_sampled(ctx->F, T, n_replicas, nullptr));
+    return GRLX_OK;
+  }, &in_streams);
+}
+
+int fqi_ensemble_sampled_admit(const char *who, int n_replicas, int group_size, int n_starts, int strategy, double tau, int member, double member_param,
+                               const uint64_t *streams)
+{
+  if (int rc = fqi_ensemble_admit(who, n_replicas, group_size)) return rc;
+  if (strategy != GRLX_ENSEMBLE_MAJORITY && strategy != GRLX_ENSEMBLE_RANK)
+    return fail(GRLX_ERR_INVALID, "%s: unknown strategy %d (GRLX_ENSEMBLE_MAJORITY = 0, GRLX_ENSEMBLE_RANK = 1)", who, strategy);
+  if (!std::isfinite(tau) || !(tau > 0.)) return fail(GRLX_ERR_INVALID, "%s: tau = %g is not a finite temperature above 0", who, tau);
+  switch (member)
+  {
+    case GRLX_MEMBER_GREEDY: break;
+    case GRLX_MEMBER_EPSILON:
+      if (int rc = fqi_epsilon_ok(who, member_param, " (GRLX_MEMBER_EPSILON)")) return rc;
+      break;
+    case GRLX_MEMBER_SOFTMAX:
+      if (!std::isfinite(member_param) || !(member_param > 0.))
+        return fail(GRLX_ERR_INVALID, "%s: tau_m = %g is not a finite temperature above 0 (GRLX_MEMBER_SOFTMAX)", who, member_param);
+      break;
+    default:
+      return fail(GRLX_ERR_INVALID, "%s: unknown member sampler %d (GRLX_MEMBER_GREEDY = 0, GRLX_MEMBER_EPSILON = 1, GRLX_MEMBER_SOFTMAX = 2)", who, member);
+  }
+  if (streams)
+    for (int64_t row = 0; row < (int64_t)(n_replicas / group_size) * n_starts; ++row)
+      if (streams[row] >> 48)
+        return fail(GRLX_ERR_INVALID, "%s: stream row %lld (group %lld, start state %lld) is 0x%llx: a rand48 state is below 2^48", who, (long long)row,
+                    (long long)(row / n_starts), (long long)(row % n_starts), (unsigned long long)streams[row]);
+  return GRLX_OK;
+}
+
+int fqi_evaluate_ensemble_sampled_impl(grlx_fqi_ctx *ctx, const char *who, const char *sibling, int first_replica, int n_replicas, int group_size, int strategy,
+                                       double tau, int member, double member_param, const double *states, int n_starts, int max_steps,
+                                       const uint64_t *streams, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                                       int64_t *member_ties, int64_t *agreement, int32_t *explored, double *final_state, uint64_t *streams_out,
+                                       double *records)
+{
+  if (int rc = fqi_evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps)) return rc;
+  if (int rc = fqi_ensemble_sampled_admit(who, n_replicas, group_size, n_starts, strategy, tau, member, member_param, streams)) return rc;
+  const int groups = n_replicas / group_size;
+  FqiEpisodes e;
+  if (int rc = fqi_episodes(e, who, sibling, groups, n_starts, &max_steps, ret, disc, steps, terminal, ties, final_state, {member_ties, agreement}, records,
+                            kFqiEnsSampledTrajWords,
+                            {ReadOut{explored, sizeof(int32_t), groups, true}, ReadOut{streams_out, sizeof(uint64_t), groups, true}}, sizeof(uint64_t)))
+    return rc;
+  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  ReadIn in_streams = {streams, sizeof(uint64_t), groups, nullptr};      // [group][start]: a chunk is strided
+  return chunked_read(kPlainRead, e.outs, e.n_outs, n_starts, states, kFqiS, e.chunk, true, [&](int nc, const double *dst, const DevPtr *d) -> int {
+    FqiEnsSampledArgs T;
+    FqiEnsArgs &A = T.e;
+    A.first_replica = first_replica; A.group_size = group_size; A.rule = strategy; A.n_starts = nc; A.max_steps = max_steps; A.states = dst;
+    A.ret = d[0].as<double>(); A.disc = d[1].as<double>(); A.steps = d[2].as<int32_t>(); A.terminal = d[3].as<int32_t>(); A.ties = d[4].as<int32_t>();
+    A.final_state = d[5].as<double>(); A.member_ties = d[6].as<int64_t>(); A.agreement = d[7].as<int64_t>(); A.records = d[10].as<double>();
+    T.tau = tau; T.member = member; T.member_param = member_param; T.streams = (const uint64_t *)in_streams.dev;
+    T.explored = d[8].as<int32_t>(); T.streams_out = d[9].as<uint64_t>();
+    HIP_TRY(launch_fqi_evaluate_ensemble_sampled(ctx->F, T, groups, nullptr));
+    return GRLX_OK;
+  }, &in_streams);
 }
 
 } // namespace
@@ -418,6 +540,54 @@ int grlx_fqi_evaluate_ensemble_trajectory(grlx_fqi_ctx *ctx, int first_replica, 
 {
   return fqi_evaluate_ensemble_impl(ctx, "grlx_fqi_evaluate_ensemble_trajectory", "grlx_fqi_evaluate_ensemble", first_replica, n_replicas, group_size, rule,
                                     states, n_starts, max_steps, ret, disc, steps, terminal, ties, member_ties, agreement, final_state, records);
+}
+
+int grlx_fqi_evaluate_sampled(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, int sampler,
+                              double epsilon, const uint64_t *streams, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                              int32_t *explored, double *final_state, uint64_t *streams_out)
+{
+  return fqi_evaluate_sampled_impl(ctx, "grlx_fqi_evaluate_sampled", nullptr, first_replica, n_replicas, states, n_starts, max_steps, sampler, epsilon, streams,
+                                   ret, disc, steps, terminal, ties, explored, final_state, streams_out, nullptr);
+}
+
+int grlx_fqi_sampled_trajectory_record_words(grlx_fqi_ctx *ctx)
+{
+  if (!ctx) return fail(GRLX_ERR_INVALID, "grlx_fqi_sampled_trajectory_record_words: ctx is null");
+  return kFqiSampledTrajWords;
+}
+
+int grlx_fqi_evaluate_sampled_trajectory(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, int sampler,
+                                         double epsilon, const uint64_t *streams, double *ret, double *disc, int32_t *steps, int32_t *terminal,
+                                         int32_t *ties, int32_t *explored, double *final_state, uint64_t *streams_out, double *records)
+{
+  return fqi_evaluate_sampled_impl(ctx, "grlx_fqi_evaluate_sampled_trajectory", "grlx_fqi_evaluate_sampled", first_replica, n_replicas, states, n_starts,
+                                   max_steps, sampler, epsilon, streams, ret, disc, steps, terminal, ties, explored, final_state, streams_out, records);
+}
+
+int grlx_fqi_evaluate_ensemble_sampled(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, int group_size, int strategy, double tau, int member,
+                                       double member_param, const double *states, int n_starts, int max_steps, const uint64_t *streams, double *ret,
+                                       double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, int64_t *member_ties, int64_t *agreement,
+                                       int32_t *explored, double *final_state, uint64_t *streams_out)
+{
+  return fqi_evaluate_ensemble_sampled_impl(ctx, "grlx_fqi_evaluate_ensemble_sampled", nullptr, first_replica, n_replicas, group_size, strategy, tau, member,
+                                            member_param, states, n_starts, max_steps, streams, ret, disc, steps, terminal, ties, member_ties, agreement,
+                                            explored, final_state, streams_out, nullptr);
+}
+
+int grlx_fqi_ensemble_sampled_trajectory_record_words(grlx_fqi_ctx *ctx)
+{
+  if (!ctx) return fail(GRLX_ERR_INVALID, "grlx_fqi_ensemble_sampled_trajectory_record_words: ctx is null");
+  return kFqiEnsSampledTrajWords;
+}
+
+int grlx_fqi_evaluate_ensemble_sampled_trajectory(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, int group_size, int strategy, double tau, int member,
+                                                  double member_param, const double *states, int n_starts, int max_steps, const uint64_t *streams,
+                                                  double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, int64_t *member_ties,
+                                                  int64_t *agreement, int32_t *explored, double *final_state, uint64_t *streams_out, double *records)
+{
+  return fqi_evaluate_ensemble_sampled_impl(ctx, "grlx_fqi_evaluate_ensemble_sampled_trajectory", "grlx_fqi_evaluate_ensemble_sampled", first_replica,
+                                            n_replicas, group_size, strategy, tau, member, member_param, states, n_starts, max_steps, streams, ret, disc,
+                                            steps, terminal, ties, member_ties, agreement, explored, final_state, streams_out, records);
 }
 
 } // extern "C"

@@ -68,6 +68,30 @@ struct FqiEnsArgs {
   double  *records;                                // RECORD: [groups][n_starts][max_steps][kFqiEnsTrajWords]
 };
 
+// ---- the sampled episodes (grlx_fqi_evaluate_sampled, grlx_fqi_evaluate_ensemble_sampled): the greedy calls' arguments, the sampler,
+// and the rand48 words every episode carries in and out
+constexpr int kFqiSampledTrajWords = kFqiTrajWords + 1;              // ... then `explored`
+constexpr int kFqiEnsSampledTrajWords = kFqiEnsTrajWords + 2;        // ... then `explored`, `prob`
+
+struct FqiSampledArgs {
+  FqiEvalArgs e;                                   // e.records: [n_replicas][n_starts][max_steps][kFqiSampledTrajWords]
+  int32_t sampler;                                 // GRLX_SAMPLER_*
+  double  epsilon;                                 // [0, 1]
+  const uint64_t *streams;                         // [n_replicas][n_starts][2]: {sampler's, global}; null: {0, the replica's G}
+  int32_t  *explored;                              // [n_replicas][n_starts]
+  uint64_t *streams_out;                           // [n_replicas][n_starts][2]
+};
+
+struct FqiEnsSampledArgs {
+  FqiEnsArgs e;                                    // e.rule: GRLX_ENSEMBLE_MAJORITY / _RANK; e.records: [...][kFqiEnsSampledTrajWords]
+  double  tau;                                     // the combined softmax's temperature, > 0
+  int32_t member;                                  // GRLX_MEMBER_*
+  double  member_param;                            // e in [0, 1] (EPSILON), tau_m > 0 (SOFTMAX)
+  const uint64_t *streams;                         // [groups][n_starts]; null: G of the group's first replica
+  int32_t  *explored;                              // [groups][n_starts]
+  uint64_t *streams_out;                           // [groups][n_starts]
+};
+
 // How a context launches the epochs kernel: FqiShape<hidden>'s blocks per replica and threads per block, how many replicas' blocks are
 // resident at once, and whether the launch is plain -- GRLX_FQI_NO_COOP=1 (diagnostic), or the runtime refused the cooperative launch
 // because another process holds the device's cooperative queue (launch_fqi_batch sets it then)
@@ -88,6 +112,9 @@ hipError_t launch_fqi_query(const FqiParams &F, int first_replica, int n_replica
 // the episodes of a chunk for `rows` replicas (groups); A.records null: the sums alone
 hipError_t launch_fqi_evaluate(const FqiParams &F, const FqiEvalArgs &A, int rows, hipStream_t stream);
 hipError_t launch_fqi_evaluate_ensemble(const FqiParams &F, const FqiEnsArgs &A, int rows, hipStream_t stream);
+// the sampled episodes; every output pointer is written without a test
+hipError_t launch_fqi_evaluate_sampled(const FqiParams &F, const FqiSampledArgs &A, int rows, hipStream_t stream);
+hipError_t launch_fqi_evaluate_ensemble_sampled(const FqiParams &F, const FqiEnsSampledArgs &A, int rows, hipStream_t stream);
 hipError_t launch_fqi_query_ensemble(const FqiParams &F, int first_replica, int groups, int group_size, const double *obs, int n_obs, double *out,
                                      hipStream_t stream);
 

@@ -986,6 +986,400 @@ __global__ __launch_bounds__(64) void fqi_query_ensemble_kernel(FqiParams F, int
     }
 }
 
+// ------------------------------------------------------------------------------------------ sampled episodes ---
+// grlx_fqi_evaluate_sampled, grlx_fqi_evaluate_sampled_trajectory: fqi_evaluate_kernel's episode -- its layout, its staging of the network,
+// its wave-uniform loop -- acted by the reference's samplers on two rand48 words the lane carries: S, the sampler's stream (the epsilon
+// draw), and G, the global stream (the random action index, the tie break).  The order of draws is fqi_test_kernel's and
+// grlx_evaluate_sampled.hip's: S first, then G for the random action or, on a step that does not explore, for the tie break.  The Q-values of
+// a step are kept (selects over kMaxActions, no run-time index: see above) because the (jj + 1)-th maximum and Q of the action taken are read
+// after the last pass.  A kernel of its own and no shared body: fqi_evaluate_kernel keeps its instruction stream.
+template <int H, bool RECORD>
+__global__ __launch_bounds__(64) void fqi_evaluate_sampled_kernel(FqiParams F, FqiSampledArgs T)
+{
+  constexpr int R = kFqiSampledTrajWords;
+  __shared__ double sh_net[(kFqiNIn + 1) * H + H + 1];
+  const FqiEvalArgs &A = T.e;
+  const int rl = blockIdx.y, r = A.first_replica + rl;
+  const double *net = F.net + (size_t)r * 4 * F.P;
+  for (int k = threadIdx.x; k < F.P; k += blockDim.x) sh_net[k] = net[k];
+  __syncthreads();
+  const int s = (int)blockIdx.x * 64 + (int)threadIdx.x;
+  const bool live = s < A.n_starts;                    // dead lanes of the last block neither load nor store nor draw
+  const size_t pair = (size_t)rl * (size_t)A.n_starts + (size_t)(live ? s : 0);
+  double *rec = RECORD ? A.records + pair * (size_t)A.max_steps * R : nullptr;
+  double x[kFqiS], obs[kFqiD];
+#pragma unroll
+  for (int i = 0; i < kFqiS; ++i) x[i] = live ? A.states[(size_t)s * kFqiS + i] : 0.;
+  (void)Env<GRLX_ENV_PENDULUM>::observe(F.env, x, obs);                // the start state's terminal code is ignored
+  uint64_t S = 0, G = 0;
+  if (live)
+  {
+    S = T.streams ? T.streams[pair * 2] : 0ull;
+    G = T.streams ? T.streams[pair * 2 + 1] : F.rep[r].G;              // a copy: the replica's own stream does not move
+  }
+
+  double ret = 0, disc = 0, g = 1;
+  int steps = 0, code = 0, ties = 0, explored = 0;
+  bool active = live;
+  for (int step = 0; step < A.max_steps; ++step)
+  {
+    if (__ballot(active) == 0ull) break;               // wave-uniform
+    if (active)
+    { // the draws sit under the step's predicate: a finished lane's streams stand where its last step left them
+      double q[kMaxActions], best = 0;
+#pragma unroll
+      for (int a = 0; a < kMaxActions; ++a) q[a] = 0;
+      int mai = 0, man = 1;                            // GreedySampler::findmax (greedy.cpp:47-61)
+      for (int k = 0; k < F.A; ++k)
+      {
+        double ak = F.actions[0];
+#pragma unroll
+        for (int a = 1; a < kMaxActions; ++a) ak = (k == a) ? F.actions[a] : ak;
+        double in[kFqiNIn];
+        fqi_normalise(F, obs, ak, in);
+        const double qk = ann_forward<H>(sh_net, in, nullptr);
+#pragma unroll
+        for (int a = 0; a < kMaxActions; ++a) q[a] = (k == a) ? qk : q[a];
+        if (k == 0 || qk > best) { best = qk; mai = k; man = 1; }
+        else if (qk == best) man++;
+      }
+      int idx = mai;
+      bool tie = false, random = false;
+      if (T.sampler == GRLX_SAMPLER_EPSILON_GREEDY)
+      { // EpsilonGreedySampler::sample (greedy.cpp:144-218)
+        S = lcg_next(S);
+        if (lcg_double(S) < T.epsilon)
+        {
+          G = lcg_next(G);
+          idx = (int)(lcg_long(G) % (uint32_t)F.A);
+          random = true;
+        }
+      }
+      if (!random && man > 1)
+      { // greedy.cpp:77-85 by selects: the entry at which the countdown over the maximal entries stands at zero
+        G = lcg_next(G);
+        int jj = (int)(lcg_long(G) % (uint32_t)man);
+#pragma unroll
+        for (int a = 0; a < kMaxActions; ++a)
+        {
+          const bool m = a < F.A && q[a] == best;
+          idx = (m && jj == 0) ? a : idx;
+          jj -= m ? 1 : 0;
+        }
+        tie = true;
+      }
+      double action = 0, value = 0;
+#pragma unroll
+      for (int a = 0; a < kMaxActions; ++a)
+      {
+        action = (idx == a) ? F.actions[a] : action;
+        value = (idx == a) ? q[a] : value;
+      }
+      double before[kFqiD];
+#pragma unroll
+      for (int i = 0; i < kFqiD; ++i) before[i] = obs[i];
+      double reward = 0;
+      int terminal = 0;
+      uint32_t status = 0;
+      env_step<GRLX_ENV_PENDULUM, false>(F.env, x, action, obs, reward, terminal, status);
+      ret += reward;
+      disc += g * reward;
+      g = g * F.gamma_tau;
+      ties += tie ? 1 : 0;
+      explored += random ? 1 : 0;
+      code = (status & ST_DOMAIN) ? kFqiEvalDomain : terminal;
+      active = code == 0;
+      if constexpr (RECORD)
+      {
+        double *w = rec + (size_t)steps * R;
+        w[GRLX_TRAJ_ACTION] = action;
+        w[GRLX_TRAJ_REWARD] = reward;
+        w[GRLX_TRAJ_VALUE] = value;
+        w[GRLX_TRAJ_ACTION_INDEX] = (double)idx;
+        w[GRLX_TRAJ_N_MAX] = (double)man;
+        w[GRLX_TRAJ_TERMINAL] = (double)code;
+#pragma unroll
+        for (int i = 0; i < kFqiD; ++i) w[GRLX_TRAJ_OBS + i] = before[i];
+#pragma unroll
+        for (int i = 0; i < kFqiS; ++i) w[GRLX_TRAJ_OBS + kFqiD + i] = x[i];
+        w[R - 1] = random ? 1.0 : 0.0;
+      }
+      steps++;
+    }
+  }
+  if (!live) return;
+  if constexpr (RECORD)
+    for (size_t k = (size_t)steps * R; k < (size_t)A.max_steps * R; ++k) rec[k] = 0.;       // behind the episode's end: all-zero bits
+  A.ret[pair] = ret;
+  A.disc[pair] = disc;
+  A.steps[pair] = steps;
+  A.terminal[pair] = code;
+  A.ties[pair] = ties;
+  T.explored[pair] = explored;
+  T.streams_out[pair * 2] = S;
+  T.streams_out[pair * 2 + 1] = G;
+#pragma unroll
+  for (int i = 0; i < kFqiS; ++i) A.final_state[pair * kFqiS + i] = x[i];
+}
+
+// grlx_fqi_evaluate_ensemble_sampled, grlx_fqi_evaluate_ensemble_sampled_trajectory: fqi_evaluate_ensemble_kernel's episodes with the action
+// DRAWN from softmax(score / tau), the score being the members' votes (GRLX_ENSEMBLE_MAJORITY) or their summed ranks (GRLX_ENSEMBLE_RANK);
+// include/grlx.h states the step (grlx_evaluate_ensemble_sampled).  Every score is an integer, so the members may be summed in any order,
+// and that is what the layout is built on: the members of a group work side by side.
+//
+// Layout.  A ROW of 16 lanes is one (group, start state) pair; a wave holds four pairs of one group (blockIdx.y), blockIdx.x covers the start
+// states four at a time, the block is one wave.  Lane j of a row serves the members j, j + 16, j + 32, ... of its group: a step costs
+// ceil(G / 16) members' forward passes, where fqi_evaluate_ensemble_kernel's lane walks all G.  Per member the lane computes the A
+// Q-values (fqi_member_values, as it is), the member's distribution, its vote and its ranks, and adds them to int accumulators of its own;
+// a lane whose member index is >= G skips the member and adds nothing.  Then ONE all-reduce over the row: four DPP row rotations (8, 4, 2,
+// 1) and adds per word, A vote words, A rank words under RANK, one word for the members with a tie -- no LDS, no barrier; after it every
+// lane of the row holds the same totals.  Every lane of a row also holds the same model state and the same stream word, so all 16 run the
+// combined softmax, the draw and env_step themselves, on identical bits: nothing is broadcast.  Lane 0 of the row writes the record, the
+// outputs and the zeros behind the episode's end.  The step loop is wave-uniform (a ballot over the rows' `active`); a row is active or
+// not as a whole, so the row rotations never cross a predicate's edge.
+//
+// Member parameters.  The lanes of a row read 16 DIFFERENT networks, so the block-uniform address of fqi_evaluate_ensemble_kernel is gone:
+// each lane reads its member through its own global address (the four rows of a wave read the same 16 members).  Staging a round of 16
+// members in LDS at an odd stride of P = 5 H + 1 doubles was measured against this: 5 % shorter calls for groups of exactly 16 at hidden =
+// 20, up to 80 % longer ones for groups of 4 and of 64 (41 KB of LDS per wave at hidden = 64; a restaging per round and step beyond 16
+// members), so it is not kept: DESIGN.md section 4.2o.
+template <int N>
+__device__ __forceinline__ int fqi_row_ror(int v)
+{ // lane i of a row of 16 receives the value of lane (i - N) mod 16 of the same row (DPP row_ror: N)
+  return __builtin_amdgcn_update_dpp(v, v, 0x120 + N, 0xF, 0xF, false);
+}
+__device__ __forceinline__ int fqi_row_sum(int v)
+{ // the sum over the row's 16 lanes, in every one of them
+  v += fqi_row_ror<8>(v);
+  v += fqi_row_ror<4>(v);
+  v += fqi_row_ror<2>(v);
+  v += fqi_row_ror<1>(v);
+  return v;
+}
+
+// SoftmaxSampler::distribution (softmax.cpp:65-110) over the first NA of v[] at temperature t, as include/grlx.h restates it; entries
+// behind NA come out 0.  NA is a kernel argument: every branch on it is scalar.
+__device__ __forceinline__ void fqi_softmax(const double (&v)[kMaxActions], int NA, double t, double (&d)[kMaxActions])
+{
+  double p[kMaxActions], e[kMaxActions];
+  double maxp = -0x1.fffffffffffffp+1023;                 // -DBL_MAX
+#pragma unroll
+  for (int a = 0; a < kMaxActions; ++a)
+  {
+    p[a] = v[a] / t;
+    if (a < NA) maxp = (maxp < p[a]) ? p[a] : maxp;
+  }
+  const double minp = maxp + (-100), center = (maxp + minp) / 2.0;
+  double sum = 0;
+#pragma unroll
+  for (int a = 0; a < kMaxActions; ++a)
+  {
+    e[a] = 0.0;
+    if (a < NA)
+    {
+      const bool kept = p[a] > minp;
+      e[a] = kept ? pexp(p[a] - center) : 0.0;
+      sum = kept ? sum + e[a] : sum;
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < kMaxActions; ++a) d[a] = (a < NA && p[a] > minp) ? e[a] / sum : 0.0;
+}
+
+template <int H, bool RECORD>
+__global__ __launch_bounds__(64) void fqi_ensemble_sampled_kernel(FqiParams F, FqiEnsSampledArgs T)
+{
+  constexpr int R = kFqiEnsSampledTrajWords;
+  const FqiEnsArgs &A = T.e;
+  const int gl = blockIdx.y, G = A.group_size, NA = F.A;
+  const int lane = threadIdx.x, row = lane >> 4, j = lane & 15;
+  const bool rank = A.rule == GRLX_ENSEMBLE_RANK;
+  const int r0 = A.first_replica + gl * G;
+  const double *nets = F.net + (size_t)r0 * 4 * F.P;                   // member m: nets + m * 4 * F.P, its first P-block
+  const int s = (int)blockIdx.x * 4 + row;
+  const bool live = s < A.n_starts;                    // dead rows of the last block neither load nor store nor draw
+  const size_t pair = (size_t)gl * (size_t)A.n_starts + (size_t)(live ? s : 0);
+  double *rec = RECORD ? A.records + pair * (size_t)A.max_steps * R : nullptr;
+  double x[kFqiS], obs[kFqiD];
+#pragma unroll
+  for (int i = 0; i < kFqiS; ++i) x[i] = live ? A.states[(size_t)s * kFqiS + i] : 0.;
+  (void)Env<GRLX_ENV_PENDULUM>::observe(F.env, x, obs);                // the start state's terminal code is ignored
+  uint64_t rng = 0;
+  if (live) rng = T.streams ? T.streams[pair] : F.rep[r0].G;           // a copy: the replica's own stream does not move
+
+  double ret = 0, disc = 0, g = 1;
+  int steps = 0, code = 0, ties = 0, explored = 0;
+  long long member_ties = 0, agreement = 0;
+  bool active = live;
+  for (int step = 0; step < A.max_steps; ++step)
+  {
+    if (__ballot(active) == 0ull) break;               // wave-uniform
+    int votes[kMaxActions], ranks[kMaxActions], mties = 0;
+#pragma unroll
+    for (int a = 0; a < kMaxActions; ++a) { votes[a] = 0; ranks[a] = 0; }
+    for (int m0 = 0; m0 < G; m0 += 16)
+    {
+      const int m = m0 + j;
+      if (active && m < G)
+      {
+        const double *w = nets + (size_t)m * 4 * F.P;
+        double q[kMaxActions], unused[kMaxActions], d[kMaxActions], best;
+#pragma unroll
+        for (int a = 0; a < kMaxActions; ++a) unused[a] = 0.;
+        int mai, man;
+        fqi_member_values<H>(F, w, obs, q, unused, best, mai, man);
+        if (T.member == GRLX_MEMBER_SOFTMAX) fqi_softmax(q, NA, T.member_param, d);
+        else
+        { // greedy.cpp:88-98, and :229-236 for the epsilon-greedy member
+#pragma unroll
+          for (int a = 0; a < kMaxActions; ++a)
+          {
+            d[a] = (a < NA && q[a] == best) ? 1. / (double)man : 0.;
+            if (T.member == GRLX_MEMBER_EPSILON)
+            {
+              d[a] = (d[a] == 1) ? 1 - T.member_param : d[a];
+              d[a] += T.member_param / (double)NA;
+            }
+          }
+        }
+        // the member's vote (multi_discrete.cpp:218-229): the first entry above every entry before it and above 0.0; NA - 1 without one
+        double top = 0.0;
+        int vote = NA - 1;
+#pragma unroll
+        for (int a = 0; a < kMaxActions; ++a)
+        {
+          const bool up = a < NA && d[a] > top;
+          vote = up ? a : vote;
+          top = up ? d[a] : top;
+        }
+#pragma unroll
+        for (int a = 0; a < kMaxActions; ++a) votes[a] += (vote == a) ? 1 : 0;
+        mties += man > 1 ? 1 : 0;
+        if (rank)
+        { // the rank of action a among the member's entries: 1 + the entries strictly below it (:237-281)
+#pragma unroll
+          for (int a = 0; a < kMaxActions; ++a)
+          {
+            int below = 1;
+#pragma unroll
+            for (int k = 0; k < kMaxActions; ++k) below += (k < NA && d[a] > d[k]) ? 1 : 0;
+            ranks[a] += (a < NA) ? below : 0;
+          }
+        }
+      }
+    }
+    // the row's totals, in every lane of the row: integer adds, exact in any order
+#pragma unroll
+    for (int a = 0; a < kMaxActions; ++a)
+      if (a < NA)
+      {
+        votes[a] = fqi_row_sum(votes[a]);
+        if (rank) ranks[a] = fqi_row_sum(ranks[a]);
+      }
+    mties = fqi_row_sum(mties);
+    if (active)
+    {
+      double sc[kMaxActions], dist[kMaxActions];
+      int score[kMaxActions];
+#pragma unroll
+      for (int a = 0; a < kMaxActions; ++a)
+      {
+        score[a] = rank ? ranks[a] : votes[a];
+        sc[a] = (double)score[a];
+      }
+      fqi_softmax(sc, NA, T.tau, dist);
+      // grl::sample (utils.h:227-250) on one drand48 of the episode's stream
+      double sum = 0;
+#pragma unroll
+      for (int a = 0; a < kMaxActions; ++a)
+        if (a < NA) sum += dist[a];
+      rng = lcg_next(rng);
+      const double u = lcg_double(rng) * sum;
+      double acc = 0;
+      int idx = NA - 1;
+      bool found = false;
+#pragma unroll
+      for (int a = 0; a < kMaxActions; ++a)
+        if (a < NA)
+        {
+          acc += dist[a];
+          const bool here = !found && u < acc;
+          idx = here ? a : idx;
+          found = found || here;
+        }
+      int mai = 0, man = 1, top = score[0];            // findmax over the score
+#pragma unroll
+      for (int a = 1; a < kMaxActions; ++a)
+        if (a < NA)
+        {
+          if (score[a] > top) { top = score[a]; mai = a; man = 1; }
+          else if (score[a] == top) man++;
+        }
+      double action = 0, value = 0, prob = 0;
+      int agree = 0;
+#pragma unroll
+      for (int a = 0; a < kMaxActions; ++a)
+      {
+        action = (idx == a) ? F.actions[a] : action;
+        value = (idx == a) ? sc[a] : value;
+        prob = (idx == a) ? dist[a] : prob;
+        agree = (idx == a) ? votes[a] : agree;
+      }
+      const bool off = idx != mai;
+      double before[kFqiD];
+#pragma unroll
+      for (int i = 0; i < kFqiD; ++i) before[i] = obs[i];
+      double reward = 0;
+      int terminal = 0;
+      uint32_t status = 0;
+      env_step<GRLX_ENV_PENDULUM, false>(F.env, x, action, obs, reward, terminal, status);
+      ret += reward;
+      disc += g * reward;
+      g = g * F.gamma_tau;
+      ties += man > 1 ? 1 : 0;
+      member_ties += mties;
+      agreement += agree;
+      explored += off ? 1 : 0;
+      code = (status & ST_DOMAIN) ? kFqiEvalDomain : terminal;
+      active = code == 0;
+      if constexpr (RECORD)
+        if (j == 0)
+        {
+          double *w = rec + (size_t)steps * R;
+          w[GRLX_TRAJ_ACTION] = action;
+          w[GRLX_TRAJ_REWARD] = reward;
+          w[GRLX_TRAJ_VALUE] = value;
+          w[GRLX_TRAJ_ACTION_INDEX] = (double)idx;
+          w[GRLX_TRAJ_N_MAX] = (double)man;
+          w[GRLX_TRAJ_TERMINAL] = (double)code;
+          w[GRLX_TRAJ_ENS_AGREEMENT] = (double)agree;
+          w[GRLX_TRAJ_ENS_MEMBER_TIES] = (double)mties;
+#pragma unroll
+          for (int i = 0; i < kFqiD; ++i) w[GRLX_TRAJ_ENS_OBS + i] = before[i];
+#pragma unroll
+          for (int i = 0; i < kFqiS; ++i) w[GRLX_TRAJ_ENS_OBS + kFqiD + i] = x[i];
+          w[R - 2] = off ? 1.0 : 0.0;
+          w[R - 1] = prob;
+        }
+      steps++;
+    }
+  }
+  if (!live || j != 0) return;
+  if constexpr (RECORD)
+    for (size_t k = (size_t)steps * R; k < (size_t)A.max_steps * R; ++k) rec[k] = 0.;       // behind the episode's end: all-zero bits
+  A.ret[pair] = ret;
+  A.disc[pair] = disc;
+  A.steps[pair] = steps;
+  A.terminal[pair] = code;
+  A.ties[pair] = ties;
+  A.member_ties[pair] = member_ties;
+  A.agreement[pair] = agreement;
+  T.explored[pair] = explored;
+  T.streams_out[pair] = rng;
+#pragma unroll
+  for (int i = 0; i < kFqiS; ++i) A.final_state[pair * kFqiS + i] = x[i];
+}
+
 // ------------------------------------------------------------------------------------------------ host launchers ---
 // What grlx_api_fqi.cpp needs from the kernel symbols above (grlx_fqi.h).  Host code does not live in this unit beyond this block, and
 // kernels are appended above it, not inserted: every kernel keeps its instruction stream.
@@ -1080,6 +1474,23 @@ hipError_t launch_fqi_evaluate_ensemble(const FqiParams &F, const FqiEnsArgs &A,
   const dim3 grid((unsigned)((A.n_starts + 63) / 64), (unsigned)rows), block(64);
   if (A.records) { FQI_FOR_H(F.H, hipLaunchKernelGGL((fqi_evaluate_ensemble_kernel<HH, true>), grid, block, 0, stream, F, A)); }
   else { FQI_FOR_H(F.H, hipLaunchKernelGGL((fqi_evaluate_ensemble_kernel<HH, false>), grid, block, 0, stream, F, A)); }
+  return hipGetLastError();
+}
+
+hipError_t launch_fqi_evaluate_sampled(const FqiParams &F, const FqiSampledArgs &A, int rows, hipStream_t stream)
+{
+  const dim3 grid((unsigned)((A.e.n_starts + 63) / 64), (unsigned)rows), block(64);
+  if (A.e.records) { FQI_FOR_H(F.H, hipLaunchKernelGGL((fqi_evaluate_sampled_kernel<HH, true>), grid, block, 0, stream, F, A)); }
+  else { FQI_FOR_H(F.H, hipLaunchKernelGGL((fqi_evaluate_sampled_kernel<HH, false>), grid, block, 0, stream, F, A)); }
+  return hipGetLastError();
+}
+
+// one wave per block, four (group, start state) pairs per wave
+hipError_t launch_fqi_evaluate_ensemble_sampled(const FqiParams &F, const FqiEnsSampledArgs &A, int rows, hipStream_t stream)
+{
+  const dim3 grid((unsigned)((A.e.n_starts + 3) / 4), (unsigned)rows), block(64);
+  if (A.e.records) { FQI_FOR_H(F.H, hipLaunchKernelGGL((fqi_ensemble_sampled_kernel<HH, true>), grid, block, 0, stream, F, A)); }
+  else { FQI_FOR_H(F.H, hipLaunchKernelGGL((fqi_ensemble_sampled_kernel<HH, false>), grid, block, 0, stream, F, A)); }
   return hipGetLastError();
 }
 

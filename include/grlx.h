@@ -637,7 +637,8 @@ int  grlx_evaluate_trajectory_stream(grlx_ctx *ctx, int first_replica, int n_rep
  * a stream word >= 2^48 (row and word named); the actor-critic ("not built": its Gaussian / Ornstein-Uhlenbeck exploration needs the
  * policy's noise state, which grlx_evaluate_noisy below carries).  n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
  * A sampled ENSEMBLE, the draw from softmax(votes / tau): grlx_evaluate_ensemble_sampled (below).
- * NOT BUILT: a softmax sampler for a single policy, the tie-breaking draw of grlx_fqi_evaluate, the decay at episode time 0. */
+ * The batch path's: grlx_fqi_evaluate_sampled (at the end of this file).
+ * NOT BUILT: a softmax sampler for a single policy, the decay at episode time 0. */
 enum { GRLX_SAMPLER_GREEDY = 0, GRLX_SAMPLER_EPSILON_GREEDY = 1 };
 #define GRLX_EPSILON_OWN (-1.0)
 int  grlx_evaluate_sampled(grlx_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][state_dims]*/, int n_starts,
@@ -831,7 +832,8 @@ int  grlx_evaluate_actor_ensemble_trajectory(grlx_ctx *ctx, int first_replica, i
  * to read); an unknown strategy or member sampler; tau, or tau_m under GRLX_MEMBER_SOFTMAX, that is not finite or <= 0; under
  * GRLX_MEMBER_EPSILON an e that is not finite, or outside [0, 1] and not exactly GRLX_EPSILON_OWN; a stream word >= 2^48 (row named).
  * n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
- * NOT BUILT: add / multiply; the members' own draws; a sampled ensemble of FQI replicas; a streamed variant. */
+ * The batch path's: grlx_fqi_evaluate_ensemble_sampled (at the end of this file).
+ * NOT BUILT: add / multiply; the members' own draws; a streamed variant. */
 enum { GRLX_ENSEMBLE_MAJORITY = 0, GRLX_ENSEMBLE_RANK = 1 };
 enum { GRLX_MEMBER_GREEDY = 0, GRLX_MEMBER_EPSILON = 1, GRLX_MEMBER_SOFTMAX = 2 };
 int  grlx_evaluate_ensemble_sampled(grlx_ctx *ctx, int first_replica, int n_replicas, int group_size, int strategy, double tau, int member,
@@ -972,8 +974,9 @@ int  grlx_fqi_query(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, const 
  * Validated on the host before anything is launched (GRLX_ERR_INVALID, nothing written; row and component named): a null ctx, null
  * states, n_starts < 0, the replica range, max_steps out of range, a state component that is not finite or reaches 2^17 in magnitude.
  * n_starts == 0 or n_replicas == 0: GRLX_OK, nothing written.
- * The same episodes on a group's vote or mean Q: grlx_fqi_evaluate_ensemble (below).
- * NOT BUILT: the reference's tie-breaking draw, tasks other than the pendulum's swing-up. */
+ * The same episodes on a group's vote or mean Q: grlx_fqi_evaluate_ensemble (below).  With the reference's tie-breaking draw, or
+ * epsilon-greedy: grlx_fqi_evaluate_sampled (below).
+ * NOT BUILT: tasks other than the pendulum's swing-up. */
 int  grlx_fqi_evaluate(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][3]*/, int n_starts, int max_steps,
                        double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state);
 int  grlx_fqi_trajectory_record_words(grlx_fqi_ctx *ctx);      /* R = 11; a negative status for a null ctx */
@@ -1010,8 +1013,8 @@ int  grlx_fqi_evaluate_trajectory(grlx_fqi_ctx *ctx, int first_replica, int n_re
  * Validated on the host before anything is launched (GRLX_ERR_INVALID, nothing written, the entry point and the reason named):
  * everything grlx_fqi_evaluate / grlx_fqi_query refuse, group_size < 1, n_replicas % group_size != 0, an unknown rule.  n_starts == 0,
  * n_obs == 0 or n_replicas == 0: GRLX_OK, nothing written.
- * NOT BUILT: sampling from the combined distribution, the reference's other discrete strategies (multiply, rank voting, density based),
- * the reference's tie-breaking draw. */
+ * The draw from the combined distribution and rank voting: grlx_fqi_evaluate_ensemble_sampled (below).
+ * NOT BUILT: the reference's other discrete strategies (add, multiply). */
 int  grlx_fqi_query_ensemble(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, int group_size, const double *obs /*[n_obs][2]*/, int n_obs,
                              double *out);
 int  grlx_fqi_evaluate_ensemble(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule,
@@ -1024,6 +1027,72 @@ int  grlx_fqi_evaluate_ensemble_trajectory(grlx_fqi_ctx *ctx, int first_replica,
                                            double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
                                            int64_t *member_ties, int64_t *agreement, double *final_state,
                                            double *records /*[n_replicas / group_size][n_starts][max_steps][R]*/);
+/* The batch path's sampled episodes: grlx_evaluate_sampled and grlx_evaluate_sampled_trajectory (above) restated for a grlx_fqi_ctx.
+ * grlx_fqi_evaluate's episodes -- its loop, terminal codes, max_steps, the 2^17 bound, the replica range, the staging under
+ * grlx_set_query_chunk_bytes and "changes nothing" -- in which the action index comes from a SAMPLER; q = grlx_fqi_query's Q-values.
+ *   A step.     grlx_evaluate_sampled's, word for word: GRLX_SAMPLER_GREEDY draws the tie break on the global stream (man > 1: the stream
+ *               advances, lrand48 % man picks among the maxima, ties++); GRLX_SAMPLER_EPSILON_GREEDY advances the sampler's stream,
+ *               rnd = drand48; rnd < e: the global stream advances, lrand48 % action_steps acts, explored++; else the greedy sampler's step.
+ *   Streams.    streams[n_replicas][n_starts][2], grlx_episode_streams' layout: [..][0] the sampler's stream, [..][1] the global stream.
+ *               streams == NULL is accepted under GRLX_SAMPLER_GREEDY only: word 1 is then a COPY of the replica's global stream as it
+ *               stands (grlx_fqi_info's rng[0]; the context's own does not move), word 0 is 0 and comes back as 0.  A batch context has no
+ *               sampler stream and no epsilon of its own: under GRLX_SAMPLER_EPSILON_GREEDY a null streams is refused by name, and so is
+ *               GRLX_EPSILON_OWN under either sampler.
+ *   Outputs.    the sibling's: ret, disc, steps, terminal, ties, explored [n_replicas][n_starts], final_state [..][3], streams_out [..][2];
+ *               any may be NULL.
+ *   Records.    grlx_fqi_evaluate_trajectory's, every word at its index (GRLX_TRAJ_ACTION_INDEX the index that ACTED, GRLX_TRAJ_VALUE Q of
+ *               the action taken), plus one last word `explored`: R = grlx_fqi_sampled_trajectory_record_words() = 12.
+ * Consequences.  Under GRLX_SAMPLER_GREEDY with ties == 0 every output equals grlx_fqi_evaluate's and streams_out == streams.  The batch
+ * path draws from a replica's global stream in its test trial only, so an episode from the task's start (pi, 0, 0) on the global stream
+ * read BEFORE a batch returns, as ret, the reward of the row that batch wrote, bit for bit, WITH its ties.  The test trial asks its policy
+ * once more at the observation the timeout ends on (fqi.c: the action of a step that is never taken): when that observation ties, the
+ * replica's stream after the batch is streams_out[..][1] advanced by that one draw, otherwise it is streams_out[..][1].
+ * Validated on the host before anything is launched (GRLX_ERR_INVALID, nothing written, the function and the reason named): everything
+ * grlx_fqi_evaluate refuses; an unknown sampler; epsilon that is not finite or outside [0, 1]; a stream word >= 2^48 (row and word named). */
+int  grlx_fqi_evaluate_sampled(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][3]*/, int n_starts,
+                               int max_steps, int sampler, double epsilon, const uint64_t *streams /*[n_replicas][n_starts][2] or NULL*/,
+                               double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, int32_t *explored,
+                               double *final_state, uint64_t *streams_out /*[n_replicas][n_starts][2]*/);
+int  grlx_fqi_sampled_trajectory_record_words(grlx_fqi_ctx *ctx);      /* R = 12; a negative status for a null ctx */
+int  grlx_fqi_evaluate_sampled_trajectory(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][3]*/,
+                                          int n_starts, int max_steps, int sampler, double epsilon,
+                                          const uint64_t *streams /*[n_replicas][n_starts][2] or NULL*/, double *ret, double *disc,
+                                          int32_t *steps, int32_t *terminal, int32_t *ties, int32_t *explored, double *final_state,
+                                          uint64_t *streams_out /*[n_replicas][n_starts][2]*/,
+                                          double *records /*[n_replicas][n_starts][max_steps][R]*/);
+/* The batch path's sampled ensemble: grlx_evaluate_ensemble_sampled and grlx_evaluate_ensemble_sampled_trajectory (above) restated for a
+ * grlx_fqi_ctx.  grlx_fqi_evaluate_ensemble's episodes -- its groups of group_size CONSECUTIVE replicas, its pair index, its
+ * gamma^control_step -- in which the action is DRAWN: a step is exactly "A step, exactly" of grlx_evaluate_ensemble_sampled with q_m =
+ * grlx_fqi_query's Q-values of member m and NA = action_steps.  Strategies GRLX_ENSEMBLE_MAJORITY and GRLX_ENSEMBLE_RANK; members
+ * GRLX_MEMBER_GREEDY, GRLX_MEMBER_EPSILON (member_param = e in [0, 1]; GRLX_EPSILON_OWN is refused by name, as above) and
+ * GRLX_MEMBER_SOFTMAX (member_param = tau_m > 0, over the portable pexp).  The scores are integers: the device sums the members in no
+ * particular order.
+ *   Stream.     One rand48 word per episode in and out, streams[groups][n_starts], one drand48 per step taken.  streams == NULL: a COPY of
+ *               the global stream of the group's first replica as it stands; the context's own does not move.
+ *   Outputs.    the online call's: ret, disc, steps, terminal, ties, member_ties, agreement, explored, streams_out [groups][n_starts],
+ *               final_state [..][3]; any may be NULL.
+ *   Records.    grlx_fqi_evaluate_ensemble_trajectory's words at their indices as the online call reads them, plus `explored` and `prob`:
+ *               R = grlx_fqi_ensemble_sampled_trajectory_record_words() = 15.
+ * The calls change nothing in the context.  Validated on the host before anything is launched: everything grlx_fqi_evaluate_ensemble
+ * refuses but its rule; an unknown strategy or member sampler; tau, or tau_m under GRLX_MEMBER_SOFTMAX, that is not finite or <= 0; under
+ * GRLX_MEMBER_EPSILON an e that is not finite or outside [0, 1]; a stream word >= 2^48 (row named).
+ * NOT BUILT: add / multiply; the members' own draws; a softmax sampler for a single policy; streamed variants; the greedy ensemble on this
+ * call's member-parallel layout (its mean-Q sum is ordered). */
+int  grlx_fqi_evaluate_ensemble_sampled(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, int group_size, int strategy, double tau, int member,
+                                        double member_param, const double *states /*[n_starts][3]*/, int n_starts, int max_steps,
+                                        const uint64_t *streams /*[n_replicas / group_size][n_starts] or NULL*/,
+                                        double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                                        int64_t *member_ties, int64_t *agreement, int32_t *explored, double *final_state,
+                                        uint64_t *streams_out /*[n_replicas / group_size][n_starts]*/);
+int  grlx_fqi_ensemble_sampled_trajectory_record_words(grlx_fqi_ctx *ctx);      /* R = 15; a negative status for a null ctx */
+int  grlx_fqi_evaluate_ensemble_sampled_trajectory(grlx_fqi_ctx *ctx, int first_replica, int n_replicas, int group_size, int strategy, double tau,
+                                                   int member, double member_param, const double *states /*[n_starts][3]*/,
+                                                   int n_starts, int max_steps,
+                                                   const uint64_t *streams /*[n_replicas / group_size][n_starts] or NULL*/,
+                                                   double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                                                   int64_t *member_ties, int64_t *agreement, int32_t *explored, double *final_state,
+                                                   uint64_t *streams_out /*[n_replicas / group_size][n_starts]*/,
+                                                   double *records /*[n_replicas / group_size][n_starts][max_steps][R]*/);
 
 #ifdef __cplusplus
 }
