@@ -10,7 +10,9 @@ from .runner import SampledEvaluation, SampledTrajectory, episode_streams  # noq
 from .runner import NoisyEvaluation, NoisyTrajectory, episode_stream_words  # noqa: F401
 from .runner import ActorEnsembleEvaluation, ActorEnsembleTrajectory  # noqa: F401
 from .runner import SampledEnsembleEvaluation, SampledEnsembleTrajectory  # noqa: F401
+from .runner import LspiRunner, pendulum_lspi_config  # noqa: F401
 
 __all__ = ["capi", "runner", "Runner", "FqiRunner", "pendulum_fqi_config", "pendulum_sarsa_config", "cart_pole_ac_config", "acrobot_q_config", "compass_walker_q_config", "sweep_grid", "snapshot_info", "observation_grid", "EnsembleResult", "Evaluation", "EnsembleEvaluation", "Trajectory", "EnsembleTrajectory",
            "SampledEvaluation", "SampledTrajectory", "episode_streams", "NoisyEvaluation", "NoisyTrajectory", "episode_stream_words",
-           "ActorEnsembleEvaluation", "ActorEnsembleTrajectory", "SampledEnsembleEvaluation", "SampledEnsembleTrajectory"]
+           "ActorEnsembleEvaluation", "ActorEnsembleTrajectory", "SampledEnsembleEvaluation", "SampledEnsembleTrajectory",
+           "LspiRunner", "pendulum_lspi_config"]

@@ -57,6 +57,15 @@ class FqiConfig(C.Structure):
                 ("epochs", C.c_int32), ("hidden", C.c_int32), ("max_batches", C.c_int32), ("eta", C.c_double)]
 
 
+class LspiConfig(C.Structure):
+    """grlx_lspi_config (include/grlx.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("n_replicas", C.c_int32), ("env", C.c_int32), ("integration_steps", C.c_int32),
+                ("control_step", C.c_double), ("timeout", C.c_double), ("action_min", C.c_double), ("action_max", C.c_double),
+                ("action_steps", C.c_int32), ("batch_size", C.c_int32), ("max_batches", C.c_int32), ("iterations", C.c_int32),
+                ("gamma", C.c_double), ("projector", C.c_int32), ("steps", C.c_int32 * 3), ("sigma", C.c_double), ("cutoff", C.c_double),
+                ("init_min", C.c_double), ("init_max", C.c_double)]
+
+
 class Tap(C.Structure):
     _fields_ = [("test", C.c_int32), ("action_index", C.c_int32), ("terminal", C.c_int32), ("trace_len", C.c_int32),
                 ("obs", C.c_double * MAX_DIMS), ("action", C.c_double), ("reward", C.c_double), ("delta", C.c_double),
@@ -227,6 +236,17 @@ _SIGS = {
                                                                 _P(C.c_double), C.c_int, C.c_int, _P(C.c_uint64), _P(C.c_double), _P(C.c_double),
                                                                 _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64), _P(C.c_int32),
                                                                 _P(C.c_double), _P(C.c_uint64), _P(C.c_double)]),
+    "grlx_lspi_config_pendulum": (None, [_P(LspiConfig), C.c_int]),
+    "grlx_lspi_create": (C.c_int, [_P(LspiConfig), _P(C.c_int64), _P(C.c_void_p)]),
+    "grlx_lspi_destroy": (C.c_int, [C.c_void_p]),
+    "grlx_lspi_run_batch": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "grlx_lspi_sync": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "grlx_lspi_read_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_int64), _P(C.c_int64), _P(C.c_double)]),
+    "grlx_lspi_get_params": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P(C.c_double), C.c_int]),
+    "grlx_lspi_get_transitions": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _P(C.c_double), _P(C.c_double), _P(C.c_double), _P(C.c_int32)]),
+    "grlx_lspi_get_system": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_double), _P(C.c_double)]),
+    "grlx_lspi_query": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P(C.c_double), C.c_int, _P(C.c_double)]),
+    "grlx_lspi_info": (C.c_int, [C.c_void_p, C.c_int, _P(C.c_int64), _P(C.c_int64), _P(C.c_uint32), _P(C.c_int64), _P(C.c_uint64)]),
 }
 
 # include/grlx_diag.h: diagnostic exports (tools, tests, bench.py), not part of the boundary
@@ -258,7 +278,9 @@ _NEWER_SIGS = ("grlx_snapshot_size", "grlx_snapshot_save", "grlx_snapshot_load",
                "grlx_evaluate_ensemble_sampled", "grlx_ensemble_sampled_trajectory_record_words", "grlx_evaluate_ensemble_sampled_trajectory",
                "grlx_fqi_evaluate_sampled", "grlx_fqi_sampled_trajectory_record_words", "grlx_fqi_evaluate_sampled_trajectory",
                "grlx_fqi_evaluate_ensemble_sampled", "grlx_fqi_ensemble_sampled_trajectory_record_words",
-               "grlx_fqi_evaluate_ensemble_sampled_trajectory")
+               "grlx_fqi_evaluate_ensemble_sampled_trajectory",
+               "grlx_lspi_config_pendulum", "grlx_lspi_create", "grlx_lspi_destroy", "grlx_lspi_run_batch", "grlx_lspi_sync", "grlx_lspi_read_rows",
+               "grlx_lspi_get_params", "grlx_lspi_get_transitions", "grlx_lspi_get_system", "grlx_lspi_query", "grlx_lspi_info")
 # grlx_kernel_plan flags
 PLAN_STAMPS_IN_PLACE, PLAN_STAMPS_DEFERRED, PLAN_SWEEP, PLAN_SERVER_OFF, PLAN_WALKER_SERVER, PLAN_FITS_YES, PLAN_FITS_NO = 1, 2, 4, 8, 16, 32, 64
 ENSEMBLE_VOTE, ENSEMBLE_MEAN_Q = 0, 1       # grlx_evaluate_ensemble's rule
@@ -273,6 +295,7 @@ ACTOR_ENSEMBLE_MEAN, ACTOR_ENSEMBLE_BINNING, ACTOR_ENSEMBLE_DATA_CENTER, ACTOR_E
 # grlx_evaluate_ensemble_sampled's strategy and its members' sampler (GRLX_ENSEMBLE_MAJORITY / _RANK, GRLX_MEMBER_*)
 ENSEMBLE_MAJORITY, ENSEMBLE_RANK = 0, 1
 MEMBER_GREEDY, MEMBER_EPSILON, MEMBER_SOFTMAX = 0, 1, 2
+RBF_TRIANGLE, RBF_GAUSS = 0, 1                     # grlx_lspi_config.projector (GRLX_RBF_*)
 ABI_VERSION = 2        # include/grlx.h: GRLX_ABI_VERSION
 
 

@@ -1338,6 +1338,102 @@ class FqiRunner:
         return dict(n=n.value, maxdelta=md.value, iterations=it.value, error=err.value, rng=[rng[0], rng[1]])
 
 
+def pendulum_lspi_config(n_replicas: int = 1, projector="triangle", **overrides) -> capi.LspiConfig:
+    """Config of the reference's cfg/pendulum/lspi_triangle.yaml or lspi_gauss.yaml (experiment/batch_learning + predictor/lspi over
+    projector/rbf); steps=[a, b, c] overrides the basis functions per dimension."""
+    lib = capi.load()
+    cfg = capi.LspiConfig()
+    projector = {"triangle": capi.RBF_TRIANGLE, "gauss": capi.RBF_GAUSS}[projector] if isinstance(projector, str) else int(projector)
+    lib.grlx_lspi_config_pendulum(C.byref(cfg), projector)
+    cfg.n_replicas = n_replicas
+    for k, v in overrides.items():
+        if k == "steps":
+            cfg.steps[:] = [int(s) for s in v]
+        else:
+            setattr(cfg, k, v)
+    return cfg
+
+
+class LspiRunner:
+    """N independent-seed replicas of the batch-learning experiment with least-squares policy iteration over a triangle or Gauss RBF
+    representation on the current GPU: include/grlx.h, grlx_lspi_*."""
+
+    def __init__(self, cfg: capi.LspiConfig, seeds):
+        self.lib = capi.load()
+        self.cfg = cfg
+        seeds = np.ascontiguousarray(seeds, dtype=np.int64)
+        if seeds.shape != (cfg.n_replicas,):
+            raise ValueError("need one seed per replica")
+        self._ctx = C.c_void_p()
+        capi.check(self.lib.grlx_lspi_create(C.byref(cfg), _ptr(seeds, C.c_int64), C.byref(self._ctx)))
+        self.n_params = int(cfg.steps[0]) * int(cfg.steps[1]) * int(cfg.steps[2])
+
+    def close(self):
+        if self._ctx:
+            self.lib.grlx_lspi_destroy(self._ctx)
+            self._ctx = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run_batch(self, stream: int = 0):
+        capi.check(self.lib.grlx_lspi_run_batch(self._ctx, C.c_void_p(stream)))
+
+    def sync(self, stream: int = 0):
+        capi.check(self.lib.grlx_lspi_sync(self._ctx, C.c_void_p(stream)))
+
+    def rows(self, replica: int, count: int):
+        b = np.zeros(count, np.int64); t = np.zeros(count, np.int64); rew = np.zeros(count, np.float64)
+        capi.check(self.lib.grlx_lspi_read_rows(self._ctx, replica, 0, count, _ptr(b, C.c_int64), _ptr(t, C.c_int64), _ptr(rew, C.c_double)))
+        return b, t, rew
+
+    def params(self, replica: int, which: int = 0):
+        """the weights [F]: which=0 the current ones, which=1 those on which the last iteration's greedy choice was made"""
+        out = np.zeros(self.n_params, np.float64)
+        capi.check(self.lib.grlx_lspi_get_params(self._ctx, replica, int(which), _ptr(out, C.c_double), out.size))
+        return out
+
+    def transitions(self, replica: int, first: int = 0, count=None):
+        """(obs_action[count][3], next_obs[count][2], reward[count], best[count]) of the store; count None: everything stored"""
+        if count is None:
+            count = self.info(replica)["n"] - first
+        oa = np.zeros((count, 3), np.float64); nobs = np.zeros((count, 2), np.float64)
+        rew = np.zeros(count, np.float64); best = np.zeros(count, np.int32)
+        capi.check(self.lib.grlx_lspi_get_transitions(self._ctx, replica, first, count, _ptr(oa, C.c_double), _ptr(nobs, C.c_double),
+                                                      _ptr(rew, C.c_double), _ptr(best, C.c_int32)))
+        return oa, nobs, rew, best
+
+    def system(self, replica: int):
+        """(A[F][F], b[F]): the system of the last iteration as it was solved"""
+        A = np.zeros((self.n_params, self.n_params), np.float64); b = np.zeros(self.n_params, np.float64)
+        capi.check(self.lib.grlx_lspi_get_system(self._ctx, replica, _ptr(A, C.c_double), _ptr(b, C.c_double)))
+        return A, b
+
+    def query(self, obs, replicas=None):
+        """q[replica][obs][action] on every replica's current weights (grlx_lspi_query); replicas: None = all, else a range or a
+        (first, count) pair.  Changes nothing in the context."""
+        obs = np.ascontiguousarray(obs, dtype=np.float64)
+        if obs.ndim != 2 or obs.shape[1] != 2:
+            raise ValueError(f"expected observations of shape (n, 2), got {obs.shape}")
+        if replicas is None:
+            first, count = 0, self.cfg.n_replicas
+        elif isinstance(replicas, range):
+            first, count = replicas.start, len(replicas)
+        else:
+            first, count = (int(x) for x in replicas)
+        q = np.zeros((count, obs.shape[0], self.cfg.action_steps), np.float64)
+        capi.check(self.lib.grlx_lspi_query(self._ctx, first, count, _ptr(obs, C.c_double), obs.shape[0], _ptr(q, C.c_double)))
+        return q
+
+    def info(self, replica: int):
+        n = C.c_int64(); done = C.c_int64(); st = C.c_uint32(); ties = C.c_int64(); rng = (C.c_uint64 * 2)()
+        capi.check(self.lib.grlx_lspi_info(self._ctx, replica, C.byref(n), C.byref(done), C.byref(st), C.byref(ties), rng))
+        return dict(n=n.value, batches=done.value, status=st.value, ties=ties.value, rng=[rng[0], rng[1]])
+
+
 # ---- stateless batched operators --------------------------------------------
 def project(spec: capi.TileSpec, x):
     """Projector::project (TileCodingProjector::_project) for a batch of inputs."""

@@ -1094,6 +1094,69 @@ int  grlx_fqi_evaluate_ensemble_sampled_trajectory(grlx_fqi_ctx *ctx, int first_
                                                    uint64_t *streams_out /*[n_replicas / group_size][n_starts]*/,
                                                    double *records /*[n_replicas / group_size][n_starts][max_steps][R]*/);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * The batch path's second predictor: experiment/batch_learning + predictor/lspi + representation/parameterized/linear over
+ * projector/rbf/triangle or projector/rbf/gauss on the (observation ++ action) pair, as the reference's cfg/pendulum/lspi_triangle.yaml
+ * and lspi_gauss.yaml compose them for the pendulum swing-up; n_replicas independent-seed copies per GPU.
+ * PARITY UNPINNED, as for FQI: Eigen's sums and its LU have no order that can be restated.  What is computed instead -- sampling as
+ * the FQI context's, draw for draw; the triangle projection operation for operation; the Gauss projection with four numbered
+ * deviations; the read with products and sums rounded separately; A = 1e-5 I + Phi^T Phi - Phi^T Psi and b = Phi^T r on the f64 matrix
+ * instruction in a fixed order; LU with partial pivoting (first largest magnitude, lowest row on equal magnitude) -- is specified at
+ * the top of grl_amd/csrc/grlx_lspi.h and in DESIGN.md section 4.4.
+ * NOT BUILT: projector/monomial; the YAML host layer for predictor/lspi; evaluation episodes from caller-chosen states; ensembles;
+ * snapshots; several GPUs. */
+#define GRLX_RBF_TRIANGLE 0
+#define GRLX_RBF_GAUSS    1
+typedef struct {
+  uint32_t struct_size;               /* = sizeof(grlx_lspi_config)                                               */
+  int32_t  n_replicas;
+  int32_t  env;                       /* GRLX_ENV_PENDULUM (the task must support invert(), pendulum.cpp:147-155) */
+  int32_t  integration_steps;         /* model/dynamical                                                          */
+  double   control_step;
+  double   timeout;                   /* task/pendulum/swingup                                                    */
+  double   action_min, action_max;    /* discretizer/uniform over the task's action range                         */
+  int32_t  action_steps;
+  int32_t  batch_size;                /* experiment/batch_learning:batch_size (transitions drawn per batch)       */
+  int32_t  max_batches;               /* batches reserved (transition store and rows): experiment:batches         */
+  int32_t  iterations;                /* predictor/lspi                                                           */
+  double   gamma;
+  int32_t  projector;                 /* GRLX_RBF_TRIANGLE or GRLX_RBF_GAUSS                                      */
+  int32_t  steps[3];                  /* projector/rbf:steps over (angle, velocity, action); each >= 2, product <= 512 */
+  double   sigma, cutoff;             /* projector/rbf/gauss: sigma > 0, 0 < cutoff < 1                           */
+  double   init_min, init_max;        /* representation/parameterized/linear                                      */
+} grlx_lspi_config;
+typedef struct grlx_lspi_ctx grlx_lspi_ctx;
+/* Fill *cfg with the values of the reference's cfg/pendulum/lspi_triangle.yaml or lspi_gauss.yaml (sigma: the projector's default, 1). */
+void grlx_lspi_config_pendulum(grlx_lspi_config *cfg, int projector);
+/* Validated on the host before any device work, GRLX_ERR_INVALID with the field named: a value that is not finite; an environment other
+ * than the pendulum; an unknown projector; steps[d] < 2; more than 512 features; under GRLX_RBF_GAUSS sigma <= 0 or cutoff outside
+ * (0, 1); counts below 1; the model's and the task's bounds as grlx_fqi_create states them.  Without a device: GRLX_ERR_NO_DEVICE. */
+int  grlx_lspi_create(const grlx_lspi_config *cfg, const int64_t *seeds, grlx_lspi_ctx **out);
+int  grlx_lspi_destroy(grlx_lspi_ctx *ctx);
+/* One pass of the batch loop of BatchLearningExperiment::run for every replica: batch_size random transitions, LSPIPredictor::rebuild
+ * over the whole store (lspi.cpp:110-206: `iterations` x (greedy choice, system, solve)), one greedy test trial on the first maximum
+ * -> one row.  Asynchronous on `stream`. */
+int  grlx_lspi_run_batch(grlx_lspi_ctx *ctx, void *stream);
+/* Waits for `stream`; GRLX_ERR_DOMAIN if a solve met a zero or non-finite pivot, the other codes as grlx_fqi_sync. */
+int  grlx_lspi_sync(grlx_lspi_ctx *ctx, void *stream);
+/* rows as grlx_fqi_read_rows gives them: batch, batch*batch_size, return of the test trial */
+int  grlx_lspi_read_rows(grlx_lspi_ctx *ctx, int replica, int first, int count, int64_t *batch, int64_t *transitions, double *reward);
+/* LinearRepresentation::params_, n = the product of steps.  which 0: the current weights; which 1: the weights on which the last
+ * iteration's greedy choice was made (before the first batch: the initial weights both) */
+int  grlx_lspi_get_params(grlx_lspi_ctx *ctx, int replica, int which, double *out, int n);
+/* the transition store: raw (observation, action) [count][3], next observations [count][2], rewards, and the next-state action index
+ * the last iteration chose; any pointer may be NULL */
+int  grlx_lspi_get_transitions(grlx_lspi_ctx *ctx, int replica, int first, int count, double *obs_action, double *next_obs, double *reward,
+                               int32_t *best);
+/* the system of the last iteration as it was solved: A[F][F] row-major, b[F]; either may be NULL */
+int  grlx_lspi_get_system(grlx_lspi_ctx *ctx, int replica, double *A, double *b);
+/* q[n_replicas][n_obs][action_steps] = Q(s, a_k) on the replicas' CURRENT weights at obs[n_obs][2], validated and staged as
+ * grlx_fqi_query; changes nothing in the context */
+int  grlx_lspi_query(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, const double *obs /*[n_obs][2]*/, int n_obs, double *q);
+/* state of a replica: transitions stored, batches done, its status bits, the steps of its test trials at which the maximum was not
+ * unique, RNG streams {global, thread-local}; any pointer may be NULL */
+int  grlx_lspi_info(grlx_lspi_ctx *ctx, int replica, int64_t *n_transitions, int64_t *batches_done, uint32_t *status, int64_t *ties, uint64_t rng[2]);
+
 #ifdef __cplusplus
 }
 #endif
