@@ -38,15 +38,6 @@ int fqi_query_admit(const grlx_fqi_ctx *ctx, const char *who, int first_replica,
   return GRLX_OK;
 }
 
-// what the grouped calls check after their single-policy sibling's rules
-int fqi_ensemble_admit(const char *who, int n_replicas, int group_size)
-{
-  if (int rc = group_size_ok(who, group_size)) return rc;
-  if (n_replicas % group_size != 0)
-    return fail(GRLX_ERR_INVALID, "%s: n_replicas = %d is not a multiple of group_size = %d", who, n_replicas, group_size);
-  return GRLX_OK;
-}
-
 // ---- greedy evaluation episodes: one per (replica, start state) pair, or per (group, start state) pair on the group's vote or mean Q.
 // The kernels write every output of a pair, and behind an episode's end the zeros of its records, themselves: nothing is cleared here.
 // what every episode call checks before it touches the device
@@ -56,49 +47,13 @@ int fqi_evaluate_admit(grlx_fqi_ctx *ctx, const char *who, int first_replica, in
   return episode_pairs_ok(who, ctx->F.R, kFqiS, first_replica, n_replicas, states, n_starts, max_steps);
 }
 
-// An admitted episode call over `rows` replicas or groups, as the skeleton takes it: the start states per chunk and the outputs -- the six
-// every call has, `own` (the ensemble's two), `more` (the sampled calls': explored, the streams after), the records of `words` doubles per
-// step.  sibling null: the sums alone, max_steps = 0 is the cap; else trajectory_admit's checks come first.  in_bytes: what a pair stages
-// beside its start state (the streams that go in).
-struct FqiEpisodes {
-  int     chunk = 0, n_outs = 0;
-  ReadOut outs[kMaxReadOuts];
-};
-int fqi_episodes(FqiEpisodes &e, const char *who, const char *sibling, int rows, int n_starts, int *max_steps, double *ret, double *disc, int32_t *steps,
-                 int32_t *terminal, int32_t *ties, double *final_state, std::initializer_list<int64_t *> own, double *records, int words,
-                 std::initializer_list<ReadOut> more = {}, size_t in_bytes = 0)
-{
-  size_t extra = own.size() * sizeof(int64_t) + in_bytes;
-  for (const ReadOut &o : more) extra += o.elem;
-  const size_t in_and_sums = episode_start_bytes(kFqiS, rows, extra);
-  // the launches read d[6 + own + more] for the records whether they were asked for or not: that slot exists in the skeleton's arrays
-  if (6 + own.size() + more.size() + 1 > (size_t)kMaxReadOuts)
-    return fail(GRLX_ERR_INVALID, "%s: %zu outputs exceed the read skeleton's kMaxReadOuts = %d", who, 6 + own.size() + more.size() + 1, kMaxReadOuts);
-  if (sibling)
-  {
-    if (int rc = trajectory_admit(who, sibling, records, *max_steps, rows, n_starts, words, in_and_sums, &e.chunk)) return rc;
-  }
-  else
-  {
-    if (*max_steps == 0) *max_steps = GRLX_MAX_EPISODE_STEPS;
-    e.chunk = query_chunk(n_starts, in_and_sums);
-  }
-  for (const ReadOut &o : {ReadOut{ret, sizeof(double), rows, true}, ReadOut{disc, sizeof(double), rows, true}, ReadOut{steps, sizeof(int32_t), rows, true},
-                           ReadOut{terminal, sizeof(int32_t), rows, true}, ReadOut{ties, sizeof(int32_t), rows, true},
-                           ReadOut{final_state, sizeof(double) * kFqiS, rows, true}})
-    e.outs[e.n_outs++] = o;
-  for (int64_t *p : own) e.outs[e.n_outs++] = {p, sizeof(int64_t), rows, true};
-  for (const ReadOut &o : more) e.outs[e.n_outs++] = o;
-  if (sibling) e.outs[e.n_outs++] = {records, sizeof(double) * (size_t)words * (size_t)*max_steps, rows, true};
-  return GRLX_OK;
-}
-
+// (the outputs and the chunk of an admitted call: batch_episodes, grlx_read.h, shared with the LSPI context)
 int fqi_evaluate_impl(grlx_fqi_ctx *ctx, const char *who, const char *sibling, int first_replica, int n_replicas, const double *states, int n_starts,
                       int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state, double *records)
 {
   if (int rc = fqi_evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps)) return rc;
-  FqiEpisodes e;
-  if (int rc = fqi_episodes(e, who, sibling, n_replicas, n_starts, &max_steps, ret, disc, steps, terminal, ties, final_state, {}, records, kFqiTrajWords))
+  BatchEpisodes e;
+  if (int rc = batch_episodes(e, who, sibling, kFqiS, n_replicas, n_starts, &max_steps, ret, disc, steps, terminal, ties, final_state, {}, records, kFqiTrajWords))
     return rc;
   if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
   HIP_TRY(hipDeviceSynchronize());
@@ -117,12 +72,12 @@ int fqi_evaluate_ensemble_impl(grlx_fqi_ctx *ctx, const char *who, const char *s
                                int32_t *ties, int64_t *member_ties, int64_t *agreement, double *final_state, double *records)
 {
   if (int rc = fqi_evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps)) return rc;
-  if (int rc = fqi_ensemble_admit(who, n_replicas, group_size)) return rc;
+  if (int rc = batch_ensemble_admit(who, n_replicas, group_size)) return rc;
   if (rule != GRLX_ENSEMBLE_VOTE && rule != GRLX_ENSEMBLE_MEAN_Q)
     return fail(GRLX_ERR_INVALID, "%s: rule = %d is neither GRLX_ENSEMBLE_VOTE (0) nor GRLX_ENSEMBLE_MEAN_Q (1)", who, rule);
   const int groups = n_replicas / group_size;
-  FqiEpisodes e;
-  if (int rc = fqi_episodes(e, who, sibling, groups, n_starts, &max_steps, ret, disc, steps, terminal, ties, final_state, {member_ties, agreement}, records,
+  BatchEpisodes e;
+  if (int rc = batch_episodes(e, who, sibling, kFqiS, groups, n_starts, &max_steps, ret, disc, steps, terminal, ties, final_state, {member_ties, agreement}, records,
                             kFqiEnsTrajWords))
     return rc;
   if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
@@ -172,8 +127,8 @@ int fqi_evaluate_sampled_impl(grlx_fqi_ctx *ctx, const char *who, const char *si
 {
   if (int rc = fqi_evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps)) return rc;
   if (int rc = fqi_sampled_admit(who, n_replicas, n_starts, sampler, epsilon, streams)) return rc;
-  FqiEpisodes e;
-  if (int rc = fqi_episodes(e, who, sibling, n_replicas, n_starts, &max_steps, ret, disc, steps, terminal, ties, final_state, {}, records, kFqiSampledTrajWords,
+  BatchEpisodes e;
+  if (int rc = batch_episodes(e, who, sibling, kFqiS, n_replicas, n_starts, &max_steps, ret, disc, steps, terminal, ties, final_state, {}, records, kFqiSampledTrajWords,
                             {ReadOut{explored, sizeof(int32_t), n_replicas, true}, ReadOut{streams_out, 2 * sizeof(uint64_t), n_replicas, true}},
                             2 * sizeof(uint64_t)))
     return rc;
@@ -196,7 +151,7 @@ int fqi_evaluate_sampled_impl(grlx_fqi_ctx *ctx, const char *who, const char *si
 int fqi_ensemble_sampled_admit(const char *who, int n_replicas, int group_size, int n_starts, int strategy, double tau, int member, double member_param,
                                const uint64_t *streams)
 {
-  if (int rc = fqi_ensemble_admit(who, n_replicas, group_size)) return rc;
+  if (int rc = batch_ensemble_admit(who, n_replicas, group_size)) return rc;
   if (strategy != GRLX_ENSEMBLE_MAJORITY && strategy != GRLX_ENSEMBLE_RANK)
     return fail(GRLX_ERR_INVALID, "%s: unknown strategy %d (GRLX_ENSEMBLE_MAJORITY = 0, GRLX_ENSEMBLE_RANK = 1)", who, strategy);
   if (!std::isfinite(tau) || !(tau > 0.)) return fail(GRLX_ERR_INVALID, "%s: tau = %g is not a finite temperature above 0", who, tau);
@@ -230,8 +185,8 @@ int fqi_evaluate_ensemble_sampled_impl(grlx_fqi_ctx *ctx, const char *who, const
   if (int rc = fqi_evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps)) return rc;
   if (int rc = fqi_ensemble_sampled_admit(who, n_replicas, group_size, n_starts, strategy, tau, member, member_param, streams)) return rc;
   const int groups = n_replicas / group_size;
-  FqiEpisodes e;
-  if (int rc = fqi_episodes(e, who, sibling, groups, n_starts, &max_steps, ret, disc, steps, terminal, ties, final_state, {member_ties, agreement}, records,
+  BatchEpisodes e;
+  if (int rc = batch_episodes(e, who, sibling, kFqiS, groups, n_starts, &max_steps, ret, disc, steps, terminal, ties, final_state, {member_ties, agreement}, records,
                             kFqiEnsSampledTrajWords,
                             {ReadOut{explored, sizeof(int32_t), groups, true}, ReadOut{streams_out, sizeof(uint64_t), groups, true}}, sizeof(uint64_t)))
     return rc;
@@ -487,7 +442,7 @@ int grlx_fqi_query_ensemble(grlx_fqi_ctx *ctx, int first_replica, int n_replicas
   if (!ctx) return fail(GRLX_ERR_INVALID, "%s: ctx is null", who);
   if (!out) return fail(GRLX_ERR_INVALID, "%s: out is null", who);
   if (int rc = fqi_query_admit(ctx, who, first_replica, n_replicas, obs, n_obs)) return rc;
-  if (int rc = fqi_ensemble_admit(who, n_replicas, group_size)) return rc;
+  if (int rc = batch_ensemble_admit(who, n_replicas, group_size)) return rc;
   if (n_obs == 0 || n_replicas == 0) return GRLX_OK;
   HIP_TRY(hipDeviceSynchronize());
   const int groups = n_replicas / group_size;

@@ -1,9 +1,11 @@
 // grlx_api_lspi.cpp -- the C ABI declared in include/grlx.h: least-squares policy iteration on the batch path (grlx_lspi_*) -- its
-// context, a batch, the getters and the policy query (the kernels: grlx_lspi.hip; the specification: grlx_lspi.h).
+// context, a batch, the getters, the policy query (the kernels: grlx_lspi.hip; the specification: grlx_lspi.h), and the rest of its read
+// side: greedy episodes and their trajectories, per replica and per group of replicas (the kernels: grlx_lspi_evaluate.hip).
 #include <memory>
 #include "grlx_host.h"
 #include "grlx_read.h"
 #include "grlx_lspi.h"
+#include "grlx_lspi_evaluate.h"
 
 struct grlx_lspi_ctx {
   grlx_lspi_config cfg;
@@ -64,6 +66,70 @@ int lspi_replica_ok(const grlx_lspi_ctx *ctx, const char *who, int replica)
   if (!ctx) return fail(GRLX_ERR_INVALID, "%s: ctx is null", who);
   if (replica < 0 || replica >= ctx->L.R) return fail(GRLX_ERR_INVALID, "%s: replica %d is outside the context's %d replicas", who, replica, ctx->L.R);
   return GRLX_OK;
+}
+
+// what both queries check before they touch the device
+int lspi_query_admit(const grlx_lspi_ctx *ctx, const char *who, int first_replica, int n_replicas, const double *obs, int n_obs)
+{
+  if (!obs) return fail(GRLX_ERR_INVALID, "%s: obs is null", who);
+  if (n_obs < 0) return fail(GRLX_ERR_INVALID, "%s: n_obs = %d", who, n_obs);
+  if (int rc = replica_range_ok(who, ctx->L.R, first_replica, n_replicas)) return rc;
+  for (int o = 0; o < n_obs; ++o)
+    for (int d = 0; d < kLspiD; ++d)
+      if (!std::isfinite(obs[(size_t)o * kLspiD + d])) return fail(GRLX_ERR_INVALID, "%s: observation row %d, dimension %d is not finite", who, o, d);
+  return GRLX_OK;
+}
+
+// ---- greedy evaluation episodes, after grlx_api_fqi.cpp's: one per (replica, start state) pair, or per (group, start state) pair on the
+// group's vote or mean Q.  The kernels write every output of a pair, and behind an episode's end the zeros of its records, themselves.
+int lspi_evaluate_admit(grlx_lspi_ctx *ctx, const char *who, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps)
+{
+  if (!ctx) return fail(GRLX_ERR_INVALID, "%s: ctx is null", who);
+  return episode_pairs_ok(who, ctx->L.R, kLspiS, first_replica, n_replicas, states, n_starts, max_steps);
+}
+
+int lspi_evaluate_impl(grlx_lspi_ctx *ctx, const char *who, const char *sibling, int first_replica, int n_replicas, const double *states, int n_starts,
+                       int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state, double *records)
+{
+  if (int rc = lspi_evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps)) return rc;
+  BatchEpisodes e;
+  if (int rc = batch_episodes(e, who, sibling, kLspiS, n_replicas, n_starts, &max_steps, ret, disc, steps, terminal, ties, final_state, {}, records, kLspiTrajWords))
+    return rc;
+  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  return chunked_read(kPlainRead, e.outs, e.n_outs, n_starts, states, kLspiS, e.chunk, true, [&](int nc, const double *dst, const DevPtr *d) -> int {
+    LspiEvalArgs A;
+    A.first_replica = first_replica; A.n_starts = nc; A.max_steps = max_steps; A.states = dst;
+    A.ret = d[0].as<double>(); A.disc = d[1].as<double>(); A.steps = d[2].as<int32_t>(); A.terminal = d[3].as<int32_t>(); A.ties = d[4].as<int32_t>();
+    A.final_state = d[5].as<double>(); A.records = d[6].as<double>();      // (past the outputs: null, the sums alone)
+    HIP_TRY(launch_lspi_evaluate(ctx->L, A, n_replicas, nullptr));
+    return GRLX_OK;
+  });
+}
+
+int lspi_evaluate_ensemble_impl(grlx_lspi_ctx *ctx, const char *who, const char *sibling, int first_replica, int n_replicas, int group_size, int rule,
+                                const double *states, int n_starts, int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal,
+                                int32_t *ties, int64_t *member_ties, int64_t *agreement, double *final_state, double *records)
+{
+  if (int rc = lspi_evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps)) return rc;
+  if (int rc = batch_ensemble_admit(who, n_replicas, group_size)) return rc;
+  if (rule != GRLX_ENSEMBLE_VOTE && rule != GRLX_ENSEMBLE_MEAN_Q)
+    return fail(GRLX_ERR_INVALID, "%s: rule = %d is neither GRLX_ENSEMBLE_VOTE (0) nor GRLX_ENSEMBLE_MEAN_Q (1)", who, rule);
+  const int groups = n_replicas / group_size;
+  BatchEpisodes e;
+  if (int rc = batch_episodes(e, who, sibling, kLspiS, groups, n_starts, &max_steps, ret, disc, steps, terminal, ties, final_state, {member_ties, agreement}, records,
+                             kLspiEnsTrajWords))
+    return rc;
+  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  return chunked_read(kPlainRead, e.outs, e.n_outs, n_starts, states, kLspiS, e.chunk, true, [&](int nc, const double *dst, const DevPtr *d) -> int {
+    LspiEnsArgs A;
+    A.first_replica = first_replica; A.group_size = group_size; A.rule = rule; A.n_starts = nc; A.max_steps = max_steps; A.states = dst;
+    A.ret = d[0].as<double>(); A.disc = d[1].as<double>(); A.steps = d[2].as<int32_t>(); A.terminal = d[3].as<int32_t>(); A.ties = d[4].as<int32_t>();
+    A.final_state = d[5].as<double>(); A.member_ties = d[6].as<int64_t>(); A.agreement = d[7].as<int64_t>(); A.records = d[8].as<double>();
+    HIP_TRY(launch_lspi_evaluate_ensemble(ctx->L, A, groups, nullptr));
+    return GRLX_OK;
+  });
 }
 
 } // namespace
@@ -296,6 +362,68 @@ int grlx_lspi_query(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, const
     HIP_TRY(launch_lspi_query(ctx->L, first_replica, n_replicas, dobs, nc, d[0].as<double>(), nullptr));
     return GRLX_OK;
   });
+}
+
+// grlx_query_ensemble's columns over groups of group_size consecutive replicas: out[group][n_obs][2 + 2 A]
+int grlx_lspi_query_ensemble(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, int group_size, const double *obs, int n_obs, double *out)
+{
+  const char *who = "grlx_lspi_query_ensemble";
+  if (!ctx) return fail(GRLX_ERR_INVALID, "%s: ctx is null", who);
+  if (!out) return fail(GRLX_ERR_INVALID, "%s: out is null", who);
+  if (int rc = lspi_query_admit(ctx, who, first_replica, n_replicas, obs, n_obs)) return rc;
+  if (int rc = batch_ensemble_admit(who, n_replicas, group_size)) return rc;
+  if (n_obs == 0 || n_replicas == 0) return GRLX_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  const int groups = n_replicas / group_size;
+  const size_t elem = sizeof(double) * (2 + 2 * (size_t)ctx->L.A);
+  const int chunk = query_chunk(n_obs, sizeof(double) * kLspiD + elem * (size_t)groups);
+  const ReadOut outs[1] = {{out, elem, groups, true}};
+  return chunked_read(kPlainRead, outs, 1, n_obs, obs, kLspiD, chunk, false, [&](int nc, const double *dobs, const DevPtr *d) -> int {
+    HIP_TRY(launch_lspi_query_ensemble(ctx->L, first_replica, groups, group_size, dobs, nc, d[0].as<double>(), nullptr));
+    return GRLX_OK;
+  });
+}
+
+int grlx_lspi_evaluate(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, double *ret, double *disc,
+                       int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state)
+{
+  return lspi_evaluate_impl(ctx, "grlx_lspi_evaluate", nullptr, first_replica, n_replicas, states, n_starts, max_steps, ret, disc, steps, terminal, ties,
+                            final_state, nullptr);
+}
+
+int grlx_lspi_trajectory_record_words(grlx_lspi_ctx *ctx)
+{
+  if (!ctx) return fail(GRLX_ERR_INVALID, "grlx_lspi_trajectory_record_words: ctx is null");
+  return kLspiTrajWords;
+}
+
+int grlx_lspi_evaluate_trajectory(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, double *ret,
+                                  double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state, double *records)
+{
+  return lspi_evaluate_impl(ctx, "grlx_lspi_evaluate_trajectory", "grlx_lspi_evaluate", first_replica, n_replicas, states, n_starts, max_steps, ret, disc,
+                            steps, terminal, ties, final_state, records);
+}
+
+int grlx_lspi_evaluate_ensemble(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule, const double *states, int n_starts,
+                                int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, int64_t *member_ties,
+                                int64_t *agreement, double *final_state)
+{
+  return lspi_evaluate_ensemble_impl(ctx, "grlx_lspi_evaluate_ensemble", nullptr, first_replica, n_replicas, group_size, rule, states, n_starts, max_steps,
+                                     ret, disc, steps, terminal, ties, member_ties, agreement, final_state, nullptr);
+}
+
+int grlx_lspi_ensemble_trajectory_record_words(grlx_lspi_ctx *ctx)
+{
+  if (!ctx) return fail(GRLX_ERR_INVALID, "grlx_lspi_ensemble_trajectory_record_words: ctx is null");
+  return kLspiEnsTrajWords;
+}
+
+int grlx_lspi_evaluate_ensemble_trajectory(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule, const double *states,
+                                           int n_starts, int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                                           int64_t *member_ties, int64_t *agreement, double *final_state, double *records)
+{
+  return lspi_evaluate_ensemble_impl(ctx, "grlx_lspi_evaluate_ensemble_trajectory", "grlx_lspi_evaluate_ensemble", first_replica, n_replicas, group_size,
+                                     rule, states, n_starts, max_steps, ret, disc, steps, terminal, ties, member_ties, agreement, final_state, records);
 }
 
 } // extern "C"

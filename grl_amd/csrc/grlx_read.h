@@ -2,6 +2,7 @@
 // neither: the staging bound, the skeleton that takes a call's columns through the device a chunk at a time, and the rules both sides
 // state about replica ranges, start states and records.  Host code only.
 #pragma once
+#include <initializer_list>
 #include "grlx_host.h"
 
 namespace grlx {
@@ -164,6 +165,53 @@ inline int trajectory_admit(const char *who, const char *sibling, const void *re
                 "the staging bound of %llu bytes: ask for fewer replicas per call, a smaller max_steps, or raise the bound with grlx_set_query_chunk_bytes", who,
                 (unsigned long long)column, rows, max_steps, R, (unsigned long long)(column + in_and_sums), (unsigned long long)g_query_chunk_bytes);
   *chunk = rows ? query_chunk(n_starts, (size_t)column + in_and_sums) : n_starts;
+  return GRLX_OK;
+}
+
+// ---- what the two batch contexts' episode calls (grlx_fqi_evaluate*, grlx_lspi_evaluate*) share
+// what their grouped calls check after their single-policy sibling's rules
+inline int batch_ensemble_admit(const char *who, int n_replicas, int group_size)
+{
+  if (int rc = group_size_ok(who, group_size)) return rc;
+  if (n_replicas % group_size != 0)
+    return fail(GRLX_ERR_INVALID, "%s: n_replicas = %d is not a multiple of group_size = %d", who, n_replicas, group_size);
+  return GRLX_OK;
+}
+
+// An admitted episode call over `rows` replicas or groups of a batch context whose model state has S components, as the skeleton takes
+// it: the start states per chunk and the outputs -- the six every call has, `own` (the ensemble's two), `more` (the sampled calls':
+// explored, the streams after), the records of `words` doubles per step.  sibling null: the sums alone, max_steps = 0 is the cap; else
+// trajectory_admit's checks come first.  in_bytes: what a pair stages beside its start state (the streams that go in).
+struct BatchEpisodes {
+  int     chunk = 0, n_outs = 0;
+  ReadOut outs[kMaxReadOuts];
+};
+inline int batch_episodes(BatchEpisodes &e, const char *who, const char *sibling, int S, int rows, int n_starts, int *max_steps, double *ret, double *disc,
+                          int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state, std::initializer_list<int64_t *> own, double *records,
+                          int words, std::initializer_list<ReadOut> more = {}, size_t in_bytes = 0)
+{
+  size_t extra = own.size() * sizeof(int64_t) + in_bytes;
+  for (const ReadOut &o : more) extra += o.elem;
+  const size_t in_and_sums = episode_start_bytes(S, rows, extra);
+  // the launches read d[6 + own + more] for the records whether they were asked for or not: that slot exists in the skeleton's arrays
+  if (6 + own.size() + more.size() + 1 > (size_t)kMaxReadOuts)
+    return fail(GRLX_ERR_INVALID, "%s: %zu outputs exceed the read skeleton's kMaxReadOuts = %d", who, 6 + own.size() + more.size() + 1, kMaxReadOuts);
+  if (sibling)
+  {
+    if (int rc = trajectory_admit(who, sibling, records, *max_steps, rows, n_starts, words, in_and_sums, &e.chunk)) return rc;
+  }
+  else
+  {
+    if (*max_steps == 0) *max_steps = GRLX_MAX_EPISODE_STEPS;
+    e.chunk = query_chunk(n_starts, in_and_sums);
+  }
+  for (const ReadOut &o : {ReadOut{ret, sizeof(double), rows, true}, ReadOut{disc, sizeof(double), rows, true}, ReadOut{steps, sizeof(int32_t), rows, true},
+                           ReadOut{terminal, sizeof(int32_t), rows, true}, ReadOut{ties, sizeof(int32_t), rows, true},
+                           ReadOut{final_state, sizeof(double) * (size_t)S, rows, true}})
+    e.outs[e.n_outs++] = o;
+  for (int64_t *p : own) e.outs[e.n_outs++] = {p, sizeof(int64_t), rows, true};
+  for (const ReadOut &o : more) e.outs[e.n_outs++] = o;
+  if (sibling) e.outs[e.n_outs++] = {records, sizeof(double) * (size_t)words * (size_t)*max_steps, rows, true};
   return GRLX_OK;
 }
 

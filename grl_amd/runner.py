@@ -1418,15 +1418,96 @@ class LspiRunner:
         obs = np.ascontiguousarray(obs, dtype=np.float64)
         if obs.ndim != 2 or obs.shape[1] != 2:
             raise ValueError(f"expected observations of shape (n, 2), got {obs.shape}")
-        if replicas is None:
-            first, count = 0, self.cfg.n_replicas
-        elif isinstance(replicas, range):
-            first, count = replicas.start, len(replicas)
-        else:
-            first, count = (int(x) for x in replicas)
+        first, count = self._replica_range(replicas)
         q = np.zeros((count, obs.shape[0], self.cfg.action_steps), np.float64)
         capi.check(self.lib.grlx_lspi_query(self._ctx, first, count, _ptr(obs, C.c_double), obs.shape[0], _ptr(q, C.c_double)))
         return q
+
+    def _replica_range(self, replicas):
+        if replicas is None:
+            return 0, self.cfg.n_replicas
+        if isinstance(replicas, range):
+            return replicas.start, len(replicas)
+        first, count = (int(x) for x in replicas)
+        return first, count
+
+    # ---- greedy evaluation episodes and the ensemble over groups of replicas: FqiRunner's calls of the same names restated
+    STATE_DIMS = 3          # the pendulum's model state: angle, velocity, time
+
+    def evaluate(self, states, replicas=None, max_steps=0):
+        """One greedy episode of the solved policy per (replica, start state) pair, on the device, from states[n][3] (angle, velocity,
+        time) to its end or to max_steps (0 = GRLX_MAX_EPISODE_STEPS): Evaluation(ret, disc, steps, terminal, ties, final_state), each
+        [replica][start], as FqiRunner.evaluate defines them.  The context is not changed (include/grlx.h: grlx_lspi_evaluate)."""
+        states = _state_rows(states, self.STATE_DIMS)
+        first, count = self._replica_range(replicas)
+        n = states.shape[0]
+        out, ptrs = _episode_outputs(count, n, self.STATE_DIMS, "ret disc steps terminal ties final_state")
+        capi.check(self.lib.grlx_lspi_evaluate(self._ctx, first, count, _ptr(states, C.c_double), n, int(max_steps), *ptrs))
+        return Evaluation(*out)
+
+    def trajectory_record_words(self):
+        """R = 11, the doubles of one trajectory record (grlx_lspi_trajectory_record_words)"""
+        return capi.check(self.lib.grlx_lspi_trajectory_record_words(self._ctx))
+
+    def evaluate_trajectory(self, states, max_steps, replicas=None):
+        """LspiRunner.evaluate with every step of every episode: Trajectory(..., records), records[replica][start][max_steps][11] with
+        one record per step taken and zeros behind an episode's end (include/grlx.h: grlx_lspi_evaluate_trajectory)."""
+        states = _state_rows(states, self.STATE_DIMS)
+        first, count = self._replica_range(replicas)
+        n, max_steps = states.shape[0], int(max_steps)
+        out, ptrs = _episode_outputs(count, n, self.STATE_DIMS, "ret disc steps terminal ties final_state",
+                                     records=(max_steps, self.trajectory_record_words()))
+        capi.check(self.lib.grlx_lspi_evaluate_trajectory(self._ctx, first, count, _ptr(states, C.c_double), n, max_steps, *ptrs))
+        return Trajectory(*out)
+
+    def _groups(self, replicas, group_size):
+        first, count = self._replica_range(replicas)
+        group_size = max(count, 1) if group_size is None else int(group_size)      # an empty range is GRLX_OK with nothing written
+        return first, count, group_size, (count // group_size if group_size > 0 else 0)
+
+    def query_ensemble_raw(self, obs, group_size=None, replicas=None):
+        """grlx_lspi_query_ensemble as it is: out[group][obs][2 + 2A] = {sum value, sum value^2, sum q[0..A), votes[0..A)}, every sum over
+        the group's replicas in ascending order (FqiRunner.query_ensemble_raw's columns)."""
+        obs = np.ascontiguousarray(obs, dtype=np.float64)
+        if obs.ndim != 2 or obs.shape[1] != 2:
+            raise ValueError(f"expected observations of shape (n, 2), got {obs.shape}")
+        first, count, group_size, groups = self._groups(replicas, group_size)
+        out = np.zeros((groups, obs.shape[0], 2 + 2 * int(self.cfg.action_steps)), np.float64)
+        capi.check(self.lib.grlx_lspi_query_ensemble(self._ctx, first, count, group_size, _ptr(obs, C.c_double), obs.shape[0], _ptr(out, C.c_double)))
+        return out
+
+    def query_ensemble(self, obs, group_size=None, replicas=None):
+        """Ensemble statistics per group of `group_size` consecutive replicas (default: one group of all) and observation."""
+        group_size = self._groups(replicas, group_size)[2]
+        return EnsembleResult(self.query_ensemble_raw(obs, group_size, replicas), group_size, int(self.cfg.action_steps))
+
+    def evaluate_ensemble(self, states, group_size, rule="vote", replicas=None, max_steps=0):
+        """One greedy episode per (group of `group_size` consecutive replicas, start state) pair on the first maximum of the members' votes
+        (rule "vote") or summed Q (rule "mean"), members in ascending order: EnsembleEvaluation(ret, disc, steps, terminal, ties,
+        member_ties, agreement, final_state), each [group][start].  The context is not changed (grlx_lspi_evaluate_ensemble)."""
+        rule = _rule(rule)
+        states = _state_rows(states, self.STATE_DIMS)
+        first, count, group_size, groups = self._groups(replicas, group_size)
+        n = states.shape[0]
+        out, ptrs = _episode_outputs(groups, n, self.STATE_DIMS, _ENSEMBLE_FIELDS, member_ties=np.int64, agreement=np.int64)
+        capi.check(self.lib.grlx_lspi_evaluate_ensemble(self._ctx, first, count, group_size, rule, _ptr(states, C.c_double), n, int(max_steps), *ptrs))
+        return EnsembleEvaluation(*out)
+
+    def ensemble_trajectory_record_words(self):
+        """R = 13, the doubles of one record of the ensemble's trajectory (grlx_lspi_ensemble_trajectory_record_words)"""
+        return capi.check(self.lib.grlx_lspi_ensemble_trajectory_record_words(self._ctx))
+
+    def evaluate_ensemble_trajectory(self, states, group_size, max_steps, rule="vote", replicas=None):
+        """LspiRunner.evaluate_ensemble with every step of every episode: EnsembleTrajectory(..., records), records[group][start]
+        [max_steps][13] (include/grlx.h: grlx_lspi_evaluate_ensemble_trajectory)."""
+        rule = _rule(rule)
+        states = _state_rows(states, self.STATE_DIMS)
+        first, count, group_size, groups = self._groups(replicas, group_size)
+        n, max_steps = states.shape[0], int(max_steps)
+        out, ptrs = _episode_outputs(groups, n, self.STATE_DIMS, _ENSEMBLE_FIELDS, member_ties=np.int64, agreement=np.int64,
+                                     records=(max_steps, self.ensemble_trajectory_record_words()))
+        capi.check(self.lib.grlx_lspi_evaluate_ensemble_trajectory(self._ctx, first, count, group_size, rule, _ptr(states, C.c_double), n, max_steps, *ptrs))
+        return EnsembleTrajectory(*out)
 
     def info(self, replica: int):
         n = C.c_int64(); done = C.c_int64(); st = C.c_uint32(); ties = C.c_int64(); rng = (C.c_uint64 * 2)()

@@ -1103,8 +1103,8 @@ int  grlx_fqi_evaluate_ensemble_sampled_trajectory(grlx_fqi_ctx *ctx, int first_
  * deviations; the read with products and sums rounded separately; A = 1e-5 I + Phi^T Phi - Phi^T Psi and b = Phi^T r on the f64 matrix
  * instruction in a fixed order; LU with partial pivoting (first largest magnitude, lowest row on equal magnitude) -- is specified at
  * the top of grl_amd/csrc/grlx_lspi.h and in DESIGN.md section 4.4.
- * NOT BUILT: projector/monomial; the YAML host layer for predictor/lspi; evaluation episodes from caller-chosen states; ensembles;
- * snapshots; several GPUs. */
+ * NOT BUILT: projector/monomial; the YAML host layer for predictor/lspi; sampled episodes (the tie-breaking draw, epsilon-greedy, the
+ * draw from a group's votes); streamed trajectories; snapshots; several GPUs; tasks other than the pendulum's swing-up. */
 #define GRLX_RBF_TRIANGLE 0
 #define GRLX_RBF_GAUSS    1
 typedef struct {
@@ -1153,6 +1153,51 @@ int  grlx_lspi_get_system(grlx_lspi_ctx *ctx, int replica, double *A, double *b)
 /* q[n_replicas][n_obs][action_steps] = Q(s, a_k) on the replicas' CURRENT weights at obs[n_obs][2], validated and staged as
  * grlx_fqi_query; changes nothing in the context */
 int  grlx_lspi_query(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, const double *obs /*[n_obs][2]*/, int n_obs, double *q);
+/* The LSPI context's greedy evaluation episodes, their per-step trajectories and the ensemble over groups of replicas: grlx_fqi_evaluate,
+ * grlx_fqi_evaluate_trajectory, grlx_fqi_query_ensemble, grlx_fqi_evaluate_ensemble and grlx_fqi_evaluate_ensemble_trajectory (above)
+ * restated word for word for a grlx_lspi_ctx -- arguments, outputs, refusals (entry point and reason named, before anything is
+ * launched), staging in chunks of start states or observations under grlx_set_query_chunk_bytes' bound.  states[n_starts][3] are MODEL
+ * states of the pendulum (angle, velocity, time); pair = (replica - first_replica) * n_starts + start.
+ *   The step.   q[k] = the read of S5 (grl_amd/csrc/grlx_lspi.h) at (obs, actions[k]), k < action_steps, on the replica's CURRENT weights
+ *               (which = 0) by the operations of grlx_lspi_query: the unpruned projection, products and sums rounded separately, in the
+ *               projection's order, from 0.  (mai, man) = the first maximum and the number of maxima (strict >, counting ==);
+ *               actions[mai] acts; ties += (man > 1); the pendulum's step; ret += reward; disc += g * reward; g = g * gamma^control_step.
+ *               The start state's own terminal code is ignored.  With ties == 0 an episode from (pi, 0, 0) returns, as ret, the reward of
+ *               the row the last batch wrote, bit for bit.
+ *   terminal    0 cut at max_steps, 1 timed out, 2 absorbing, 3 left the portable math's domain.  max_steps: 1 ... GRLX_MAX_EPISODE_STEPS,
+ *               0 = that cap, except where it sizes the records: there 0 and a null records are refused.
+ *   records     grlx_lspi_evaluate_trajectory: records[n_replicas][n_starts][max_steps][11], the GRLX_TRAJ_* words, value = q[mai];
+ *               grlx_lspi_evaluate_ensemble_trajectory: records[groups][n_starts][max_steps][13], the GRLX_TRAJ_* and GRLX_TRAJ_ENS_*
+ *               words, value = (double)votes[mai] or sumq[mai].  Records at index >= the pair's steps are all-zero bits.
+ *   The ensemble.  Groups of group_size CONSECUTIVE replicas (an LspiRunner's replicas are independently seeded solutions fitted to
+ *               independently drawn transitions); members in ASCENDING replica order: votes[mai_m] += 1; sumq[k] += q_m[k], one
+ *               accumulator per action from 0.0; member_ties += (man_m > 1).  score = votes (GRLX_ENSEMBLE_VOTE) or sumq
+ *               (GRLX_ENSEMBLE_MEAN_Q); its first maximum acts; agreement += votes[mai].  group_size == 1 is grlx_lspi_evaluate bit for bit.
+ *               grlx_lspi_query_ensemble: out[groups][n_obs][2 + 2 * action_steps], grlx_fqi_query_ensemble's columns.
+ * Host pointers; any output but records may be NULL.  The calls wait for the device, are allowed before the first grlx_lspi_run_batch
+ * and CHANGE NOTHING in the context: no row, no counter, no stream, no status bit, no weight.
+ * Refused (GRLX_ERR_INVALID, nothing written): a null ctx, null states / obs / out, n_starts or n_obs < 0, the replica range, max_steps out
+ * of range, a state component that is not finite or reaches 2^17 in magnitude, an observation that is not finite, group_size < 1,
+ * n_replicas % group_size != 0, an unknown rule, a start state's column of records beyond the staging bound (remedies named).
+ * n_starts == 0, n_obs == 0 or n_replicas == 0: GRLX_OK, nothing written. */
+int  grlx_lspi_evaluate(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][3]*/, int n_starts, int max_steps,
+                        double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state);
+int  grlx_lspi_trajectory_record_words(grlx_lspi_ctx *ctx);      /* R = 11; a negative status for a null ctx */
+int  grlx_lspi_evaluate_trajectory(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][3]*/, int n_starts,
+                                   int max_steps, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, double *final_state,
+                                   double *records /*[n_replicas][n_starts][max_steps][R]*/);
+int  grlx_lspi_query_ensemble(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, int group_size, const double *obs /*[n_obs][2]*/, int n_obs,
+                              double *out);
+int  grlx_lspi_evaluate_ensemble(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule,
+                                 const double *states /*[n_starts][3]*/, int n_starts, int max_steps,
+                                 double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                                 int64_t *member_ties, int64_t *agreement, double *final_state);
+int  grlx_lspi_ensemble_trajectory_record_words(grlx_lspi_ctx *ctx);      /* R = 13; a negative status for a null ctx */
+int  grlx_lspi_evaluate_ensemble_trajectory(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, int group_size, int rule,
+                                            const double *states /*[n_starts][3]*/, int n_starts, int max_steps,
+                                            double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                                            int64_t *member_ties, int64_t *agreement, double *final_state,
+                                            double *records /*[n_replicas / group_size][n_starts][max_steps][R]*/);
 /* state of a replica: transitions stored, batches done, its status bits, the steps of its test trials at which the maximum was not
  * unique, RNG streams {global, thread-local}; any pointer may be NULL */
 int  grlx_lspi_info(grlx_lspi_ctx *ctx, int replica, int64_t *n_transitions, int64_t *batches_done, uint32_t *status, int64_t *ties, uint64_t rng[2]);
