@@ -14,7 +14,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libgrlx.so")
 # the C ABI (include/grlx.h), one unit per subject; they share grlx_host.h
 API_UNITS = ["grlx_api_config.cpp", "grlx_api_context.cpp", "grlx_api_run.cpp", "grlx_api_tables.cpp", "grlx_api_step.cpp", "grlx_api_read.cpp", "grlx_api_fqi.cpp", "grlx_api_lspi.cpp", "grlx_api_snapshot.cpp"]
-SOURCES = ["grlx_kernels.hip", "grlx_fqi.hip", "grlx_lspi.hip", "grlx_lspi_evaluate.hip", "grlx_snapshot.hip", "grlx_query.hip", "grlx_evaluate.hip", "grlx_evaluate_sampled.hip", "grlx_evaluate_noisy.hip", "grlx_evaluate_actor_ensemble.hip", "grlx_evaluate_ensemble_sampled.hip", "grlx_evaluate_stream.hip"] + API_UNITS + ["grlx_plan.cpp", "grlx_snapshot_format.cpp"]
+SOURCES = ["grlx_kernels.hip", "grlx_fqi.hip", "grlx_lspi.hip", "grlx_lspi_evaluate.hip", "grlx_lspi_evaluate_sampled.hip", "grlx_snapshot.hip", "grlx_query.hip", "grlx_evaluate.hip", "grlx_evaluate_sampled.hip", "grlx_evaluate_noisy.hip", "grlx_evaluate_actor_ensemble.hip", "grlx_evaluate_ensemble_sampled.hip", "grlx_evaluate_stream.hip"] + API_UNITS + ["grlx_plan.cpp", "grlx_snapshot_format.cpp"]
 GRLX_H = os.path.join("..", "..", "include", "grlx.h")
 # what grlx_kernels.hip includes
 HEADERS = ["grlx_internal.h", "grlx_math.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_envs.h", "grlx_policy.h", "grlx_update.h", "grlx_frame.h",
@@ -109,17 +109,19 @@ def _build_hip_object(hipcc, src, tmp, flags, verbose, report):
 
 
 # what each translation unit includes (besides itself): an object whose inputs did not change is taken from the object cache
-# (outside the tree: $GRLX_OBJCACHE or /tmp/grlx_objcache), so that editing a unit of the C ABI does not recompile the kernels
-API_DEPS = ["grlx_host.h", "grlx_host_rules.h", "grlx_read.h", "grlx_fqi.h", "grlx_lspi.h", "grlx_lspi_evaluate.h", "grlx_internal.h", "grlx_snapshot.h", "grlx_snapshot_format.h", "grlx_query.h", "grlx_evaluate.h", "grlx_evaluate_sampled.h", "grlx_evaluate_noisy.h", "grlx_evaluate_actor_ensemble.h", "grlx_evaluate_ensemble_sampled.h", "grlx_evaluate_stream.h", GRLX_H,
+# (outside the tree: $GRLX_OBJCACHE or the user's own grlx_objcache-<uid> under the temporary directory), so that editing a unit of the C ABI does not recompile the kernels
+API_DEPS = ["grlx_host.h", "grlx_host_rules.h", "grlx_read.h", "grlx_fqi.h", "grlx_lspi.h", "grlx_lspi_evaluate.h", "grlx_lspi_evaluate_sampled.h", "grlx_internal.h", "grlx_snapshot.h", "grlx_snapshot_format.h", "grlx_query.h", "grlx_evaluate.h", "grlx_evaluate_sampled.h", "grlx_evaluate_noisy.h", "grlx_evaluate_actor_ensemble.h", "grlx_evaluate_ensemble_sampled.h", "grlx_evaluate_stream.h", GRLX_H,
             os.path.join("..", "..", "include", "grlx_diag.h")]
 # what the six units of the evaluation episodes share; grlx_episode.h: their common device helpers and dispatch
 EVALUATE_DEPS = ["grlx_internal.h", "grlx_math.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_envs.h", "grlx_query_weights.h", "grlx_evaluate.h",
                  "grlx_episode.h", GRLX_H]
 UNIT_DEPS = {
     "grlx_kernels.hip": HEADERS,
-    "grlx_fqi.hip": ["grlx_fqi.h", "grlx_internal.h", "grlx_math.h", "grlx_math_batch.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_envs.h", GRLX_H],
+    "grlx_fqi.hip": ["grlx_fqi.h", "grlx_softmax.h", "grlx_internal.h", "grlx_math.h", "grlx_math_batch.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_envs.h", GRLX_H],
     "grlx_lspi.hip": ["grlx_lspi.h", "grlx_lspi_read.h", "grlx_internal.h", "grlx_math.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_envs.h", GRLX_H],
-    "grlx_lspi_evaluate.hip": EVALUATE_DEPS + ["grlx_lspi.h", "grlx_lspi_read.h", "grlx_lspi_evaluate.h"],
+    "grlx_lspi_evaluate.hip": EVALUATE_DEPS + ["grlx_lspi.h", "grlx_lspi_read.h", "grlx_lspi_evaluate.h", "grlx_lspi_quad.h"],
+    "grlx_lspi_evaluate_sampled.hip": EVALUATE_DEPS + ["grlx_lspi.h", "grlx_lspi_read.h", "grlx_lspi_evaluate.h", "grlx_lspi_quad.h", "grlx_softmax.h",
+                                       "grlx_lspi_evaluate_sampled.h"],
     "grlx_snapshot.hip": ["grlx_internal.h", "grlx_snapshot.h", "grlx_snapshot_format.h", GRLX_H],
     "grlx_query.hip": ["grlx_internal.h", "grlx_math.h", "grlx_rng.h", "grlx_tile.h", "grlx_table.h", "grlx_query.h", "grlx_query_weights.h", GRLX_H],
     "grlx_evaluate.hip": EVALUATE_DEPS,
@@ -144,14 +146,30 @@ def _unit_key(name: str, flags) -> str:
     return h.hexdigest()[:24]
 
 
+def _object_cache():
+    """The directory of the object cache, or None where there is none to write to: $GRLX_OBJCACHE, else a directory of this user's own
+    under the temporary directory (one that another user made is not shared: it cannot be written, and its objects are not this user's)."""
+    import sys
+    import tempfile
+    d = os.environ.get("GRLX_OBJCACHE") or os.path.join(tempfile.gettempdir(), "grlx_objcache-%d" % os.getuid())
+    try:
+        os.makedirs(d, mode=0o700, exist_ok=True)
+        why = "it belongs to another user" if os.stat(d).st_uid != os.getuid() else "" if os.access(d, os.W_OK | os.X_OK) else "it cannot be written"
+    except OSError as ex:
+        why = str(ex)
+    if why:
+        print(f"grl_amd._build: the object cache {d} is not used ({why}): every unit is compiled", file=sys.stderr)
+        return None
+    return d
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     """Compile libgrlx.so if missing or older than its sources; return its path."""
     if not force and not _stale():
         return LIB
     import tempfile
     from concurrent.futures import ThreadPoolExecutor
-    cache = os.environ.get("GRLX_OBJCACHE", "/tmp/grlx_objcache")
-    os.makedirs(cache, exist_ok=True)
+    cache = _object_cache()
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         raise RuntimeError("hipcc not found: cannot build the HIP extension")
@@ -161,21 +179,26 @@ def build(force: bool = False, verbose: bool = False) -> str:
     with tempfile.TemporaryDirectory(prefix="grlx_build_") as tmp:
         def one(name):
             src = os.path.join(CSRC, name)
-            key = os.path.join(cache, name + "." + _unit_key(name, flags))
-            if not force and os.path.exists(key + ".o") and (not name.endswith(".hip") or os.path.exists(key + ".report")):
+            key = os.path.join(cache, name + "." + _unit_key(name, flags)) if cache else None
+            if key and not force and os.path.exists(key + ".o") and (not name.endswith(".hip") or os.path.exists(key + ".report")):
                 if name.endswith(".hip"):
                     with open(key + ".report") as f:
                         report[name] = tuple(int(x) for x in f.read().split())
                 return key + ".o"
             if name.endswith(".hip"):
                 obj = _build_hip_object(hipcc, src, tmp, flags, verbose, report)
-                with open(key + ".report", "w") as f:
-                    f.write("%d %d" % report[name])
             else:
                 obj = os.path.join(tmp, os.path.splitext(name)[0] + ".o")
                 _run([hipcc] + flags + [TAG_DEFINE + '"' + PIPELINE + '"', "-c", src, "-o", obj], verbose)
-            shutil.copy(obj, key + ".o")
-            return key + ".o"
+            if key:
+                try:                     # the cache saves time and nothing else: an object that cannot be kept is linked from where it is
+                    if name.endswith(".hip"):
+                        with open(key + ".report", "w") as f:
+                            f.write("%d %d" % report[name])
+                    shutil.copy(obj, key + ".o")
+                except OSError as ex:
+                    print(f"grl_amd._build: {name} is not kept in the object cache ({ex})")
+            return obj
         with ThreadPoolExecutor(max_workers=min(len(SOURCES), 16)) as pool:
             objs = list(pool.map(one, SOURCES))
         _run([hipcc, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", LIB] + objs, verbose)

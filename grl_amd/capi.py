@@ -259,6 +259,21 @@ _SIGS = {
     "grlx_lspi_evaluate_ensemble_trajectory": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _P(C.c_double), C.c_int, C.c_int, _P(C.c_double),
                                                          _P(C.c_double), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64),
                                                          _P(C.c_double), _P(C.c_double)]),
+    "grlx_lspi_evaluate_sampled": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P(C.c_double), C.c_int, C.c_int, C.c_int, C.c_double, _P(C.c_uint64),
+                                             _P(C.c_double), _P(C.c_double), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_double),
+                                             _P(C.c_uint64)]),
+    "grlx_lspi_sampled_trajectory_record_words": (C.c_int, [C.c_void_p]),
+    "grlx_lspi_evaluate_sampled_trajectory": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _P(C.c_double), C.c_int, C.c_int, C.c_int, C.c_double, _P(C.c_uint64),
+                                                        _P(C.c_double), _P(C.c_double), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32),
+                                                        _P(C.c_double), _P(C.c_uint64), _P(C.c_double)]),
+    "grlx_lspi_evaluate_ensemble_sampled": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, _P(C.c_double), C.c_int,
+                                                      C.c_int, _P(C.c_uint64), _P(C.c_double), _P(C.c_double), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32),
+                                                      _P(C.c_int64), _P(C.c_int64), _P(C.c_int32), _P(C.c_double), _P(C.c_uint64)]),
+    "grlx_lspi_ensemble_sampled_trajectory_record_words": (C.c_int, [C.c_void_p]),
+    "grlx_lspi_evaluate_ensemble_sampled_trajectory": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double,
+                                                                 _P(C.c_double), C.c_int, C.c_int, _P(C.c_uint64), _P(C.c_double), _P(C.c_double),
+                                                                 _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64), _P(C.c_int64), _P(C.c_int32),
+                                                                 _P(C.c_double), _P(C.c_uint64), _P(C.c_double)]),
 }
 
 # include/grlx_diag.h: diagnostic exports (tools, tests, bench.py), not part of the boundary
@@ -294,7 +309,10 @@ _NEWER_SIGS = ("grlx_snapshot_size", "grlx_snapshot_save", "grlx_snapshot_load",
                "grlx_lspi_config_pendulum", "grlx_lspi_create", "grlx_lspi_destroy", "grlx_lspi_run_batch", "grlx_lspi_sync", "grlx_lspi_read_rows",
                "grlx_lspi_get_params", "grlx_lspi_get_transitions", "grlx_lspi_get_system", "grlx_lspi_query", "grlx_lspi_info",
                "grlx_lspi_evaluate", "grlx_lspi_trajectory_record_words", "grlx_lspi_evaluate_trajectory", "grlx_lspi_query_ensemble",
-               "grlx_lspi_evaluate_ensemble", "grlx_lspi_ensemble_trajectory_record_words", "grlx_lspi_evaluate_ensemble_trajectory")
+               "grlx_lspi_evaluate_ensemble", "grlx_lspi_ensemble_trajectory_record_words", "grlx_lspi_evaluate_ensemble_trajectory",
+               "grlx_lspi_evaluate_sampled", "grlx_lspi_sampled_trajectory_record_words", "grlx_lspi_evaluate_sampled_trajectory",
+               "grlx_lspi_evaluate_ensemble_sampled", "grlx_lspi_ensemble_sampled_trajectory_record_words",
+               "grlx_lspi_evaluate_ensemble_sampled_trajectory")
 # grlx_kernel_plan flags
 PLAN_STAMPS_IN_PLACE, PLAN_STAMPS_DEFERRED, PLAN_SWEEP, PLAN_SERVER_OFF, PLAN_WALKER_SERVER, PLAN_FITS_YES, PLAN_FITS_NO = 1, 2, 4, 8, 16, 32, 64
 ENSEMBLE_VOTE, ENSEMBLE_MEAN_Q = 0, 1       # grlx_evaluate_ensemble's rule

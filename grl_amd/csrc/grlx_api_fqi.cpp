@@ -92,41 +92,14 @@ int fqi_evaluate_ensemble_impl(grlx_fqi_ctx *ctx, const char *who, const char *s
   });
 }
 
-// ---- sampled episodes: the samplers of one network, the draw from a group's majority or rank votes.  What they check beyond their greedy
-// siblings follows grlx_api_read.cpp's sampled_admit / ensemble_sampled_admit; a batch context has no sampler stream and no epsilon of
-// its own, so what would read them is refused by name.
-int fqi_epsilon_ok(const char *who, double e, const char *of)
-{
-  if (!std::isfinite(e)) return fail(GRLX_ERR_INVALID, "%s: epsilon is not finite (%g)%s", who, e, of);
-  if (e == GRLX_EPSILON_OWN)
-    return fail(GRLX_ERR_INVALID, "%s: GRLX_EPSILON_OWN (-1) is refused: a batch context has no epsilon of its own; name a number in [0, 1]%s", who, of);
-  if (!(e >= 0. && e <= 1.)) return fail(GRLX_ERR_INVALID, "%s: epsilon = %g is outside [0, 1]%s", who, e, of);
-  return GRLX_OK;
-}
-
-int fqi_sampled_admit(const char *who, int n_replicas, int n_starts, int sampler, double epsilon, const uint64_t *streams)
-{
-  if (sampler != GRLX_SAMPLER_GREEDY && sampler != GRLX_SAMPLER_EPSILON_GREEDY)
-    return fail(GRLX_ERR_INVALID, "%s: unknown sampler %d (GRLX_SAMPLER_GREEDY = 0, GRLX_SAMPLER_EPSILON_GREEDY = 1)", who, sampler);
-  if (int rc = fqi_epsilon_ok(who, epsilon, "")) return rc;
-  if (!streams && sampler == GRLX_SAMPLER_EPSILON_GREEDY)
-    return fail(GRLX_ERR_INVALID, "%s: streams is null under GRLX_SAMPLER_EPSILON_GREEDY: a batch context has no sampler stream of its own to copy "
-                "(grlx_episode_streams makes them)", who);
-  if (streams)
-    for (int64_t row = 0; row < (int64_t)n_replicas * n_starts; ++row)
-      for (int w = 0; w < 2; ++w)
-        if (streams[row * 2 + w] >> 48)
-          return fail(GRLX_ERR_INVALID, "%s: stream row %lld (replica %lld, start state %lld), word %d is 0x%llx: a rand48 state is below 2^48", who,
-                      (long long)row, (long long)(row / n_starts), (long long)(row % n_starts), w, (unsigned long long)streams[row * 2 + w]);
-  return GRLX_OK;
-}
-
+// ---- sampled episodes: the samplers of one network, the draw from a group's majority or rank votes; what they check beyond their greedy
+// siblings: grlx_read.h (batch_sampled_admit, batch_ensemble_sampled_admit)
 int fqi_evaluate_sampled_impl(grlx_fqi_ctx *ctx, const char *who, const char *sibling, int first_replica, int n_replicas, const double *states, int n_starts,
                               int max_steps, int sampler, double epsilon, const uint64_t *streams, double *ret, double *disc, int32_t *steps,
                               int32_t *terminal, int32_t *ties, int32_t *explored, double *final_state, uint64_t *streams_out, double *records)
 {
   if (int rc = fqi_evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps)) return rc;
-  if (int rc = fqi_sampled_admit(who, n_replicas, n_starts, sampler, epsilon, streams)) return rc;
+  if (int rc = batch_sampled_admit(who, n_replicas, n_starts, sampler, epsilon, streams)) return rc;
   BatchEpisodes e;
   if (int rc = batch_episodes(e, who, sibling, kFqiS, n_replicas, n_starts, &max_steps, ret, disc, steps, terminal, ties, final_state, {}, records, kFqiSampledTrajWords,
                             {ReadOut{explored, sizeof(int32_t), n_replicas, true}, ReadOut{streams_out, 2 * sizeof(uint64_t), n_replicas, true}},
@@ -148,34 +121,6 @@ int fqi_evaluate_sampled_impl(grlx_fqi_ctx *ctx, const char *who, const char *si
   }, &in_streams);
 }
 
-int fqi_ensemble_sampled_admit(const char *who, int n_replicas, int group_size, int n_starts, int strategy, double tau, int member, double member_param,
-                               const uint64_t *streams)
-{
-  if (int rc = batch_ensemble_admit(who, n_replicas, group_size)) return rc;
-  if (strategy != GRLX_ENSEMBLE_MAJORITY && strategy != GRLX_ENSEMBLE_RANK)
-    return fail(GRLX_ERR_INVALID, "%s: unknown strategy %d (GRLX_ENSEMBLE_MAJORITY = 0, GRLX_ENSEMBLE_RANK = 1)", who, strategy);
-  if (!std::isfinite(tau) || !(tau > 0.)) return fail(GRLX_ERR_INVALID, "%s: tau = %g is not a finite temperature above 0", who, tau);
-  switch (member)
-  {
-    case GRLX_MEMBER_GREEDY: break;
-    case GRLX_MEMBER_EPSILON:
-      if (int rc = fqi_epsilon_ok(who, member_param, " (GRLX_MEMBER_EPSILON)")) return rc;
-      break;
-    case GRLX_MEMBER_SOFTMAX:
-      if (!std::isfinite(member_param) || !(member_param > 0.))
-        return fail(GRLX_ERR_INVALID, "%s: tau_m = %g is not a finite temperature above 0 (GRLX_MEMBER_SOFTMAX)", who, member_param);
-      break;
-    default:
-      return fail(GRLX_ERR_INVALID, "%s: unknown member sampler %d (GRLX_MEMBER_GREEDY = 0, GRLX_MEMBER_EPSILON = 1, GRLX_MEMBER_SOFTMAX = 2)", who, member);
-  }
-  if (streams)
-    for (int64_t row = 0; row < (int64_t)(n_replicas / group_size) * n_starts; ++row)
-      if (streams[row] >> 48)
-        return fail(GRLX_ERR_INVALID, "%s: stream row %lld (group %lld, start state %lld) is 0x%llx: a rand48 state is below 2^48", who, (long long)row,
-                    (long long)(row / n_starts), (long long)(row % n_starts), (unsigned long long)streams[row]);
-  return GRLX_OK;
-}
-
 int fqi_evaluate_ensemble_sampled_impl(grlx_fqi_ctx *ctx, const char *who, const char *sibling, int first_replica, int n_replicas, int group_size, int strategy,
                                        double tau, int member, double member_param, const double *states, int n_starts, int max_steps,
                                        const uint64_t *streams, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
@@ -183,7 +128,7 @@ int fqi_evaluate_ensemble_sampled_impl(grlx_fqi_ctx *ctx, const char *who, const
                                        double *records)
 {
   if (int rc = fqi_evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps)) return rc;
-  if (int rc = fqi_ensemble_sampled_admit(who, n_replicas, group_size, n_starts, strategy, tau, member, member_param, streams)) return rc;
+  if (int rc = batch_ensemble_sampled_admit(who, n_replicas, group_size, n_starts, strategy, tau, member, member_param, streams)) return rc;
   const int groups = n_replicas / group_size;
   BatchEpisodes e;
   if (int rc = batch_episodes(e, who, sibling, kFqiS, groups, n_starts, &max_steps, ret, disc, steps, terminal, ties, final_state, {member_ties, agreement}, records,

@@ -1,11 +1,13 @@
 // grlx_api_lspi.cpp -- the C ABI declared in include/grlx.h: least-squares policy iteration on the batch path (grlx_lspi_*) -- its
 // context, a batch, the getters, the policy query (the kernels: grlx_lspi.hip; the specification: grlx_lspi.h), and the rest of its read
-// side: greedy episodes and their trajectories, per replica and per group of replicas (the kernels: grlx_lspi_evaluate.hip).
+// side: greedy episodes and their trajectories, per replica and per group of replicas (the kernels: grlx_lspi_evaluate.hip), and the
+// sampled ones (grlx_lspi_evaluate_sampled.hip).
 #include <memory>
 #include "grlx_host.h"
 #include "grlx_read.h"
 #include "grlx_lspi.h"
 #include "grlx_lspi_evaluate.h"
+#include "grlx_lspi_evaluate_sampled.h"
 
 struct grlx_lspi_ctx {
   grlx_lspi_config cfg;
@@ -130,6 +132,66 @@ int lspi_evaluate_ensemble_impl(grlx_lspi_ctx *ctx, const char *who, const char 
     HIP_TRY(launch_lspi_evaluate_ensemble(ctx->L, A, groups, nullptr));
     return GRLX_OK;
   });
+}
+
+// ---- sampled episodes, after grlx_api_fqi.cpp's: the samplers of one policy, the draw from a group's majority or rank votes (the kernels:
+// grlx_lspi_evaluate_sampled.hip; what they check beyond their greedy siblings: grlx_read.h)
+int lspi_evaluate_sampled_impl(grlx_lspi_ctx *ctx, const char *who, const char *sibling, int first_replica, int n_replicas, const double *states, int n_starts,
+                               int max_steps, int sampler, double epsilon, const uint64_t *streams, double *ret, double *disc, int32_t *steps,
+                               int32_t *terminal, int32_t *ties, int32_t *explored, double *final_state, uint64_t *streams_out, double *records)
+{
+  if (int rc = lspi_evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps)) return rc;
+  if (int rc = batch_sampled_admit(who, n_replicas, n_starts, sampler, epsilon, streams)) return rc;
+  BatchEpisodes e;
+  if (int rc = batch_episodes(e, who, sibling, kLspiS, n_replicas, n_starts, &max_steps, ret, disc, steps, terminal, ties, final_state, {}, records,
+                             kLspiSampledTrajWords,
+                             {ReadOut{explored, sizeof(int32_t), n_replicas, true}, ReadOut{streams_out, 2 * sizeof(uint64_t), n_replicas, true}},
+                             2 * sizeof(uint64_t)))
+    return rc;
+  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  ReadIn in_streams = {streams, 2 * sizeof(uint64_t), n_replicas, nullptr};      // [replica][start][2]: a chunk is strided, not contiguous
+  return chunked_read(kPlainRead, e.outs, e.n_outs, n_starts, states, kLspiS, e.chunk, true, [&](int nc, const double *dst, const DevPtr *d) -> int {
+    LspiSampledArgs T;
+    LspiEvalArgs &A = T.e;
+    A.first_replica = first_replica; A.n_starts = nc; A.max_steps = max_steps; A.states = dst;
+    A.ret = d[0].as<double>(); A.disc = d[1].as<double>(); A.steps = d[2].as<int32_t>(); A.terminal = d[3].as<int32_t>(); A.ties = d[4].as<int32_t>();
+    A.final_state = d[5].as<double>(); A.records = d[8].as<double>();      // (past the outputs: null, the sums alone)
+    T.sampler = sampler; T.epsilon = epsilon; T.streams = (const uint64_t *)in_streams.dev;
+    T.explored = d[6].as<int32_t>(); T.streams_out = d[7].as<uint64_t>();
+    HIP_TRY(launch_lspi_evaluate_sampled(ctx->L, T, n_replicas, nullptr));
+    return GRLX_OK;
+  }, &in_streams);
+}
+
+int lspi_evaluate_ensemble_sampled_impl(grlx_lspi_ctx *ctx, const char *who, const char *sibling, int first_replica, int n_replicas, int group_size,
+                                        int strategy, double tau, int member, double member_param, const double *states, int n_starts, int max_steps,
+                                        const uint64_t *streams, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                                        int64_t *member_ties, int64_t *agreement, int32_t *explored, double *final_state, uint64_t *streams_out,
+                                        double *records)
+{
+  if (int rc = lspi_evaluate_admit(ctx, who, first_replica, n_replicas, states, n_starts, max_steps)) return rc;
+  if (int rc = batch_ensemble_sampled_admit(who, n_replicas, group_size, n_starts, strategy, tau, member, member_param, streams)) return rc;
+  const int groups = n_replicas / group_size;
+  BatchEpisodes e;
+  if (int rc = batch_episodes(e, who, sibling, kLspiS, groups, n_starts, &max_steps, ret, disc, steps, terminal, ties, final_state, {member_ties, agreement}, records,
+                             kLspiEnsSampledTrajWords,
+                             {ReadOut{explored, sizeof(int32_t), groups, true}, ReadOut{streams_out, sizeof(uint64_t), groups, true}}, sizeof(uint64_t)))
+    return rc;
+  if (n_starts == 0 || n_replicas == 0) return GRLX_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  ReadIn in_streams = {streams, sizeof(uint64_t), groups, nullptr};      // [group][start]: a chunk is strided
+  return chunked_read(kPlainRead, e.outs, e.n_outs, n_starts, states, kLspiS, e.chunk, true, [&](int nc, const double *dst, const DevPtr *d) -> int {
+    LspiEnsSampledArgs T;
+    LspiEnsArgs &A = T.e;
+    A.first_replica = first_replica; A.group_size = group_size; A.rule = strategy; A.n_starts = nc; A.max_steps = max_steps; A.states = dst;
+    A.ret = d[0].as<double>(); A.disc = d[1].as<double>(); A.steps = d[2].as<int32_t>(); A.terminal = d[3].as<int32_t>(); A.ties = d[4].as<int32_t>();
+    A.final_state = d[5].as<double>(); A.member_ties = d[6].as<int64_t>(); A.agreement = d[7].as<int64_t>(); A.records = d[10].as<double>();
+    T.tau = tau; T.member = member; T.member_param = member_param; T.cap = 0; T.streams = (const uint64_t *)in_streams.dev;
+    T.explored = d[8].as<int32_t>(); T.streams_out = d[9].as<uint64_t>();
+    HIP_TRY(launch_lspi_evaluate_ensemble_sampled(ctx->L, T, groups, nullptr));
+    return GRLX_OK;
+  }, &in_streams);
 }
 
 } // namespace
@@ -424,6 +486,54 @@ int grlx_lspi_evaluate_ensemble_trajectory(grlx_lspi_ctx *ctx, int first_replica
 {
   return lspi_evaluate_ensemble_impl(ctx, "grlx_lspi_evaluate_ensemble_trajectory", "grlx_lspi_evaluate_ensemble", first_replica, n_replicas, group_size,
                                      rule, states, n_starts, max_steps, ret, disc, steps, terminal, ties, member_ties, agreement, final_state, records);
+}
+
+int grlx_lspi_evaluate_sampled(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, int sampler,
+                               double epsilon, const uint64_t *streams, double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                               int32_t *explored, double *final_state, uint64_t *streams_out)
+{
+  return lspi_evaluate_sampled_impl(ctx, "grlx_lspi_evaluate_sampled", nullptr, first_replica, n_replicas, states, n_starts, max_steps, sampler, epsilon, streams,
+                                    ret, disc, steps, terminal, ties, explored, final_state, streams_out, nullptr);
+}
+
+int grlx_lspi_sampled_trajectory_record_words(grlx_lspi_ctx *ctx)
+{
+  if (!ctx) return fail(GRLX_ERR_INVALID, "grlx_lspi_sampled_trajectory_record_words: ctx is null");
+  return kLspiSampledTrajWords;
+}
+
+int grlx_lspi_evaluate_sampled_trajectory(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, const double *states, int n_starts, int max_steps, int sampler,
+                                          double epsilon, const uint64_t *streams, double *ret, double *disc, int32_t *steps, int32_t *terminal,
+                                          int32_t *ties, int32_t *explored, double *final_state, uint64_t *streams_out, double *records)
+{
+  return lspi_evaluate_sampled_impl(ctx, "grlx_lspi_evaluate_sampled_trajectory", "grlx_lspi_evaluate_sampled", first_replica, n_replicas, states, n_starts,
+                                    max_steps, sampler, epsilon, streams, ret, disc, steps, terminal, ties, explored, final_state, streams_out, records);
+}
+
+int grlx_lspi_evaluate_ensemble_sampled(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, int group_size, int strategy, double tau, int member,
+                                        double member_param, const double *states, int n_starts, int max_steps, const uint64_t *streams, double *ret,
+                                        double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, int64_t *member_ties, int64_t *agreement,
+                                        int32_t *explored, double *final_state, uint64_t *streams_out)
+{
+  return lspi_evaluate_ensemble_sampled_impl(ctx, "grlx_lspi_evaluate_ensemble_sampled", nullptr, first_replica, n_replicas, group_size, strategy, tau, member,
+                                             member_param, states, n_starts, max_steps, streams, ret, disc, steps, terminal, ties, member_ties, agreement,
+                                             explored, final_state, streams_out, nullptr);
+}
+
+int grlx_lspi_ensemble_sampled_trajectory_record_words(grlx_lspi_ctx *ctx)
+{
+  if (!ctx) return fail(GRLX_ERR_INVALID, "grlx_lspi_ensemble_sampled_trajectory_record_words: ctx is null");
+  return kLspiEnsSampledTrajWords;
+}
+
+int grlx_lspi_evaluate_ensemble_sampled_trajectory(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, int group_size, int strategy, double tau, int member,
+                                                   double member_param, const double *states, int n_starts, int max_steps, const uint64_t *streams,
+                                                   double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, int64_t *member_ties,
+                                                   int64_t *agreement, int32_t *explored, double *final_state, uint64_t *streams_out, double *records)
+{
+  return lspi_evaluate_ensemble_sampled_impl(ctx, "grlx_lspi_evaluate_ensemble_sampled_trajectory", "grlx_lspi_evaluate_ensemble_sampled", first_replica,
+                                             n_replicas, group_size, strategy, tau, member, member_param, states, n_starts, max_steps, streams, ret, disc,
+                                             steps, terminal, ties, member_ties, agreement, explored, final_state, streams_out, records);
 }
 
 } // extern "C"

@@ -21,6 +21,7 @@
 #include "grlx_tile.h"
 #include "grlx_table.h"
 #include "grlx_envs.h"
+#include "grlx_softmax.h"
 #include "grlx_fqi.h"
 
 namespace grlx {
@@ -1157,35 +1158,7 @@ __device__ __forceinline__ int fqi_row_sum(int v)
   return v;
 }
 
-// SoftmaxSampler::distribution (softmax.cpp:65-110) over the first NA of v[] at temperature t, as include/grlx.h restates it; entries
-// behind NA come out 0.  NA is a kernel argument: every branch on it is scalar.
-__device__ __forceinline__ void fqi_softmax(const double (&v)[kMaxActions], int NA, double t, double (&d)[kMaxActions])
-{
-  double p[kMaxActions], e[kMaxActions];
-  double maxp = -0x1.fffffffffffffp+1023;                 // -DBL_MAX
-#pragma unroll
-  for (int a = 0; a < kMaxActions; ++a)
-  {
-    p[a] = v[a] / t;
-    if (a < NA) maxp = (maxp < p[a]) ? p[a] : maxp;
-  }
-  const double minp = maxp + (-100), center = (maxp + minp) / 2.0;
-  double sum = 0;
-#pragma unroll
-  for (int a = 0; a < kMaxActions; ++a)
-  {
-    e[a] = 0.0;
-    if (a < NA)
-    {
-      const bool kept = p[a] > minp;
-      e[a] = kept ? pexp(p[a] - center) : 0.0;
-      sum = kept ? sum + e[a] : sum;
-    }
-  }
-#pragma unroll
-  for (int a = 0; a < kMaxActions; ++a) d[a] = (a < NA && p[a] > minp) ? e[a] / sum : 0.0;
-}
-
+// (the distributions: batch_softmax, grlx_softmax.h)
 template <int H, bool RECORD>
 __global__ __launch_bounds__(64) void fqi_ensemble_sampled_kernel(FqiParams F, FqiEnsSampledArgs T)
 {
@@ -1228,7 +1201,7 @@ __global__ __launch_bounds__(64) void fqi_ensemble_sampled_kernel(FqiParams F, F
         for (int a = 0; a < kMaxActions; ++a) unused[a] = 0.;
         int mai, man;
         fqi_member_values<H>(F, w, obs, q, unused, best, mai, man);
-        if (T.member == GRLX_MEMBER_SOFTMAX) fqi_softmax(q, NA, T.member_param, d);
+        if (T.member == GRLX_MEMBER_SOFTMAX) batch_softmax(q, NA, T.member_param, d);
         else
         { // greedy.cpp:88-98, and :229-236 for the epsilon-greedy member
 #pragma unroll
@@ -1287,7 +1260,7 @@ __global__ __launch_bounds__(64) void fqi_ensemble_sampled_kernel(FqiParams F, F
         score[a] = rank ? ranks[a] : votes[a];
         sc[a] = (double)score[a];
       }
-      fqi_softmax(sc, NA, T.tau, dist);
+      batch_softmax(sc, NA, T.tau, dist);
       // grl::sample (utils.h:227-250) on one drand48 of the episode's stream
       double sum = 0;
 #pragma unroll

@@ -1092,9 +1092,107 @@ def pendulum_fqi_config(n_replicas=1, **overrides) -> capi.FqiConfig:
     return cfg
 
 
-class FqiRunner:
+class _BatchSampledEpisodes:
+    """The sampled episodes of a batch context (FqiRunner, LspiRunner): Runner's calls of the same names restated; a batch context has no
+    epsilon and no sampler stream of its own.  The runner names its entry points' prefix (_PREFIX) and has _replica_range and _groups."""
+
+    def _call(self, name):
+        return getattr(self.lib, self._PREFIX + name)
+
+    def _sampled_args(self, states, sampler, epsilon, streams, replicas):
+        samplers = {"greedy": capi.SAMPLER_GREEDY, "epsilon": capi.SAMPLER_EPSILON_GREEDY, "epsilon_greedy": capi.SAMPLER_EPSILON_GREEDY}
+        sampler = samplers[sampler] if isinstance(sampler, str) else int(sampler)
+        if epsilon is None:
+            if sampler != capi.SAMPLER_GREEDY:
+                raise ValueError("epsilon: a number in [0, 1] (a batch context has none of its own)")
+            epsilon = 0.0
+        states = _state_rows(states, self.STATE_DIMS)
+        first, count = self._replica_range(replicas)
+        n = states.shape[0]
+        if streams is not None:
+            streams = np.ascontiguousarray(streams, dtype=np.uint64)
+            if streams.shape != (count, n, 2):
+                raise ValueError(f"expected streams of shape ({count}, {n}, 2), got {streams.shape}")
+        return states, sampler, float(epsilon), streams, first, count, n
+
+    def evaluate_sampled(self, states, sampler="greedy", epsilon=None, streams=None, replicas=None, max_steps=0):
+        """evaluate's episodes acted by a sampler of the reference: "greedy" (a tie broken by a draw, as the batch's test trial
+        breaks it) or "epsilon" (epsilon a number in [0, 1]).  streams[replica][start][2] as Runner.evaluate_sampled takes them (see
+        episode_streams); None, under "greedy" only: the global stream is a copy of the replica's own.  SampledEvaluation(ret, disc, steps,
+        terminal, ties, explored, final_state, streams).  The context is not changed (include/grlx.h: grlx_fqi_evaluate_sampled / grlx_lspi_evaluate_sampled)."""
+        states, sampler, epsilon, streams, first, count, n = self._sampled_args(states, sampler, epsilon, streams, replicas)
+        out, ptrs = _episode_outputs(count, n, self.STATE_DIMS, _SAMPLED_FIELDS, explored=np.int32, streams=(np.uint64, 2))
+        capi.check(self._call("evaluate_sampled")(self._ctx, first, count, _ptr(states, C.c_double), n, int(max_steps), sampler, epsilon,
+                                                 None if streams is None else _ptr(streams, C.c_uint64), *ptrs))
+        return SampledEvaluation(*out)
+
+    def sampled_trajectory_record_words(self):
+        """R = 12 (grlx_fqi_sampled_trajectory_record_words / grlx_lspi_sampled_trajectory_record_words)"""
+        return capi.check(self._call("sampled_trajectory_record_words")(self._ctx))
+
+    def evaluate_sampled_trajectory(self, states, max_steps, sampler="greedy", epsilon=None, streams=None, replicas=None):
+        """evaluate_sampled with every step of every episode: SampledTrajectory(..., records), records[replica][start][max_steps]
+        [12], the views Runner.evaluate_sampled_trajectory's (include/grlx.h: grlx_fqi_evaluate_sampled_trajectory / grlx_lspi_evaluate_sampled_trajectory)."""
+        states, sampler, epsilon, streams, first, count, n = self._sampled_args(states, sampler, epsilon, streams, replicas)
+        max_steps = int(max_steps)
+        out, ptrs = _episode_outputs(count, n, self.STATE_DIMS, _SAMPLED_FIELDS, explored=np.int32, streams=(np.uint64, 2),
+                                     records=(max_steps, self.sampled_trajectory_record_words()))
+        capi.check(self._call("evaluate_sampled_trajectory")(self._ctx, first, count, _ptr(states, C.c_double), n, max_steps, sampler, epsilon,
+                                                            None if streams is None else _ptr(streams, C.c_uint64), *ptrs))
+        return SampledTrajectory(*out)
+
+    def _ensemble_sampled_args(self, states, group_size, strategy, tau, member, member_param, streams, replicas):
+        strategy = _STRATEGIES[strategy] if isinstance(strategy, str) else int(strategy)
+        member = _MEMBERS[member] if isinstance(member, str) else int(member)
+        if member_param is None:
+            if member == capi.MEMBER_EPSILON:
+                raise ValueError("member_param: epsilon, a number in [0, 1] (a batch context has none of its own)")
+            member_param = 1.0 if member == capi.MEMBER_SOFTMAX else 0.0
+        states = _state_rows(states, self.STATE_DIMS)
+        first, count, group_size, groups = self._groups(replicas, group_size)
+        n = states.shape[0]
+        if streams is not None:
+            streams = np.ascontiguousarray(streams, dtype=np.uint64)
+            if streams.shape != (groups, n):
+                raise ValueError(f"expected streams of shape ({groups}, {n}), got {streams.shape}")
+        head = (self._ctx, first, count, group_size, strategy, float(tau), member, float(member_param), _ptr(states, C.c_double), n)
+        return head, None if streams is None else _ptr(streams, C.c_uint64), groups, n, (states, streams)
+
+    def evaluate_ensemble_sampled(self, states, group_size, strategy="majority", tau=0.1, member="greedy", member_param=None, streams=None, replicas=None,
+                                  max_steps=0):
+        """evaluate_ensemble's episodes with the action DRAWN from softmax(score / tau), the score being the members' votes
+        ("majority") or their summed ranks ("rank"); member "greedy", "epsilon" (member_param: e in [0, 1], required) or "softmax"
+        (member_param: its temperature, default 1).  streams[group][start]: one rand48 word per episode; None = a copy of the global stream
+        of the group's first replica.  SampledEnsembleEvaluation, as Runner.evaluate_ensemble_sampled defines it.  The context is not
+        changed (include/grlx.h: grlx_fqi_evaluate_ensemble_sampled / grlx_lspi_evaluate_ensemble_sampled)."""
+        head, streams, groups, n, _keep = self._ensemble_sampled_args(states, group_size, strategy, tau, member, member_param, streams, replicas)
+        out, ptrs = _episode_outputs(groups, n, self.STATE_DIMS, _SAMPLED_ENSEMBLE_FIELDS, member_ties=np.int64, agreement=np.int64, explored=np.int32,
+                                     streams=np.uint64)
+        capi.check(self._call("evaluate_ensemble_sampled")(*head, int(max_steps), streams, *ptrs))
+        return SampledEnsembleEvaluation(*out)
+
+    def ensemble_sampled_trajectory_record_words(self):
+        """R = 15 (grlx_fqi_ensemble_sampled_trajectory_record_words / grlx_lspi_ensemble_sampled_trajectory_record_words)"""
+        return capi.check(self._call("ensemble_sampled_trajectory_record_words")(self._ctx))
+
+    def evaluate_ensemble_sampled_trajectory(self, states, group_size, max_steps, strategy="majority", tau=0.1, member="greedy", member_param=None,
+                                             streams=None, replicas=None):
+        """evaluate_ensemble_sampled with every step of every episode: SampledEnsembleTrajectory(..., records),
+        records[group][start][max_steps][15], the views Runner.evaluate_ensemble_sampled_trajectory's (include/grlx.h:
+        grlx_fqi_evaluate_ensemble_sampled_trajectory / grlx_lspi_evaluate_ensemble_sampled_trajectory)."""
+        head, streams, groups, n, _keep = self._ensemble_sampled_args(states, group_size, strategy, tau, member, member_param, streams, replicas)
+        max_steps = int(max_steps)
+        out, ptrs = _episode_outputs(groups, n, self.STATE_DIMS, _SAMPLED_ENSEMBLE_FIELDS, member_ties=np.int64, agreement=np.int64, explored=np.int32,
+                                     streams=np.uint64, records=(max_steps, self.ensemble_sampled_trajectory_record_words()))
+        capi.check(self._call("evaluate_ensemble_sampled_trajectory")(*head, max_steps, streams, *ptrs))
+        return SampledEnsembleTrajectory(*out)
+
+
+class FqiRunner(_BatchSampledEpisodes):
     """N independent-seed replicas of the batch-learning experiment (fitted Q-iteration over a 3-H-1 network) on the
     current GPU: include/grlx.h, grlx_fqi_*."""
+
+    _PREFIX = "grlx_fqi_"
 
     def __init__(self, cfg: capi.FqiConfig, seeds):
         self.lib = capi.load()
@@ -1243,95 +1341,6 @@ class FqiRunner:
         capi.check(self.lib.grlx_fqi_evaluate_ensemble_trajectory(self._ctx, first, count, group_size, rule, _ptr(states, C.c_double), n, max_steps, *ptrs))
         return EnsembleTrajectory(*out)
 
-    # ---- sampled episodes: Runner's calls of the same names restated; a batch context has no epsilon and no sampler stream of its own
-    def _sampled_args(self, states, sampler, epsilon, streams, replicas):
-        samplers = {"greedy": capi.SAMPLER_GREEDY, "epsilon": capi.SAMPLER_EPSILON_GREEDY, "epsilon_greedy": capi.SAMPLER_EPSILON_GREEDY}
-        sampler = samplers[sampler] if isinstance(sampler, str) else int(sampler)
-        if epsilon is None:
-            if sampler != capi.SAMPLER_GREEDY:
-                raise ValueError("epsilon: a number in [0, 1] (a batch context has none of its own)")
-            epsilon = 0.0
-        states = _state_rows(states, self.STATE_DIMS)
-        first, count = self._replica_range(replicas)
-        n = states.shape[0]
-        if streams is not None:
-            streams = np.ascontiguousarray(streams, dtype=np.uint64)
-            if streams.shape != (count, n, 2):
-                raise ValueError(f"expected streams of shape ({count}, {n}, 2), got {streams.shape}")
-        return states, sampler, float(epsilon), streams, first, count, n
-
-    def evaluate_sampled(self, states, sampler="greedy", epsilon=None, streams=None, replicas=None, max_steps=0):
-        """FqiRunner.evaluate's episodes acted by a sampler of the reference: "greedy" (a tie broken by a draw, as the batch's test trial
-        breaks it) or "epsilon" (epsilon a number in [0, 1]).  streams[replica][start][2] as Runner.evaluate_sampled takes them (see
-        episode_streams); None, under "greedy" only: the global stream is a copy of the replica's own.  SampledEvaluation(ret, disc, steps,
-        terminal, ties, explored, final_state, streams).  The context is not changed (include/grlx.h: grlx_fqi_evaluate_sampled)."""
-        states, sampler, epsilon, streams, first, count, n = self._sampled_args(states, sampler, epsilon, streams, replicas)
-        out, ptrs = _episode_outputs(count, n, self.STATE_DIMS, _SAMPLED_FIELDS, explored=np.int32, streams=(np.uint64, 2))
-        capi.check(self.lib.grlx_fqi_evaluate_sampled(self._ctx, first, count, _ptr(states, C.c_double), n, int(max_steps), sampler, epsilon,
-                                                      None if streams is None else _ptr(streams, C.c_uint64), *ptrs))
-        return SampledEvaluation(*out)
-
-    def sampled_trajectory_record_words(self):
-        """R = 12 (grlx_fqi_sampled_trajectory_record_words)"""
-        return capi.check(self.lib.grlx_fqi_sampled_trajectory_record_words(self._ctx))
-
-    def evaluate_sampled_trajectory(self, states, max_steps, sampler="greedy", epsilon=None, streams=None, replicas=None):
-        """FqiRunner.evaluate_sampled with every step of every episode: SampledTrajectory(..., records), records[replica][start][max_steps]
-        [12], the views Runner.evaluate_sampled_trajectory's (include/grlx.h: grlx_fqi_evaluate_sampled_trajectory)."""
-        states, sampler, epsilon, streams, first, count, n = self._sampled_args(states, sampler, epsilon, streams, replicas)
-        max_steps = int(max_steps)
-        out, ptrs = _episode_outputs(count, n, self.STATE_DIMS, _SAMPLED_FIELDS, explored=np.int32, streams=(np.uint64, 2),
-                                     records=(max_steps, self.sampled_trajectory_record_words()))
-        capi.check(self.lib.grlx_fqi_evaluate_sampled_trajectory(self._ctx, first, count, _ptr(states, C.c_double), n, max_steps, sampler, epsilon,
-                                                                 None if streams is None else _ptr(streams, C.c_uint64), *ptrs))
-        return SampledTrajectory(*out)
-
-    def _ensemble_sampled_args(self, states, group_size, strategy, tau, member, member_param, streams, replicas):
-        strategy = _STRATEGIES[strategy] if isinstance(strategy, str) else int(strategy)
-        member = _MEMBERS[member] if isinstance(member, str) else int(member)
-        if member_param is None:
-            if member == capi.MEMBER_EPSILON:
-                raise ValueError("member_param: epsilon, a number in [0, 1] (a batch context has none of its own)")
-            member_param = 1.0 if member == capi.MEMBER_SOFTMAX else 0.0
-        states = _state_rows(states, self.STATE_DIMS)
-        first, count, group_size, groups = self._groups(replicas, group_size)
-        n = states.shape[0]
-        if streams is not None:
-            streams = np.ascontiguousarray(streams, dtype=np.uint64)
-            if streams.shape != (groups, n):
-                raise ValueError(f"expected streams of shape ({groups}, {n}), got {streams.shape}")
-        head = (self._ctx, first, count, group_size, strategy, float(tau), member, float(member_param), _ptr(states, C.c_double), n)
-        return head, None if streams is None else _ptr(streams, C.c_uint64), groups, n, (states, streams)
-
-    def evaluate_ensemble_sampled(self, states, group_size, strategy="majority", tau=0.1, member="greedy", member_param=None, streams=None, replicas=None,
-                                  max_steps=0):
-        """FqiRunner.evaluate_ensemble's episodes with the action DRAWN from softmax(score / tau), the score being the members' votes
-        ("majority") or their summed ranks ("rank"); member "greedy", "epsilon" (member_param: e in [0, 1], required) or "softmax"
-        (member_param: its temperature, default 1).  streams[group][start]: one rand48 word per episode; None = a copy of the global stream
-        of the group's first replica.  SampledEnsembleEvaluation, as Runner.evaluate_ensemble_sampled defines it.  The context is not
-        changed (include/grlx.h: grlx_fqi_evaluate_ensemble_sampled)."""
-        head, streams, groups, n, _keep = self._ensemble_sampled_args(states, group_size, strategy, tau, member, member_param, streams, replicas)
-        out, ptrs = _episode_outputs(groups, n, self.STATE_DIMS, _SAMPLED_ENSEMBLE_FIELDS, member_ties=np.int64, agreement=np.int64, explored=np.int32,
-                                     streams=np.uint64)
-        capi.check(self.lib.grlx_fqi_evaluate_ensemble_sampled(*head, int(max_steps), streams, *ptrs))
-        return SampledEnsembleEvaluation(*out)
-
-    def ensemble_sampled_trajectory_record_words(self):
-        """R = 15 (grlx_fqi_ensemble_sampled_trajectory_record_words)"""
-        return capi.check(self.lib.grlx_fqi_ensemble_sampled_trajectory_record_words(self._ctx))
-
-    def evaluate_ensemble_sampled_trajectory(self, states, group_size, max_steps, strategy="majority", tau=0.1, member="greedy", member_param=None,
-                                             streams=None, replicas=None):
-        """FqiRunner.evaluate_ensemble_sampled with every step of every episode: SampledEnsembleTrajectory(..., records),
-        records[group][start][max_steps][15], the views Runner.evaluate_ensemble_sampled_trajectory's (include/grlx.h:
-        grlx_fqi_evaluate_ensemble_sampled_trajectory)."""
-        head, streams, groups, n, _keep = self._ensemble_sampled_args(states, group_size, strategy, tau, member, member_param, streams, replicas)
-        max_steps = int(max_steps)
-        out, ptrs = _episode_outputs(groups, n, self.STATE_DIMS, _SAMPLED_ENSEMBLE_FIELDS, member_ties=np.int64, agreement=np.int64, explored=np.int32,
-                                     streams=np.uint64, records=(max_steps, self.ensemble_sampled_trajectory_record_words()))
-        capi.check(self.lib.grlx_fqi_evaluate_ensemble_sampled_trajectory(*head, max_steps, streams, *ptrs))
-        return SampledEnsembleTrajectory(*out)
-
     def info(self, replica: int):
         n = C.c_int64(); md = C.c_double(); it = C.c_int32(); err = C.c_double(); rng = (C.c_uint64 * 2)()
         capi.check(self.lib.grlx_fqi_info(self._ctx, replica, C.byref(n), C.byref(md), C.byref(it), C.byref(err), rng))
@@ -1354,9 +1363,11 @@ def pendulum_lspi_config(n_replicas: int = 1, projector="triangle", **overrides)
     return cfg
 
 
-class LspiRunner:
+class LspiRunner(_BatchSampledEpisodes):
     """N independent-seed replicas of the batch-learning experiment with least-squares policy iteration over a triangle or Gauss RBF
     representation on the current GPU: include/grlx.h, grlx_lspi_*."""
+
+    _PREFIX = "grlx_lspi_"
 
     def __init__(self, cfg: capi.LspiConfig, seeds):
         self.lib = capi.load()

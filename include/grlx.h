@@ -1103,8 +1103,8 @@ int  grlx_fqi_evaluate_ensemble_sampled_trajectory(grlx_fqi_ctx *ctx, int first_
  * deviations; the read with products and sums rounded separately; A = 1e-5 I + Phi^T Phi - Phi^T Psi and b = Phi^T r on the f64 matrix
  * instruction in a fixed order; LU with partial pivoting (first largest magnitude, lowest row on equal magnitude) -- is specified at
  * the top of grl_amd/csrc/grlx_lspi.h and in DESIGN.md section 4.4.
- * NOT BUILT: projector/monomial; the YAML host layer for predictor/lspi; sampled episodes (the tie-breaking draw, epsilon-greedy, the
- * draw from a group's votes); streamed trajectories; snapshots; several GPUs; tasks other than the pendulum's swing-up. */
+ * NOT BUILT: projector/monomial; the YAML host layer for predictor/lspi; streamed trajectories; snapshots; several GPUs; tasks other
+ * than the pendulum's swing-up. */
 #define GRLX_RBF_TRIANGLE 0
 #define GRLX_RBF_GAUSS    1
 typedef struct {
@@ -1198,6 +1198,59 @@ int  grlx_lspi_evaluate_ensemble_trajectory(grlx_lspi_ctx *ctx, int first_replic
                                             double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
                                             int64_t *member_ties, int64_t *agreement, double *final_state,
                                             double *records /*[n_replicas / group_size][n_starts][max_steps][R]*/);
+/* The LSPI context's sampled episodes: grlx_fqi_evaluate_sampled, grlx_fqi_evaluate_sampled_trajectory, grlx_fqi_evaluate_ensemble_sampled and
+ * grlx_fqi_evaluate_ensemble_sampled_trajectory (above) restated word for word for a grlx_lspi_ctx -- arguments, outputs, NULL-able
+ * pointers, refusals (entry point and reason named, before anything is launched), staging in chunks of start states.  The episodes are
+ * grlx_lspi_evaluate's and grlx_lspi_evaluate_ensemble's; q[k] is "The step"'s read of S5 on the replica's CURRENT weights.
+ *   One policy.  GRLX_SAMPLER_GREEDY: man > 1: the global stream advances, lrand48 % man picks among the maxima, ties++.
+ *               GRLX_SAMPLER_EPSILON_GREEDY: the sampler's stream advances, rnd = drand48; rnd < e: the global stream advances, lrand48 %
+ *               action_steps acts, explored++; else the greedy sampler's step.  streams[n_replicas][n_starts][2], grlx_episode_streams'
+ *               layout.  streams == NULL is accepted under GRLX_SAMPLER_GREEDY only: word 1 is then a COPY of the replica's global stream
+ *               (grlx_lspi_info's rng[0]; the context's own does not move), word 0 is 0.  An LSPI context has neither an epsilon nor a
+ *               sampler stream of its own: GRLX_EPSILON_OWN is refused by name, and so is a null streams under epsilon-greedy.
+ *               Records: grlx_lspi_evaluate_trajectory's 11 words, each at its index (GRLX_TRAJ_ACTION_INDEX the index that ACTED,
+ *               GRLX_TRAJ_VALUE q of the action taken), then `explored`: R = grlx_lspi_sampled_trajectory_record_words() = 12.
+ *   Ensemble.   GRLX_ENSEMBLE_MAJORITY or GRLX_ENSEMBLE_RANK over members GRLX_MEMBER_GREEDY, GRLX_MEMBER_EPSILON (member_param = e in
+ *               [0, 1]; GRLX_EPSILON_OWN refused by name) or GRLX_MEMBER_SOFTMAX (member_param = tau_m > 0, over the portable pexp): a step
+ *               is exactly "A step, exactly" of grlx_evaluate_ensemble_sampled with q_m = the reads of member m and NA = action_steps --
+ *               vote_m, ranks, softmax(score, tau) and grl::sample on one drand48 of the episode's one rand48 word.  The scores are
+ *               integers: the device sums the members in no particular order.  streams[groups][n_starts]; NULL: a COPY of the global
+ *               stream of the group's first replica.  ties, member_ties, agreement, explored and the record are the FQI sibling's:
+ *               R = grlx_lspi_ensemble_sampled_trajectory_record_words() = 15.
+ * Consequence.  LSPI's own test trial takes the first maximum (D7 of grl_amd/csrc/grlx_lspi.h) and draws nothing.  Under
+ * GRLX_SAMPLER_GREEDY with ties == 0 every output therefore equals grlx_lspi_evaluate's and streams_out == streams; with ties the sampled
+ * call is what the reference's test agent would do, and the batch's row is not.
+ * The calls change nothing in the context.  Refused (GRLX_ERR_INVALID, nothing written): everything the greedy siblings refuse but the
+ * rule; an unknown sampler, strategy or member sampler; epsilon that is not finite or outside [0, 1]; tau, or tau_m under
+ * GRLX_MEMBER_SOFTMAX, that is not finite or <= 0; a stream word >= 2^48 (row and word named).
+ * NOT BUILT: add / multiply; the members' own draws; a softmax sampler for a single policy; streamed variants; the greedy ensemble on the
+ * sampled ensemble's member-parallel layout (its mean-Q sum is ordered). */
+int  grlx_lspi_evaluate_sampled(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][3]*/, int n_starts,
+                                int max_steps, int sampler, double epsilon, const uint64_t *streams /*[n_replicas][n_starts][2] or NULL*/,
+                                double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties, int32_t *explored,
+                                double *final_state, uint64_t *streams_out /*[n_replicas][n_starts][2]*/);
+int  grlx_lspi_sampled_trajectory_record_words(grlx_lspi_ctx *ctx);      /* R = 12; a negative status for a null ctx */
+int  grlx_lspi_evaluate_sampled_trajectory(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, const double *states /*[n_starts][3]*/,
+                                           int n_starts, int max_steps, int sampler, double epsilon,
+                                           const uint64_t *streams /*[n_replicas][n_starts][2] or NULL*/, double *ret, double *disc,
+                                           int32_t *steps, int32_t *terminal, int32_t *ties, int32_t *explored, double *final_state,
+                                           uint64_t *streams_out /*[n_replicas][n_starts][2]*/,
+                                           double *records /*[n_replicas][n_starts][max_steps][R]*/);
+int  grlx_lspi_evaluate_ensemble_sampled(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, int group_size, int strategy, double tau, int member,
+                                         double member_param, const double *states /*[n_starts][3]*/, int n_starts, int max_steps,
+                                         const uint64_t *streams /*[n_replicas / group_size][n_starts] or NULL*/,
+                                         double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                                         int64_t *member_ties, int64_t *agreement, int32_t *explored, double *final_state,
+                                         uint64_t *streams_out /*[n_replicas / group_size][n_starts]*/);
+int  grlx_lspi_ensemble_sampled_trajectory_record_words(grlx_lspi_ctx *ctx);      /* R = 15; a negative status for a null ctx */
+int  grlx_lspi_evaluate_ensemble_sampled_trajectory(grlx_lspi_ctx *ctx, int first_replica, int n_replicas, int group_size, int strategy, double tau,
+                                                    int member, double member_param, const double *states /*[n_starts][3]*/,
+                                                    int n_starts, int max_steps,
+                                                    const uint64_t *streams /*[n_replicas / group_size][n_starts] or NULL*/,
+                                                    double *ret, double *disc, int32_t *steps, int32_t *terminal, int32_t *ties,
+                                                    int64_t *member_ties, int64_t *agreement, int32_t *explored, double *final_state,
+                                                    uint64_t *streams_out /*[n_replicas / group_size][n_starts]*/,
+                                                    double *records /*[n_replicas / group_size][n_starts][max_steps][R]*/);
 /* state of a replica: transitions stored, batches done, its status bits, the steps of its test trials at which the maximum was not
  * unique, RNG streams {global, thread-local}; any pointer may be NULL */
 int  grlx_lspi_info(grlx_lspi_ctx *ctx, int replica, int64_t *n_transitions, int64_t *batches_done, uint32_t *status, int64_t *ties, uint64_t rng[2]);
