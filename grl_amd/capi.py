@@ -289,6 +289,7 @@ _DIAG_SIGS = {
     "grlx_snapshot_naive_copy": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_double), _P(C.c_double)]),
     "grlx_set_query_chunk_bytes": (C.c_int, [C.c_uint64]),
     "grlx_read_kernel_timing": (C.c_int, [C.c_int, _P(C.c_double), _P(C.c_int)]),
+    "grlx_lspi_solve_systems": (C.c_int, [C.c_void_p, _P(C.c_double), _P(C.c_double), _P(C.c_double)]),
 }
 # entry points of include/grlx.h that a library named by GRLX_LIB may predate (A/B timing of an older build against this binding); the
 # library in the tree must export every one of them, as it must every other symbol of _SIGS

@@ -389,6 +389,27 @@ int grlx_lspi_get_system(grlx_lspi_ctx *ctx, int replica, double *A, double *b)
   return GRLX_OK;
 }
 
+// include/grlx_diag.h: lspi_solve_kernel on systems of the caller's choice, through the launch an iteration makes
+int grlx_lspi_solve_systems(grlx_lspi_ctx *ctx, const double *A, const double *b, double *x)
+{
+  const char *who = "grlx_lspi_solve_systems";
+  if (!ctx) return fail(GRLX_ERR_INVALID, "%s: ctx is null", who);
+  if (!A) return fail(GRLX_ERR_INVALID, "%s: A is null", who);
+  if (!b) return fail(GRLX_ERR_INVALID, "%s: b is null", who);
+  if (!x) return fail(GRLX_ERR_INVALID, "%s: x is null", who);
+  const LspiParams &L = ctx->L;
+  const size_t R = (size_t)L.R, F = (size_t)L.F, Fp = (size_t)L.Fp;
+  HIP_TRY(hipDeviceSynchronize());
+  // rows of F doubles into rows of pitch Fp: the padding stays what it is, zero (the allocation's, or a rebuild's sums over zero columns)
+  for (size_t r = 0; r < R; ++r)
+    HIP_TRY(hipMemcpy2D(L.Asys + r * Fp * Fp, Fp * sizeof(double), A + r * F * F, F * sizeof(double), F * sizeof(double), F, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy2D(L.b, Fp * sizeof(double), b, F * sizeof(double), F * sizeof(double), R, hipMemcpyHostToDevice));
+  HIP_TRY(launch_lspi_solve(L, nullptr));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy2D(x, F * sizeof(double), L.w, 2 * Fp * sizeof(double), F * sizeof(double), R, hipMemcpyDeviceToHost));
+  return GRLX_OK;
+}
+
 int grlx_lspi_info(grlx_lspi_ctx *ctx, int replica, int64_t *n_transitions, int64_t *batches_done, uint32_t *status, int64_t *ties, uint64_t rng[2])
 {
   if (int rc = lspi_replica_ok(ctx, "grlx_lspi_info", replica)) return rc;

@@ -97,6 +97,8 @@ struct LspiParams {
 hipError_t launch_lspi_init(const LspiParams &L, const uint64_t *r0, hipStream_t stream);
 // one batch: generate, rebuild (A_s and b once, then iterations x (greedy choice, Phi^T Psi, solve)), the test trial
 hipError_t launch_lspi_batch(const LspiParams &L, int batches_run, int iterations, hipStream_t stream);
+// lspi_solve_kernel alone, on whatever Asys and b hold: one block per replica, w[1] = w[0], w[0] = x, ST_LSPI_PIVOT or-ed into the status
+hipError_t launch_lspi_solve(const LspiParams &L, hipStream_t stream);
 hipError_t launch_lspi_query(const LspiParams &L, int first_replica, int n_replicas, const double *obs, int n_obs, double *q, hipStream_t stream);
 
 } // namespace grlx

@@ -532,7 +532,8 @@ static hipError_t lspi_product(const LspiParams &L, int n, hipStream_t stream)
 
 static size_t lspi_solve_lds(int F) { return ((size_t)F * kPanelPitch + (size_t)kPanel * (F + 1) + 16) * sizeof(double) + (16 + kPanel) * sizeof(int); }
 
-hipError_t launch_lspi_batch(const LspiParams &L, int batches_run, int iterations, hipStream_t stream)
+// the one launch of lspi_solve_kernel: an iteration's (launch_lspi_batch) and the diagnostic's (grlx_lspi_solve_systems)
+hipError_t launch_lspi_solve(const LspiParams &L, hipStream_t stream)
 {
   static bool sized = false;                               // as in lspi_product: once per process, one device, one calling thread
   if (!sized)
@@ -540,6 +541,12 @@ hipError_t launch_lspi_batch(const LspiParams &L, int batches_run, int iteration
     if (hipError_t e = hipFuncSetAttribute((const void *)lspi_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lspi_solve_lds(kLspiMaxF))) return e;
     sized = true;
   }
+  hipLaunchKernelGGL(lspi_solve_kernel, dim3(L.R), dim3(1024), lspi_solve_lds(L.F), stream, L);
+  return hipGetLastError();
+}
+
+hipError_t launch_lspi_batch(const LspiParams &L, int batches_run, int iterations, hipStream_t stream)
+{
   const int n = (batches_run + 1) * L.batch_size;
   hipLaunchKernelGGL(lspi_generate_kernel, dim3((L.batch_size + 255) / 256, L.R), dim3(256), 0, stream, L);
   hipLaunchKernelGGL(lspi_batch_begin_kernel, dim3((L.R + 63) / 64), dim3(64), 0, stream, L);
@@ -548,7 +555,7 @@ hipError_t launch_lspi_batch(const LspiParams &L, int batches_run, int iteration
   {
     hipLaunchKernelGGL(lspi_greedy_kernel, dim3((n + 255) / 256, L.R), dim3(256), 0, stream, L, n);
     if (hipError_t e = lspi_product<1>(L, n, stream)) return e;
-    hipLaunchKernelGGL(lspi_solve_kernel, dim3(L.R), dim3(1024), lspi_solve_lds(L.F), stream, L);
+    if (hipError_t e = launch_lspi_solve(L, stream)) return e;
   }
   hipLaunchKernelGGL(lspi_test_kernel, dim3((L.R + 63) / 64), dim3(64), 0, stream, L);
   return hipGetLastError();

@@ -1423,6 +1423,18 @@ class LspiRunner(_BatchSampledEpisodes):
         capi.check(self.lib.grlx_lspi_get_system(self._ctx, replica, _ptr(A, C.c_double), _ptr(b, C.c_double)))
         return A, b
 
+    def solve_systems(self, A, b):
+        """x[replica][F] of A[replica][F][F] x = b[replica][F] by the context's own solve kernel (include/grlx_diag.h:
+        grlx_lspi_solve_systems).  Overwrites the context's system and weights and may set status bit 64 for good: a diagnostic."""
+        R, F = self.cfg.n_replicas, self.n_params
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        if A.shape != (R, F, F) or b.shape != (R, F):
+            raise ValueError(f"expected A of shape {(R, F, F)} and b of shape {(R, F)}, got {A.shape} and {b.shape}")
+        x = np.zeros((R, F), np.float64)
+        capi.check(self.lib.grlx_lspi_solve_systems(self._ctx, _ptr(A, C.c_double), _ptr(b, C.c_double), _ptr(x, C.c_double)))
+        return x
+
     def query(self, obs, replicas=None):
         """q[replica][obs][action] on every replica's current weights (grlx_lspi_query); replicas: None = all, else a range or a
         (first, count) pair.  Changes nothing in the context."""

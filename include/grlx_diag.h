@@ -66,6 +66,16 @@ int grlx_set_query_chunk_bytes(uint64_t bytes);
  * receives the milliseconds and *chunks (may be NULL) the number of chunks timed since the last enabling call.  Process-wide, off by default. */
 int grlx_read_kernel_timing(int enable, double *ms, int *chunks);
 
+/* Least-squares policy iteration: lspi_solve_kernel (grl_amd/csrc/grlx_lspi.hip) on systems of the caller's choice, for tests/test_gpu_lspi_solve.py.
+ * One F x F system per replica of the context, F = the product of the configuration's steps: A[replica][F][F] row-major and b[replica][F]
+ * are copied over the context's own system (what grlx_lspi_get_system returns), the kernel is launched as an iteration of
+ * grlx_lspi_run_batch launches it, the call waits, and x[replica][F] receives the solutions.  A NaN or an infinity in A or b is not
+ * refused.  The context is left as the kernel leaves it: x becomes each replica's current weights and the former current weights become
+ * those of the last greedy choice (grlx_lspi_get_params, which = 0 and 1); a zero or non-finite pivot sets the replica's status bit 64,
+ * which NOTHING clears -- the call itself still returns GRLX_OK, and every later grlx_lspi_sync of the context returns GRLX_ERR_DOMAIN.
+ * Use a context of its own.  GRLX_ERR_INVALID: a null argument. */
+int grlx_lspi_solve_systems(grlx_lspi_ctx *ctx, const double *A, const double *b, double *x);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,14 +2,17 @@
 the read written as grl_amd/csrc/grlx_lspi.h specifies them (S3-S6, D2-D5), the oracle's pendulum step and orc_pexp.
 
 Shapes: F = 27 (one full and one ragged 16-tile), 60, 108 and the reference's 363; batch sizes 5 (one full K-step of 4 and a ragged one),
-64, and 257 = kLspiChunkMin + 1 (two blocks' partial tiles meet; three after the second batch).  Every case runs two batches of two
-replicas with different seeds, so the second rebuild runs over 2 x batch_size transitions from non-initial weights."""
+64, and 257 = kLspiChunkMin + 1 (two blocks' partial tiles meet; three after the second batch); and the bounds: F = 64 (nothing padded),
+F = 512 = kLspiMaxF, 4097 transitions (kLspiMaxSplits chunks, a ragged last one), Gauss weights between the cutoff and the prune of S6,
+a Gauss box wider than the grid, five actions.  Every case runs two batches of two replicas with different seeds, so the second rebuild
+runs over 2 x batch_size transitions from non-initial weights."""
 import ctypes as C
 import math
 
 import numpy as np
 import pytest
 
+from tests import lspi_solve_ref
 from tests import oracle_binding as ob
 
 pytestmark = pytest.mark.gpu
@@ -18,12 +21,21 @@ pytestmark = pytest.mark.gpu
 # draws them (rand48 replay, the oracle's pendulum step): 1, 2, 3, 5 ... 9 all do.  Seed 4 does not: a basis function that no stored
 # transition touches keeps A = 1e-5 I and b = 0, so its weight is exactly 0, and none of seed 4's first five transitions has an angle below
 # pi -- at steps [3, 3, 3] the three nodes that the start observation (0, 0) reads stay untouched and step 0 is a tie of zeros.
+# A row with a `seeds` entry runs on those instead: at F = 512 seed 3's first 64 transitions leave the start observation's nodes untouched
+# under the first and the last action (step 0 reads 0, -22.8, 0); 1, 2, 5 ... 9 do not tie there.
 SEEDS = [3, 5]
 CASES = {"f27-tri-n5-it1": dict(steps=[3, 3, 3], projector="triangle", batch_size=5, iterations=1),
          "f60-tri-n64-it3": dict(steps=[5, 4, 3], projector="triangle", batch_size=64, iterations=3),
          "f60-gauss-n64-it3": dict(steps=[5, 4, 3], projector="gauss", batch_size=64, iterations=3),
          "f108-tri-n257-it1": dict(steps=[6, 6, 3], projector="triangle", batch_size=257, iterations=1),
-         "f363-tri-n300-it3": dict(steps=[11, 11, 3], projector="triangle", batch_size=300, iterations=3)}
+         "f363-tri-n300-it3": dict(steps=[11, 11, 3], projector="triangle", batch_size=300, iterations=3),
+         # the bounds of the accumulation and of the greedy choice
+         "f64-tri-n64-it2": dict(steps=[4, 4, 4], projector="triangle", batch_size=64, iterations=2),                # F = Fp: no padding anywhere
+         "f512-tri-n64-it1": dict(steps=[8, 8, 8], projector="triangle", batch_size=64, iterations=1, seeds=[5, 6]),             # kLspiMaxF: both LDS maxima, 1024 tiles, 32 panels
+         "f27-tri-n4097-it1": dict(steps=[3, 3, 3], projector="triangle", batch_size=4097, iterations=1),            # kLspiMaxSplits chunks of 272, the last of 17 rows; then 16 of 528
+         "f64-gauss-n64-it2-c1e8": dict(steps=[4, 4, 4], projector="gauss", batch_size=64, iterations=2, cutoff=1e-8),      # kept weights in (1e-8, 1e-5]: read, pruned from Phi and Psi
+         "f27-gauss-n5-s2": dict(steps=[3, 3, 3], projector="gauss", batch_size=5, iterations=1, sigma=2.0),         # every function kept; the ragged tail of the f += 16 loop
+         "f60-tri-n64-it3-a5": dict(steps=[5, 4, 3], projector="triangle", batch_size=64, iterations=3, action_steps=5)}    # a five-way greedy choice and action select
 EPS = 2.0 ** -52
 # both ends of each range, points outside them, a cell boundary and general points
 GRID = np.array([[a, v] for a in (-0.5, 0.0, 1.0, math.pi, 2 * math.pi, 7.0) for v in (-40.0, -12 * math.pi, -3.3, 0.0, 12 * math.pi, 50.0)])
@@ -98,11 +110,15 @@ class Ref:
 _made = {}
 
 
+def seeds_of(name):
+    return CASES[name].get("seeds", SEEDS)
+
+
 def case(grlx, name):
     """(reference, runner, snapshots after each of the two batches per replica); made once, never advanced again"""
     if name not in _made:
-        cfg = grlx.pendulum_lspi_config(len(SEEDS), max_batches=2, **CASES[name])
-        r = grlx.LspiRunner(cfg, SEEDS)
+        cfg = grlx.pendulum_lspi_config(len(SEEDS), max_batches=2, **{k: v for k, v in CASES[name].items() if k != "seeds"})
+        r = grlx.LspiRunner(cfg, seeds_of(name))
         ref = Ref(cfg)
         snaps = [[dict(w=r.params(k), q=r.query(GRID)[k]) for k in range(len(SEEDS))]]
         for _ in range(2):
@@ -139,7 +155,7 @@ def test_greedy_choice(grlx, name):
                 assert best[j] == q.index(max(q))
 
 
-_systems = {}
+_systems, _solves = {}, {}
 
 
 def system_reference(ref, tr, key):
@@ -171,12 +187,24 @@ def test_the_system(grlx, name):
         print(f"{name} batch {b_} replica {k}: max |dA| / bound = {float(np.max(errA / np.maximum(tolA, 1e-300))):.3g}, max |db| / bound = {float(np.max(errb / np.maximum(tolb, 1e-300))):.3g}")
         assert (errA <= tolA).all(), f"batch {b_}, replica {k}: A misses its bound at {np.argwhere(errA > tolA)[:5].tolist()}"
         assert (errb <= tolb).all(), f"batch {b_}, replica {k}: b misses its bound at {np.argwhere(errb > tolb)[:5].tolist()}"
-    again = grlx.LspiRunner(r.cfg, SEEDS)
+    again = grlx.LspiRunner(r.cfg, seeds_of(name))
     for b_ in (1, 2):
         again.run_batch(); again.sync()
         for k in range(len(SEEDS)):
             assert (bits(again.system(k)[0]) == bits(snaps[b_][k]["sys"][0])).all(), f"batch {b_}, replica {k}: A differs between two runs"
     again.close()
+
+
+def test_the_small_cutoff_keeps_weights_that_s6_prunes(grlx):
+    """what the c1e8 row is for: among each replica's stored transitions some unpruned projection weight lies in (cutoff, 1e-5] -- read
+    by the greedy choice, dropped from Phi or Psi.  (Ref.project keeps distsq < -sigma^2 log(cutoff), i.e. weights above the cutoff.)"""
+    name = "f64-gauss-n64-it2-c1e8"
+    ref, r, snaps = case(grlx, name)
+    for k, s in enumerate(snaps[2]):
+        oa, nobs, _, best = s["tr"]
+        for side, inputs in (("Phi", [list(x) for x in oa]), ("Psi", [[o[0], o[1], ref.actions[a]] for o, a in zip(nobs, best)])):
+            small = sum(1 for x in inputs for _, wt in ref.project(x) if r.cfg.cutoff < wt <= 0.00001)
+            assert small > 0, f"replica {k}: no weight of {side} in (cutoff, 1e-5]"
 
 
 def backward_error(A, b, w):
@@ -195,6 +223,12 @@ def test_the_solve(grlx, name):
         print(f"{name} batch {b_} replica {k}: eta = {eta:.3e}, numpy's = {eta_np:.3e}")
         assert s["info"]["status"] == 0
         assert eta <= max(4 * eta_np, ref.F * EPS), f"batch {b_}, replica {k}: eta = {eta:.3e}, numpy's = {eta_np:.3e}"
+        # and the elimination order restated (tests/lspi_solve_ref.py): the weights bit for bit
+        if (name, b_, k) not in _solves:
+            _solves[name, b_, k] = lspi_solve_ref.solve(A, b)
+        want, _, flagged = _solves[name, b_, k]
+        bad = np.nonzero(bits(s["w"]) != bits(want))[0]
+        assert not flagged and bad.size == 0, f"batch {b_}, replica {k}: {bad.size} of {ref.F} weights differ from the restated order, first at {bad[:1]}"
 
 
 @pytest.mark.parametrize("name", sorted(CASES))

@@ -22,9 +22,15 @@ CASES = {"tri-f27-n5": dict(steps=[3, 3, 3], projector="triangle", batch_size=5,
          "gauss-f60": dict(steps=[5, 4, 3], projector="gauss", batch_size=64, iterations=3),            # the box is clipped on every side
          "gauss-f363": dict(steps=[11, 11, 3], projector="gauss", batch_size=64, iterations=1),         # an interior box
          "gauss-f363-s05": dict(steps=[11, 11, 3], projector="gauss", batch_size=64, iterations=1, sigma=0.5),      # a box of about one cell
-         "tri-f60-a5": dict(steps=[5, 4, 3], projector="triangle", batch_size=64, iterations=3, action_steps=5)}   # lane 0 owns two actions
+         "tri-f60-a5": dict(steps=[5, 4, 3], projector="triangle", batch_size=64, iterations=3, action_steps=5),   # lane 0 owns two actions
+         "gauss-f60-s2": dict(steps=[5, 4, 3], projector="gauss", batch_size=64, iterations=3, sigma=2.0),          # the box is wider than the grid on every axis
+         "gauss-f363-c1e8": dict(steps=[11, 11, 3], projector="gauss", batch_size=64, iterations=1, cutoff=1e-8)}   # a radius of 4.3 cells, twice the default's
 PI = math.pi
-FAR = 7          # index of the start whose velocity lies beyond the cutoff radius of every Gauss case (200 > 12 pi + 2.15 * 8 pi)
+# index of the start whose velocity lies beyond the cutoff radius of every Gauss case: 200 > 12 pi + radius * delta, radius =
+# sigma sqrt(-log cutoff) cells of delta = 24 pi / (steps[1] - 1).  The defaults at steps[1] = 4: 37.7 + 2.15 * 25.1 = 91.6; gauss-f60-s2:
+# 37.7 + 4.29 * 25.1 = 145.6; gauss-f363-c1e8: 37.7 + 4.29 * 7.54 = 70.1; tests/test_gpu_lspi_evaluate_sampled.py's gauss-f512-s3:
+# 37.7 + 6.44 * 10.8 = 107.0
+FAR = 7
 # model states (angle, velocity, time); the observation's angle is (angle + pi) mod 2 pi
 STARTS = np.array([[PI, 0.0, 0.0], [-PI, -12 * PI, 2.8], [PI - 1e-9, 12 * PI, 2.9], [7.0, -40.0, 2.95], [-0.5 * PI, 50.0, 2.97], [-4.0, 3.3, 3.0],
                    [0.3, -2.0, 2.7], [1.0, 200.0, 2.9], [2.0, 8 * PI, 2.93]])

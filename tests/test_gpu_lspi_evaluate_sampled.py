@@ -24,8 +24,16 @@ CASES = {"tri27": dict(n=65, batches=1, steps=[3, 3, 3], projector="triangle", b
          "gauss60": dict(n=6, batches=1, steps=[5, 4, 3], projector="gauss", batch_size=64, iterations=3),
          "gauss363": dict(n=6, batches=1, steps=[11, 11, 3], projector="gauss", batch_size=64, iterations=1),
          "gauss363-s05": dict(n=6, batches=1, steps=[11, 11, 3], projector="gauss", batch_size=64, iterations=1, sigma=0.5),
-         "zero": dict(n=6, batches=0, steps=[3, 3, 3], projector="triangle", init_min=0.0, init_max=0.0)}
-TIED = {"tri27", "gauss60", "gauss363", "gauss363-s05", "zero"}      # seed 4's zeros; the far start's empty Gauss projection; all-zero weights
+         "zero": dict(n=6, batches=0, steps=[3, 3, 3], projector="triangle", init_min=0.0, init_max=0.0),
+         "gauss-f60-s2": dict(n=6, batches=1, steps=[5, 4, 3], projector="gauss", batch_size=64, iterations=3, sigma=2.0),       # a box wider than the grid
+         "gauss-f363-c1e8": dict(n=6, batches=1, steps=[11, 11, 3], projector="gauss", batch_size=64, iterations=1, cutoff=1e-8),      # a radius of 4.3 cells
+         # the capacity of the ensemble kernel's pair list at its bound.  lspi_ens_cap (grlx_lspi_evaluate_sampled.hip) by hand: the radius is
+         # 3 sqrt(log 100) = 6.44 cells, ceil(2 * 6.44) + 3 = 16 candidates per dimension, more than the 8 the grid has, so cap = 8 * 8 * 8 = 512
+         # = kLspiMaxF slots per action -- and a state whose position on each axis lies in [0.56, 6.44] cells, the middle action among them,
+         # fills all 512
+         "gauss-f512-s3": dict(n=6, batches=1, steps=[8, 8, 8], projector="gauss", batch_size=64, iterations=1, sigma=3.0)}
+# seed 4's zeros; the far start's empty Gauss projection; all-zero weights
+TIED = {"tri27", "gauss60", "gauss363", "gauss363-s05", "zero", "gauss-f60-s2", "gauss-f363-c1e8", "gauss-f512-s3"}
 SAMPLERS = [("greedy", None), ("epsilon", 0.0), ("epsilon", 0.3), ("epsilon", 1.0)]
 MAX_STEPS = 12
 TAU = {"majority": 1.0, "rank": 2.0}                                 # draws leave the first maximum
